@@ -13,9 +13,14 @@ anything touches the GPU.  The sample batch is sharded (weak scaling: B per GPU;
 BASELINE.json's "1M sampled x0 over 8 GPUs"), no collective during the solves and ONE RCCL gather of the first moves
 over xGMI at the end of every step -- through the library (nnmpc_comm_*); this file binds nothing but libnnmpc_hip.so.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  At N = 1 the default run also measures, outside the
-headline's timed region, the other single-GPU configurations of BASELINE.json (`configs`), the active-fraction sweep,
-the lock-step chain workload, the PDIP path, the PCIe-inclusive rate, the parity checks and the CPU baseline.
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run does only what the headline needs: set-up,
+W warm-up steps, the K timed steps, the line.  With --full (N = 1) it also measures, outside the headline's timed region,
+the other single-GPU configurations of BASELINE.json (`configs`), the active-fraction sweep, the lock-step chain workload,
+the PDIP path, the PCIe-inclusive rate, the parity checks and the CPU baseline (minutes).
+
+--dump-outputs DIR writes what the timed path returned in its LAST timed step as DIR/<name>.npy (float64; active-set bits
+as float32; at most 64 MB, larger outputs as a fixed seeded sample of rows).  Inputs are seeded: the same arguments give
+the same inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -60,6 +65,7 @@ FP32_PEAK_TFLOPS = 157.3  # MI355X dense f32 matrix/vector peak (MI355X_MICROARC
 FP64_PEAK_TFLOPS = 78.6   # f64 vector = matrix peak (half the f32 rate; v_mfma_f64_16x16x4_f64)
 BF16_PEAK_TFLOPS = 2500.0
 NSETS_MAX = 32           # distinct input batches kept in HBM for the headline's steps
+DUMP_LIMIT = 64 << 20    # bytes of --dump-outputs, all files together
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -621,8 +627,59 @@ def emit(out):
     sys.stdout.flush()
 
 
-def bench_qp(ctx, workload, B, steps, warmup, sx, method="auto", slots=0, seed0=1000, want_buffers=False):
-    """K timed steps of the regulator QP batch on this rank (+ the gather at world > 1).  Returns (result dict, handles)."""
+# ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path returned in its last step, for comparing two builds output for output
+def sample_rows(B, k, seed=2021):
+    """A fixed, seeded sample of k of B rows in increasing order (all B rows when B <= k)."""
+    if B <= k:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(seed).choice(B, k, replace=False))
+
+
+def write_outputs(d, arrays):
+    """{name: array} -> d/<name>.npy; float32 stays float32, everything else is written as float64.  Refuses more than
+    DUMP_LIMIT bytes in all."""
+    out = {}
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        out[k] = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, over the limit of {DUMP_LIMIT}")
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
+def dump_qp(d, buf, n, nu, gathered=None):
+    """The outputs of the last solve, under the names BatchedBoxQP.solve_batch gives them: `u` and `active` (bits in the row
+    order of the reference's G) for a seeded sample of rows (`u_rows`; B x n doubles are 3.6 GB at the CDU size), `status`,
+    `ipm_iters`, `factorizations` and `first_moves` (u[:, :nu] + us) for every problem up to a cap, beyond it for a seeded
+    sample (`problem_rows`, `first_move_rows`).  At world > 1 `first_moves` are the gathered ones of all ranks, the rest
+    are rank 0's own shard."""
+    B = buf.B
+    rows = sample_rows(B, max(1, min(256, (20 << 20) // (16 * n))))               # u + active: <= 20 MB
+    words = buf.act.shape[1]
+    u = np.stack([np.frombuffer(_row(buf.u, r, n * 8), np.float64) for r in rows])
+    act = np.stack([np.frombuffer(_row(buf.act, r, words * 4), np.uint32) for r in rows])
+    out = {"u": u, "active": np.unpackbits(act.view(np.uint8), axis=1, bitorder="little")[:, :2 * n].astype(np.float32),
+           "u_rows": rows}
+    prow = sample_rows(B, (6 << 20) // 24)                                       # status + iteration counts: <= 6 MB
+    iters = buf.iters.to_host()[prow]
+    out.update(status=buf.status.to_host()[prow], ipm_iters=iters[:, 0], factorizations=iters[:, 1])
+    first = (gathered if gathered is not None else buf.first).to_host()
+    frow = sample_rows(first.shape[0], (32 << 20) // (8 * nu))                    # first moves: <= 32 MB
+    out["first_moves"] = first[frow]
+    if prow.size < B:
+        out["problem_rows"] = prow
+    if frow.size < first.shape[0]:
+        out["first_move_rows"] = frow
+    write_outputs(d, out)
+
+
+def bench_qp(ctx, workload, B, steps, warmup, sx, method="auto", slots=0, seed0=1000, want_buffers=False, dump_dir=None):
+    """K timed steps of the regulator QP batch on this rank (+ the gather at world > 1).  Returns (result dict, handles).
+    dump_dir: rank 0 writes the outputs of the last timed step there (dump_qp)."""
     from industrial_nnmpc_2021_amd.qp import BatchedBoxQP
     lib = ctx.lib
     pl, P, tq, nu = make_problem(workload)
@@ -680,6 +737,9 @@ def bench_qp(ctx, workload, B, steps, warmup, sx, method="auto", slots=0, seed0=
     dt = ctx.max_over_ranks(dt_local)
     st = qp.stats()
     qp.set_profiling(False)
+    if dump_dir and ctx.rank == 0:
+        lib.synchronize()
+        dump_qp(dump_dir, buf, n, nu, gathered)
     status_h, iters_h = buf.status.to_host(), buf.iters.to_host()
     res = {"value": ctx.world * B * steps / dt, "unit": "solves/s", "ms_per_step": 1e3 * dt / steps,
            "per_rank_solves_per_s_this_rank": B * steps / dt_local, "distinct_input_batches": nsets,
@@ -1144,11 +1204,12 @@ def cdu_offline_simulator(tasks, T, seed=1, procs_per_task=1):
     return sim
 
 
-def chains_task_leg(ctx, tasks=149, T=2400):
+def chains_task_leg(ctx, tasks=149, T=2400, dump_dir=None):
     """The reference's actual deliverable at its real length (cdu_parameters.py:211: 357 600 steps = 149 tasks x 2400): PRBS-like
     setpoints and disturbances, target selector (deduplicated, batched: the other QP of every step, lib/linearMPC.py:851)
     included, all chains in lock-step on the device, records back on the host.  At world > 1 the tasks are sharded over the
-    ranks (OfflineSimulator.generate_dataset: contiguous blocks of tasks, ONE gather of the records)."""
+    ranks (OfflineSimulator.generate_dataset: contiguous blocks of tasks, ONE gather of the records).
+    dump_dir: rank 0 writes the data set's records (x, uprev, xs, us, u, status) for a seeded sample of its rows there."""
     from industrial_nnmpc_2021_amd import linearMPC as lm
     from industrial_nnmpc_2021_amd.chain import DeviceChains
     t0 = time.perf_counter()
@@ -1177,6 +1238,10 @@ def chains_task_leg(ctx, tasks=149, T=2400):
     dt = ctx.max_over_ranks(time.perf_counter() - t0)
     if ctx.rank != 0:
         return None
+    if dump_dir:
+        keys = sim._REC_KEYS
+        rows = sample_rows(data["u"].shape[0], (48 << 20) // (8 * (1 + sum(data[k].shape[1] for k in keys))))
+        write_outputs(dump_dir, dict({k: data[k][rows] for k in keys}, status=data["status"][rows], rows=rows))
     ts = sim.target_selectors[0]
     distinct = getattr(getattr(ts, "_batched", None), "last_distinct", None)
     return {"value": tasks * T / dt, "unit": "chain-steps/s (target QP + regulator QP + model step each)", "chains": tasks, "steps_per_chain": T,
@@ -1190,13 +1255,16 @@ def chains_task_leg(ctx, tasks=149, T=2400):
                     "(state, targets, records in HBM), PCIe both ways" + (", the RCCL gather of the records" if ctx.world > 1 else "")}
 
 
-def bench_nn(ctx, B, steps, warmup, with_uprev=False, modes=("f32", "bf16", "bf16x3")):
+def bench_nn(ctx, B, steps, warmup, with_uprev=False, modes=None, full=True, dump_dir=None):
     """Config 5: structured-NN controller forward, CDU architecture [536, 832, 832, 832, 32]
     (RegulatorLayerWithoutUprev, what the reference uses for the CDU: cdu_train.py:33, :77-80; with_uprev: the 568-input
-    RegulatorLayerWithUprev BASELINE.json names, lib/LinearMPCLayers.py:40-61), B states per GPU per step, f32 and bf16."""
+    RegulatorLayerWithUprev BASELINE.json names, lib/LinearMPCLayers.py:40-61), B states per GPU per step, f32 and bf16.
+    full=False: the f32 headline alone (no other precision, no oracle comparison, no 568-input variant).
+    dump_dir: rank 0 writes the f32 outputs of the last timed step for a seeded sample of rows there."""
     from industrial_nnmpc_2021_amd.nn import StructuredNN
     from oracle import nn as onn
     lib = ctx.lib
+    modes = modes or (("f32", "bf16", "bf16x3") if full else ("f32",))
     nx, nu, hid = 252, 32, 832
     dims = [2 * nx + (2 if with_uprev else 1) * nu, hid, hid, hid, nu]
     rng = np.random.default_rng(0)
@@ -1220,7 +1288,8 @@ def bench_nn(ctx, B, steps, warmup, with_uprev=False, modes=("f32", "bf16", "bf1
     res = {}
     k = min(B, 4096)
     rows = np.concatenate(([0], np.sort(np.random.default_rng(9).choice(B, k - 1, replace=False)))) if B > k else np.arange(B)
-    ref = onn.control_input(W, x_h[rows], up_h[rows] if with_uprev else None, xs_h[rows], us_h[rows], xscale, -np.ones(nu), np.ones(nu), with_uprev)
+    if full:
+        ref = onn.control_input(W, x_h[rows], up_h[rows] if with_uprev else None, xs_h[rows], us_h[rows], xscale, -np.ones(nu), np.ones(nu), with_uprev)
     for mode in modes:
         net = StructuredNN(W, nx, nu, nnwithuprev=with_uprev, xscale=xscale, ulb=-np.ones(nu), uub=np.ones(nu),
                            max_batch=262144, use_bf16={"f32": False, "bf16": True, "bf16x3": "split"}[mode])
@@ -1237,14 +1306,19 @@ def bench_nn(ctx, B, steps, warmup, with_uprev=False, modes=("f32", "bf16", "bf1
             hm += net.last_hidden_ms()[0]; hl += net.last_hidden_ms()[1]
         ctx.sync()
         dt = ctx.max_over_ranks(time.perf_counter() - t0)
-        u_h = u.to_host()
-        err = float(np.abs(u_h[rows] - ref).max() / max(1.0, np.abs(ref).max()))
         res[mode] = dict(states_per_s=ctx.world * B * steps / dt, ms_per_step=1e3 * dt / steps,
-                         gemm_TFLOPs=flops_per_state * B * steps / (gm * 1e-3) / 1e12, max_rel_err_vs_fp64_oracle=err,
-                         rows_checked=int(rows.size), steady_state_row_exact=bool(np.array_equal(u_h[0], np.clip(us_h[0], -1, 1))),
+                         gemm_TFLOPs=flops_per_state * B * steps / (gm * 1e-3) / 1e12,
                          device_ms_per_step=dm / steps, gemm_ms_per_step=gm / steps,
                          hidden_TFLOPs=hidden_flops_per_state * B * steps / (hm * 1e-3) / 1e12,
                          hidden_launches=hl, hidden_avg_launch_ms=hm / max(1, hl))
+        if full or (dump_dir and mode == "f32"):
+            u_h = u.to_host()
+        if full:
+            res[mode].update(max_rel_err_vs_fp64_oracle=float(np.abs(u_h[rows] - ref).max() / max(1.0, np.abs(ref).max())),
+                             rows_checked=int(rows.size), steady_state_row_exact=bool(np.array_equal(u_h[0], np.clip(us_h[0], -1, 1))))
+        if dump_dir and mode == "f32" and ctx.rank == 0:
+            r_d = sample_rows(B, (32 << 20) // (8 * nu))
+            write_outputs(dump_dir, {"u": u_h[r_d], "rows": r_d})
         net.close()
     for a in (x, xs, us, u, up):
         if a is not None:
@@ -1252,7 +1326,7 @@ def bench_nn(ctx, B, steps, warmup, with_uprev=False, modes=("f32", "bf16", "bf1
     if with_uprev:                                     # the variant entry of the main line: rates and errors only
         return {"dims": dims, **{m: {k: res[m][k] for k in ("states_per_s", "ms_per_step", "max_rel_err_vs_fp64_oracle", "steady_state_row_exact",
                                                               "hidden_TFLOPs", "rows_checked")} for m in modes}}
-    f, h, s3 = res["f32"], res["bf16"], res["bf16x3"]
+    f = res["f32"]
     traffic, tnote = pmc_traffic(f"nn_b{B}")
     rows2 = 2 * min(B, 262144)
     kavg = (((dims[0] + 63) // 64) * 64 + 2 * hid) / 3.0
@@ -1266,9 +1340,12 @@ def bench_nn(ctx, B, steps, warmup, with_uprev=False, modes=("f32", "bf16", "bf1
                         "launches": f["hidden_launches"], "avg_launch_ms": f["hidden_avg_launch_ms"],
                         "algorithmic_bytes_per_launch": rows2 * (896 + 896) * 4,
                         "algorithmic_flops": "2 passes x 2 x sum(d_in d_out) per state, unpadded (SURVEY 8d)"},
-           "parity": {"max_rel_err_vs_fp64_oracle": f["max_rel_err_vs_fp64_oracle"], "rows_checked": f["rows_checked"],
-                      "steady_state_row_exact": f["steady_state_row_exact"], "tolerance": 1e-4},
-           "f32": f,
+           "f32": f}
+    if not full:
+        return out
+    h, s3 = res["bf16"], res["bf16x3"]
+    out.update({"parity": {"max_rel_err_vs_fp64_oracle": f["max_rel_err_vs_fp64_oracle"], "rows_checked": f["rows_checked"],
+                           "steady_state_row_exact": f["steady_state_row_exact"], "tolerance": 1e-4},
            "bf16": dict(h, tolerance=3e-2,
                         roofline={"kernel": "gemm_nt_bf16_wide_k (256 x 208 tiles, v_mfma_f32_16x16x32_bf16, persistent workgroups)", "dtype": "bf16",
                                   "bound": "mfma", "achieved": h["hidden_TFLOPs"], "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -1284,7 +1361,7 @@ def bench_nn(ctx, B, steps, warmup, with_uprev=False, modes=("f32", "bf16", "bf1
                           note="f32-grade results from the bf16 matrix pipes: hi hi' + hi lo' + lo hi' per layer (gemm_nt_bf16_wide_k, "
                                "K three times as deep); hidden_TFLOPs counts the algorithmic flops, the pipes execute 3 x that",
                           executed_hidden_TFLOPs=3.0 * s3["hidden_TFLOPs"], frac_of_bf16_peak_executed=3.0 * s3["hidden_TFLOPs"] / BF16_PEAK_TFLOPS,
-                          speedup_over_f32=s3["states_per_s"] / f["states_per_s"])}
+                          speedup_over_f32=s3["states_per_s"] / f["states_per_s"])})
     # BASELINE.json config 5 as literally written: RegulatorLayerWithUprev (568 inputs) at the same batch, f32 and bf16
     out["with_uprev_568_inputs"] = bench_nn(ctx, B, max(2, steps // 2), 1, with_uprev=True, modes=("f32", "bf16"))
     return out
@@ -1312,6 +1389,12 @@ def main():
     ap.add_argument("--pdip-batch", type=int, default=0)
     ap.add_argument("--parity-rows", type=int, default=32)
     ap.add_argument("--chain-steps", type=int, default=0, help="--workload chains: simulation steps per chain (2400 = the reference's task length)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline (minutes): parity checks, PDIP path, PCIe-inclusive rate, first-move calls, "
+                         "active-fraction sweep, chains, the other configurations, CPU baseline; --workload nn: bf16, split bf16, "
+                         "the oracle comparison and the 568-input variant.  The --no-* switches apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (at most 64 MB)")
     args = ap.parse_args()
     if args.no_cpu_baseline:
         args.cpu_baseline = "none"
@@ -1319,7 +1402,8 @@ def main():
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(sys.argv[1:], args.gpus))
 
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload in ("cdu", "cstrs") and not (args.no_parity and args.cpu_baseline == "none"):
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload in ("cdu", "cstrs")
+            and not (args.no_parity and args.cpu_baseline == "none")):
         start_workers(min(16, max(1, (os.cpu_count() or 1) // 4)))     # forked BEFORE the first GPU call (see WORKERS)
     ctx = Ctx(args)
     rank, world = ctx.rank, ctx.world
@@ -1327,14 +1411,14 @@ def main():
               "vs_baseline": None, "data": "synthetic"}
 
     if args.workload == "nn":
-        out = bench_nn(ctx, args.batch or (1 << 20), args.steps, args.warmup)
+        out = bench_nn(ctx, args.batch or (1 << 20), args.steps, args.warmup, full=args.full, dump_dir=args.dump_outputs)
         if rank == 0:
             emit(dict(out, **common))
         return
     if args.workload == "chains":
         # the reference's task layout: `--batch` chains (default 149 = cdu_parameters.py:211) x `--chain-steps` steps each
         # (default: --steps, at least 8; 2400 = the reference's length), sharded over the ranks by contiguous blocks of tasks
-        out = chains_task_leg(ctx, args.batch or 149, args.chain_steps or max(args.steps, 8))
+        out = chains_task_leg(ctx, args.batch or 149, args.chain_steps or max(args.steps, 8), dump_dir=args.dump_outputs)
         if rank == 0:
             line = {"metric": "closed-loop offline data generation: chain steps/sec (CDU size; target QP + regulator QP + model step)"}
             line.update(common)
@@ -1346,9 +1430,9 @@ def main():
         return
 
     B = args.batch or default_batch(args.workload, world)
-    extras = world == 1 and not args.no_extras
+    extras = args.full and world == 1 and not args.no_extras
     res, h = bench_qp(ctx, args.workload, B, args.steps, args.warmup, args.sx, method=args.method, slots=args.slots,
-                      want_buffers=(rank == 0 and world == 1))
+                      want_buffers=(rank == 0 and world == 1), dump_dir=args.dump_outputs)
     if rank != 0:
         return
     n, n_aug = (h["n"], h["tq"].shape[1]) if h else (None, None)
@@ -1361,7 +1445,9 @@ def main():
                                  + f", {B} sampled x0 per GPU per step, whole sequences u* written out",
                      "batch_per_gpu": B, "total_batch": B * world, "sx": args.sx, "method": args.method,
                      "parallelism": f"dp{world} (sharded samples, 1 RCCL gather of the first moves per step, nnmpc_comm_gather_rows)"}
-    if world == 1 and h is not None:
+    if h is not None and not args.full:
+        h["qp"].close(); h["buf"].free()                  # a plain run: the headline alone
+    elif world == 1 and h is not None:
         legs = {}
 
         def timed(name, fn, *a):

@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from industrial_nnmpc_2021_amd import synthetic
 from industrial_nnmpc_2021_amd.linearMPC_build import build_regulator_matrices

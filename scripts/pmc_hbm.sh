@@ -5,7 +5,7 @@
 # --kernel-trace only (FETCH_SIZE costs 3 of the 4 TCC slots, WRITE_SIZE 2: they do not fit one pass).
 set -u
 name=$1; shift
-out=$PWD/gpurun_out/pmc_hbm_$name
+out=${PASS_OUT:-$PWD/pass_out}/pmc_hbm_$name
 rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -- python3 bench.py "$@" > "$out/fetch.log" 2>&1 || { echo "FETCH pass failed"; tail -5 "$out/fetch.log"; }

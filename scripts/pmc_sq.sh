@@ -5,7 +5,7 @@
 # Counter names are filtered by `rocprofv3 -L` so an unknown name cannot fail a pass.
 set -u
 tag=$1; shift
-out=$PWD/gpurun_out/pmc_$tag
+out=${PASS_OUT:-$PWD/pass_out}/pmc_$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 rocprofv3 -L > "$out/counters_list.txt" 2>&1 || true

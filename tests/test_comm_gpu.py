@@ -40,7 +40,7 @@ def test_bench_rank_code_with_forced_communicator():
     env = dict(os.environ, NNMPC_FORCE_DIST="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "4096", "--steps", "1", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "4096", "--steps", "1", "--warmup", "1", "--full", "--no-extras",
                         "--no-pdip", "--no-host-io", "--no-cpu-baseline", "--parity-rows", "2"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -9,6 +9,7 @@ import sys
 import types
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -19,14 +20,16 @@ class _Obj:
         return lambda *a, **k: None
 
 
-def _fake_main(monkeypatch, tmp_path, capsys, argv):
+def _fake_main(monkeypatch, tmp_path, capsys, argv, on_bench_qp=None, started=None):
     import bench
     detail = json.load(open(os.path.join(ROOT, "profiles", "r03c_cdu_b100000_bench.json")))
     ctx = types.SimpleNamespace(rank=0, world=1, comm=None, lib=_Obj(), sync=lambda: None, max_over_ranks=lambda v: v)
     monkeypatch.setattr(bench, "Ctx", lambda args: ctx)
-    monkeypatch.setattr(bench, "start_workers", lambda n: None)
+    monkeypatch.setattr(bench, "start_workers", lambda n: None if started is None else started.append(n))
 
     def fake_bench_qp(ctx_, workload, B, steps, warmup, sx, **kw):
+        if on_bench_qp:
+            on_bench_qp(ctx_, workload, B, steps, warmup, sx, **kw)
         src = detail if workload == "cdu" else detail["configs"]["cstrs_10k"]
         res = {k: src[k] for k in ("value", "unit", "ms_per_step", "solver", "roofline", "roofline_step", "time_shares", "dtype")}
         res["roofline_gemm_group"] = detail["roofline"]
@@ -51,7 +54,9 @@ def _fake_main(monkeypatch, tmp_path, capsys, argv):
 
 
 def test_final_line_is_small_and_carries_roofline_and_cpu_baseline(monkeypatch, tmp_path, capsys):
-    lines = _fake_main(monkeypatch, tmp_path, capsys, ["--steps", "20", "--warmup", "5"])
+    started = []
+    lines = _fake_main(monkeypatch, tmp_path, capsys, ["--steps", "20", "--warmup", "5", "--full"], started=started)
+    assert len(started) == 1                           # the worker pool of the parity leg and the CPU baseline
     last = lines[-1]
     assert len(last) < 4096, len(last)
     line = json.loads(last)
@@ -70,6 +75,43 @@ def test_final_line_is_small_and_carries_roofline_and_cpu_baseline(monkeypatch, 
     # the detail went to the side file, whole
     d = json.load(open(tmp_path / "detail.json"))
     assert "leg_seconds" in d and "sweep_sx" in d and d["value"] == line["value"] or abs(d["value"] - line["value"]) / d["value"] < 1e-5
+
+
+def test_plain_run_is_the_headline_alone(monkeypatch, tmp_path, capsys):
+    """Without --full: no worker pool, no leg beyond the K timed steps, and the line still says what the headline is."""
+    import bench
+
+    def refuse(*a, **k):
+        raise AssertionError("a plain run measures the headline alone")
+    for leg in ("parity_leg", "pdip_leg", "host_io_leg", "first_move_leg", "sweep_leg", "chains_leg", "chains_task_leg", "unstable_leg",
+                "bench_nn", "cpu_baseline"):
+        monkeypatch.setattr(bench, leg, refuse)
+    seen, started = [], []
+    lines = _fake_main(monkeypatch, tmp_path, capsys, ["--steps", "7", "--warmup", "2"], on_bench_qp=lambda *a, **k: seen.append((a, k)),
+                       started=started)
+    assert started == []
+    assert len(seen) == 1 and seen[0][0][1:5] == ("cdu", 100000, 7, 2) and seen[0][1].get("dump_dir") is None
+    line = json.loads(lines[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["higher_is_better"] is True and line["unit"] == "solves/s"
+    assert not {"parity", "cpu_baseline", "configs", "sweep_sx_solves_per_s", "first_move_solves_per_s"} & set(line)
+    assert "leg_seconds" not in json.load(open(tmp_path / "detail.json"))
+
+
+def test_dump_helpers_are_seeded_float_and_bounded(tmp_path):
+    import bench
+    a, b = bench.sample_rows(100000, 256), bench.sample_rows(100000, 256)
+    assert np.array_equal(a, b) and a.size == 256 and (np.diff(a) > 0).all() and a.max() < 100000
+    assert np.array_equal(bench.sample_rows(10, 256), np.arange(10))
+    bench.write_outputs(str(tmp_path / "d"), {"u": np.ones((3, 4)), "active": np.ones((3, 8), np.float32),
+                                              "status": np.zeros(3, np.int32), "rows": np.arange(3)})
+    got = {f: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert set(got) == {"u.npy", "active.npy", "status.npy", "rows.npy"}
+    assert got["active.npy"].dtype == np.float32 and all(got[f].dtype == np.float64 for f in ("u.npy", "status.npy", "rows.npy"))
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / "e"), {"u": np.zeros(bench.DUMP_LIMIT // 8 + 1)})
+    assert not os.path.exists(tmp_path / "e")
 
 
 def test_compact_line_never_exceeds_the_limit():
