@@ -276,6 +276,78 @@ int nnmpc_ts_destroy(nnmpc_ts* h);
 int nnmpc_ts_solve_batch(nnmpc_ts* h, int32_t B, const double* q, const double* e, double* us,
                          double* lam_eq, uint8_t* active, int32_t* status, int32_t ptr_kind);
 
+/* ---- Lock-step closed-loop evaluation  <-  online_simulation (lib/linearMPC.py:703-718) with LinearMPCController.control_law
+ * (:646-701), NeuralNetworkController (lib/controller_evaluation.py:841-892), SatDlqrController / SteadyStateController
+ * (:918-1087), one (controller, scenario, noise seed) per call in the reference (_simulate_scenarios / _simulate_neural_networks,
+ * :322-523).  All nb instances advance together; plant, estimator, running cost and records stay in HBM.  Per step t:
+ *   filter   xp = Aaug xhat + Baug uprev,  xhat = xp + L (y_t - Caug xp) = [x^; d^]                          (:133-176, :646-650)
+ *   target   b = tb [ysp_t; d^],  q = Qb b + Qy (ysp_t - Cd d^) + q0,  e = Eb b,  us = the reduced target QP (nnmpc_ts),
+ *            xs = Xb b + Xu us                                                                                 (:298-311)
+ *   control  MPC: first move of the regulator QP at [x^ - xs; uprev - us], bounds ulb - us / uub - us, + us (:682-689), warm-
+ *            started on the instance's previous active set shifted by one stage;  NN: clip(us + NN(x^, uprev, xs, us) -
+ *            NN(xs, us, xs, us)) (:863-892);  SATDLQR: clip(Kaug [x^ - xs; uprev - us] + us) (:1003-1005);  US: us (:1076)
+ *   cost     z = [x^ - xs; uprev - us], w = u - us, ell = z'Qaug z + w'Raug w + z'Maug w + w'Maug'z,
+ *            avg_{t+1} = (avg_t t + ell) / (t + 1)                                                             (:691-701)
+ *   plant    uprev = u,  x = A x + B u + Bp p_t,  y_{t+1} = C x + sigma o v_{t+1}                               (:87-131)
+ * Nothing random runs on the device: v holds the standard-normal draws of every instance. */
+typedef struct nnmpc_cl nnmpc_cl;
+#define NNMPC_CL_MPC 0
+#define NNMPC_CL_NN 1
+#define NNMPC_CL_SATDLQR 2
+#define NNMPC_CL_US 3
+/* Shared model data (fp64, row-major, host), na = nx + nd, nb_ = nx + nz:
+ *   plant   A nx x nx, B nx x nu, C ny x nx, Bp nx x nd
+ *   filter  Aaug na x na, Baug na x nu, Caug ny x na, L na x ny (steady-state gain, dlqe)
+ *   target  tb nb_ x (ny + nd), Qb nu x nb_, Qy nu x ny, q0 nu, Cd ny x nd, Eb nz x nb_, Xb nx x nb_, Xu nx x nu
+ *           (target.ReducedTargetProblem; the QP itself is the borrowed nnmpc_ts handle, created with nu, nz)
+ *   cost    Qaug (nx + nu)^2, Raug nu x nu, Maug (nx + nu) x nu
+ *   bounds  ulb, uub (nu);  initial values x0 (nx), xhat0 (na), uprev0 (nu) shared by every instance */
+typedef struct {
+  int32_t nx, nu, ny, nd, nz;
+  const double *A, *B, *C, *Bp;
+  const double *Aaug, *Baug, *Caug, *L;
+  const double *tb, *Qb, *Qy, *q0, *Cd, *Eb, *Xb, *Xu;
+  const double *Qaug, *Raug, *Maug;
+  const double *ulb, *uub, *x0, *xhat0, *uprev0;
+} nnmpc_cl_model;
+/* One controller of the evaluation.  MPC: qp = the borrowed regulator handle (n_aug = nx + nu; any horizon).  NN: dims / W / b
+ * as nnmpc_nn_create (copied to HBM in f32; hidden widths <= 2048), with_uprev, xscale (nx, NULL = ones).  SATDLQR: Kaug
+ * (nu x (nx + nu)).  US: nothing. */
+typedef struct {
+  int32_t kind;
+  nnmpc_qp* qp;
+  int32_t nlayers;
+  const int32_t* dims;
+  const double* const* W;
+  const double* const* b;
+  int32_t with_uprev;
+  const double* xscale;
+  const double* Kaug;
+} nnmpc_cl_slot;
+/* inst_slot: nb slot indices, non-decreasing (the instances of a slot are contiguous; the host wrapper sorts and un-sorts) */
+int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32_t nslots, const nnmpc_cl_slot* slots,
+                    int32_t nb, const int32_t* inst_slot);
+int nnmpc_cl_destroy(nnmpc_cl* h);
+/* T steps.  setpoints: nscen x T x ny, dist: nscen x T x nd (this call's rows of every scenario), scen: nb scenario indices,
+ * v: (T + 1) x nb x ny standard-normal draws -- row 0 gives y_0 = C x0 + sigma o v_0 on the first call after create / reset and
+ * is ignored otherwise (a chunked run passes rows [t0, t0 + T] of the whole draw), row t + 1 the noise of y_{t+1}; sigma: ny
+ * (sqrt(diag(Rv))).  y0 (nb x ny, may be NULL): the first measurement of every instance instead of C x0 + sigma o v_0 (row 0 of
+ * v is then unused) -- the reference's evaluation scripts load a plant whose y[0] was drawn when it was pickled and seed the
+ * noise afterwards (_simulate_scenarios, lib/controller_evaluation.py:353-360).  Records (NULL = not recorded): y_rec, x_rec, xhat_rec, avg_rec (T + 1) x nb x {ny, nx, na, 1} (row 0 = the
+ * state at the start of the call); u_rec, xs_rec, us_rec T x nb x {nu, nx, nu}; ts_status, reg_status T x nb (NNMPC_ST_*;
+ * reg_status is 0 for other kinds).  All host or all device (ptr_kind).  The state carries over between calls. */
+int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints, const double* dist, const int32_t* scen,
+                 const double* v, const double* sigma, const double* y0, double* y_rec, double* x_rec, double* xhat_rec, double* u_rec,
+                 double* xs_rec, double* us_rec, double* avg_rec, int32_t* ts_status, int32_t* reg_status, int32_t ptr_kind);
+/* every instance back to (x0, xhat0, uprev0), avg = 0, step 0, no warm start */
+int nnmpc_cl_reset(nnmpc_cl* h);
+/* hipEvent times of the last run: total; phase_ms[6] summed over its steps = filter + target reduction, target QP, expansion
+ * and controller inputs (incl. SATDLQR / US), grouped NN forward, MPC solves (to the last slot's end), clip + cost + plant;
+ * slot_step_ms (T x nslots, may be NULL): each step's controller phase of each slot for the whole batch (MPC: its solve,
+ * NN: the grouped forward, SATDLQR / US: the expansion kernel).  The phase events of at most 256 steps are alive at a time: a
+ * longer run drains its stream once per 256 steps to add them up, so the handle holds (7 + MPC slots) x 256 + 2 events at most. */
+int nnmpc_cl_last_ms(nnmpc_cl* h, double* total_ms, double* phase_ms, double* slot_step_ms);
+
 /* ---- Device plumbing: HBM buffers, copies and synchronisation for host programs that bind only this library. */
 int nnmpc_device_count(void);
 int nnmpc_set_device(int32_t dev);

@@ -35,6 +35,20 @@ class QpStats(C.Structure):
                 ("asm_predict_flops", C.c_double)]
 
 
+CL_MPC, CL_NN, CL_SATDLQR, CL_US = 0, 1, 2, 3
+
+
+class ClModel(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("nx", "nu", "ny", "nd", "nz")] + \
+               [(k, C.c_void_p) for k in ("A", "B", "C", "Bp", "Aaug", "Baug", "Caug", "L", "tb", "Qb", "Qy", "q0", "Cd",
+                                          "Eb", "Xb", "Xu", "Qaug", "Raug", "Maug", "ulb", "uub", "x0", "xhat0", "uprev0")]
+
+
+class ClSlot(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("qp", C.c_void_p), ("nlayers", C.c_int32), ("dims", C.c_void_p), ("W", C.c_void_p),
+                ("b", C.c_void_p), ("with_uprev", C.c_int32), ("xscale", C.c_void_p), ("Kaug", C.c_void_p)]
+
+
 EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_solve_batch",
            "nnmpc_qp_solve_batch_warm", "nnmpc_qp_solve_batch_ex", "nnmpc_qp_set_inverse", "nnmpc_qp_dims",
            "nnmpc_qp_first_moves", "nnmpc_qp_set_farfield", "nnmpc_qp_farfield_missing",
@@ -42,6 +56,7 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_nn_create", "nnmpc_nn_destroy", "nnmpc_nn_forward", "nnmpc_nn_last_ms", "nnmpc_nn_last_hidden_ms",
            "nnmpc_chain_create", "nnmpc_chain_destroy", "nnmpc_chain_run", "nnmpc_chain_reset", "nnmpc_chain_last_ms",
            "nnmpc_ts_create", "nnmpc_ts_destroy", "nnmpc_ts_solve_batch",
+           "nnmpc_cl_create", "nnmpc_cl_destroy", "nnmpc_cl_run", "nnmpc_cl_reset", "nnmpc_cl_last_ms",
            "nnmpc_device_count", "nnmpc_set_device", "nnmpc_device_synchronize", "nnmpc_dev_mem_info",
            "nnmpc_dev_malloc", "nnmpc_dev_free", "nnmpc_dev_memset", "nnmpc_memcpy_h2d", "nnmpc_memcpy_d2h",
            "nnmpc_memcpy_d2d", "nnmpc_host_alloc_pinned", "nnmpc_host_free_pinned",
@@ -122,6 +137,16 @@ def load():
     lib.nnmpc_ts_destroy.argtypes = [vp]
     lib.nnmpc_ts_solve_batch.restype = i32
     lib.nnmpc_ts_solve_batch.argtypes = [vp, i32, dp, dp, dp, dp, dp, dp, i32]
+    lib.nnmpc_cl_create.restype = i32
+    lib.nnmpc_cl_create.argtypes = [C.POINTER(vp), C.POINTER(ClModel), vp, i32, C.POINTER(ClSlot), i32, C.POINTER(i32)]
+    lib.nnmpc_cl_destroy.restype = i32
+    lib.nnmpc_cl_destroy.argtypes = [vp]
+    lib.nnmpc_cl_run.restype = i32
+    lib.nnmpc_cl_run.argtypes = [vp, i32, i32, dp, dp, dp, dp, dp, dp] + [dp] * 9 + [i32]
+    lib.nnmpc_cl_reset.restype = i32
+    lib.nnmpc_cl_reset.argtypes = [vp]
+    lib.nnmpc_cl_last_ms.restype = i32
+    lib.nnmpc_cl_last_ms.argtypes = [vp, C.POINTER(C.c_double), dp, dp]
     lib.nnmpc_device_count.restype = i32
     lib.nnmpc_device_count.argtypes = []
     lib.nnmpc_set_device.restype = i32

@@ -567,6 +567,26 @@ int nnmpc_ts_destroy(nnmpc_ts* h) {
   return NNMPC_OK;
 }
 
+}  // extern "C"
+
+int nnmpc_ts_dims_internal(nnmpc_ts* h, int* nu, int* nz) {
+  if (!h) return NNMPC_EINVAL;
+  *nu = h->nu; *nz = h->nz;
+  return NNMPC_OK;
+}
+
+int nnmpc_ts_launch_internal(nnmpc_ts* h, int B, const double* q, const double* e, double* us, int* status, hipStream_t s) {
+  if (!h || B < 0 || !q || (h->nz && !e) || !us || !status) { set_error("nnmpc_ts_launch_internal: bad arguments"); return NNMPC_EINVAL; }
+  if (B == 0) return NNMPC_OK;
+  const int N = h->nu + h->nz;
+  const size_t lds = ((size_t)N * (N + 2) + N) * sizeof(double);
+  hipLaunchKernelGGL(ts_solve_k, dim3(B), dim3(64), lds, s, B, h->nu, h->nz, h->Pr, h->E, h->lb, h->ub, q, e, us, nullptr, nullptr,
+                     status, 1e-9);
+  return NNMPC_OK;
+}
+
+extern "C" {
+
 int nnmpc_ts_solve_batch(nnmpc_ts* h, int32_t B, const double* q, const double* e, double* us,
                          double* lam_eq, uint8_t* active, int32_t* status, int32_t ptr_kind) {
   if (!h || B < 0 || !q || (h->nz && !e) || !us || !status) { set_error("nnmpc_ts_solve_batch: bad arguments"); return NNMPC_EINVAL; }

@@ -1,0 +1,791 @@
+// Lock-step closed-loop evaluation (gfx950): online_simulation (lib/linearMPC.py:703-718) for every (controller, scenario,
+// noise seed) instance of an evaluation at once -- see include/nnmpc.h (nnmpc_cl_*).  Per step:
+//   cl_filter_k    filter update and the target problem's reduction (one workgroup per instance)
+//   ts_solve_k     the reduced target QPs of all instances (nnmpc_ts_launch_internal, one wave per instance)
+//   cl_expand_k    xs, the regulator's inputs (MPC), Kaug z + us (SATDLQR), us (US), the two NN input rows (NN)
+//   cl_nn_layer_k  grouped structured-NN forward: ONE launch per layer index for all networks (workgroup = network x 64 columns)
+//   nnmpc_qp_solve_batch_ex per MPC slot on the borrowed handle's stream (first moves, warm-started), beside the NN layers
+//   cl_post_k      u (NN combine + clip, SATDLQR clip, MPC first move + us), stage cost, running mean, plant step, records
+// Shared matrices are read by all instances from L2; a thread owns one output element and walks a stored transpose so that
+// the lanes of a wave read consecutive doubles.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <algorithm>
+#include <vector>
+#include "../../include/nnmpc.h"
+#include "common.h"
+
+using namespace nnmpc;
+
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(e_)); return NNMPC_EHIP; } } while (0)
+
+namespace {
+
+constexpr int CL_THREADS = 256;
+constexpr int NN_RB = 8;          // rows of a network per pass of cl_nn_layer_k (register accumulators per thread)
+constexpr int NN_KS = 4;          // K slices of a workgroup (4 waves x 64 columns), summed in a fixed order
+constexpr int NN_MAXK = 2048;     // LDS: NN_RB x K floats
+constexpr int CL_EV_BLOCK = 256;  // steps whose phase events are alive at once (nnmpc_cl_run)
+
+struct SlotDev {                  // per slot, device copy
+  int kind, base, count, n, words, with_uprev, row0;
+  const double* Kt;               // SATDLQR: Kaug' ((nx + nu) x nu)
+  const double* xscale;           // NN: nx
+  const double* first;            // MPC: first moves [count][nu]
+  const uint32_t* act;            // MPC: active-set words [count][words]
+  const int* status;              // MPC: [count]
+  unsigned char* guess;           // MPC: next warm start [count][n]
+};
+
+struct NNLayer {                  // one layer of one network
+  const float* W;                 // [K][N] (Keras kernel layout)
+  const float* bias;              // [N] or null (output layer)
+  int K, N, row0, rows, last;
+};
+
+// y = v^T M for a row-major M (rows x cols) and v in LDS: thread c owns column c (consecutive lanes, consecutive doubles)
+__device__ __forceinline__ double colsum(const double* __restrict__ M, int rows, int cols, const double* v, int c) {
+  double a = 0.0;
+  for (int j = 0; j < rows; ++j) a += M[(size_t)j * cols + c] * v[j];
+  return a;
+}
+
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int s = CL_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// ---- every instance to the shared initial values (nnmpc_cl_reset)
+__global__ __launch_bounds__(CL_THREADS) void cl_reset_k(int nx, int na, int nu, const double* __restrict__ x0,
+                                                          const double* __restrict__ xhat0, const double* __restrict__ uprev0,
+                                                          double* __restrict__ x, double* __restrict__ xhat, double* __restrict__ uprev,
+                                                          double* __restrict__ avg) {
+  const int i = blockIdx.x, tid = threadIdx.x;
+  for (int k = tid; k < nx; k += CL_THREADS) x[(size_t)i * nx + k] = x0[k];
+  for (int k = tid; k < na; k += CL_THREADS) xhat[(size_t)i * na + k] = xhat0[k];
+  for (int k = tid; k < nu; k += CL_THREADS) uprev[(size_t)i * nu + k] = uprev0[k];
+  if (tid == 0) avg[i] = 0.0;
+}
+
+// ---- start of a call: after a reset y_0 = C x0 + sigma o v_0 (LinearPlantSimulator.__init__, :87-100) or the caller's y0; row 0
+// of the records
+__global__ __launch_bounds__(CL_THREADS) void cl_begin_k(int fresh, int nx, int na, int ny, const double* __restrict__ Ct,
+                                                          const double* __restrict__ sigma, const double* __restrict__ v0,
+                                                          const double* __restrict__ y0,
+                                                          const double* __restrict__ x, const double* __restrict__ xhat,
+                                                          const double* __restrict__ avg, double* __restrict__ y,
+                                                          double* __restrict__ y_rec, double* __restrict__ x_rec,
+                                                          double* __restrict__ xhat_rec, double* __restrict__ avg_rec) {
+  extern __shared__ double sx[];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  for (int k = tid; k < nx; k += CL_THREADS) sx[k] = x[(size_t)i * nx + k];
+  __syncthreads();
+  if (fresh)
+    for (int j = tid; j < ny; j += CL_THREADS)
+      y[(size_t)i * ny + j] = y0 ? y0[(size_t)i * ny + j] : colsum(Ct, nx, ny, sx, j) + sigma[j] * v0[(size_t)i * ny + j];
+  __syncthreads();
+  if (y_rec) for (int j = tid; j < ny; j += CL_THREADS) y_rec[(size_t)i * ny + j] = y[(size_t)i * ny + j];
+  if (x_rec) for (int k = tid; k < nx; k += CL_THREADS) x_rec[(size_t)i * nx + k] = sx[k];
+  if (xhat_rec) for (int k = tid; k < na; k += CL_THREADS) xhat_rec[(size_t)i * na + k] = xhat[(size_t)i * na + k];
+  if (avg_rec && tid == 0) avg_rec[i] = avg[i];
+}
+
+// ---- step part 1: filter (KalmanFilter.solve, :108-112) and the reduction of the target problem (target.ReducedTargetProblem)
+struct FilterArgs {
+  int nx, nu, ny, nd, nz, na, nbv, T;
+  const double *Aat, *Bat, *Cat, *Lt;           // transposes: Aaug' (na x na), Baug' (nu x na), Caug' (na x ny), L' (ny x na)
+  const double *tbt, *Qbt, *Qyt, *q0, *Cdt, *Ebt; // tb' ((ny + nd) x nbv), Qb' (nbv x nu), Qy' (ny x nu), Cd' (nd x ny), Eb' (nbv x nz)
+};
+__global__ __launch_bounds__(CL_THREADS) void cl_filter_k(FilterArgs a, int t, const int* __restrict__ scen,
+                                                           const double* __restrict__ sp, double* __restrict__ xhat,
+                                                           const double* __restrict__ uprev, const double* __restrict__ y,
+                                                           double* __restrict__ b, double* __restrict__ q, double* __restrict__ e) {
+  extern __shared__ double sm[];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int na = a.na, nu = a.nu, ny = a.ny, nd = a.nd, nx = a.nx, nbv = a.nbv;
+  double* z = sm;                    // [na]  xhat
+  double* up = z + na;               // [nu]
+  double* xp = up + nu;              // [na]
+  double* r = xp + na;               // [ny]  innovation, then ysp - Cd dhat
+  double* bin = r + ny;              // [ny + nd]  [ysp; dhat]
+  double* bv = bin + ny + nd;        // [nbv]
+  const double* ysp = sp + ((size_t)scen[i] * a.T + t) * ny;
+  for (int k = tid; k < na; k += CL_THREADS) z[k] = xhat[(size_t)i * na + k];
+  for (int k = tid; k < nu; k += CL_THREADS) up[k] = uprev[(size_t)i * nu + k];
+  __syncthreads();
+  for (int k = tid; k < na; k += CL_THREADS) xp[k] = colsum(a.Aat, na, na, z, k) + colsum(a.Bat, nu, na, up, k);
+  __syncthreads();
+  for (int j = tid; j < ny; j += CL_THREADS) r[j] = y[(size_t)i * ny + j] - colsum(a.Cat, na, ny, xp, j);
+  __syncthreads();
+  for (int k = tid; k < na; k += CL_THREADS) {
+    const double v = xp[k] + colsum(a.Lt, ny, na, r, k);
+    xhat[(size_t)i * na + k] = v;
+    if (k >= nx) bin[ny + k - nx] = v;
+  }
+  for (int j = tid; j < ny; j += CL_THREADS) bin[j] = ysp[j];
+  __syncthreads();
+  for (int m = tid; m < nbv; m += CL_THREADS) {
+    const double v = colsum(a.tbt, ny + nd, nbv, bin, m);
+    bv[m] = v;
+    b[(size_t)i * nbv + m] = v;
+  }
+  for (int j = tid; j < ny; j += CL_THREADS) r[j] = bin[j] - colsum(a.Cdt, nd, ny, bin + ny, j);
+  __syncthreads();
+  for (int k = tid; k < nu; k += CL_THREADS) q[(size_t)i * nu + k] = (colsum(a.Qbt, nbv, nu, bv, k) + colsum(a.Qyt, ny, nu, r, k)) + a.q0[k];
+  for (int k = tid; k < a.nz; k += CL_THREADS) e[(size_t)i * a.nz + k] = colsum(a.Ebt, nbv, a.nz, bv, k);
+}
+
+// ---- step part 2: xs = Xb b + Xu us and each kind's controller input
+struct ExpandArgs {
+  int nx, nu, na, nbv, ldA;
+  const double *Xbt, *Xut, *ulb, *uub;          // Xb' (nbv x nx), Xu' (nu x nx)
+};
+__global__ __launch_bounds__(CL_THREADS) void cl_expand_k(ExpandArgs a, const int* __restrict__ inst_slot, const SlotDev* __restrict__ slots,
+                                                           const int* __restrict__ nn_row, const double* __restrict__ b,
+                                                           const double* __restrict__ us, const double* __restrict__ xhat,
+                                                           const double* __restrict__ uprev, double* __restrict__ xs,
+                                                           double* __restrict__ qx0, double* __restrict__ lb, double* __restrict__ ub,
+                                                           double* __restrict__ ctl_u, float* __restrict__ act) {
+  extern __shared__ double sm[];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int nx = a.nx, nu = a.nu, nbv = a.nbv;
+  double* bv = sm;                   // [nbv]
+  double* su = bv + nbv;             // [nu]  us
+  double* zz = su + nu;              // [nx + nu]  [xhat - xs; uprev - us]
+  double* xsv = zz + nx + nu;        // [nx]
+  for (int m = tid; m < nbv; m += CL_THREADS) bv[m] = b[(size_t)i * nbv + m];
+  for (int k = tid; k < nu; k += CL_THREADS) su[k] = us[(size_t)i * nu + k];
+  __syncthreads();
+  for (int k = tid; k < nx; k += CL_THREADS) {
+    const double v = colsum(a.Xbt, nbv, nx, bv, k) + colsum(a.Xut, nu, nx, su, k);
+    xsv[k] = v;
+    xs[(size_t)i * nx + k] = v;
+    zz[k] = xhat[(size_t)i * a.na + k] - v;
+  }
+  for (int k = tid; k < nu; k += CL_THREADS) zz[nx + k] = uprev[(size_t)i * nu + k] - su[k];
+  __syncthreads();
+  const SlotDev& s = slots[inst_slot[i]];
+  if (s.kind == NNMPC_CL_MPC) {                          // get_control_sequence (:682-689)
+    for (int k = tid; k < nx + nu; k += CL_THREADS) qx0[(size_t)i * (nx + nu) + k] = zz[k];
+    for (int k = tid; k < nu; k += CL_THREADS) {
+      lb[(size_t)i * nu + k] = a.ulb[k] - su[k];
+      ub[(size_t)i * nu + k] = a.uub[k] - su[k];
+    }
+  } else if (s.kind == NNMPC_CL_SATDLQR) {               // Kaug [x^ - xs; uprev - us] + us (:1003)
+    for (int k = tid; k < nu; k += CL_THREADS) ctl_u[(size_t)i * nu + k] = colsum(s.Kt, nx + nu, nu, zz, k) + su[k];
+  } else if (s.kind == NNMPC_CL_US) {
+    for (int k = tid; k < nu; k += CL_THREADS) ctl_u[(size_t)i * nu + k] = su[k];
+  } else {                                               // NN rows: pass 1 [x^, (uprev), xs^, us], pass 2 [xs^, (us), xs^, us]
+    const int wu = s.with_uprev, o2 = nx + (wu ? nu : 0);
+    float* d1 = act + (size_t)nn_row[i] * a.ldA;
+    float* d2 = act + (size_t)(nn_row[i] + s.count) * a.ldA;
+    for (int k = tid; k < nx; k += CL_THREADS) {
+      const double sc = s.xscale[k];
+      const float xv = (float)(xhat[(size_t)i * a.na + k] / sc), sv = (float)(xsv[k] / sc);
+      d1[k] = xv; d1[o2 + k] = sv;
+      d2[k] = sv; d2[o2 + k] = sv;
+    }
+    for (int k = tid; k < nu; k += CL_THREADS) {
+      const float uv = (float)su[k];
+      d1[o2 + nx + k] = uv; d2[o2 + nx + k] = uv;
+      if (wu) { d1[nx + k] = (float)uprev[(size_t)i * nu + k]; d2[nx + k] = uv; }
+    }
+  }
+}
+
+// ---- grouped structured-NN layer: one launch per layer index for ALL networks.  Workgroup = (network, 64 output columns);
+// the 4 waves take 4 contiguous K slices, every thread one column and NN_RB rows in registers, the activation rows in LDS.
+// A row's sum runs over k in a fixed order inside each slice and the slices are added in a fixed order: its value does not
+// depend on how many rows or networks share the launch.  Bias + ReLU fused; the output layer writes o (rows x nu) for cl_post_k.
+__global__ __launch_bounds__(256) void cl_nn_layer_k(const NNLayer* __restrict__ desc, const int2* __restrict__ tiles,
+                                                     const float* __restrict__ in, float* __restrict__ out, float* __restrict__ o,
+                                                     int ldA, int nu) {
+  extern __shared__ float sa[];                          // [NN_RB][K]
+  __shared__ float red[NN_KS - 1][NN_RB][64];
+  const int2 tl = tiles[blockIdx.x];
+  const NNLayer d = desc[tl.x];
+  const int lane = threadIdx.x & 63, ks = threadIdx.x >> 6;
+  const int col = tl.y + lane, K = d.K, N = d.N;
+  const int kc = (K + NN_KS - 1) / NN_KS, k0 = ks * kc, k1 = min(K, k0 + kc);
+  for (int r0 = 0; r0 < d.rows; r0 += NN_RB) {
+    const int nr = min(NN_RB, d.rows - r0);
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < NN_RB * K; idx += 256) {
+      const int r = idx / K, k = idx - r * K;
+      sa[idx] = r < nr ? in[(size_t)(d.row0 + r0 + r) * ldA + k] : 0.f;
+    }
+    __syncthreads();
+    float acc[NN_RB];
+#pragma unroll
+    for (int r = 0; r < NN_RB; ++r) acc[r] = 0.f;
+    if (col < N) {
+      const float* w = d.W + col;
+#pragma unroll 8
+      for (int k = k0; k < k1; ++k) {
+        const float wv = w[(size_t)k * N];
+#pragma unroll
+        for (int r = 0; r < NN_RB; ++r) acc[r] = fmaf(sa[r * K + k], wv, acc[r]);
+      }
+    }
+    if (ks > 0) {
+#pragma unroll
+      for (int r = 0; r < NN_RB; ++r) red[ks - 1][r][lane] = acc[r];
+    }
+    __syncthreads();
+    if (ks == 0 && col < N) {
+      const float bb = d.bias ? d.bias[col] : 0.f;
+      for (int r = 0; r < nr; ++r) {
+        float v = ((acc[r] + red[0][r][lane]) + red[1][r][lane]) + red[2][r][lane];
+        const size_t row = (size_t)(d.row0 + r0 + r);
+        if (d.last) o[row * nu + col] = v;
+        else out[row * ldA + col] = fmaxf(v + bb, 0.f);
+      }
+    }
+  }
+}
+
+// ---- step part 3: the move, the stage cost and its running mean (:691-701), the plant step (:88-93), records, MPC warm start
+struct PostArgs {
+  int nx, nu, ny, nd, na, T;
+  const double *At, *Bt, *Bpt, *Ct;             // A' (nx x nx), B' (nu x nx), Bp' (nd x nx), C' (nx x ny)
+  const double *Qaug, *Raug, *Maug, *ulb, *uub, *sigma;
+};
+struct PostRec {
+  double *y, *x, *xhat, *u, *xs, *us, *avg;     // this step's rows (u/xs/us: row t, the others row t + 1), may be null
+  int *tst, *rst;
+};
+__global__ __launch_bounds__(CL_THREADS) void cl_post_k(PostArgs a, int t, int tglob, const int* __restrict__ inst_slot,
+                                                         const SlotDev* __restrict__ slots, const int* __restrict__ nn_row,
+                                                         const int* __restrict__ scen, const double* __restrict__ dist,
+                                                         const double* __restrict__ vnext, const float* __restrict__ o,
+                                                         const double* __restrict__ ctl_u, const double* __restrict__ us,
+                                                         const double* __restrict__ xs, const int* __restrict__ tstat,
+                                                         double* __restrict__ x, const double* __restrict__ xhat,
+                                                         double* __restrict__ uprev, double* __restrict__ y, double* __restrict__ avg,
+                                                         PostRec rec) {
+  extern __shared__ double sm[];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int nx = a.nx, nu = a.nu, ny = a.ny, nd = a.nd, nz = nx + nu;
+  double* z = sm;                    // [nx + nu]
+  double* w = z + nz;                // [nu]  u - us
+  double* pz = w + nu;               // [nx + nu + nd]  [x; u; p]
+  double* xn = pz + nx + nu + nd;    // [nx]
+  double* red = xn + nx;             // [CL_THREADS]
+  const SlotDev& s = slots[inst_slot[i]];
+  const int li = i - s.base;
+  for (int k = tid; k < nx; k += CL_THREADS) {
+    z[k] = xhat[(size_t)i * a.na + k] - xs[(size_t)i * nx + k];
+    pz[k] = x[(size_t)i * nx + k];
+  }
+  for (int k = tid; k < nu; k += CL_THREADS) {
+    const double sk = us[(size_t)i * nu + k];
+    z[nx + k] = uprev[(size_t)i * nu + k] - sk;
+    double u;
+    if (s.kind == NNMPC_CL_MPC) u = s.first[(size_t)li * nu + k] + sk;
+    else if (s.kind == NNMPC_CL_NN) {
+      const int r1 = nn_row[i], r2 = r1 + s.count;
+      u = sk + ((double)o[(size_t)r1 * nu + k] - (double)o[(size_t)r2 * nu + k]);
+    } else u = ctl_u[(size_t)i * nu + k];
+    if (s.kind == NNMPC_CL_NN || s.kind == NNMPC_CL_SATDLQR) {   // _clip_control_input
+      u = u > a.uub[k] ? a.uub[k] : u;
+      u = u < a.ulb[k] ? a.ulb[k] : u;
+    }
+    w[k] = u - sk;
+    pz[nx + k] = u;
+    if (rec.u) rec.u[(size_t)i * nu + k] = u;
+    if (rec.us) rec.us[(size_t)i * nu + k] = sk;
+  }
+  const int sc = scen[i];
+  for (int k = tid; k < nd; k += CL_THREADS) pz[nx + nu + k] = dist[((size_t)sc * a.T + t) * nd + k];
+  __syncthreads();
+  // ell = z'Qaug z + w'Raug w + z'Maug w + w'Maug'z
+  double part = 0.0;
+  for (int k = tid; k < nz; k += CL_THREADS) {
+    double qz = 0.0, mw = 0.0;
+    for (int j = 0; j < nz; ++j) qz += a.Qaug[(size_t)j * nz + k] * z[j];
+    for (int j = 0; j < nu; ++j) mw += a.Maug[(size_t)k * nu + j] * w[j];
+    part += z[k] * qz + z[k] * mw;
+  }
+  for (int k = tid; k < nu; k += CL_THREADS) {
+    double rw = 0.0, mz = 0.0;
+    for (int j = 0; j < nu; ++j) rw += a.Raug[(size_t)j * nu + k] * w[j];
+    for (int j = 0; j < nz; ++j) mz += a.Maug[(size_t)j * nu + k] * z[j];
+    part += w[k] * rw + w[k] * mz;
+  }
+  const double ell = block_sum(part, red);
+  // plant: x+ = (A x + B u) + Bp p
+  for (int k = tid; k < nx; k += CL_THREADS) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int j = 0; j < nx; ++j) a0 += a.At[(size_t)j * nx + k] * pz[j];
+    for (int j = 0; j < nu; ++j) a1 += a.Bt[(size_t)j * nx + k] * pz[nx + j];
+    for (int j = 0; j < nd; ++j) a2 += a.Bpt[(size_t)j * nx + k] * pz[nx + nu + j];
+    const double v = (a0 + a1) + a2;
+    xn[k] = v;
+    x[(size_t)i * nx + k] = v;
+    if (rec.x) rec.x[(size_t)i * nx + k] = v;
+  }
+  for (int k = tid; k < nu; k += CL_THREADS) uprev[(size_t)i * nu + k] = pz[nx + k];
+  __syncthreads();
+  for (int j = tid; j < ny; j += CL_THREADS) {
+    const double v = colsum(a.Ct, nx, ny, xn, j) + a.sigma[j] * vnext[(size_t)i * ny + j];
+    y[(size_t)i * ny + j] = v;
+    if (rec.y) rec.y[(size_t)i * ny + j] = v;
+  }
+  if (rec.xs) for (int k = tid; k < nx; k += CL_THREADS) rec.xs[(size_t)i * nx + k] = xs[(size_t)i * nx + k];
+  if (rec.xhat) for (int k = tid; k < a.na; k += CL_THREADS) rec.xhat[(size_t)i * a.na + k] = xhat[(size_t)i * a.na + k];
+  if (tid == 0) {
+    const double m = (avg[i] * (double)tglob + ell) / (double)(tglob + 1);
+    avg[i] = m;
+    if (rec.avg) rec.avg[i] = m;
+    if (rec.tst) rec.tst[i] = tstat[i];
+    if (rec.rst) rec.rst[i] = s.kind == NNMPC_CL_MPC ? s.status[li] : 0;
+  }
+  if (s.kind == NNMPC_CL_MPC) {                          // next warm start: this step's set shifted by one stage (chain_post_k)
+    const uint32_t* aw = s.act + (size_t)li * s.words;
+    for (int r = tid; r < s.n; r += CL_THREADS) {
+      const int rs = r + nu < s.n ? r + nu : r;
+      const int k = rs / nu, j = rs - k * nu;
+      const int bu = k * 2 * nu + j, bl = bu + nu;
+      const int su_ = (aw[bu >> 5] >> (bu & 31)) & 1u, sl = (aw[bl >> 5] >> (bl & 31)) & 1u;
+      s.guess[(size_t)li * s.n + r] = (unsigned char)(su_ ? 1 : (sl ? 2 : 0));
+    }
+  }
+}
+
+std::vector<double> transpose(const double* M, int rows, int cols) {
+  std::vector<double> t((size_t)rows * cols);
+  for (int i = 0; i < rows; ++i)
+    for (int j = 0; j < cols; ++j) t[(size_t)j * rows + i] = M[(size_t)i * cols + j];
+  return t;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------
+struct nnmpc_cl {
+  int device = 0, nx = 0, nu = 0, ny = 0, nd = 0, nz = 0, na = 0, nbv = 0, nb = 0, nslots = 0;
+  nnmpc_ts* ts = nullptr;
+  std::vector<int> kind, base, count;               // per slot (host)
+  std::vector<nnmpc_qp*> qp;
+  std::vector<bool> have_guess;
+  std::vector<SlotDev> sd;                          // host copy of the slot table
+  SlotDev* slots_d = nullptr;
+  int* inst_slot = nullptr;
+  int* nn_row = nullptr;
+  // shared matrices (device)
+  double *At, *Bt, *Bpt, *Ct, *Aat, *Bat, *Cat, *Lt, *tbt, *Qbt, *Qyt, *q0, *Cdt, *Ebt, *Xbt, *Xut, *Qaug, *Raug, *Maug;
+  double *ulb, *uub, *x0, *xhat0, *uprev0;
+  // instance state and step workspace
+  double *x, *xhat, *uprev, *y, *avg, *b, *q, *e, *us, *xs, *qx0, *lb, *ub, *first, *ctl_u;
+  int *tstat, *rstat;
+  // grouped NN
+  int nn_rows = 0, ldA = 0, nn_layers = 0;
+  float *act[2] = {nullptr, nullptr}, *o = nullptr;
+  NNLayer* desc_d = nullptr;
+  int2* tiles_d = nullptr;
+  std::vector<int> tile_off, tile_cnt;              // per layer index
+  int maxK = 0;
+  bool fresh = true;
+  int64_t tglob = 0;
+  hipStream_t stream = nullptr;
+  std::vector<hipEvent_t> ev;
+  double total_ms = 0.0, phase_ms[6] = {0, 0, 0, 0, 0, 0};
+  std::vector<double> slot_ms;                      // [T][nslots] of the last run
+  int last_T = 0;
+  std::vector<void*> allocs;
+  void* stage[16] = {};
+  size_t stage_cap[16] = {};
+};
+
+namespace {
+template <class T>
+int cl_alloc(nnmpc_cl* h, T** p, size_t count) {
+  void* q = nullptr;
+  const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
+  if (e != hipSuccess) { set_error("hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e)); return NNMPC_ENOMEM; }
+  hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(T));
+  h->allocs.push_back(q);
+  *p = (T*)q;
+  return 0;
+}
+template <class T>
+int cl_upload(nnmpc_cl* h, T** p, const T* src, size_t count) {
+  int rc = cl_alloc(h, p, count);
+  if (!rc && count && hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("nnmpc_cl_create: upload failed"); rc = NNMPC_EHIP;
+  }
+  return rc;
+}
+template <class T>
+int cl_stage(nnmpc_cl* h, int which, T** out, size_t bytes) {
+  if (h->stage_cap[which] < bytes) {
+    if (h->stage[which]) { hipFree(h->stage[which]); h->stage[which] = nullptr; h->stage_cap[which] = 0; }
+    const hipError_t e = hipMalloc(&h->stage[which], bytes + 256);
+    if (e != hipSuccess) { h->stage[which] = nullptr; set_error("hipMalloc(%zu bytes of staging): %s", bytes, hipGetErrorString(e)); return NNMPC_ENOMEM; }
+    h->stage_cap[which] = bytes + 256;
+  }
+  *out = (T*)h->stage[which];
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32_t nslots, const nnmpc_cl_slot* slots,
+                    int32_t nb, const int32_t* inst_slot) {
+  if (!out || !m || !ts || nslots <= 0 || !slots || nb <= 0 || !inst_slot) {
+    set_error("nnmpc_cl_create: bad arguments (nslots=%d nb=%d)", nslots, nb);
+    return NNMPC_EINVAL;
+  }
+  const int nx = m->nx, nu = m->nu, ny = m->ny, nd = m->nd, nz = m->nz;
+  if (nx <= 0 || nu <= 0 || ny <= 0 || nd < 0 || nz < 0) { set_error("nnmpc_cl_create: bad sizes nx=%d nu=%d ny=%d nd=%d nz=%d", nx, nu, ny, nd, nz); return NNMPC_EINVAL; }
+  const double* need[] = {m->A, m->B, m->C, m->Aaug, m->Baug, m->Caug, m->L, m->tb, m->Qb, m->Qy, m->q0, m->Xb, m->Xu,
+                          m->Qaug, m->Raug, m->Maug, m->ulb, m->uub, m->x0, m->xhat0, m->uprev0};
+  for (const double* p : need) if (!p) { set_error("nnmpc_cl_create: a model matrix is NULL"); return NNMPC_EINVAL; }
+  if ((nd && (!m->Bp || !m->Cd)) || (nz && !m->Eb)) { set_error("nnmpc_cl_create: Bp / Cd (nd > 0) or Eb (nz > 0) is NULL"); return NNMPC_EINVAL; }
+  int tnu = 0, tnz = 0;
+  if (nnmpc_ts_dims_internal(ts, &tnu, &tnz) || tnu != nu || tnz != nz) {
+    set_error("nnmpc_cl_create: target handle has nu=%d nz=%d, the model nu=%d nz=%d", tnu, tnz, nu, nz);
+    return NNMPC_EINVAL;
+  }
+  for (int i = 0; i < nb; ++i)
+    if (inst_slot[i] < 0 || inst_slot[i] >= nslots || (i && inst_slot[i] < inst_slot[i - 1])) {
+      set_error("nnmpc_cl_create: inst_slot[%d] = %d (slots 0..%d, non-decreasing)", i, inst_slot[i], nslots - 1);
+      return NNMPC_EINVAL;
+    }
+  for (int k = 0; k < nslots; ++k) {
+    const nnmpc_cl_slot& s = slots[k];
+    if (s.kind == NNMPC_CL_MPC) {
+      int n = 0, qnu = 0, qna = 0;
+      if (!s.qp || nnmpc_qp_dims(s.qp, &n, &qnu, &qna) || qnu != nu || qna != nx + nu) {
+        set_error("nnmpc_cl_create: slot %d (MPC) needs a regulator handle with nu=%d n_aug=%d", k, nu, nx + nu);
+        return NNMPC_EINVAL;
+      }
+    } else if (s.kind == NNMPC_CL_NN) {
+      const int din = 2 * nx + (s.with_uprev ? 2 : 1) * nu;
+      if (s.nlayers < 1 || !s.dims || !s.W || !s.b || s.dims[0] != din || s.dims[s.nlayers] != nu) {
+        set_error("nnmpc_cl_create: slot %d (NN) needs dims [%d, ..., %d] with weights and biases", k, din, nu);
+        return NNMPC_EINVAL;
+      }
+      for (int l = 0; l < s.nlayers; ++l)
+        if (s.dims[l] <= 0 || s.dims[l] > NN_MAXK || s.dims[l + 1] <= 0 || !s.W[l] || (l < s.nlayers - 1 && !s.b[l])) {
+          set_error("nnmpc_cl_create: slot %d (NN) layer %d: widths 1..%d, weights and (hidden) biases required", k, l, NN_MAXK);
+          return NNMPC_EINVAL;
+        }
+    } else if (s.kind == NNMPC_CL_SATDLQR) {
+      if (!s.Kaug) { set_error("nnmpc_cl_create: slot %d (SATDLQR) has no Kaug", k); return NNMPC_EINVAL; }
+    } else if (s.kind != NNMPC_CL_US) {
+      set_error("nnmpc_cl_create: slot %d has unknown kind %d", k, s.kind);
+      return NNMPC_EINVAL;
+    }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("nnmpc_cl_create: no HIP device available (no CPU fallback)"); return NNMPC_EHIP; }
+  nnmpc_cl* h = new nnmpc_cl();
+  h->nx = nx; h->nu = nu; h->ny = ny; h->nd = nd; h->nz = nz; h->na = nx + nd; h->nbv = nx + nz; h->nb = nb; h->nslots = nslots;
+  h->ts = ts;
+  if (hipGetDevice(&h->device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
+    set_error("nnmpc_cl_create: no HIP device / stream"); nnmpc_cl_destroy(h); return NNMPC_EHIP;
+  }
+  const int na = h->na, nbv = h->nbv, nzz = nx + nu;
+  int rc = 0;
+  std::vector<double> zero1(1, 0.0);
+  auto up = [&](double** p, const std::vector<double>& v) { if (!rc) rc = cl_upload(h, p, v.data(), v.size()); };
+  auto upT = [&](double** p, const double* M, int r, int c) { if (!rc) rc = (M && r * c) ? cl_upload(h, p, transpose(M, r, c).data(), (size_t)r * c) : cl_alloc(h, p, 1); };
+  auto upD = [&](double** p, const double* M, size_t cnt) { if (!rc) rc = (M && cnt) ? cl_upload(h, p, M, cnt) : cl_alloc(h, p, 1); };
+  upT(&h->At, m->A, nx, nx); upT(&h->Bt, m->B, nx, nu); upT(&h->Bpt, m->Bp, nx, nd); upT(&h->Ct, m->C, ny, nx);
+  upT(&h->Aat, m->Aaug, na, na); upT(&h->Bat, m->Baug, na, nu); upT(&h->Cat, m->Caug, ny, na); upT(&h->Lt, m->L, na, ny);
+  upT(&h->tbt, m->tb, nbv, ny + nd); upT(&h->Qbt, m->Qb, nu, nbv); upT(&h->Qyt, m->Qy, nu, ny); upD(&h->q0, m->q0, nu);
+  upT(&h->Cdt, m->Cd, ny, nd); upT(&h->Ebt, m->Eb, nz, nbv); upT(&h->Xbt, m->Xb, nx, nbv); upT(&h->Xut, m->Xu, nx, nu);
+  upD(&h->Qaug, m->Qaug, (size_t)nzz * nzz); upD(&h->Raug, m->Raug, (size_t)nu * nu); upD(&h->Maug, m->Maug, (size_t)nzz * nu);
+  upD(&h->ulb, m->ulb, nu); upD(&h->uub, m->uub, nu); upD(&h->x0, m->x0, nx); upD(&h->xhat0, m->xhat0, na); upD(&h->uprev0, m->uprev0, nu);
+#define A_(ptr, cnt) if (!rc) rc = cl_alloc(h, &(ptr), (size_t)(cnt))
+  A_(h->x, (size_t)nb * nx); A_(h->xhat, (size_t)nb * na); A_(h->uprev, (size_t)nb * nu); A_(h->y, (size_t)nb * ny); A_(h->avg, nb);
+  A_(h->b, (size_t)nb * nbv); A_(h->q, (size_t)nb * nu); A_(h->e, (size_t)nb * std::max(nz, 1)); A_(h->us, (size_t)nb * nu);
+  A_(h->xs, (size_t)nb * nx); A_(h->qx0, (size_t)nb * nzz); A_(h->lb, (size_t)nb * nu); A_(h->ub, (size_t)nb * nu);
+  A_(h->first, (size_t)nb * nu); A_(h->ctl_u, (size_t)nb * nu); A_(h->tstat, nb); A_(h->rstat, nb);
+  // slot table and instance ranges
+  h->kind.resize(nslots); h->base.assign(nslots, 0); h->count.assign(nslots, 0); h->qp.assign(nslots, nullptr);
+  h->have_guess.assign(nslots, false); h->sd.resize(nslots);
+  for (int i = 0; i < nb; ++i) h->count[inst_slot[i]]++;
+  for (int k = 1; k < nslots; ++k) h->base[k] = h->base[k - 1] + h->count[k - 1];
+  std::vector<int> nn_row(nb, 0);
+  std::vector<std::vector<NNLayer>> layers(nslots);
+  for (int k = 0; k < nslots && !rc; ++k) {
+    const nnmpc_cl_slot& s = slots[k];
+    SlotDev& d = h->sd[k];
+    memset(&d, 0, sizeof(d));
+    d.kind = s.kind; d.base = h->base[k]; d.count = h->count[k];
+    h->kind[k] = s.kind;
+    if (s.kind == NNMPC_CL_MPC) {
+      int n = 0, qnu = 0, qna = 0;
+      nnmpc_qp_dims(s.qp, &n, &qnu, &qna);
+      h->qp[k] = s.qp;
+      d.n = n; d.words = (2 * n + 31) / 32;
+      d.first = h->first + (size_t)d.base * nu;
+      d.status = h->rstat + d.base;
+      uint32_t* act = nullptr; unsigned char* g = nullptr;
+      A_(act, (size_t)std::max(d.count, 1) * d.words);
+      A_(g, (size_t)std::max(d.count, 1) * n);
+      d.act = act; d.guess = g;
+    } else if (s.kind == NNMPC_CL_SATDLQR) {
+      double* kt = nullptr;
+      upT(&kt, s.Kaug, nu, nzz);
+      d.Kt = kt;
+    } else if (s.kind == NNMPC_CL_NN) {
+      d.with_uprev = s.with_uprev ? 1 : 0;
+      d.row0 = h->nn_rows;
+      std::vector<double> xsc(nx, 1.0);
+      if (s.xscale) for (int j = 0; j < nx; ++j) xsc[j] = s.xscale[j];
+      double* xd = nullptr;
+      up(&xd, xsc);
+      d.xscale = xd;
+      for (int j = 0; j < d.count; ++j) nn_row[d.base + j] = h->nn_rows + j;
+      for (int l = 0; l < s.nlayers && !rc; ++l) {
+        const int K = s.dims[l], N = s.dims[l + 1];
+        std::vector<float> wf((size_t)K * N), bf(N, 0.f);
+        for (size_t j = 0; j < wf.size(); ++j) wf[j] = (float)s.W[l][j];
+        const bool last = l == s.nlayers - 1;
+        if (!last) for (int j = 0; j < N; ++j) bf[j] = (float)s.b[l][j];
+        float *wd = nullptr, *bd = nullptr;
+        if (!rc) rc = cl_upload(h, &wd, wf.data(), wf.size());
+        if (!rc && !last) rc = cl_upload(h, &bd, bf.data(), bf.size());
+        layers[k].push_back(NNLayer{wd, bd, K, N, h->nn_rows, 2 * d.count, last ? 1 : 0});
+        h->maxK = std::max(h->maxK, K);
+        if (!last) h->ldA = std::max(h->ldA, N);
+      }
+      h->ldA = std::max(h->ldA, s.dims[0]);
+      h->nn_layers = std::max(h->nn_layers, s.nlayers);
+      h->nn_rows += 2 * d.count;
+    }
+  }
+  if (!rc) rc = cl_upload(h, &h->slots_d, h->sd.data(), h->sd.size());
+  if (!rc) rc = cl_upload(h, &h->inst_slot, (const int*)inst_slot, (size_t)nb);
+  if (!rc) rc = cl_upload(h, &h->nn_row, nn_row.data(), nn_row.size());
+  if (!rc && h->nn_rows) {
+    // layer-major descriptor table and the (network, column tile) list of every layer index
+    std::vector<NNLayer> desc;
+    std::vector<int2> tiles;
+    for (int l = 0; l < h->nn_layers; ++l) {
+      h->tile_off.push_back((int)tiles.size());
+      for (int k = 0; k < nslots; ++k) {
+        if ((int)layers[k].size() <= l || h->count[k] == 0) continue;
+        const NNLayer& L = layers[k][l];
+        const int di = (int)desc.size();
+        desc.push_back(L);
+        for (int c0 = 0; c0 < L.N; c0 += 64) tiles.push_back(make_int2(di, c0));
+      }
+      h->tile_cnt.push_back((int)tiles.size() - h->tile_off.back());
+    }
+    if (!rc) rc = cl_upload(h, &h->desc_d, desc.data(), desc.size());
+    if (!rc) rc = cl_upload(h, &h->tiles_d, tiles.data(), tiles.size());
+    A_(h->act[0], (size_t)h->nn_rows * h->ldA); A_(h->act[1], (size_t)h->nn_rows * h->ldA); A_(h->o, (size_t)h->nn_rows * nu);
+    if (!rc && hipFuncSetAttribute((const void*)cl_nn_layer_k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   NN_RB * NN_MAXK * (int)sizeof(float)) != hipSuccess) {
+      set_error("nnmpc_cl_create: hipFuncSetAttribute(cl_nn_layer_k) failed"); rc = NNMPC_EHIP;
+    }
+  }
+#undef A_
+  if (rc) { nnmpc_cl_destroy(h); return rc; }
+  rc = nnmpc_cl_reset(h);
+  if (rc) { nnmpc_cl_destroy(h); return rc; }
+  *out = h;
+  return NNMPC_OK;
+}
+
+int nnmpc_cl_destroy(nnmpc_cl* h) {
+  if (!h) return NNMPC_OK;
+  hipSetDevice(h->device);
+  if (h->stream) hipStreamSynchronize(h->stream);
+  for (void* p : h->allocs) hipFree(p);
+  for (void* p : h->stage) if (p) hipFree(p);
+  for (hipEvent_t e : h->ev) hipEventDestroy(e);
+  if (h->stream) hipStreamDestroy(h->stream);
+  delete h;
+  return NNMPC_OK;
+}
+
+int nnmpc_cl_reset(nnmpc_cl* h) {
+  if (!h) { set_error("nnmpc_cl_reset: null handle"); return NNMPC_EINVAL; }
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(cl_reset_k, dim3(h->nb), dim3(CL_THREADS), 0, h->stream, h->nx, h->na, h->nu, h->x0, h->xhat0, h->uprev0,
+                     h->x, h->xhat, h->uprev, h->avg);
+  HIPCHK(stream_sync(h->stream));
+  HIPCHK(hipGetLastError());
+  h->fresh = true;
+  h->tglob = 0;
+  h->have_guess.assign(h->nslots, false);
+  return NNMPC_OK;
+}
+
+int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints, const double* dist, const int32_t* scen,
+                 const double* v, const double* sigma, const double* y0, double* y_rec, double* x_rec, double* xhat_rec, double* u_rec,
+                 double* xs_rec, double* us_rec, double* avg_rec, int32_t* ts_status, int32_t* reg_status, int32_t ptr_kind) {
+  if (!h || T < 0 || nscen <= 0 || !setpoints || (h->nd && !dist) || !scen || !v || !sigma ||
+      (ptr_kind != NNMPC_HOST && ptr_kind != NNMPC_DEVICE)) {
+    set_error("nnmpc_cl_run: bad arguments");
+    return NNMPC_EINVAL;
+  }
+  if (T == 0) return NNMPC_OK;
+  HIPCHK(hipSetDevice(h->device));
+  const int nb = h->nb, nx = h->nx, nu = h->nu, ny = h->ny, nd = h->nd, na = h->na, nbv = h->nbv;
+  // scenario indices are checked on the host before anything is launched (device pointers: one copy of nb ints)
+  std::vector<int32_t> sc(nb);
+  if (ptr_kind == NNMPC_HOST) memcpy(sc.data(), scen, (size_t)nb * 4);
+  else HIPCHK(hipMemcpy(sc.data(), scen, (size_t)nb * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < nb; ++i)
+    if (sc[i] < 0 || sc[i] >= nscen) { set_error("nnmpc_cl_run: scen[%d] = %d outside 0..%d", i, sc[i], nscen - 1); return NNMPC_EINVAL; }
+  const size_t n_sp = (size_t)nscen * T * ny, n_d = (size_t)nscen * T * nd, n_v = (size_t)(T + 1) * nb * ny;
+  const double *sp_d = setpoints, *d_d = dist, *v_d = v, *sig_d = sigma, *y0_d = y0;
+  const int* sc_d = scen;
+  double* rd[7] = {y_rec, x_rec, xhat_rec, u_rec, xs_rec, us_rec, avg_rec};
+  int* rs[2] = {ts_status, reg_status};
+  const size_t rsz[7] = {(size_t)(T + 1) * nb * ny, (size_t)(T + 1) * nb * nx, (size_t)(T + 1) * nb * na, (size_t)T * nb * nu,
+                         (size_t)T * nb * nx, (size_t)T * nb * nu, (size_t)(T + 1) * nb};
+  double* rdd[7];
+  int* rsd[2];
+  for (int k = 0; k < 7; ++k) rdd[k] = rd[k];
+  for (int k = 0; k < 2; ++k) rsd[k] = rs[k];
+  if (ptr_kind == NNMPC_HOST) {
+    double *a = nullptr, *b = nullptr, *c = nullptr, *s = nullptr;
+    int* si = nullptr;
+    int rc = cl_stage(h, 0, &a, n_sp * 8);
+    if (!rc) rc = cl_stage(h, 1, &b, std::max<size_t>(n_d, 1) * 8);
+    if (!rc) rc = cl_stage(h, 2, &c, n_v * 8);
+    if (!rc) rc = cl_stage(h, 3, &s, (size_t)ny * 8);
+    if (!rc) rc = cl_stage(h, 4, &si, (size_t)nb * 4);
+    double* yy = nullptr;
+    if (!rc && y0) rc = cl_stage(h, 14, &yy, (size_t)nb * ny * 8);
+    for (int k = 0; k < 7 && !rc; ++k) if (rd[k]) rc = cl_stage(h, 5 + k, &rdd[k], rsz[k] * 8);
+    for (int k = 0; k < 2 && !rc; ++k) if (rs[k]) rc = cl_stage(h, 12 + k, &rsd[k], (size_t)T * nb * 4);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(a, setpoints, n_sp * 8, hipMemcpyHostToDevice));
+    if (n_d) HIPCHK(hipMemcpy(b, dist, n_d * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c, v, n_v * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s, sigma, (size_t)ny * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(si, scen, (size_t)nb * 4, hipMemcpyHostToDevice));
+    if (y0) HIPCHK(hipMemcpy(yy, y0, (size_t)nb * ny * 8, hipMemcpyHostToDevice));
+    sp_d = a; d_d = b; v_d = c; sig_d = s; sc_d = si; y0_d = yy;
+  }
+  std::vector<int> mpc;
+  for (int k = 0; k < h->nslots; ++k) if (h->kind[k] == NNMPC_CL_MPC && h->count[k]) mpc.push_back(k);
+  const int nm = (int)mpc.size(), ne = 7 + nm;          // events per step: start, filter, target, expand, nn, [mpc...], join, post
+  // phase events of at most CL_EV_BLOCK steps are alive at a time: after each block the stream is drained once and the block's
+  // times are added up, so the pool is bounded whatever T is
+  const int blk = std::min(T, CL_EV_BLOCK);
+  while (h->ev.size() < (size_t)blk * ne + 2) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev.push_back(e); }
+  hipEvent_t ev_t0 = h->ev[(size_t)blk * ne], ev_t1 = h->ev[(size_t)blk * ne + 1];
+  hipStream_t s = h->stream;
+  FilterArgs fa{nx, nu, ny, nd, h->nz, na, nbv, T, h->Aat, h->Bat, h->Cat, h->Lt, h->tbt, h->Qbt, h->Qyt, h->q0, h->Cdt, h->Ebt};
+  ExpandArgs xa{nx, nu, na, nbv, h->ldA, h->Xbt, h->Xut, h->ulb, h->uub};
+  PostArgs pa{nx, nu, ny, nd, na, T, h->At, h->Bt, h->Bpt, h->Ct, h->Qaug, h->Raug, h->Maug, h->ulb, h->uub, sig_d};
+  const size_t lds_f = (size_t)(2 * na + nu + 2 * ny + nd + nbv) * 8;
+  const size_t lds_x = (size_t)(nbv + 2 * nu + 2 * nx) * 8;
+  const size_t lds_p = (size_t)(2 * (nx + nu) + nu + nd + nx + CL_THREADS) * 8 + (size_t)nx * 8;
+  for (double& p : h->phase_ms) p = 0.0;
+  h->slot_ms.assign((size_t)T * h->nslots, 0.0);
+  auto el = [&](hipEvent_t a, hipEvent_t b) { float ms = 0.f; hipEventElapsedTime(&ms, a, b); return (double)ms; };
+  std::vector<double> ms(nm);
+  auto collect = [&](int t0, int t1) {                   // steps [t0, t1) of the current block, stream drained
+    for (int t = t0; t < t1; ++t) {
+      hipEvent_t* E = h->ev.data() + (size_t)(t - t0) * ne;
+      const double f = el(E[0], E[1]), tg = el(E[1], E[2]), xp = el(E[2], E[3]), nn = el(E[3], E[4]);
+      double mp = 0.0;
+      for (int j = 0; j < nm; ++j) { ms[j] = el(E[3], E[5 + j]); mp = std::max(mp, ms[j]); }
+      h->phase_ms[0] += f; h->phase_ms[1] += tg; h->phase_ms[2] += xp; h->phase_ms[3] += nn; h->phase_ms[4] += mp;
+      h->phase_ms[5] += el(E[5 + nm], E[6 + nm]);
+      for (int k = 0, j = 0; k < h->nslots; ++k) {
+        double v_ = xp;
+        if (h->kind[k] == NNMPC_CL_NN) v_ = nn;
+        else if (h->kind[k] == NNMPC_CL_MPC) v_ = h->count[k] ? ms[j++] : 0.0;
+        h->slot_ms[(size_t)t * h->nslots + k] = v_;
+      }
+    }
+  };
+  HIPCHK(hipEventRecord(ev_t0, s));
+  hipLaunchKernelGGL(cl_begin_k, dim3(nb), dim3(CL_THREADS), (size_t)nx * 8, s, h->fresh ? 1 : 0, nx, na, ny, h->Ct, sig_d, v_d, y0_d,
+                     h->x, h->xhat, h->avg, h->y, rdd[0], rdd[1], rdd[2], rdd[6]);
+  int tb = 0;                                            // first step of the current event block
+  for (int t = 0; t < T; ++t) {
+    if (t - tb == blk) {
+      HIPCHK(stream_sync(s));
+      collect(tb, t);
+      tb = t;
+    }
+    hipEvent_t* E = h->ev.data() + (size_t)(t - tb) * ne;
+    hipEventRecord(E[0], s);
+    hipLaunchKernelGGL(cl_filter_k, dim3(nb), dim3(CL_THREADS), lds_f, s, fa, t, sc_d, sp_d, h->xhat, h->uprev, h->y, h->b, h->q, h->e);
+    hipEventRecord(E[1], s);
+    int rc = nnmpc_ts_launch_internal(h->ts, nb, h->q, h->e, h->us, h->tstat, s);
+    if (rc) { hipStreamSynchronize(s); return rc; }
+    hipEventRecord(E[2], s);
+    hipLaunchKernelGGL(cl_expand_k, dim3(nb), dim3(CL_THREADS), lds_x, s, xa, h->inst_slot, h->slots_d, h->nn_row, h->b, h->us,
+                       h->xhat, h->uprev, h->xs, h->qx0, h->lb, h->ub, h->ctl_u, h->act[0]);
+    hipEventRecord(E[3], s);
+    for (int l = 0; l < h->nn_layers; ++l)
+      if (h->tile_cnt[l])
+        hipLaunchKernelGGL(cl_nn_layer_k, dim3(h->tile_cnt[l]), dim3(256), (size_t)NN_RB * h->maxK * 4, s, h->desc_d,
+                           h->tiles_d + h->tile_off[l], h->act[l & 1], h->act[(l + 1) & 1], h->o, h->ldA, nu);
+    hipEventRecord(E[4], s);
+    for (int j = 0; j < nm; ++j) {                       // the regulator QPs, beside the NN layers
+      const int k = mpc[j];
+      const SlotDev& d = h->sd[k];
+      hipStream_t qs = nnmpc_qp_stream_internal(h->qp[k]);
+      HIPCHK(hipStreamWaitEvent(qs, E[3], 0));
+      rc = nnmpc_qp_solve_batch_ex(h->qp[k], d.count, h->qx0 + (size_t)d.base * (nx + nu), h->lb + (size_t)d.base * nu,
+                                   h->ub + (size_t)d.base * nu, h->have_guess[k] ? d.guess : nullptr, h->first + (size_t)d.base * nu,
+                                   const_cast<uint32_t*>(d.act), h->rstat + d.base, nullptr, NNMPC_DEVICE, NNMPC_OUT_FIRST_MOVE);
+      if (rc) {
+        // half a step done: drain and drop the warm starts (the caller should nnmpc_cl_reset)
+        hipStreamSynchronize(s);
+        h->have_guess.assign(h->nslots, false);
+        return rc;
+      }
+      HIPCHK(hipEventRecord(E[5 + j], qs));
+      HIPCHK(hipStreamWaitEvent(s, E[5 + j], 0));
+    }
+    hipEventRecord(E[5 + nm], s);
+    PostRec pr{rdd[0] ? rdd[0] + (size_t)(t + 1) * nb * ny : nullptr, rdd[1] ? rdd[1] + (size_t)(t + 1) * nb * nx : nullptr,
+               rdd[2] ? rdd[2] + (size_t)(t + 1) * nb * na : nullptr, rdd[3] ? rdd[3] + (size_t)t * nb * nu : nullptr,
+               rdd[4] ? rdd[4] + (size_t)t * nb * nx : nullptr, rdd[5] ? rdd[5] + (size_t)t * nb * nu : nullptr,
+               rdd[6] ? rdd[6] + (size_t)(t + 1) * nb : nullptr, rsd[0] ? rsd[0] + (size_t)t * nb : nullptr,
+               rsd[1] ? rsd[1] + (size_t)t * nb : nullptr};
+    hipLaunchKernelGGL(cl_post_k, dim3(nb), dim3(CL_THREADS), lds_p, s, pa, t, (int)h->tglob, h->inst_slot, h->slots_d, h->nn_row, sc_d,
+                       d_d, v_d + (size_t)(t + 1) * nb * ny, h->o, h->ctl_u, h->us, h->xs, h->tstat, h->x, h->xhat, h->uprev, h->y,
+                       h->avg, pr);
+    hipEventRecord(E[6 + nm], s);
+    for (int k : mpc) h->have_guess[k] = true;
+    h->fresh = false;
+    ++h->tglob;
+  }
+  HIPCHK(hipEventRecord(ev_t1, s));
+  HIPCHK(stream_sync(s));
+  HIPCHK(hipGetLastError());
+  collect(tb, T);
+  h->total_ms = el(ev_t0, ev_t1);
+  h->last_T = T;
+  if (ptr_kind == NNMPC_HOST) {
+    for (int k = 0; k < 7; ++k) if (rd[k]) HIPCHK(hipMemcpy(rd[k], rdd[k], rsz[k] * 8, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; ++k) if (rs[k]) HIPCHK(hipMemcpy(rs[k], rsd[k], (size_t)T * nb * 4, hipMemcpyDeviceToHost));
+  }
+  return NNMPC_OK;
+}
+
+int nnmpc_cl_last_ms(nnmpc_cl* h, double* total_ms, double* phase_ms, double* slot_step_ms) {
+  if (!h) { set_error("nnmpc_cl_last_ms: null handle"); return NNMPC_EINVAL; }
+  if (total_ms) *total_ms = h->total_ms;
+  if (phase_ms) for (int k = 0; k < 6; ++k) phase_ms[k] = h->phase_ms[k];
+  if (slot_step_ms && !h->slot_ms.empty()) memcpy(slot_step_ms, h->slot_ms.data(), h->slot_ms.size() * 8);
+  return NNMPC_OK;
+}
+
+}  // extern "C"

@@ -27,3 +27,8 @@ inline hipError_t stream_sync(hipStream_t s) {
 // lock-step step on it, so that a step needs no host wait between them and the solve
 struct nnmpc_qp;
 hipStream_t nnmpc_qp_stream_internal(nnmpc_qp* h);
+// (library-internal) the batched target kernel of a nnmpc_ts handle, launched on the caller's stream with device pointers and
+// no host wait: nnmpc_cl_run solves every instance's target problem of a step this way (lam_eq and the bound states are not kept)
+struct nnmpc_ts;
+int nnmpc_ts_dims_internal(nnmpc_ts* h, int* nu, int* nz);
+int nnmpc_ts_launch_internal(nnmpc_ts* h, int B, const double* q, const double* e, double* us, int* status, hipStream_t s);
