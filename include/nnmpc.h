@@ -347,6 +347,31 @@ int nnmpc_cl_reset(nnmpc_cl* h);
  * NN: the grouped forward, SATDLQR / US: the expansion kernel).  The phase events of at most 256 steps are alive at a time: a
  * longer run drains its stream once per 256 steps to add them up, so the handle holds (7 + MPC slots) x 256 + 2 events at most. */
 int nnmpc_cl_last_ms(nnmpc_cl* h, double* total_ms, double* phase_ms, double* slot_step_ms);
+/* ---- Nonlinear plant of the closed loop: the CSTRs-with-flash plant of the reference's study (cstrs_parameters.py,
+ * NonlinearPlantSimulator, lib/nonlinearMPC.py:11-48).  Its 12-state ODE is integrated over each sample by classical RK4 with
+ * `substeps` fixed steps in fp64 (the host's nonlinearMPC.DiscreteSimulator: same tableau, same substeps), in deviation
+ * variables: states x (12) about xs, inputs u (6) scaled, U = u o uscale + us, disturbances p (5), P = p o pscale + ps.
+ * Parameter block (NNMPC_CSTRS_NPAR doubles, in this order):
+ *   [0..16]  alphaA alphaB alphaC pho Cp Ar Am Ab kr km kb delH1 delH2 EbyR k1star k2star Td   (cstrs_parameters.CONSTANTS)
+ *   [17..28] xs (the rectified steady state), [29..34] us, [35..39] ps, [40..45] uscale, [46..50] pscale
+ * All finite; pho, Cp, Ar, Am, Ab > 0; sample_time > 0; 1 <= substeps <= 4096 (NNMPC_EINVAL otherwise).  A level that goes
+ * non-positive makes that instance's state NaN from then on (no clamping, no data-dependent loop count). */
+#define NNMPC_CL_PLANT_LINEAR 0
+#define NNMPC_CL_PLANT_CSTRS_FLASH 1
+#define NNMPC_CSTRS_NPAR 51
+/* Plant of a closed-loop handle: NNMPC_CL_PLANT_LINEAR (the default; par may be NULL) or NNMPC_CL_PLANT_CSTRS_FLASH (the
+ * handle must have nx = 12, nu = 6, nd = 5).  With the nonlinear plant a step's plant part is x = Phi(x, u_t, p_t) and
+ * y_{t+1} = C x + sigma o v_{t+1} with the model's C (diag(1 / yscale)); the model's A, B, Bp (the linearisation) are not
+ * used for the plant.  Phase "post" of nnmpc_cl_last_ms is then clip + cost + records without the integration, which
+ * nnmpc_cl_last_plant_ms reports.  Takes effect at the next nnmpc_cl_run. */
+int nnmpc_cl_set_plant(nnmpc_cl* h, int32_t kind, const double* par, int32_t npar, double sample_time, int32_t substeps);
+/* device time of the nonlinear plant's step kernel (integration + measurement) summed over the last run's steps; 0 when the
+ * plant is linear */
+int nnmpc_cl_last_plant_ms(nnmpc_cl* h, double* plant_ms);
+/* batched flow map: x_out[i] = Phi(x[i], u[i], p[i]) for nb instances, x / x_out nb x 12, u nb x 6, p nb x 5 (row-major),
+ * all host or all device (ptr_kind).  Instances are independent: one lane each. */
+int nnmpc_cstrs_flow(int32_t nb, const double* par, int32_t npar, double sample_time, int32_t substeps, const double* x,
+                     const double* u, const double* p, double* x_out, int32_t ptr_kind);
 
 /* ---- Device plumbing: HBM buffers, copies and synchronisation for host programs that bind only this library. */
 int nnmpc_device_count(void);

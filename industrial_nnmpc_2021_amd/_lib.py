@@ -36,6 +36,7 @@ class QpStats(C.Structure):
 
 
 CL_MPC, CL_NN, CL_SATDLQR, CL_US = 0, 1, 2, 3
+CL_PLANT_LINEAR, CL_PLANT_CSTRS_FLASH, CSTRS_NPAR = 0, 1, 51
 
 
 class ClModel(C.Structure):
@@ -57,6 +58,7 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_chain_create", "nnmpc_chain_destroy", "nnmpc_chain_run", "nnmpc_chain_reset", "nnmpc_chain_last_ms",
            "nnmpc_ts_create", "nnmpc_ts_destroy", "nnmpc_ts_solve_batch",
            "nnmpc_cl_create", "nnmpc_cl_destroy", "nnmpc_cl_run", "nnmpc_cl_reset", "nnmpc_cl_last_ms",
+           "nnmpc_cl_set_plant", "nnmpc_cl_last_plant_ms", "nnmpc_cstrs_flow",
            "nnmpc_device_count", "nnmpc_set_device", "nnmpc_device_synchronize", "nnmpc_dev_mem_info",
            "nnmpc_dev_malloc", "nnmpc_dev_free", "nnmpc_dev_memset", "nnmpc_memcpy_h2d", "nnmpc_memcpy_d2h",
            "nnmpc_memcpy_d2d", "nnmpc_host_alloc_pinned", "nnmpc_host_free_pinned",
@@ -147,6 +149,12 @@ def load():
     lib.nnmpc_cl_reset.argtypes = [vp]
     lib.nnmpc_cl_last_ms.restype = i32
     lib.nnmpc_cl_last_ms.argtypes = [vp, C.POINTER(C.c_double), dp, dp]
+    lib.nnmpc_cl_set_plant.restype = i32
+    lib.nnmpc_cl_set_plant.argtypes = [vp, i32, dp, i32, C.c_double, i32]
+    lib.nnmpc_cl_last_plant_ms.restype = i32
+    lib.nnmpc_cl_last_plant_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.nnmpc_cstrs_flow.restype = i32
+    lib.nnmpc_cstrs_flow.argtypes = [i32, dp, i32, C.c_double, i32, dp, dp, dp, dp, i32]
     lib.nnmpc_device_count.restype = i32
     lib.nnmpc_device_count.argtypes = []
     lib.nnmpc_set_device.restype = i32

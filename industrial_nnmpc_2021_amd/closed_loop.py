@@ -125,6 +125,19 @@ class DeviceClosedLoop:
                 fa()
         return out
 
+    def set_plant_cstrs(self, parameters, sample_time, substeps):
+        """Switch the plant to the CSTRs-with-flash ODE (nnmpc_cl_set_plant): ``parameters`` the plant's parameter dict."""
+        from .cstrs_parameters import device_parameter_block
+        blk = _f(device_parameter_block(parameters))
+        _lib.check(self._lib.nnmpc_cl_set_plant(self._h, _lib.CL_PLANT_CSTRS_FLASH, blk.ctypes.data_as(C.c_void_p), blk.size,
+                                                float(sample_time), int(substeps)), "nnmpc_cl_set_plant")
+
+    def last_plant_ms(self):
+        """Device ms of the nonlinear plant's step kernel summed over the last run (0 for the linear plant)."""
+        v = C.c_double()
+        _lib.check(self._lib.nnmpc_cl_last_plant_ms(self._h, C.byref(v)), "nnmpc_cl_last_plant_ms")
+        return v.value
+
     def last_ms(self):
         """(total ms, {phase: ms summed over the steps}, slot_step_ms (T, nslots)) of the last run (hipEvent times)."""
         tot = C.c_double()
@@ -149,8 +162,29 @@ def _kind(ctl):
     raise TypeError(f"simulate_closed_loop_batch: unsupported controller {type(ctl).__name__}")
 
 
+def _nonlinear(plant):
+    """True for a NonlinearPlantSimulator (only the CSTRs-with-flash model runs on the device: TypeError for any other)."""
+    from .nonlinearMPC import NonlinearPlantSimulator
+    if not isinstance(plant, NonlinearPlantSimulator):
+        return False
+    from .cstrs_parameters import CstrsMeasurement, CstrsOde
+    if not isinstance(getattr(plant.fxup, "fxup", None), CstrsOde) or not isinstance(plant.hx, CstrsMeasurement):
+        raise TypeError("simulate_closed_loop_batch: a NonlinearPlantSimulator runs on the device only with the CSTRs-with-flash "
+                        "model (fxup = cstrs_parameters.CstrsOde, hx = cstrs_parameters.CstrsMeasurement)")
+    return True
+
+
+def _plant_dims(plant):
+    """(Nu, Ny, Np) of a linear or nonlinear plant."""
+    if _nonlinear(plant):
+        return plant.Nu, plant.Ny, plant.Np
+    return plant.B.shape[1], plant.C.shape[0], plant.Bp.shape[1]
+
+
 def _validate(plant, controllers, scenarios, Nsim, seeds, instances, record):
     """Everything that can be checked without the device; returns (kinds, instances)."""
+    if _nonlinear(plant) and (plant.Nx, plant.Nu, plant.Np, plant.Ny) != (12, 6, 5, 12):
+        raise ValueError("simulate_closed_loop_batch: the CSTRs-with-flash plant has Nx=12 Nu=6 Np=5 Ny=12")
     if not isinstance(Nsim, (int, np.integer)) or Nsim <= 0:
         raise ValueError("simulate_closed_loop_batch: Nsim must be a positive integer")
     if not controllers:
@@ -164,8 +198,9 @@ def _validate(plant, controllers, scenarios, Nsim, seeds, instances, record):
                 raise ValueError(f"simulate_closed_loop_batch: controller {j} differs from controller 0 in {k}; all controllers "
                                  "of one evaluation share the filter, target, cost and plant data")
     Nu, Ny, Nd = ref.B.shape[1], ref.C.shape[0], ref.Bd.shape[1]
-    if plant.B.shape[1] != Nu or plant.C.shape[0] != Ny or plant.Bp.shape[1] != Nd:
-        raise ValueError("simulate_closed_loop_batch: plant and controllers disagree on Nu / Ny / Nd")
+    if _plant_dims(plant) != (Nu, Ny, Nd):
+        raise ValueError("simulate_closed_loop_batch: plant and controllers disagree on Nu / Ny / Nd (the plant's Np must "
+                         "equal the filter's Nd)")
     if not scenarios:
         raise ValueError("simulate_closed_loop_batch: no scenarios")
     for s, sc in enumerate(scenarios):
@@ -197,7 +232,9 @@ def _model(plant, ctl):
     red = ReducedTargetProblem(ctl.A, ctl.B, ctl.C, ctl.H, ctl.Bd, ctl.Cd, ctl.Qs, ctl.Rs, ctl.usp)
     f = ctl.filter
     Nx, Nu = ctl.B.shape
-    return dict(nx=Nx, nu=Nu, ny=ctl.C.shape[0], nd=ctl.Bd.shape[1], nz=red.Nz, A=plant.A, B=plant.B, C=plant.C, Bp=plant.Bp,
+    # nonlinear plant: the linearisation fills the plant matrices nnmpc_cl_create requires; the integration replaces the step
+    A, B, Cm, Bp = (ctl.A, ctl.B, plant.hx.C, ctl.Bd) if _nonlinear(plant) else (plant.A, plant.B, plant.C, plant.Bp)
+    return dict(nx=Nx, nu=Nu, ny=ctl.C.shape[0], nd=ctl.Bd.shape[1], nz=red.Nz, A=A, B=B, C=Cm, Bp=Bp,
                 Aaug=f.A, Baug=f.B, Caug=f.C, L=f.L, tb=red.tb, Qb=red.Qb, Qy=red.Qy, q0=red.q0, Cd=ctl.Cd, Eb=red.Eb, Xb=red.Xb,
                 Xu=red.Xu, Qaug=ctl.Qaug, Raug=np.atleast_2d(ctl.Raug), Maug=ctl.Maug, ulb=ctl.ulb, uub=ctl.uub,
                 x0=plant.x[0], xhat0=f.xhat[0], uprev0=ctl.uprev)
@@ -207,7 +244,10 @@ def simulate_closed_loop_batch(plant, controllers, *, scenarios, Nsim, seeds, in
                                return_objects=False, allow_uncertified=False, plant_y0=False):
     """All (controller, scenario, seed) instances of an evaluation in one device run.
 
-    plant: a ``LinearPlantSimulator`` (A, B, C, Bp, the noise std of Rv, x[0]; its own noise draws are not used); controllers:
+    plant: a ``LinearPlantSimulator`` (A, B, C, Bp, the noise std of Rv, x[0]; its own noise draws are not used) or a
+    ``nonlinearMPC.NonlinearPlantSimulator`` of the CSTRs-with-flash model (``cstrs_parameters._get_cstrs_plant(linear=False)``:
+    the ODE is integrated on the device with the host simulator's RK4 scheme, y = C x + noise with C = hx.C; any other
+    nonlinear model raises ``TypeError``); controllers:
     ``LinearMPCController`` (any horizon), ``NeuralNetworkController``, ``SatDlqrController``, ``SteadyStateController`` in
     their initial state, sharing the filter, target, cost and plant data (``ValueError`` otherwise, before any device work);
     scenarios: (setpoints (>= Nsim, Ny), disturbances (>= Nsim, Nd)) pairs; seeds: noise seeds.  ``instances`` defaults to
@@ -222,7 +262,7 @@ def simulate_closed_loop_batch(plant, controllers, *, scenarios, Nsim, seeds, in
     (n_instances, Nsim): the per-step device time of the instance's controller phase FOR THE WHOLE LOCK-STEP BATCH (MPC: its
     slot's batched regulator solve, NN: the grouped forward of all networks, satK / us: the expansion kernel).  These are
     not the per-instance batch-1 latencies the reference's time.time() pairs measure.  ``phase_ms``: device time per phase,
-    ``wall_s``.  With ``return_objects`` also ``plants`` / ``controllers``: objects with the reference's attributes
+    ``plant_ms``: device time of the nonlinear plant's integration (0 for the linear plant), ``wall_s``.  With ``return_objects`` also ``plants`` / ``controllers``: objects with the reference's attributes
     (x, u, y lists; filter.xhat, average_stage_costs, computation_times) that its plotting code reads.
     """
     import time
@@ -265,7 +305,14 @@ def simulate_closed_loop_batch(plant, controllers, *, scenarios, Nsim, seeds, in
     DS = np.stack([np.asarray(s[1], float)[:Nsim] for s in scenarios]).reshape(len(scenarios), Nsim, -1)
     t0 = time.time()
     dev = DeviceClosedLoop(model, target, slots, inst_slot)
+    if _nonlinear(plant):
+        try:
+            dev.set_plant_cstrs(plant.fxup.fxup.parameters, plant.sample_time, plant.fxup.substeps)
+        except Exception:
+            dev.close()
+            raise
     step = int(chunk or Nsim)
+    plant_ms = 0.0
     parts, slot_ms, phase = [], [], dict.fromkeys(("filter", "target", "expand", "nn", "mpc", "post"), 0.0)
     total_ms = 0.0
     try:
@@ -274,13 +321,14 @@ def simulate_closed_loop_batch(plant, controllers, *, scenarios, Nsim, seeds, in
             parts.append(dev.run(SP[:, a:b], DS[:, a:b], scen, V[a:b + 1], sigma, record=rec, y0=Y0 if a == 0 else None))
             tot, ph, ss = dev.last_ms()
             total_ms += tot
+            plant_ms += dev.last_plant_ms()
             for k in phase:
                 phase[k] += ph[k]
             slot_ms.append(ss)
     finally:
         dev.close()
     wall = time.time() - t0
-    out = dict(instances=instances, wall_s=wall, device_ms=total_ms, phase_ms=phase)
+    out = dict(instances=instances, wall_s=wall, device_ms=total_ms, phase_ms=phase, plant_ms=plant_ms)
     for k in ("y", "x", "xhat", "avg"):
         if k in rec:
             arr = np.concatenate([parts[0][k]] + [p_[k][1:] for p_ in parts[1:]], axis=0)
@@ -308,12 +356,36 @@ def _objects(out, plant, controllers, instances):
     """Reference-shaped plant / controller records: lists of column vectors, as online_simulation leaves them."""
     col = lambda a: [r[:, None] for r in a]
     plants, ctls = [], []
+    nonlinear = _nonlinear(plant)
     for i, (c, _, _) in enumerate(instances):
-        plants.append(types.SimpleNamespace(x=col(out["x"][i]), u=col(out["u"][i]), y=col(out["y"][i]), A=plant.A, B=plant.B,
-                                            C=plant.C, Bp=plant.Bp, sample_time=plant.sample_time,
-                                            t=list(plant.sample_time * np.arange(out["x"].shape[1]))))
+        t = list(plant.sample_time * np.arange(out["x"].shape[1]))
+        if nonlinear:                                            # NonlinearPlantSimulator's attributes (lib/nonlinearMPC.py:11-48)
+            plants.append(types.SimpleNamespace(x=col(out["x"][i]), u=col(out["u"][i]), y=col(out["y"][i]), fxup=plant.fxup,
+                                                hx=plant.hx, Nx=plant.Nx, Nu=plant.Nu, Ny=plant.Ny, Np=plant.Np,
+                                                measurement_noise_std=plant.measurement_noise_std,
+                                                sample_time=plant.sample_time, t=t))
+        else:
+            plants.append(types.SimpleNamespace(x=col(out["x"][i]), u=col(out["u"][i]), y=col(out["y"][i]), A=plant.A,
+                                                B=plant.B, C=plant.C, Bp=plant.Bp, sample_time=plant.sample_time, t=t))
         ctls.append(types.SimpleNamespace(filter=types.SimpleNamespace(xhat=col(out["xhat"][i])),
                                           average_stage_costs=[np.array([[v]]) for v in out["avg"][i]],
                                           computation_times=list(out["computation_times"][i]),
                                           uprev=out["u"][i][-1][:, None], kind=_kind(controllers[c])))
     return plants, ctls
+
+
+def cstrs_flow(parameters, X, U, P, substeps=None):
+    """Device flow map of the CSTRs-with-flash plant (nnmpc_cstrs_flow): rows X (nb, 12), U (nb, 6), P (nb, 5) -> (nb, 12),
+    the host nonlinearMPC.DiscreteSimulator's RK4 with the same substeps (default nonlinearMPC.SUBSTEPS)."""
+    from .cstrs_parameters import device_parameter_block
+    from .nonlinearMPC import SUBSTEPS
+    lib = _lib.load()
+    X = _f(X).reshape(-1, 12)
+    nb = X.shape[0]
+    U, P = _f(U).reshape(nb, 6), _f(P).reshape(nb, 5)
+    blk = _f(device_parameter_block(parameters))
+    out = np.empty_like(X)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.nnmpc_cstrs_flow(nb, p(blk), blk.size, float(parameters["sample_time"]), int(substeps or SUBSTEPS), p(X), p(U),
+                                    p(P), p(out), _lib.HOST), "nnmpc_cstrs_flow")
+    return out

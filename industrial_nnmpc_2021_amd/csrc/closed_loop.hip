@@ -258,6 +258,7 @@ struct PostArgs {
   int nx, nu, ny, nd, na, T;
   const double *At, *Bt, *Bpt, *Ct;             // A' (nx x nx), B' (nu x nx), Bp' (nd x nx), C' (nx x ny)
   const double *Qaug, *Raug, *Maug, *ulb, *uub, *sigma;
+  int nonlinear;                                // 1: the plant step is cl_cstrs_k's (x, y, their records are left to it)
 };
 struct PostRec {
   double *y, *x, *xhat, *u, *xs, *us, *avg;     // this step's rows (u/xs/us: row t, the others row t + 1), may be null
@@ -322,6 +323,9 @@ __global__ __launch_bounds__(CL_THREADS) void cl_post_k(PostArgs a, int t, int t
     part += w[k] * rw + w[k] * mz;
   }
   const double ell = block_sum(part, red);
+  if (a.nonlinear) {
+    for (int k = tid; k < nu; k += CL_THREADS) uprev[(size_t)i * nu + k] = pz[nx + k];
+  } else {
   // plant: x+ = (A x + B u) + Bp p
   for (int k = tid; k < nx; k += CL_THREADS) {
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -339,6 +343,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_post_k(PostArgs a, int t, int t
     const double v = colsum(a.Ct, nx, ny, xn, j) + a.sigma[j] * vnext[(size_t)i * ny + j];
     y[(size_t)i * ny + j] = v;
     if (rec.y) rec.y[(size_t)i * ny + j] = v;
+  }
   }
   if (rec.xs) for (int k = tid; k < nx; k += CL_THREADS) rec.xs[(size_t)i * nx + k] = xs[(size_t)i * nx + k];
   if (rec.xhat) for (int k = tid; k < a.na; k += CL_THREADS) rec.xhat[(size_t)i * a.na + k] = xhat[(size_t)i * a.na + k];
@@ -359,6 +364,145 @@ __global__ __launch_bounds__(CL_THREADS) void cl_post_k(PostArgs a, int t, int t
       s.guess[(size_t)li * s.n + r] = (unsigned char)(su_ ? 1 : (sl ? 2 : 0));
     }
   }
+}
+
+// ---- the CSTRs-with-flash plant (NNMPC_CL_PLANT_CSTRS_FLASH): classical RK4, a fixed number of substeps per sample, fp64,
+// the tableau and operation order of nonlinearMPC.DiscreteSimulator / cstrs_parameters._rhs.  One lane per instance: the
+// 12 states, the accumulator and the stage input stay in registers; the loop counts are kernel arguments, never data.
+struct CstrsPar { double c[NNMPC_CSTRS_NPAR]; };
+enum { P_aA, P_aB, P_aC, P_rho, P_Cp, P_Ar, P_Am, P_Ab, P_kr, P_km, P_kb, P_dH1, P_dH2, P_EbyR, P_k1, P_k2, P_Td,
+       P_XS = 17, P_US = 29, P_PS = 35, P_USC = 40, P_PSC = 46 };
+
+// Constant reciprocals of the right-hand side, formed once per flow map (outside the substep loop)
+struct CstrsInv { double rA, mA, bA, cp; };
+
+// f (12) at the deviation state z; U (6), P (5) absolute.  Shared subexpressions once: 2 exponentials, 3 square roots, the
+// vapour fractions (one reciprocal of their denominator), the reciprocal hold-ups and temperatures: 6 fp64 reciprocals per
+// evaluation, the constant divisors are multiplications by CstrsInv.  A level <= 0 gives NaN (sqrt) or inf (1 / hold-up),
+// as numpy does.
+__device__ __forceinline__ void cstrs_rhs(const CstrsPar& q, const CstrsInv& v, const double* z, const double* U, const double* P,
+                                          double* f) {
+  const double* c = q.c;
+  const double Hr = z[0] + c[P_XS + 0], xAr = z[1] + c[P_XS + 1], xBr = z[2] + c[P_XS + 2], Tr = z[3] + c[P_XS + 3];
+  const double Hm = z[4] + c[P_XS + 4], xAm = z[5] + c[P_XS + 5], xBm = z[6] + c[P_XS + 6], Tm = z[7] + c[P_XS + 7];
+  const double Hb = z[8] + c[P_XS + 8], xAb = z[9] + c[P_XS + 9], xBb = z[10] + c[P_XS + 10], Tb = z[11] + c[P_XS + 11];
+  const double F0 = U[0], Qr = U[1], F1 = U[2], Qm = U[3], D = U[4], Qb = U[5];
+  const double xA0 = P[0], xB0 = P[1], xA1 = P[2], xB1 = P[3], T0 = P[4];
+  const double rho = c[P_rho];
+  const double ivden = 1.0 / (c[P_aA] * xAb + c[P_aB] * xBb + c[P_aC] * (1.0 - xAb - xBb));
+  const double xAd = c[P_aA] * xAb * ivden, xBd = c[P_aB] * xBb * ivden;
+  const double Fr = c[P_kr] * sqrt(Hr), Fm = c[P_km] * sqrt(Hm), Fb = c[P_kb] * sqrt(Hb);
+  const double Fp = 0.01 * D;
+  const double er = exp(-c[P_EbyR] * (1.0 / Tr)), em = exp(-c[P_EbyR] * (1.0 / Tm));
+  const double k1r = c[P_k1] * er, k2r = c[P_k2] * er, k1m = c[P_k1] * em, k2m = c[P_k2] * em;
+  const double dH1 = c[P_dH1], dH2 = c[P_dH2], Td = c[P_Td];
+  const double imr = 1.0 / (rho * c[P_Ar] * Hr), imm = 1.0 / (rho * c[P_Am] * Hm), imb = 1.0 / (rho * c[P_Ab] * Hb);
+  f[0] = (F0 + D - Fr) * v.rA;
+  f[1] = (F0 * (xA0 - xAr) + D * (xAd - xAr)) * imr - k1r * xAr;
+  f[2] = (F0 * (xB0 - xBr) + D * (xBd - xBr)) * imr + k1r * xAr - k2r * xBr;
+  f[3] = (F0 * (T0 - Tr) + D * (Td - Tr)) * imr - (k1r * xAr * dH1 + k2r * xBr * dH2) * v.cp + Qr * imr * v.cp;
+  f[4] = (Fr + F1 - Fm) * v.mA;
+  f[5] = (Fr * (xAr - xAm) + F1 * (xA1 - xAm)) * imm - k1m * xAm;
+  f[6] = (Fr * (xBr - xBm) + F1 * (xB1 - xBm)) * imm + k1m * xAm - k2m * xBm;
+  f[7] = (Fr * (Tr - Tm) + F1 * (T0 - Tm)) * imm - (k1m * xAm * dH1 + k2m * xBm * dH2) * v.cp + Qm * imm * v.cp;
+  f[8] = (Fm - Fb - D - Fp) * v.bA;
+  f[9] = (Fm * (xAm - xAb) - (D + Fp) * (xAd - xAb)) * imb;
+  f[10] = (Fm * (xBm - xBb) - (D + Fp) * (xBd - xBb)) * imb;
+  f[11] = Fm * (Tm - Tb) * imb + Qb * imb * v.cp;
+}
+
+// x (12, deviation) <- Phi(x, u, p) over one sample; u (6), p (5) scaled deviations
+__device__ __forceinline__ void cstrs_flow(const CstrsPar& q, double h, int substeps, double* x, const double* u, const double* p) {
+  double U[6], P[5], k[12], acc[12], z[12];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) U[j] = u[j] * q.c[P_USC + j] + q.c[P_US + j];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) P[j] = p[j] * q.c[P_PSC + j] + q.c[P_PS + j];
+  const double h2 = 0.5 * h, h6 = h / 6.0;
+  const CstrsInv v{1.0 / (q.c[P_rho] * q.c[P_Ar]), 1.0 / (q.c[P_rho] * q.c[P_Am]), 1.0 / (q.c[P_rho] * q.c[P_Ab]), 1.0 / q.c[P_Cp]};
+  for (int s = 0; s < substeps; ++s) {
+    cstrs_rhs(q, v, x, U, P, k);
+#pragma unroll
+    for (int j = 0; j < 12; ++j) { acc[j] = k[j]; z[j] = x[j] + h2 * k[j]; }
+    cstrs_rhs(q, v, z, U, P, k);
+#pragma unroll
+    for (int j = 0; j < 12; ++j) { acc[j] = acc[j] + 2.0 * k[j]; z[j] = x[j] + h2 * k[j]; }
+    cstrs_rhs(q, v, z, U, P, k);
+#pragma unroll
+    for (int j = 0; j < 12; ++j) { acc[j] = acc[j] + 2.0 * k[j]; z[j] = x[j] + h * k[j]; }
+    cstrs_rhs(q, v, z, U, P, k);
+#pragma unroll
+    for (int j = 0; j < 12; ++j) x[j] = x[j] + h6 * (acc[j] + k[j]);
+  }
+}
+
+constexpr int CSTRS_THREADS = 64;
+
+// batched flow map (nnmpc_cstrs_flow): instance i = thread
+__global__ __launch_bounds__(CSTRS_THREADS) void cstrs_flow_k(CstrsPar q, double h, int substeps, int nb, const double* __restrict__ x,
+                                                              const double* __restrict__ u, const double* __restrict__ p,
+                                                              double* __restrict__ xo) {
+  const int i = blockIdx.x * CSTRS_THREADS + threadIdx.x;
+  if (i >= nb) return;
+  double xv[12], uv[6], pv[5];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) xv[j] = x[(size_t)i * 12 + j];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) uv[j] = u[(size_t)i * 6 + j];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) pv[j] = p[(size_t)i * 5 + j];
+  cstrs_flow(q, h, substeps, xv, uv, pv);
+#pragma unroll
+  for (int j = 0; j < 12; ++j) xo[(size_t)i * 12 + j] = xv[j];
+}
+
+// step part 4 (nonlinear plant): x = Phi(x, u_t, p_t) with u_t = uprev (cl_post_k wrote it), y_{t+1} = C x + sigma o v_{t+1}
+__global__ __launch_bounds__(CSTRS_THREADS) void cl_cstrs_k(CstrsPar q, double h, int substeps, int nb, int ny, int T, int t,
+                                                            const int* __restrict__ scen, const double* __restrict__ dist,
+                                                            const double* __restrict__ uprev, const double* __restrict__ Ct,
+                                                            const double* __restrict__ sigma, const double* __restrict__ vnext,
+                                                            double* __restrict__ x, double* __restrict__ y,
+                                                            double* __restrict__ x_rec, double* __restrict__ y_rec) {
+  const int i = blockIdx.x * CSTRS_THREADS + threadIdx.x;
+  if (i >= nb) return;
+  double xv[12], uv[6], pv[5];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) xv[j] = x[(size_t)i * 12 + j];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) uv[j] = uprev[(size_t)i * 6 + j];
+  const double* pt = dist + ((size_t)scen[i] * T + t) * 5;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) pv[j] = pt[j];
+  cstrs_flow(q, h, substeps, xv, uv, pv);
+#pragma unroll
+  for (int j = 0; j < 12; ++j) {
+    x[(size_t)i * 12 + j] = xv[j];
+    if (x_rec) x_rec[(size_t)i * 12 + j] = xv[j];
+  }
+  for (int j = 0; j < ny; ++j) {                         // colsum order of cl_post_k's linear measurement
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) a += Ct[(size_t)k * ny + j] * xv[k];
+    const double v = a + sigma[j] * vnext[(size_t)i * ny + j];
+    y[(size_t)i * ny + j] = v;
+    if (y_rec) y_rec[(size_t)i * ny + j] = v;
+  }
+}
+
+// the parameter block of nnmpc_cl_set_plant / nnmpc_cstrs_flow: finite, positive where a physical quantity must be
+int cstrs_check(const double* par, int32_t npar, double sample_time, int32_t substeps, CstrsPar* q, const char* who) {
+  if (!par || npar != NNMPC_CSTRS_NPAR || !(sample_time > 0.0) || !(sample_time < 1e300) || substeps < 1 || substeps > 4096) {
+    set_error("%s: needs %d parameters, sample_time > 0 and 1 <= substeps <= 4096 (got npar=%d, sample_time=%g, substeps=%d)",
+              who, NNMPC_CSTRS_NPAR, npar, sample_time, substeps);
+    return NNMPC_EINVAL;
+  }
+  for (int j = 0; j < npar; ++j)
+    if (!(fabs(par[j]) <= 1.79e308)) { set_error("%s: parameter %d is not finite", who, j); return NNMPC_EINVAL; }
+  const int pos[] = {P_rho, P_Cp, P_Ar, P_Am, P_Ab};
+  for (int j : pos)
+    if (!(par[j] > 0.0)) { set_error("%s: parameter %d (density, heat capacity, areas) must be > 0", who, j); return NNMPC_EINVAL; }
+  for (int j = 0; j < npar; ++j) q->c[j] = par[j];
+  return NNMPC_OK;
 }
 
 std::vector<double> transpose(const double* M, int rows, int cols) {
@@ -399,6 +543,10 @@ struct nnmpc_cl {
   hipStream_t stream = nullptr;
   std::vector<hipEvent_t> ev;
   double total_ms = 0.0, phase_ms[6] = {0, 0, 0, 0, 0, 0};
+  int plant = NNMPC_CL_PLANT_LINEAR;                // nnmpc_cl_set_plant
+  CstrsPar cstrs = {};
+  double plant_h = 0.0, plant_ms = 0.0;
+  int plant_substeps = 0;
   std::vector<double> slot_ms;                      // [T][nslots] of the last run
   int last_T = 0;
   std::vector<void*> allocs;
@@ -678,7 +826,8 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
   }
   std::vector<int> mpc;
   for (int k = 0; k < h->nslots; ++k) if (h->kind[k] == NNMPC_CL_MPC && h->count[k]) mpc.push_back(k);
-  const int nm = (int)mpc.size(), ne = 7 + nm;          // events per step: start, filter, target, expand, nn, [mpc...], join, post
+  const int nl = h->plant != NNMPC_CL_PLANT_LINEAR ? 1 : 0;
+  const int nm = (int)mpc.size(), ne = 7 + nm + nl;     // events per step: start, filter, target, expand, nn, [mpc...], join, post, [plant]
   // phase events of at most CL_EV_BLOCK steps are alive at a time: after each block the stream is drained once and the block's
   // times are added up, so the pool is bounded whatever T is
   const int blk = std::min(T, CL_EV_BLOCK);
@@ -687,11 +836,12 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
   hipStream_t s = h->stream;
   FilterArgs fa{nx, nu, ny, nd, h->nz, na, nbv, T, h->Aat, h->Bat, h->Cat, h->Lt, h->tbt, h->Qbt, h->Qyt, h->q0, h->Cdt, h->Ebt};
   ExpandArgs xa{nx, nu, na, nbv, h->ldA, h->Xbt, h->Xut, h->ulb, h->uub};
-  PostArgs pa{nx, nu, ny, nd, na, T, h->At, h->Bt, h->Bpt, h->Ct, h->Qaug, h->Raug, h->Maug, h->ulb, h->uub, sig_d};
+  PostArgs pa{nx, nu, ny, nd, na, T, h->At, h->Bt, h->Bpt, h->Ct, h->Qaug, h->Raug, h->Maug, h->ulb, h->uub, sig_d, nl};
   const size_t lds_f = (size_t)(2 * na + nu + 2 * ny + nd + nbv) * 8;
   const size_t lds_x = (size_t)(nbv + 2 * nu + 2 * nx) * 8;
   const size_t lds_p = (size_t)(2 * (nx + nu) + nu + nd + nx + CL_THREADS) * 8 + (size_t)nx * 8;
   for (double& p : h->phase_ms) p = 0.0;
+  h->plant_ms = 0.0;
   h->slot_ms.assign((size_t)T * h->nslots, 0.0);
   auto el = [&](hipEvent_t a, hipEvent_t b) { float ms = 0.f; hipEventElapsedTime(&ms, a, b); return (double)ms; };
   std::vector<double> ms(nm);
@@ -703,6 +853,7 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
       for (int j = 0; j < nm; ++j) { ms[j] = el(E[3], E[5 + j]); mp = std::max(mp, ms[j]); }
       h->phase_ms[0] += f; h->phase_ms[1] += tg; h->phase_ms[2] += xp; h->phase_ms[3] += nn; h->phase_ms[4] += mp;
       h->phase_ms[5] += el(E[5 + nm], E[6 + nm]);
+      if (nl) h->plant_ms += el(E[6 + nm], E[7 + nm]);
       for (int k = 0, j = 0; k < h->nslots; ++k) {
         double v_ = xp;
         if (h->kind[k] == NNMPC_CL_NN) v_ = nn;
@@ -763,6 +914,12 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
                        d_d, v_d + (size_t)(t + 1) * nb * ny, h->o, h->ctl_u, h->us, h->xs, h->tstat, h->x, h->xhat, h->uprev, h->y,
                        h->avg, pr);
     hipEventRecord(E[6 + nm], s);
+    if (nl) {
+      hipLaunchKernelGGL(cl_cstrs_k, dim3((nb + CSTRS_THREADS - 1) / CSTRS_THREADS), dim3(CSTRS_THREADS), 0, s, h->cstrs, h->plant_h,
+                         h->plant_substeps, nb, ny, T, t, sc_d, d_d, h->uprev, h->Ct, sig_d, v_d + (size_t)(t + 1) * nb * ny, h->x,
+                         h->y, pr.x, pr.y);
+      hipEventRecord(E[7 + nm], s);
+    }
     for (int k : mpc) h->have_guess[k] = true;
     h->fresh = false;
     ++h->tglob;
@@ -785,6 +942,67 @@ int nnmpc_cl_last_ms(nnmpc_cl* h, double* total_ms, double* phase_ms, double* sl
   if (total_ms) *total_ms = h->total_ms;
   if (phase_ms) for (int k = 0; k < 6; ++k) phase_ms[k] = h->phase_ms[k];
   if (slot_step_ms && !h->slot_ms.empty()) memcpy(slot_step_ms, h->slot_ms.data(), h->slot_ms.size() * 8);
+  return NNMPC_OK;
+}
+
+int nnmpc_cl_set_plant(nnmpc_cl* h, int32_t kind, const double* par, int32_t npar, double sample_time, int32_t substeps) {
+  if (!h) { set_error("nnmpc_cl_set_plant: null handle"); return NNMPC_EINVAL; }
+  if (kind == NNMPC_CL_PLANT_LINEAR) { h->plant = kind; return NNMPC_OK; }
+  if (kind != NNMPC_CL_PLANT_CSTRS_FLASH) { set_error("nnmpc_cl_set_plant: unknown plant kind %d", kind); return NNMPC_EINVAL; }
+  if (h->nx != 12 || h->nu != 6 || h->nd != 5) {
+    set_error("nnmpc_cl_set_plant: the CSTRs-with-flash plant needs nx=12 nu=6 nd=5 (handle: nx=%d nu=%d nd=%d)", h->nx, h->nu, h->nd);
+    return NNMPC_EINVAL;
+  }
+  CstrsPar q;
+  const int rc = cstrs_check(par, npar, sample_time, substeps, &q, "nnmpc_cl_set_plant");
+  if (rc) return rc;
+  h->cstrs = q;
+  h->plant_h = sample_time / substeps;
+  h->plant_substeps = substeps;
+  h->plant = kind;
+  return NNMPC_OK;
+}
+
+int nnmpc_cl_last_plant_ms(nnmpc_cl* h, double* plant_ms) {
+  if (!h || !plant_ms) { set_error("nnmpc_cl_last_plant_ms: bad arguments"); return NNMPC_EINVAL; }
+  *plant_ms = h->plant_ms;
+  return NNMPC_OK;
+}
+
+int nnmpc_cstrs_flow(int32_t nb, const double* par, int32_t npar, double sample_time, int32_t substeps, const double* x,
+                     const double* u, const double* p, double* x_out, int32_t ptr_kind) {
+  if (nb < 0 || (nb && (!x || !u || !p || !x_out)) || (ptr_kind != NNMPC_HOST && ptr_kind != NNMPC_DEVICE)) {
+    set_error("nnmpc_cstrs_flow: bad arguments (nb=%d)", nb);
+    return NNMPC_EINVAL;
+  }
+  CstrsPar q;
+  const int rc = cstrs_check(par, npar, sample_time, substeps, &q, "nnmpc_cstrs_flow");
+  if (rc) return rc;
+  if (nb == 0) return NNMPC_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("nnmpc_cstrs_flow: no HIP device available (no CPU fallback)"); return NNMPC_EHIP; }
+  const size_t bx = (size_t)nb * 12 * 8, bu = (size_t)nb * 6 * 8, bp = (size_t)nb * 5 * 8;
+  const double *xd = x, *ud = u, *pd = p;
+  double* od = x_out;
+  void* buf = nullptr;
+  if (ptr_kind == NNMPC_HOST) {
+    HIPCHK(hipMalloc(&buf, 2 * bx + bu + bp));
+    char* b = (char*)buf;
+    double *xh = (double*)b, *uh = (double*)(b + bx), *ph = (double*)(b + bx + bu);
+    od = (double*)(b + bx + bu + bp);
+    hipError_t e = hipMemcpy(xh, x, bx, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(uh, u, bu, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ph, p, bp, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(buf); set_error("nnmpc_cstrs_flow: upload: %s", hipGetErrorString(e)); return NNMPC_EHIP; }
+    xd = xh; ud = uh; pd = ph;
+  }
+  hipLaunchKernelGGL(cstrs_flow_k, dim3((nb + CSTRS_THREADS - 1) / CSTRS_THREADS), dim3(CSTRS_THREADS), 0, 0, q, sample_time / substeps,
+                     substeps, nb, xd, ud, pd, od);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess && ptr_kind == NNMPC_HOST) e = hipMemcpy(x_out, od, bx, hipMemcpyDeviceToHost);
+  if (buf) hipFree(buf);
+  if (e != hipSuccess) { set_error("nnmpc_cstrs_flow: %s", hipGetErrorString(e)); return NNMPC_EHIP; }
   return NNMPC_OK;
 }
 

@@ -1,8 +1,10 @@
 """Seeded synthetic plants and sample batches of the reference's sizes and tuning.
 
-The real plants cannot be rebuilt (CDU_Model.mat is not in the reference repo,
-the CSTRs linearisation needs casadi), so benchmarks and tests use random
-plants with the reference's dimensions and regulator tuning:
+The CDU plant cannot be rebuilt (CDU_Model.mat is not in the reference repo),
+so benchmarks and tests use random plants with the reference's dimensions and
+regulator tuning.  The real CSTRs-with-flash plant and its linearisation are
+rebuilt without casadi in cstrs_parameters.py; the CSTRs stand-in below is kept
+for the measurements quoted against it:
   CDU   Nx=252 Nu=32 Ny=90 N=140  Q=2C'C    R=0.1I S=0     (cdu_parameters.py:99-102)
   CSTRs Nx=12  Nu=6  Ny=12 N=90   Q=1e3C'C  R=0.1I S=0.1I  (cstrs_parameters.py:300-303)
 inputs scaled so that uub - ulb = 2 (cdu_parameters.py:35-40).

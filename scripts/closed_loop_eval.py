@@ -9,6 +9,9 @@ its HBM bound (every step streams all f32 weights: more than the 256 MiB Infinit
 online_simulation on a few instances for comparison.  One JSON line per size at the end.
 
     python scripts/closed_loop_eval.py --size both --steps 2880 --seeds 1
+
+``--size cstrs-flash`` is the reference's real CSTRs study instead: its linearised model and controllers, both online test
+scenarios for 4320 steps, 48 random networks of its widths, the nonlinear plant integrated on the device (run_cstrs_flash).
 """
 import argparse
 import contextlib
@@ -116,9 +119,59 @@ def run(size, args):
                 speedup=host_est / res["wall_s"], setup_s=setup_s)
 
 
+def run_cstrs_flash(args):
+    """The reference's CSTRs study end to end (cstrs_parameters.py, cstrs_mpc.py / cstrs_neural_network.py): the real
+    linearised model and controllers, both online test scenarios for 4320 steps, the nonlinear CSTRs-with-flash plant
+    integrated on the device.  Instances: MPC (N = 90), short-horizon MPC (N = 10), satK, us and 48 random networks of the
+    widths of cstrs_train.py (4 architectures x 12 training-set sizes, with uprev), on both scenarios."""
+    from industrial_nnmpc_2021_amd import controller_evaluation as ce, cstrs_parameters as cp
+    from industrial_nnmpc_2021_amd.closed_loop import simulate_closed_loop_batch
+    t0 = time.time()
+    par = cp._get_cstrs_parameters()
+    par["xs"] = cp._get_cstrs_rectified_xs(parameters=par)
+    rect_s = time.time() - t0
+    steps = 4320
+    plant = cp._get_cstrs_plant(linear=False, parameters=par)
+    mpc = cp._get_cstrs_mpc_controller(plant, par, cp.Z_INDICES, cp.EXP_DIST_INDICES)
+    scen = cp._get_cstrs_online_test_scenarios(Nsim=steps, z_indices=cp.Z_INDICES, unexp_z_indices=cp.UNEXP_Z_INDICES,
+                                               parameters=par, exp_dist_indices=cp.EXP_DIST_INDICES, seed=50, tsteps_steady=5)
+    rng = np.random.default_rng(5)
+    Ws = networks("cstrs", 12, 6, 48, rng)
+    xscale = rng.uniform(0.5, 2.0, 12)
+    nns = [ce.NeuralNetworkController(regulator_weights=W, xscale=xscale, nnwithuprev=True, build_forward=False,
+                                      **ce._shared(mpc)) for W in Ws]
+    base = [mpc, ce._get_short_horizon_controller(mpc, 10), ce._get_satdlqr_controller(mpc), ce._get_us_controller(mpc)]
+    ctls = nns + base
+    simulate_closed_loop_batch(plant, ctls, scenarios=scen, Nsim=4, seeds=[0], record=("avg",), plant_y0=True)
+    setup_s = time.time() - t0
+    res = simulate_closed_loop_batch(plant, ctls, scenarios=scen, Nsim=steps, seeds=[0], record=("x", "u", "avg", "status"),
+                                     chunk=args.chunk, plant_y0=True, allow_uncertified=True)
+    nb = len(res["instances"])
+    ph = {k: v / steps for k, v in res["phase_ms"].items()}
+    plant_us = 1e3 * res["plant_ms"] / steps
+    ok = bool((res["ts_status"] == 0).all() and (res["reg_status"] == 0).all())
+    finite = bool(all(np.isfinite(res[k]).all() for k in ("x", "u", "avg")))
+    ell = res["avg"][:, -1].reshape(len(ctls), len(scen))
+    mpc_ell = ell[len(nns)]
+    loss = {name: 100 * (ell[len(nns) + j] - mpc_ell) / mpc_ell for j, name in ((1, "sh"), (2, "satdlqr"), (3, "us"))}
+    print(f"[cstrs-flash] {len(nns)} networks + 4 baselines x {len(scen)} scenarios = {nb} instances, {steps} steps, nonlinear "
+          f"plant (RK4, {plant.fxup.substeps} substeps of {plant.sample_time / plant.fxup.substeps:g} s); rectified xs "
+          f"{rect_s:.1f} s, setup {setup_s:.1f} s")
+    print(f"[cstrs-flash] wall {res['wall_s']:.3f} s, device {res['device_ms'] / 1e3:.3f} s, "
+          f"{1e3 * res['wall_s'] / steps:.3f} ms per step; all statuses 0: {ok}; finite records: {finite}")
+    print("[cstrs-flash] per step (ms): " + ", ".join(f"{k} {v:.4f}" for k, v in ph.items()) + f", plant {plant_us / 1e3:.4f}")
+    for name, v in loss.items():
+        print(f"[cstrs-flash] performance loss {name} vs MPC: " + ", ".join(f"scenario {s} {x:.2f} %" for s, x in enumerate(v)))
+    return dict(size="cstrs-flash", networks=len(nns), instances=nb, steps=steps, wall_s=res["wall_s"],
+                device_s=res["device_ms"] / 1e3, phase_ms_per_step=ph, plant_us_per_step=plant_us,
+                substeps=plant.fxup.substeps, all_status_zero=ok, finite=finite,
+                loss_sh_vs_mpc=list(loss["sh"]), loss_satdlqr_vs_mpc=list(loss["satdlqr"]), loss_us_vs_mpc=list(loss["us"]),
+                rectify_s=rect_s, setup_s=setup_s)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--size", choices=("cstrs", "cdu", "both"), default="both")
+    ap.add_argument("--size", choices=("cstrs", "cdu", "both", "cstrs-flash"), default="both")
     ap.add_argument("--steps", type=int, default=2880)
     ap.add_argument("--seeds", type=int, default=1)
     ap.add_argument("--nets", type=int, default=52)
@@ -126,7 +179,10 @@ def main():
     ap.add_argument("--host-steps", type=int, default=30)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
-    out = [run(s, args) for s in (("cstrs", "cdu") if args.size == "both" else (args.size,))]
+    if args.size == "cstrs-flash":
+        out = [run_cstrs_flash(args)]
+    else:
+        out = [run(s, args) for s in (("cstrs", "cdu") if args.size == "both" else (args.size,))]
     for o in out:
         print(json.dumps(o))
     if args.json:
