@@ -223,7 +223,10 @@ int nnmpc_nn_create(nnmpc_nn** out, int32_t nlayers, const int32_t* dims,
                     int32_t with_uprev, const double* xscale, const double* ulb,
                     const double* uub, int32_t use_bf16, int32_t max_batch);
 int nnmpc_nn_destroy(nnmpc_nn* h);
-/* x, xs: B x nx; uprev (ignored when !with_uprev), us: B x nu; u: B x nu */
+/* x, xs: B x nx; uprev (ignored when !with_uprev), us: B x nu; u: B x nu.
+ * Non-finite inputs are not rejected and not laundered: a NaN (or an Inf that meets an opposite Inf) in a row of x, uprev, xs
+ * or us comes back as non-finite entries of that row of u, as numpy / Keras return them (the ReLU lets a NaN through; the
+ * clip keeps it); the other rows of the batch are unaffected.  The NN slots of nnmpc_cl_run behave the same. */
 int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* uprev,
                      const double* xs, const double* us, double* u, int32_t ptr_kind);
 int nnmpc_nn_last_ms(nnmpc_nn* h, double* gemm_ms, double* total_ms);

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void cl_nn_layer_k(const NNLayer* __restrict__
         float v = ((acc[r] + red[0][r][lane]) + red[1][r][lane]) + red[2][r][lane];
         const size_t row = (size_t)(d.row0 + r0 + r);
         if (d.last) o[row * nu + col] = v;
-        else out[row * ldA + col] = fmaxf(v + bb, 0.f);
+        else out[row * ldA + col] = __builtin_elementwise_maximum(v + bb, 0.f);   // IEEE 754-2019 maximum: a NaN stays a NaN (fmaxf returns 0)
       }
     }
   }

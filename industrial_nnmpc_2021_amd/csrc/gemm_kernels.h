@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_k(float* __restrict__ C, size
         const int col = n0 + wc * Cf::WT + mj * 32 + acc_col(lane);
         float v = acc[mi][mj][r];
         if (BIAS) v += bias[col];
-        if (RELU) v = v > 0.f ? v : 0.f;
+        if (RELU) v = relu_nan(v);
         C[(size_t)row * ldc + col] = v;
       }
 }

@@ -242,7 +242,7 @@ int nnmpc_nn_create(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, const 
     if (h->use_bf16) {
       const bool lastl = l == nlayers - 1;
       const int k16 = ((dims[l] + 63) / 64) * 64;
-      const int ldc = lastl ? 64 : ((dims[l + 1] + 63) / 64) * 64;
+      const int ldc = lastl ? np_ : ((dims[l + 1] + 63) / 64) * 64;   // head: the row length nn_combine_k reads (128 per 128 columns once nu > 64)
       const int nb = (!lastl && ldc >= 2 * WBN) ? WBN : (dims[l + 1] > 64 ? 128 : 64);   // WBN: the wide-tile kernel
       const int n16 = ((ldc + nb - 1) / nb) * nb;
       h->k16.push_back(k16); h->n16.push_back(n16); h->ldc16.push_back(ldc);

@@ -15,6 +15,9 @@
 namespace nnmpc {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+// ReLU of the fused epilogues.  IEEE 754-2019 maximum (one v_maximum3_f32): a NaN stays a NaN, as in numpy / Keras;
+// fmaxf(x, 0) and x > 0 ? x : 0 return 0 for it and a poisoned row would come back as an ordinary-looking move.
+__device__ __forceinline__ float relu_nan(float x) { return __builtin_elementwise_maximum(x, 0.f); }
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KC = 32;          // K chunk staged per barrier

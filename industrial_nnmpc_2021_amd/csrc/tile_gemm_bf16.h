@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_k(void* __restrict__ Cv, int
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             float x = acc[mi][mj][4 * j + e] + bv[e];
-            v[e] = RELU ? (x > 0.f ? x : 0.f) : x;
+            v[e] = RELU ? relu_nan(x) : x;
           }
           const size_t o = (size_t)(row0 + mi * 32) * (OUT == 2 ? 2 * ldc : ldc) + col;
           if (OUT == 2) {
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_wide_k(__bf16* __restrict__ 
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 const float x = acc[2 * h + m2][nt][e] + bv[e];
-                v[e] = RELU ? (x > 0.f ? x : 0.f) : x;
+                v[e] = RELU ? relu_nan(x) : x;
                 if (!SPLIT || plane == 1) acc[2 * h + m2][nt][e] = 0.f;
               }
               bf16x4 hv = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};

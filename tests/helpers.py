@@ -77,3 +77,197 @@ def oracle_box_rows(Ps, tq, nu, N, x0, lb, ub, rows):
         return [res[sub[r]] for r in rows]
     finally:
         shutil.rmtree(d, ignore_errors=True)
+
+
+# ---- structured-NN forward: inputs, references and the error measure shared by the NN parity tests ----------------------------
+
+def bf16_round(a):
+    """Round to nearest-even bf16 (returned as float32), like v_cvt_pk_bf16_f32 / the library's weight upload.  Inf stays Inf,
+    a finite value beyond the largest bf16 becomes Inf, NaN stays NaN (the carry of the rounding must not run into the sign)."""
+    f = np.ascontiguousarray(a, dtype=np.float32)
+    u = f.view(np.uint32).astype(np.uint64)
+    r = (((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16) & 0xFFFFFFFF
+    r = np.where(np.isnan(f), (u & 0x80000000) | 0x7FC00000, r)
+    return r.astype(np.uint32).view(np.float32).reshape(f.shape)
+
+
+def bf16_forward(W, x, uprev, xs, us, xscale):
+    """The structured forward (lib/controller_evaluation.py:863-886) with the bf16 path's roundings: inputs, weights
+    and hidden activations in bf16, sums and biases wider, head output unrounded.  ``W`` is any Keras-ordered list
+    [W1, b1, ..., Wout]: one matrix alone, or hidden layers of different widths."""
+    sc = (1.0 / np.asarray(xscale)).astype(np.float32) if xscale is not None else np.ones(x.shape[1], np.float32)
+
+    def mlp(a, b):
+        z = [a.astype(np.float32) * sc] + ([b.astype(np.float32)] if b is not None else []) + [xs.astype(np.float32) * sc, us.astype(np.float32)]
+        h = bf16_round(np.concatenate(z, axis=1)).astype(np.float64)
+        nl = (len(W) + 1) // 2
+        for l in range(nl - 1):
+            h = h @ bf16_round(W[2 * l]).astype(np.float64) + W[2 * l + 1].astype(np.float32).astype(np.float64)
+            h = bf16_round(np.maximum(h, 0.0)).astype(np.float64)
+        return (h @ bf16_round(W[-1]).astype(np.float64)).astype(np.float32).astype(np.float64)
+    return us + (mlp(x, uprev) - mlp(xs, us if uprev is not None else None))
+
+
+def nn_weights(rng, dims, wscale=1.0, bscale=0.05):
+    """Keras-ordered weights of an MLP with the layer widths ``dims`` = [din, h1, ..., nu]: He-scaled kernels (activations keep
+    their size from layer to layer whatever the depth), small biases on the hidden layers, none on the head."""
+    W = []
+    for i in range(len(dims) - 1):
+        W.append(wscale * rng.standard_normal((dims[i], dims[i + 1])) * np.sqrt(2.0 / dims[i]))
+        if i < len(dims) - 2:
+            W.append(bscale * rng.standard_normal(dims[i + 1]))
+    return W
+
+
+def share_on_bound(u, ulb, uub):
+    """Share of the entries of a clipped oracle output that sit exactly on a bound."""
+    return float(((u == np.ravel(ulb)) | (u == np.ravel(uub))).mean())
+
+
+def nn_case(seed, hidden, nx, nu, withu, B, *, eps=1.0, xscale=True, ulb=None, uub=None, steady_row=None):
+    """Weights and inputs of one structured-NN case from a seed, and what the fp64 oracle makes of them.
+
+    x = xs + eps N(0, 1), uprev = us + eps U(-1, 1), xs ~ 0.3 N(0, 1), us ~ U(-.5, .5): ``eps`` is the distance from the steady
+    state, i.e. the size of u - us.  Returns a dict with W, dims, the inputs, ``ref`` (the oracle's UNCLIPPED u), ``ref_clip``
+    (clipped to ulb / uub when given, else ref) and ``share`` (entries of ref_clip on a bound; 0 without bounds).
+    ``steady_row``: that row gets x = xs, uprev = us (u = clip(us) exactly, whatever the weights)."""
+    from oracle import nn as onn
+    rng = np.random.default_rng(seed)
+    dims = [2 * nx + (2 if withu else 1) * nu] + list(hidden) + [nu]
+    W = nn_weights(rng, dims)
+    xs = 0.3 * rng.standard_normal((B, nx))
+    us = rng.uniform(-0.5, 0.5, (B, nu))
+    x = xs + eps * rng.standard_normal((B, nx))
+    up = us + eps * rng.uniform(-1.0, 1.0, (B, nu)) if withu else None
+    xsc = rng.uniform(0.5, 2.0, nx) if xscale else None
+    if steady_row is not None and B > steady_row:
+        x[steady_row] = xs[steady_row]
+        if withu:
+            up[steady_row] = us[steady_row]
+    ref = onn.control_input(W, x, up, xs, us, xsc, None, None, withu)
+    c = dict(W=W, dims=dims, nx=nx, nu=nu, withu=withu, x=x, uprev=up, xs=xs, us=us, xscale=xsc, ulb=ulb, uub=uub, ref=ref,
+             ref_clip=ref, share=0.0)
+    if ulb is not None:
+        c["ref_clip"] = onn.control_input(W, x, up, xs, us, xsc, ulb, uub, withu)
+        c["share"] = share_on_bound(c["ref_clip"], ulb, uub)
+    return c
+
+
+def col_err(u, ref):
+    """Per output column: max over rows of |u - ref|, in units of max(1, max over rows of |ref[:, col]|)."""
+    return np.abs(u - ref).max(axis=0) / np.maximum(1.0, np.abs(ref).max(axis=0))
+
+
+def assert_cols_close(u, ref, tol, what=""):
+    """max_rows |u - ref| <= tol max(1, max_rows |ref[:, col]|) for EVERY column: a wrong low-magnitude column cannot hide
+    behind a large one."""
+    assert u.shape == ref.shape, (what, u.shape, ref.shape)
+    assert np.isfinite(u).all(), (what, "non-finite entries", int((~np.isfinite(u)).sum()))
+    e = col_err(u, ref)
+    assert (e <= tol).all(), (what, "worst column", int(e.argmax()), float(e.max()), "tol", tol)
+
+
+# The shape matrix of tests/test_nn_paths_gpu.py (every case runs in all three precisions), kept here so that
+# tests/test_cpu_nn_inputs.py can judge the same inputs with the oracle alone.  A sparse product: every value of every axis
+# appears at least once --
+#   depth: one matrix, one hidden layer, three, five;  hidden widths at and around every dispatch threshold of nnmpc_nn_create /
+#   nnmpc_nn_forward (64-tile <= 64 < 128-tile; bf16: wide tile from a padded width of 416, i.e. widths >= 385);  ragged nets;
+#   nu in {1, 5, 6, 16, 32, 64, 65, 80};  din a multiple of 64 (64, 192, 512) and not;  with / without uprev and xscale;
+#   batch 1, 127, 128, 129, max_batch - 1, max_batch, max_batch + 1, 3 max_batch + 7 for max_batch 128 and 256;  two cases
+#   through forward_device.
+# (name, hidden widths, nx, nu, with uprev, xscale given, B, max_batch, through forward_device)
+NN_SHAPE_CASES = [
+    ("linear_b1", [], 12, 6, True, True, 1, 128, False),
+    ("linear_din512", [], 240, 32, False, False, 127, 128, False),
+    ("h1", [1], 12, 6, True, True, 128, 128, False),
+    ("h63_nu5", [63], 7, 5, False, True, 129, 128, False),
+    ("h64_din64", [64], 16, 16, True, False, 127, 128, False),
+    ("h65", [65], 12, 6, False, True, 128, 128, False),
+    ("h127_nu1", [127], 5, 1, True, True, 129, 128, False),
+    ("h128_3mb7", [128], 12, 6, True, False, 3 * 128 + 7, 128, False),
+    ("h129_nu64_din192", [129], 32, 64, True, True, 255, 256, False),
+    ("h130", [130], 12, 6, False, True, 256, 256, False),
+    ("h200", [200], 12, 6, True, True, 257, 256, False),
+    ("h384_385", [384, 385], 12, 6, True, True, 130, 128, False),
+    ("h415_3mb7_dev", [415], 252, 32, False, True, 3 * 256 + 7, 256, True),
+    ("h416_b1", [416], 12, 6, True, False, 1, 256, False),
+    ("h417", [417], 12, 6, False, True, 127, 256, False),
+    ("h831", [831], 252, 32, True, True, 128, 128, False),
+    ("cdu_832x3_dev", [832, 832, 832], 252, 32, False, True, 129, 128, True),
+    ("h833", [833], 12, 6, True, False, 128, 256, False),
+    ("h1024_din512", [1024], 240, 32, False, True, 130, 128, False),
+    ("five_hidden", [128, 64, 416, 130, 65], 12, 6, True, True, 200, 128, False),
+    ("taper_832_416_64", [832, 416, 64], 252, 32, False, True, 300, 128, False),
+    ("grow_64_832", [64, 832], 12, 6, True, True, 129, 128, False),
+    ("ragged_130_417_200", [130, 417, 200], 7, 5, False, False, 131, 128, False),
+    ("nu65", [128], 10, 65, False, True, 129, 128, False),
+    ("nu80_taper", [416, 64], 24, 80, True, True, 257, 256, False),
+]
+
+
+def nn_shape_case(i, **kw):
+    """nn_case of NN_SHAPE_CASES[i] (seed = 100 + i)."""
+    name, hidden, nx, nu, withu, xsc, B, mb, dev = NN_SHAPE_CASES[i]
+    return nn_case(100 + i, hidden, nx, nu, withu, B, xscale=xsc, **kw)
+
+
+# Architectures of the property tests (exactness, stale state, non-finite inputs, clip): one per GEMM kernel family --
+# 64-wide tiles; 128-wide tiles with a partial last column tile; the wide tile followed by the 128- and the 64-wide one.
+NN_PROPERTY_NETS = [("n64", [64, 64], 12, 6, True), ("n130_200", [130, 200], 7, 5, False), ("taper", [832, 416, 64], 40, 32, False)]
+# distance from the steady state at which the oracle alone leaves at most 5 % of the entries on the bounds -1 / +1
+NN_BOUNDED_EPS = 0.1
+
+
+# ---- grouped closed-loop NN forward (cl_nn_layer_k): the network mix of tests/test_closed_loop_nn_gpu.py ------------------------
+# (name, hidden widths, with uprev, instances) on the mini_cstrs plant (Nx = 6, Nu = 3: first-layer K = 18 / 15, neither a multiple
+# of the kernel's 4 K slices).  Side by side in ONE batch: 1, 2, 3 and 5 weight matrices (the shallow nets end at an earlier layer
+# index while the others go on using the ping-pong buffers); widths 40, 64, 65, 130, 832, 1024 and NN_MAXK = 2048; with and
+# without uprev; 1, 3, 8 and 9 instances (two rows each, walked in blocks of NN_RB = 8 rows).
+CL_NN_MIX = [
+    ("w40", [40], True, 1),
+    ("linear", [], False, 3),
+    ("w64_65", [64, 65], True, 8),
+    ("deep_130_832_1024_65", [130, 832, 1024, 65], False, 9),
+    ("w2048", [2048], True, 1),
+]
+CL_NN_HEAD_SCALE = 1.0            # gain of u - us on [xhat - xs; uprev - us]: |u - us| stays > 100 x the f32 tolerance, the loop inside the box (share asserted)
+
+
+def cl_nn_weights(seed, din, hidden, nu, head_scale=CL_NN_HEAD_SCALE):
+    """He-scaled hidden layers (the difference of the two passes keeps its size through any depth), head scaled down."""
+    W = nn_weights(np.random.default_rng(seed), [din] + list(hidden) + [nu], bscale=0.1)
+    W[-1] = head_scale * W[-1]
+    return W
+
+
+def cl_one_step_reference(W, xscale, withu, ulb, uub, rec_u, rec_xhat, rec_xs, rec_us, uprev0, nx):
+    """What the oracle makes of the recorded inputs of every step of one instance: (unclipped u, clipped u), rows = steps.
+    The estimate a step's controller sees is row t + 1 of the xhat record: cl_filter_k overwrites xhat with the corrected estimate
+    before cl_expand_k reads it, and cl_post_k records it as row t + 1; uprev of step t is u[t - 1] (step 0: the initial uprev)."""
+    from oracle import nn as onn
+    xh = rec_xhat[1:, :nx]
+    up = np.concatenate((np.ravel(uprev0)[None, :], rec_u[:-1]), axis=0)
+    free = onn.control_input(W, xh, up, rec_xs, rec_us, np.ravel(xscale), None, None, withu)
+    clipped = onn.control_input(W, xh, up, rec_xs, rec_us, np.ravel(xscale), np.ravel(ulb), np.ravel(uub), withu)
+    return free, clipped
+
+
+def cl_assert_one_step_identity(res, ctls, common, tol, what):
+    """The one-step identity u[t] == clip(oracle(recorded inputs of step t)) for every NN instance of a
+    simulate_closed_loop_batch result, per column within tol max(1, |ref|); every column must carry a signal (|u - us| well above
+    the tolerance at some step).  Returns (share of the oracle's entries on a bound, worst column error)."""
+    Nx = common["A"].shape[0]
+    on, total, worst = 0, 0, 0.0
+    for i, (c, s, seed) in enumerate(res["instances"]):
+        ctl = ctls[c]
+        if not hasattr(ctl, "regulator_weights"):
+            continue
+        free, ref = cl_one_step_reference(ctl.regulator_weights, ctl.xscale, ctl.nnwithuprev, common["ulb"], common["uub"],
+                                          res["u"][i], res["xhat"][i], res["xs"][i], res["us"][i], common["uprev"], Nx)
+        assert (np.abs(free - res["us"][i]).max(axis=0) > 100 * tol).all(), (what, i, "u - us too small to test anything")
+        on += int(((ref == np.ravel(common["ulb"])) | (ref == np.ravel(common["uub"]))).sum())
+        total += ref.size
+        assert_cols_close(res["u"][i], ref, tol, (what, "instance", i, (c, s, seed)))
+        worst = max(worst, float(col_err(res["u"][i], ref).max()))
+    assert total > 0
+    return on / total, worst

@@ -268,13 +268,11 @@ def test_cdu_size_smoke():
     ds = np.repeat(rng.uniform(-0.1, 0.1, (2, Nd)), T // 2, axis=0)
     mpc = lm.LinearMPCController(N=pl["N"], **common)
     nns = []
-    for w in (832, 896, 960, 1024, 832, 896, 960, 1024):
-        dims = [2 * Nx + Nu, w, w, w, Nu]
-        W = []
-        for i in range(4):
-            W.append(0.05 * rng.standard_normal((dims[i], dims[i + 1])) / np.sqrt(dims[i]))
-            if i < 3:
-                W.append(0.01 * rng.standard_normal(dims[i + 1]))
+    from tests.helpers import cl_nn_weights
+    for j, w in enumerate((832, 896, 960, 1024, 832, 896, 960, 1024)):
+        # He-scaled hidden layers, head scaled down: u - us is far above the f32 tolerance of the one-step identity below (with
+        # kernels of 0.05 / sqrt(fan-in) it was ~1e-5 and any forward, right or wrong, returned us)
+        W = cl_nn_weights(30 + j, 2 * Nx + Nu, [w, w, w], Nu, head_scale=0.5)
         nns.append(ce._get_nn_controller(mpc, W, rng.uniform(0.5, 2.0, Nx), False))
     plant = lm.LinearPlantSimulator(A=pl["A"], B=pl["B"], C=pl["C"], Bp=Bd, Rv=common["Rv"], sample_time=1.0, x0=np.zeros((Nx, 1)))
     res = simulate_closed_loop_batch(plant, [mpc] + nns, scenarios=[(sp, ds)], Nsim=T, seeds=[1])
@@ -284,6 +282,11 @@ def test_cdu_size_smoke():
     h = _host(dict(A=pl["A"], B=pl["B"], C=pl["C"], Bp=Bd, Rv=common["Rv"]), lm.LinearMPCController(N=pl["N"], **common),
               sp[:20], ds[:20], 20, 1, np.zeros((Nx, 1)))
     assert np.abs(res["u"][0][:20] - h["u"]).max() < 1e-8 and np.abs(res["avg"][0][:21] - h["avg"]).max() < 1e-8
+    # the eight networks: every step of every one against the fp64 oracle on the recorded inputs of that step (f32 tolerance)
+    from tests.helpers import cl_assert_one_step_identity
+    share, worst = cl_assert_one_step_identity(res, [mpc] + nns, common, 1e-4, "cdu size")
+    print(f"cdu size: share on a bound {share:.4f}, worst column error {worst:.3e}")
+    assert share <= 0.05, share
 
 
 def test_baselines_match_reference_fixture(golden_dir):

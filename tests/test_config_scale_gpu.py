@@ -13,6 +13,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.helpers import assert_cols_close, share_on_bound
+
 pytestmark = pytest.mark.gpu
 
 
@@ -191,8 +193,10 @@ def test_nn_config_1m_states(mode, tol, withuprev):
         if i < 3:
             W.append(0.05 * rng.standard_normal(dims[i + 1]))
     xscale = rng.uniform(0.5, 2.0, nx)
-    x = rng.standard_normal((B, nx)); xs = 0.3 * rng.standard_normal((B, nx)); us = rng.uniform(-0.5, 0.5, (B, nu))
-    up = us + rng.uniform(-0.3, 0.3, (B, nu)) if withuprev else None
+    # near the steady state (x - xs ~ 0.1 N(0, 1), uprev - us ~ 0.1 U(-1, 1)): the clip leaves the arithmetic visible -- a clipped
+    # entry equals the oracle whatever the GEMM produced; the share of such entries is asserted below
+    xs = 0.3 * rng.standard_normal((B, nx)); x = xs + 0.1 * rng.standard_normal((B, nx)); us = rng.uniform(-0.5, 0.5, (B, nu))
+    up = us + 0.1 * rng.uniform(-1.0, 1.0, (B, nu)) if withuprev else None
     x[7] = xs[7]                                            # steady-state row
     if withuprev:
         up[7] = us[7]
@@ -205,9 +209,20 @@ def test_nn_config_1m_states(mode, tol, withuprev):
     u = du.to_host()
     rows = np.concatenate(([7, 0, B - 1, 262143, 262144], rng.choice(B, 4091, replace=False)))
     ref = onn.control_input(W, x[rows], up[rows] if withuprev else None, xs[rows], us[rows], xscale, -np.ones(nu), np.ones(nu), withuprev)
+    assert share_on_bound(ref, -np.ones(nu), np.ones(nu)) <= 0.05
     assert np.abs(u[rows] - ref).max() <= tol * max(1.0, np.abs(ref).max())
+    assert_cols_close(u[rows], ref, tol, mode)
     assert np.array_equal(u[7], np.clip(us[7], -1, 1))       # both passes identical: exact
     assert np.isfinite(u).all() and (np.abs(u) <= 1.0).all()
+    # (|u| <= 1 holds by construction of the clip: kept only beside the comparisons that can fail.)  The layers unclipped, far
+    # from the steady state (x ~ N(0, 1)), on the states of the last sub-batch:
+    net.close()
+    nb = 4096
+    x2 = rng.standard_normal((nb, nx)); up2 = us[-nb:] + rng.uniform(-0.3, 0.3, (nb, nu)) if withuprev else None
+    net = StructuredNN(W, nx, nu, nnwithuprev=withuprev, xscale=xscale, max_batch=1024,
+                       use_bf16={"f32": False, "bf16": True, "bf16x3": "split"}[mode])
+    assert_cols_close(net.forward(x2, up2, xs[-nb:], us[-nb:]),
+                      onn.control_input(W, x2, up2, xs[-nb:], us[-nb:], xscale, None, None, withuprev), tol, (mode, "unclipped"))
     net.close()
     for a in (dx, dxs, dus, du, dup):
         if a is not None:

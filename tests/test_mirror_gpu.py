@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.helpers import assert_cols_close, bf16_forward, share_on_bound
+
 pytestmark = pytest.mark.gpu
 
 
@@ -109,13 +111,21 @@ def test_nn_cdu_shape_batch_vs_oracle():
         if i < 3:
             W.append(0.05 * rng.standard_normal(dims[i + 1]))
     B = 1000
-    x, xs = rng.standard_normal((B, nx)), 0.3 * rng.standard_normal((B, nx))
+    xs = 0.3 * rng.standard_normal((B, nx))
+    x = xs + 0.1 * rng.standard_normal((B, nx))                # near the steady state: the clip leaves the arithmetic visible
     us = rng.uniform(-.5, .5, (B, nu))
     xscale = rng.uniform(0.5, 2.0, nx)
     net = StructuredNN(W, nx, nu, nnwithuprev=False, xscale=xscale, ulb=-np.ones(nu), uub=np.ones(nu), max_batch=512)
     u = net.forward(x, None, xs, us)
     ref = onn.control_input(W, x, None, xs, us, xscale, -np.ones(nu), np.ones(nu), False)
+    assert share_on_bound(ref, -np.ones(nu), np.ones(nu)) <= 0.05             # a clipped entry equals the oracle whatever the GEMM did
     assert np.abs(u - ref).max() <= 1e-4 * max(1.0, np.abs(ref).max())
+    assert_cols_close(u, ref, 1e-4, "clipped")
+    # the same weights without bounds and far from the steady state (x ~ N(0, 1)): nothing is clipped
+    x = rng.standard_normal((B, nx))
+    free = StructuredNN(W, nx, nu, nnwithuprev=False, xscale=xscale, max_batch=512)
+    assert_cols_close(free.forward(x, None, xs, us), onn.control_input(W, x, None, xs, us, xscale, None, None, False), 1e-4, "unclipped")
+    free.close()
     assert net.forward(x[:0], None, xs[:0], us[:0]).shape == (0, nu)      # empty batch
 
 
@@ -143,29 +153,6 @@ def test_nn_bf16_path_tolerance():
     assert np.abs(u[0] - us[0]).max() < 1e-12       # steady-state row: both passes identical -> exact
 
 
-def _bf16(a):
-    """Round to nearest-even bf16 (returned as float32), like v_cvt_pk_bf16_f32 / the library's weight upload."""
-    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(np.float32)
-
-
-def _bf16_forward(W, x, uprev, xs, us, xscale):
-    """The structured forward (lib/controller_evaluation.py:863-886) with the bf16 path's roundings: inputs, weights
-    and hidden activations in bf16, sums and biases wider, head output unrounded."""
-    sc = (1.0 / xscale).astype(np.float32) if xscale is not None else np.ones(x.shape[1], np.float32)
-
-    def mlp(a, b):
-        z = [a.astype(np.float32) * sc] + ([b.astype(np.float32)] if b is not None else []) + [xs.astype(np.float32) * sc, us.astype(np.float32)]
-        h = _bf16(np.concatenate(z, axis=1)).astype(np.float64)
-        nl = (len(W) + 1) // 2
-        for l in range(nl - 1):
-            h = h @ _bf16(W[2 * l]).astype(np.float64) + W[2 * l + 1].astype(np.float32).astype(np.float64)
-            h = _bf16(np.maximum(h, 0.0)).astype(np.float64)
-        return (h @ _bf16(W[-1]).astype(np.float64)).astype(np.float32).astype(np.float64)
-    return us + (mlp(x, uprev) - mlp(xs, us if uprev is not None else None))
-
-
 @pytest.mark.parametrize("hid,withu,B,mb", [(832, False, 700, 512), (832, True, 40, 128), (960, False, 1300, 1024),
                                             (448, True, 300, 256), (416, False, 257, 128), (1024, False, 520, 512)])
 def test_nn_bf16_wide_tile_kernel_shapes(hid, withu, B, mb):
@@ -187,7 +174,7 @@ def test_nn_bf16_wide_tile_kernel_shapes(hid, withu, B, mb):
     xscale = rng.uniform(0.5, 2.0, nx)
     net = StructuredNN(W, nx, nu, nnwithuprev=withu, xscale=xscale, max_batch=mb, use_bf16=True)
     u = net.forward(x, up if withu else None, xs, us)
-    ref = _bf16_forward(W, x, up if withu else None, xs, us, xscale)
+    ref = bf16_forward(W, x, up if withu else None, xs, us, xscale)
     assert np.abs(u - ref).max() <= 4e-3 * max(1.0, np.abs(ref).max()), np.abs(u - ref).max()
     net.close()
 
@@ -209,16 +196,25 @@ def test_nn_split_bf16_is_f32_grade(hid, withu, B, mb):
         W.append(rng.standard_normal((dims[i], dims[i + 1])) * np.sqrt(2.0 / dims[i]))
         if i < 3:
             W.append(0.05 * rng.standard_normal(dims[i + 1]))
-    x, xs = rng.standard_normal((B, nx)), 0.3 * rng.standard_normal((B, nx))
-    us, up = rng.uniform(-.5, .5, (B, nu)), rng.uniform(-1, 1, (B, nu))
+    xs = 0.3 * rng.standard_normal((B, nx))
+    us = rng.uniform(-.5, .5, (B, nu))
+    x, up = xs + 0.1 * rng.standard_normal((B, nx)), us + 0.1 * rng.uniform(-1, 1, (B, nu))   # near the steady state: few clipped entries
     x[0] = xs[0]; up[0] = us[0]                                # steady state: u = clip(us) exactly, whatever the weights
     xscale = rng.uniform(0.5, 2.0, nx)
     net = StructuredNN(W, nx, nu, nnwithuprev=withu, xscale=xscale, ulb=-np.ones(nu), uub=np.ones(nu), max_batch=mb, use_bf16="split")
     u = net.forward(x, up if withu else None, xs, us)
     net.close()
     ref = onn.control_input(W, x, up if withu else None, xs, us, xscale, -np.ones(nu), np.ones(nu), withu)
+    assert share_on_bound(ref, -np.ones(nu), np.ones(nu)) <= 0.05             # a clipped entry equals the oracle whatever the GEMM did
     assert np.abs(u - ref).max() <= 1e-4 * max(1.0, np.abs(ref).max()), np.abs(u - ref).max()
+    assert_cols_close(u, ref, 1e-4, "clipped")
     assert np.array_equal(u[0], np.clip(us[0], -1, 1))
+    # without bounds, far from the steady state (x ~ N(0, 1)): nothing is clipped
+    x, up = rng.standard_normal((B, nx)), rng.uniform(-1, 1, (B, nu))
+    free = StructuredNN(W, nx, nu, nnwithuprev=withu, xscale=xscale, max_batch=mb, use_bf16="split")
+    u = free.forward(x, up if withu else None, xs, us)
+    free.close()
+    assert_cols_close(u, onn.control_input(W, x, up if withu else None, xs, us, xscale, None, None, withu), 1e-4, "unclipped")
 
 
 def test_nn_bf16_wide_tile_kernel_row_slices(monkeypatch):
