@@ -48,7 +48,7 @@ extern "C" {
 /* per-problem status written by nnmpc_qp_solve_batch */
 #define NNMPC_ST_OPTIMAL 0   /* KKT conditions verified in fp64 */
 #define NNMPC_ST_MAXITER 1   /* round / polish budget exhausted, not certified */
-#define NNMPC_ST_NUMERIC 2   /* non-positive pivot or NaN */
+#define NNMPC_ST_NUMERIC 2   /* non-positive pivot or NaN; nnmpc_ts_*: also an infeasible or rank-deficient problem (see there) */
 
 typedef struct nnmpc_qp nnmpc_qp;
 typedef struct nnmpc_nn nnmpc_nn;
@@ -268,14 +268,31 @@ int nnmpc_chain_last_ms(nnmpc_chain* c, double* total_ms, double* solve_ms);
  *     min 1/2 us' Pr us + (Qb b + Qy y + q0)' us   s.t.  E us = Eb b,  ulb <= us <= uub          (nu variables)
  * with b = tb [ysp; dhat], y = ysp - Cd dhat; the shared matrices are formed once on the host (fp64).  One wave per
  * problem: primal-dual active-set iterations on the KKT system of the free inputs and the equalities (<= nu + nz
- * unknowns, Gaussian elimination with partial pivoting in LDS), fp64 throughout, KKT-certified. */
+ * unknowns, Gaussian elimination with partial pivoting in LDS), fp64 throughout, KKT-certified.
+ *
+ * Multipliers: Pr us + q + E' lam_eq + mu_ub - mu_lb = 0 with mu_ub, mu_lb >= 0 (mu_ub only where active = 1, mu_lb only
+ * where active = 2): lam_eq carries the sign of "+ E' lam_eq" in the gradient of the Lagrangian.
+ * Bounds: an input flagged active (1 / 2) equals its bound bitwise; a free input (0) satisfies ulb - 1e-9 <= us <= uub + 1e-9:
+ * the feasibility slack of this solver is the fixed 1e-9 (absolute, in the units of us; bound_tol of nnmpc_qp_opts belongs to
+ * the regulator only).  A bound met within the slack (weakly active, multiplier 0) may come back in either state.
+ * Status per problem: NNMPC_ST_OPTIMAL = KKT point, certified; NNMPC_ST_NUMERIC = no answer -- a NaN / Inf in q or e, some
+ * ulb_i > uub_i or a NaN bound (then every problem of the handle), E without full row rank (a repeated or a zero row, nz > the
+ * number of inputs), or NO point of the box satisfies E us = e (infeasible: an unreachable setpoint): us = NaN, active = 0;
+ * NNMPC_ST_MAXITER = the 600 steps ran out or the final certificate failed: us is the last iterate, not certified.
+ * Scaling: the rows of E are equilibrated against Pr by powers of two when the handle is created (lam_eq is returned in the
+ * caller's units), so (Pr, q) -> beta (Pr, q) and (E, e) -> alpha (E, e) change nothing but rounding: solved with
+ * max|Pr| / max|E| from 1e-16 to 1e17 (tests/test_target_kernel_gpu.py; before the equilibration every problem beyond
+ * about 1e6 was refused as NNMPC_ST_NUMERIC). */
 typedef struct nnmpc_ts nnmpc_ts;
-/* Pr: nu x nu (symmetric positive definite), E: nz x nu, lb/ub: nu.  nu + nz <= 64 (the KKT system of a step sits on the 64 lanes of one wave), nz <= 16. */
+/* Pr: nu x nu (symmetric positive definite), E: nz x nu (full row rank, so nz <= nu), lb/ub: nu.  nu >= 1, nz >= 0 and
+ * nu + nz <= 64 -- the KKT system of a step sits on the 64 lanes of one wave; that is the only size limit (NNMPC_EINVAL beyond). */
 int nnmpc_ts_create(nnmpc_ts** out, int32_t nu, int32_t nz, const double* Pr, const double* E,
                     const double* lb, const double* ub);
 int nnmpc_ts_destroy(nnmpc_ts* h);
-/* q: B x nu, e: B x nz  ->  us: B x nu, lam_eq: B x nz (multipliers of the equalities, may be NULL), active: B x nu
- * bytes (0 free / 1 at uub / 2 at ulb, may be NULL), status: B (NNMPC_ST_*) */
+/* q: B x nu, e: B x nz (may be NULL when nz = 0)  ->  us: B x nu, lam_eq: B x nz (multipliers of the equalities in the
+ * convention above, may be NULL), active: B x nu bytes (0 free / 1 at uub / 2 at ulb, may be NULL), status: B (NNMPC_ST_*).
+ * The problems of a batch are independent: a row's outputs do not depend on its position or its neighbours.  B = 0: NNMPC_OK,
+ * nothing is written. */
 int nnmpc_ts_solve_batch(nnmpc_ts* h, int32_t B, const double* q, const double* e, double* us,
                          double* lam_eq, uint8_t* active, int32_t* status, int32_t ptr_kind);
 

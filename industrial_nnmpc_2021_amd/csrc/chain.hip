@@ -9,7 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <vector>
 #include "../../include/nnmpc.h"
 #include "common.h"
@@ -147,33 +149,42 @@ __device__ __forceinline__ int ts_ge_solve(double* K, int ld, int N, double* sol
   return 0;
 }
 
-// rows of the system for the current bound states: free input i: [Pr[i,:], E[:,i]'] = rf;  held input i: unit row = rh;
-// equality k: [E[k,:], 0] = re
+// rows of the system for the current bound states.  free input i: [Pr[i,:], E[:,i]'] = rf;  held input i: dsc * unit row = dsc * rh;
+// equality k: [E[k,:], 0] = re.  The columns of the held inputs are folded into the right-hand sides (rh of a held input is the
+// value it is held at), so the unit rows are decoupled from the rest: a held input comes out of the elimination EXACTLY, whatever
+// the pivot order, and what is solved in earnest is the KKT system of the free inputs and the equalities alone.  E is the
+// row-equilibrated copy (see nnmpc_ts_create) and dsc the size of Pr, so that the pivot test compares rows of one size.
 __device__ __forceinline__ void ts_assemble(double* K, int ld, int nu, int nz, const double* __restrict__ Pr, const double* __restrict__ E,
-                                            int lane, int st, double rf, double rh, double re) {
+                                            int lane, int st, double rf, double rh, double re, double dsc) {
   const int N = nu + nz;
+  const bool solved = lane < N && !(lane < nu && st != 0);   // a free input's or an equality's row
+  double* row = K + (size_t)(lane < N ? lane : 0) * ld;
+  double fold = 0.0;
+  for (int c = 0; c < nu; ++c) {
+    const int sc = __shfl(st, c);                            // (wave-uniform) state of input c and the value it is held at
+    const double hv = __shfl(rh, c);
+    if (solved) {
+      const double a = lane < nu ? Pr[(size_t)lane * nu + c] : E[(size_t)(lane - nu) * nu + c];
+      if (sc != 0) { row[c] = 0.0; if (hv != 0.0) fold += a * hv; } else row[c] = a;
+    }
+  }
   if (lane < nu) {
-    double* row = K + (size_t)lane * ld;
     if (st == 0) {
-      for (int c = 0; c < nu; ++c) row[c] = Pr[(size_t)lane * nu + c];
       for (int k = 0; k < nz; ++k) row[nu + k] = E[(size_t)k * nu + lane];
-      row[N] = rf;
+      row[N] = rf - fold;
     } else {
-      for (int c = 0; c < N; ++c) row[c] = c == lane ? 1.0 : 0.0;
-      row[N] = rh;
+      for (int c = 0; c < N; ++c) row[c] = c == lane ? dsc : 0.0;
+      row[N] = rh * dsc;
     }
   } else if (lane < N) {
-    double* row = K + (size_t)lane * ld;
-    const int k = lane - nu;
-    for (int c = 0; c < nu; ++c) row[c] = E[(size_t)k * nu + c];
     for (int c = nu; c < N; ++c) row[c] = 0.0;
-    row[N] = re;
+    row[N] = re - fold;
   }
   __syncthreads();
 }
 
 __global__ __launch_bounds__(64) void ts_solve_k(int B, int nu, int nz, const double* __restrict__ Pr, const double* __restrict__ E,
-                                                 const double* __restrict__ lbv, const double* __restrict__ ubv,
+                                                 const double* __restrict__ esc, double dsc, const double* __restrict__ lbv, const double* __restrict__ ubv,
                                                  const double* __restrict__ q, const double* __restrict__ e,
                                                  double* __restrict__ us, double* __restrict__ lam_eq,
                                                  unsigned char* __restrict__ active, int* __restrict__ status, double bound_tol) {
@@ -188,6 +199,7 @@ __global__ __launch_bounds__(64) void ts_solve_k(int B, int nu, int nz, const do
   const bool isu = lane < nu, isy = lane >= nu && lane < N;
   const double lbi = isu ? lbv[lane] : 0.0, ubi = isu ? ubv[lane] : 0.0;
   const double qi = isu ? qp_[lane] : 0.0;
+  const double sk = isy ? esc[lane - nu] : 1.0;              // E holds row k scaled by esc[k] (a power of two): so is e, and y is lam_eq / esc
   // inputs a comparison cannot reason about
   int invalid = 0;
   if (isu) invalid = !(lbi <= ubi) || !(fabs(qi) <= 1.79e308);
@@ -198,7 +210,7 @@ __global__ __launch_bounds__(64) void ts_solve_k(int B, int nu, int nz, const do
   if (__any(invalid)) result = NNMPC_ST_NUMERIC;
   else {
     // ---- optimum under the equalities alone
-    ts_assemble(K, ld, nu, nz, Pr, E, lane, 0, -qi, 0.0, isy ? ep[lane - nu] : 0.0);
+    ts_assemble(K, ld, nu, nz, Pr, E, lane, 0, -qi, 0.0, isy ? sk * ep[lane - nu] : 0.0, dsc);
     if (ts_ge_solve(K, ld, N, sol, lane)) result = NNMPC_ST_NUMERIC;     // E itself is rank deficient
     else {
       x = isu ? sol[lane] : 0.0;
@@ -220,7 +232,7 @@ __global__ __launch_bounds__(64) void ts_solve_k(int B, int nu, int nz, const do
         // ---- steps towards bound pi
         for (;; ++it) {
           if (it >= TS_MAXIT) { done = true; break; }
-          ts_assemble(K, ld, nu, nz, Pr, E, lane, st, lane == pi ? -sp : 0.0, 0.0, 0.0);
+          ts_assemble(K, ld, nu, nz, Pr, E, lane, st, lane == pi ? -sp : 0.0, 0.0, 0.0, dsc);
           if (ts_ge_solve(K, ld, N, sol, lane)) { result = NNMPC_ST_NUMERIC; done = true; break; }
           const double z = isu ? sol[lane] : 0.0, v = isy ? sol[lane] : 0.0;
           double vi = 0.0;                                   // rate of this input's bound multiplier
@@ -256,11 +268,28 @@ __global__ __launch_bounds__(64) void ts_solve_k(int B, int nu, int nz, const do
       }
       if (result == NNMPC_ST_OPTIMAL) {
         // ---- final solve on the final set, then the KKT conditions in full
-        ts_assemble(K, ld, nu, nz, Pr, E, lane, st, -qi, st == 1 ? ubi : lbi, isy ? ep[lane - nu] : 0.0);
+        ts_assemble(K, ld, nu, nz, Pr, E, lane, st, -qi, st == 1 ? ubi : lbi, isy ? sk * ep[lane - nu] : 0.0, dsc);
         if (ts_ge_solve(K, ld, N, sol, lane)) result = NNMPC_ST_NUMERIC;
         else {
-          x = isu ? sol[lane] : 0.0;
-          y = isy ? sol[lane] : 0.0;
+          // one step of fixed-precision refinement: elimination with partial pivoting is backward stable in norm only, and
+          // where the multipliers are orders of magnitude larger than the inputs (|q| >> |Pr|) the equality rows pay for
+          // it; the residual of the re-assembled system and a second solve make the result backward stable row by row
+          const double s0 = lane < N ? sol[lane] : 0.0;
+          ts_assemble(K, ld, nu, nz, Pr, E, lane, st, -qi, st == 1 ? ubi : lbi, isy ? sk * ep[lane - nu] : 0.0, dsc);
+          if (lane < N) {
+            double* row = K + (size_t)lane * ld;
+            double r = row[N];
+            for (int c = 0; c < N; ++c) r -= row[c] * sol[c];
+            row[N] = r;
+          }
+          __syncthreads();
+          const int sing = ts_ge_solve(K, ld, N, sol, lane);   // (same matrix as above: never singular here)
+          const double s1 = sing || lane >= N ? s0 : s0 + sol[lane];
+          __syncthreads();
+          if (lane < N) sol[lane] = s1;
+          __syncthreads();
+          x = isu ? s1 : 0.0;
+          y = isy ? s1 : 0.0;
           int bad = 0;
           double scale = 1.0;
           if (isu) {
@@ -273,9 +302,9 @@ __global__ __launch_bounds__(64) void ts_solve_k(int B, int nu, int nz, const do
             if (st == 1) x = ubi; else if (st == 2) x = lbi;
           }
           if (isy) {
-            double r = -ep[lane - nu];
+            double r = -sk * ep[lane - nu];
             for (int c = 0; c < nu; ++c) r += E[(size_t)(lane - nu) * nu + c] * sol[c];
-            bad = !(fabs(r) <= 1e-9 * fmax(1.0, fabs(ep[lane - nu])));
+            bad = !(fabs(r) <= 1e-9 * sk * fmax(1.0, fabs(ep[lane - nu])));
           }
           if (__any(bad)) result = NNMPC_ST_MAXITER;
         }
@@ -286,7 +315,7 @@ __global__ __launch_bounds__(64) void ts_solve_k(int B, int nu, int nz, const do
     us[(size_t)p * nu + lane] = result == NNMPC_ST_NUMERIC ? __longlong_as_double(0x7ff8000000000000ll) : x;
     if (active) active[(size_t)p * nu + lane] = result == NNMPC_ST_NUMERIC ? 0 : (unsigned char)st;
   }
-  if (lam_eq && isy) lam_eq[(size_t)p * nz + lane - nu] = y;
+  if (lam_eq && isy) lam_eq[(size_t)p * nz + lane - nu] = y * sk;
   if (lane == 0) status[p] = result;
 }
 
@@ -503,7 +532,8 @@ int nnmpc_chain_last_ms(nnmpc_chain* c, double* total_ms, double* solve_ms) {
 // ---------------------------------------------------------------------------------------------------------------
 struct nnmpc_ts {
   int device = 0, nu = 0, nz = 0;
-  double *Pr = nullptr, *E = nullptr, *lb = nullptr, *ub = nullptr;
+  double *Pr = nullptr, *E = nullptr, *esc = nullptr, *lb = nullptr, *ub = nullptr;   // E: rows scaled by esc
+  double dsc = 1.0;
   hipStream_t stream = nullptr;
   void* stage[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t stage_cap[6] = {0, 0, 0, 0, 0, 0};
@@ -536,16 +566,35 @@ int nnmpc_ts_create(nnmpc_ts** out, int32_t nu, int32_t nz, const double* Pr, co
     set_error("nnmpc_ts_create: no HIP device available (this library has no CPU fallback)");
     return NNMPC_EHIP;
   }
+  // Equilibration, by powers of two (exact): every row of E is brought to the size of Pr, and the unit rows of held inputs
+  // too (dsc).  Without it the pivot test of ts_ge_solve -- relative to the largest entry of the WHOLE KKT matrix -- refused
+  // every problem with max|Pr| / max|E| beyond about 1e6, and partial pivoting mixed rows of very different size.
+  auto pow2_near = [](double v) {
+    if (!(v > 0.0) || !std::isfinite(v)) return 1.0;
+    return std::ldexp(1.0, std::max(-900, std::min(900, (int)std::lround(std::log2(v)))));
+  };
+  double pmax = 0.0;
+  for (size_t i = 0; i < (size_t)nu * nu; ++i) if (std::isfinite(Pr[i])) pmax = std::max(pmax, std::fabs(Pr[i]));
+  std::vector<double> Es((size_t)std::max(nz, 1) * nu, 0.0), esc(std::max(nz, 1), 1.0);
+  for (int k = 0; k < nz; ++k) {
+    double emax = 0.0;
+    for (int c = 0; c < nu; ++c) if (std::isfinite(E[(size_t)k * nu + c])) emax = std::max(emax, std::fabs(E[(size_t)k * nu + c]));
+    esc[k] = pmax > 0.0 && emax > 0.0 ? pow2_near(pmax / emax) : 1.0;
+    for (int c = 0; c < nu; ++c) Es[(size_t)k * nu + c] = esc[k] * E[(size_t)k * nu + c];
+  }
   nnmpc_ts* h = new nnmpc_ts();
   h->nu = nu; h->nz = nz;
+  h->dsc = pow2_near(pmax);
   hipGetDevice(&h->device);
   hipError_t e = hipStreamCreate(&h->stream);
   if (e == hipSuccess) e = hipMalloc((void**)&h->Pr, (size_t)nu * nu * 8);
   if (e == hipSuccess) e = hipMalloc((void**)&h->E, std::max<size_t>((size_t)nz * nu, 1) * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&h->esc, std::max<size_t>((size_t)nz, 1) * 8);
   if (e == hipSuccess) e = hipMalloc((void**)&h->lb, nu * 8);
   if (e == hipSuccess) e = hipMalloc((void**)&h->ub, nu * 8);
   if (e == hipSuccess) e = hipMemcpy(h->Pr, Pr, (size_t)nu * nu * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && nz) e = hipMemcpy(h->E, E, (size_t)nz * nu * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess && nz) e = hipMemcpy(h->E, Es.data(), (size_t)nz * nu * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(h->esc, esc.data(), std::max<size_t>((size_t)nz, 1) * 8, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(h->lb, lb, nu * 8, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(h->ub, ub, nu * 8, hipMemcpyHostToDevice);
   const int N = nu + nz;
@@ -560,7 +609,7 @@ int nnmpc_ts_destroy(nnmpc_ts* h) {
   if (!h) return NNMPC_OK;
   hipSetDevice(h->device);
   hipDeviceSynchronize();
-  for (void* p : {(void*)h->Pr, (void*)h->E, (void*)h->lb, (void*)h->ub}) if (p) hipFree(p);
+  for (void* p : {(void*)h->Pr, (void*)h->E, (void*)h->esc, (void*)h->lb, (void*)h->ub}) if (p) hipFree(p);
   for (void* p : h->stage) if (p) hipFree(p);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -580,7 +629,7 @@ int nnmpc_ts_launch_internal(nnmpc_ts* h, int B, const double* q, const double* 
   if (B == 0) return NNMPC_OK;
   const int N = h->nu + h->nz;
   const size_t lds = ((size_t)N * (N + 2) + N) * sizeof(double);
-  hipLaunchKernelGGL(ts_solve_k, dim3(B), dim3(64), lds, s, B, h->nu, h->nz, h->Pr, h->E, h->lb, h->ub, q, e, us, nullptr, nullptr,
+  hipLaunchKernelGGL(ts_solve_k, dim3(B), dim3(64), lds, s, B, h->nu, h->nz, h->Pr, h->E, h->esc, h->dsc, h->lb, h->ub, q, e, us, nullptr, nullptr,
                      status, 1e-9);
   return NNMPC_OK;
 }
@@ -611,7 +660,7 @@ int nnmpc_ts_solve_batch(nnmpc_ts* h, int32_t B, const double* q, const double* 
     qd = a; ed = b;
   }
   const size_t lds = ((size_t)N * (N + 2) + N) * sizeof(double);
-  hipLaunchKernelGGL(ts_solve_k, dim3(B), dim3(64), lds, h->stream, B, nu, nz, h->Pr, h->E, h->lb, h->ub, qd, ed, ud, ld, ad, sd, 1e-9);
+  hipLaunchKernelGGL(ts_solve_k, dim3(B), dim3(64), lds, h->stream, B, nu, nz, h->Pr, h->E, h->esc, h->dsc, h->lb, h->ub, qd, ed, ud, ld, ad, sd, 1e-9);
   if (ptr_kind == NNMPC_HOST) {
     HIPCHK(hipMemcpyAsync(us, ud, (size_t)B * nu * 8, hipMemcpyDeviceToHost, h->stream));
     if (lam_eq && nz) HIPCHK(hipMemcpyAsync(lam_eq, ld, (size_t)B * nz * 8, hipMemcpyDeviceToHost, h->stream));

@@ -210,6 +210,30 @@ def solve_exact_box(P, q, lb, ub, tol=1e-11, maxiters=80, info=None):
     lb = np.asarray(lb, float).reshape(-1)
     ub = np.asarray(ub, float).reshape(-1)
     n = q.size
+    fx = lb == ub
+    if fx.any():
+        # a variable with lb == ub has no interior: fix it, solve the rest (the interior-point phase below divides by ub - x)
+        fr = ~fx
+        x = np.where(fx, lb, 0.0)
+        sub = {}
+        if fr.any():
+            x[fr] = solve_exact_box(P[np.ix_(fr, fr)], q[fr] + P[np.ix_(fr, fx)] @ lb[fx], lb[fr], ub[fr], tol, maxiters, sub)
+        if info is not None:
+            g = P @ x + q
+            au, al = fx & (g < 0), fx & (g >= 0)         # the side whose multiplier is non-negative
+            if fr.any():
+                au[fr], al[fr] = sub["au"], sub["al"]
+            lam_u, lam_l = np.where(au, -g, 0.0), np.where(al, g, 0.0)
+            info.update(au=au, al=al, kkt=(np.abs(g + lam_u - lam_l).max(), max(np.max(x - ub), np.max(lb - x), 0.0),
+                                          max(np.max(-lam_u), np.max(-lam_l), 0.0)))
+            nu = info.get("nu")
+            if nu:
+                k, c = np.arange(n) // nu, np.arange(n) % nu
+                rows = np.zeros(2 * n, bool)
+                rows[k * 2 * nu + c] = au
+                rows[k * 2 * nu + nu + c] = al
+                info["active"] = np.flatnonzero(rows)
+        return x
     FP = sla.cho_factor(P, lower=True)
     x = np.clip(sla.cho_solve(FP, -q), lb + 0.05 * (ub - lb), ub - 0.05 * (ub - lb))
     g = P @ x + q

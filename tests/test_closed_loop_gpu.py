@@ -320,3 +320,39 @@ def test_baselines_match_reference_fixture(golden_dir):
             assert np.abs(res[k][i] - f[f"{name}_{k}"]).max() < tol, ("device", name, k)
         assert np.abs(res["avg"][i] - f[f"{name}_avg_cost"]).max() < 10 * tol, ("device", name)
     assert max(np.abs(f[f"{n}_u"]).max() for n in names) > 0.999                  # the clip / the bounds are exercised
+
+
+def test_unreachable_target_stays_inside_its_instance():
+    """nnmpc_cl_run calls ts_solve_k through nnmpc_ts_launch_internal (no active / lam_eq outputs, the loop's own stream).  One
+    instance gets a setpoint no steady state inside the input box reaches from step t0 on: its ts_status is non-zero from t0, its
+    records are non-finite from there (NaN moves are the documented behaviour, not a fault), and every other instance is bit
+    for bit what it is in a run without the bad one."""
+    from industrial_nnmpc_2021_amd import linearMPC as lm
+    from industrial_nnmpc_2021_amd.closed_loop import simulate_closed_loop_batch
+    pl, common, scen = _mini_problem()
+    mats = dict(A=pl["A"], B=pl["B"], C=pl["C"], Bp=common["Bd"], Rv=common["Rv"])
+    plant = lm.LinearPlantSimulator(x0=np.zeros((pl["A"].shape[0], 1)), sample_time=1.0, **mats)
+    t0, T = 37, 60
+    bad_sp = scen[1][0].copy()
+    bad_sp[t0:, :2] = 50.0                                                       # as in test_chain_target_gpu.py: far outside what the box reaches
+    scen3 = scen + [(bad_sp, scen[1][1])]
+    others = [(c, s, 13) for c in (0, 1, 2, 4, 5, 6) for s in (0, 1)]            # NN x 3, MPC (N = 6), satK, us
+    bad = (0, 2, 13)
+    mixed = others[:5] + [bad] + others[5:]
+    run = lambda inst: simulate_closed_loop_batch(plant, _controllers(common, SPECS), scenarios=scen3, Nsim=T, seeds=[13],
+                                                  instances=inst, allow_uncertified=True)
+    with_bad, without = run(mixed), run(others)
+    j = mixed.index(bad)
+    assert with_bad["instances"][j] == bad
+    st = with_bad["ts_status"][j]
+    assert (st[:t0] == 0).all() and (st[t0:] != 0).all()
+    for k in ("us", "xs", "u"):
+        assert np.isfinite(with_bad[k][j][:t0]).all() and not np.isfinite(with_bad[k][j][t0:]).any(), k
+    for k in ("y", "x", "avg"):                                                  # every later row of the plant's records carries it
+        a = with_bad[k][j].reshape(T + 1, -1)
+        assert np.isfinite(a[:t0 + 1]).all() and (~np.isfinite(a[t0 + 1:])).any(axis=1).all(), k
+    keep = [i for i in range(len(mixed)) if i != j]
+    assert [with_bad["instances"][i] for i in keep] == without["instances"]
+    assert (without["ts_status"] == 0).all() and (without["reg_status"] == 0).all()
+    for k in ("y", "x", "xhat", "u", "xs", "us", "avg", "ts_status", "reg_status"):
+        assert with_bad[k][keep].tobytes() == without[k].tobytes(), k
