@@ -82,6 +82,9 @@ typedef struct {
                                 the rounds (bf16 MFMA, csrc/qp_predict.h): 0 = adaptive (0.3 per bound x_unc violates, 8 .. 64, by workgroup of 64
                                 problems), > 0 = that many (<= 64), < 0 = off (first sets = the bounds x_unc violates).
                                 Affects only the number of rounds, never a result; used when n >= 512, nu <= 64, no caller's guess */
+  int32_t asm_overlap;       /* 0 = a far-field full-width pass runs on a side stream while the next round of the problems that did
+                                not settle runs beside it in a second, small row space (csrc/qp_solver.hip: solve_segment_asm);
+                                < 0 = off (every pass and round in sequence on one stream).  Affects only the order of the work */
   float ipm_tol;             /* PDIP exit, objective scaled by 1/median(diag P):
                                 |r_d|_inf and mu <= tol*max(1,|q|_inf); 0 = 1e-2 */
   double refine_tol;         /* PCG exit: |step|_inf <= tol*max(1,|x|_inf); 0 = 1e-10 */
@@ -123,6 +126,7 @@ typedef struct {
   int64_t asm_predict_launches; /* launches of the first-set predictor (asm_predict_k) */
   double asm_predict_ms;     /* their hipEvent time (profiling on) */
   double asm_predict_flops;  /* bf16 MFMA flops they executed: 2 * 64 * 512 * (columns of Y in use) per workgroup and iteration */
+  int64_t asm_overlapped_passes; /* full-width passes that ran beside the round of the problems still running (asm_overlap) */
 } nnmpc_qp_stats;
 
 const char* nnmpc_last_error(void);

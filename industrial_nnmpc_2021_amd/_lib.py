@@ -16,7 +16,7 @@ class QpOpts(C.Structure):
                 ("max_polish_rounds", C.c_int32), ("max_refine", C.c_int32),
                 ("max_rounds", C.c_int32), ("sub_steps", C.c_int32), ("stale_max_changes", C.c_int32),
                 ("stale_cg_limit", C.c_int32), ("method", C.c_int32), ("asm_max_active", C.c_int32),
-                ("asm_max_rounds", C.c_int32), ("asm_f32_rounds", C.c_int32), ("seg_max", C.c_int32), ("asm_tail_batch", C.c_int32), ("asm_predict_iters", C.c_int32), ("ipm_tol", C.c_float), ("refine_tol", C.c_double),
+                ("asm_max_rounds", C.c_int32), ("asm_f32_rounds", C.c_int32), ("seg_max", C.c_int32), ("asm_tail_batch", C.c_int32), ("asm_predict_iters", C.c_int32), ("asm_overlap", C.c_int32), ("ipm_tol", C.c_float), ("refine_tol", C.c_double),
                 ("bound_tol", C.c_double)]
 
 
@@ -32,7 +32,7 @@ class QpStats(C.Structure):
                 ("asm_lambda64_ms", C.c_double), ("asm_lambda32_flops", C.c_double),
                 ("asm_lambda32_launches", C.c_int64), ("asm_lambda64_launches", C.c_int64), ("asm_far_passes", C.c_int64), ("asm_side_ms", C.c_double),
                 ("asm_small_passes", C.c_int64), ("asm_predict_launches", C.c_int64), ("asm_predict_ms", C.c_double),
-                ("asm_predict_flops", C.c_double)]
+                ("asm_predict_flops", C.c_double), ("asm_overlapped_passes", C.c_int64)]
 
 
 CL_MPC, CL_NN, CL_SATDLQR, CL_US = 0, 1, 2, 3

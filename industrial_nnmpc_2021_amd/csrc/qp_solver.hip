@@ -713,6 +713,16 @@ struct nnmpc_qp {
   std::vector<int> far_missing;   // windows of full-width passes that ran in the dense form for want of factors (handed out once each)
   double p_inf = 0.0;       // max row sum of |P|
   double *asm_tnorm = nullptr, *asm_tslack = nullptr;
+  // Row spaces ("views") of the active-set rounds: the buffers indexed by the ROW a round hands a running problem (and that round's
+  // counters and k-ranges) rather than by the problem.  view[0] is the workspace above (seg_max rows); view[1] a second, small one
+  // for the round that runs beside a full-width pass (solve_segment_asm).  Everything indexed by problem is shared.
+  struct AsmView {
+    double *lam = nullptr, *xh = nullptr, *xhw = nullptr, *tnorm = nullptr, *tslack = nullptr;
+    float *lam32 = nullptr, *xh32 = nullptr;
+    int *rowprob = nullptr, *kblk = nullptr, *counters = nullptr;
+    int rows = 0;                    // running problems a round in this view can hold (multiple of 128; 0: no such view)
+  };
+  AsmView view[2];
   // first-set predictor (qp_predict.h): bf16 fragments of Pinv[0:512, 0:512], step sizes; set by nnmpc_qp_set_inverse when the problem is large enough
   struct PredWin { pu32x4* Hf = nullptr; double L = 0.0; int W = 0; };   // L = 1.05 lambda_max(D^-1/2 Pinv_WW D^-1/2); 0: window not available
   PredWin pred[2];              // [0]: 512 columns, 64 problems per workgroup; [1]: 1024 columns, 32 per workgroup (sets that reach further)
@@ -730,10 +740,11 @@ struct nnmpc_qp {
   hipStream_t stream3 = nullptr, stream4 = nullptr;
   int asm_tail_budget = 50000;       // iterations of asm_tail_k per problem (set in nnmpc_qp_create)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr, ev_join4 = nullptr;
+  hipEvent_t ev_wfork = nullptr, ev_wide = nullptr;   // fork / join of a full-width pass that runs on stream4 beside a round
   // pinned host copies of the active-set pass's read-backs (the round counters, the status of a segment): into pageable memory a
   // "hipMemcpyAsync" is staged and waited for inside the runtime (a blocking wait); pinned, the copy is a packet on the stream and
   // stream_sync polls for it.
-  int* pin_cnt = nullptr;            // [ASM_NCNT + 4]: the round counters, then the predictor's iteration sum
+  int* pin_cnt = nullptr;            // [2 ASM_NCNT + 4]: the round counters of both views, then the predictor's iteration sum
   int* pin_st = nullptr;             // [seg_max]
   bool profiling;
   bool gemm_error = false;      // a GEMM was asked for in a form no kernel implements (gemm64): the call in progress fails
@@ -1059,8 +1070,6 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   a.ffU = a.ffVx = a.ffVl = a.ffcu = nullptr; a.ffk = nullptr; a.ffr = a.ffW = 0; a.T = h->asm_xhw; a.tnorm = h->asm_tnorm; a.tslack = h->asm_tslack;
   a.ff_skip = 0; a.ff_err = 0.0; a.ff_efar = 0.0;
   static const bool no_far = getenv("NNMPC_NO_FARFIELD") != nullptr;      // diagnostics: dense form of the full-width pass (A/B)
-  int wide_far_rp = 0, fft_prev = 0;
-  double wide_far_ksum = 0.0;                      // the last full-width pass ran in the far-field form with this padded rank
   a.n = h->n; a.np = h->np; a.nu = h->nu; a.nseg = nprob;
   a.max_active = h->opts.asm_max_active; a.max_rounds = h->opts.asm_max_rounds;
   a.bound_tol = h->opts.bound_tol; a.stat_tol = 1e-8; a.pscale = h->pscale;
@@ -1140,11 +1149,10 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   hipLaunchKernelGGL(asm_init_k, dim3((segp + 3) / 4), dim3(256), 0, s, a, segp);
   const int lds_big = (a.max_active + ASM_TS) * 8;
   int* cnt = h->pin_cnt;
-  memset(cnt, 0, ASM_NCNT * sizeof(int));
+  memset(cnt, 0, 2 * ASM_NCNT * sizeof(int));
   int rounds = 0;
-  int prev_rows = 0;                                    // fp64 rows of the last round (of LAM): the problems that settled in them await the full-width check
-  int kprev = 0, wide_cols = 0, fused_c0 = -1;
-  HIPCHK(hipMemsetAsync(h->asm_counters, 0, ASM_NCNT * sizeof(int), s));
+  int kprev = 0;
+  HIPCHK(hipMemsetAsync(h->asm_counters, 0, 2 * ASM_NCNT * sizeof(int), s));   // (both views' counters)
   if (small) {
     EvScope es(h, 4, 0.0);
     // iterations of grace before single exchanges (the variable: diagnostics).  24, not the rounds' ASM_GRACE = 10: on the cond-4e7
@@ -1200,7 +1208,7 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
     // (the counters are read together with the status at the end of the segment -- one host round trip per call instead of two:
     // a chain step is such a call, 0.45 ms of which ~0.04 ms was this wait; the check with P is launched unconditionally then)
     if (!defer_cnt) {
-      HIPCHK(hipMemcpyAsync(cnt, h->asm_counters, ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
       HIPCHK(stream_sync(s));
     }
     h->stats.asm_rounds += 1;
@@ -1213,79 +1221,174 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       fprintf(stderr, "asm tail only: %d problems, iterations mean %.2f max %d, active bounds mean %.1f max %d\n", nprob, (double)sum / nprob, mx, (double)sm / nprob, mm);
     }
   }
+  // ---- The pass beside the round.  A far-field full-width pass does not wait on the main stream: asm_wide_t_k (+ asm_wide_tnorm_k) and
+  // asm_wide_gemm_k run on stream4 over the rows of the view the last round ran in (the "pending" view), while the problems that did
+  // NOT settle in that round -- known since its asm_update_k -- are counted and, if they fit, run their next round (or the device
+  // tail) on the main stream in the other, free view: its own rows of LAM / XH, its own counters and k-ranges.  Then the main stream
+  // waits for the pass and runs asm_wide_k.  Views swap roles from iteration to iteration.  Two rules keep this free of races:
+  //  (1) asm_wide_k is the only kernel of the pass that writes `state` (ASM_WIDE -> RUN / CERT / DONE), and asm_count_k, the bins,
+  //      asm_update_k and asm_taillist_k scan `state` over all problems: it runs on the main stream after everything the round
+  //      enqueued there and on its side streams (their joins come before the round's GEMMs).  Problems it sends back to ASM_RUN are
+  //      found by the next iteration's count, which is why the loop goes on after an overlapped tail.
+  //  (2) asm_wide_t_k / asm_wide_gemm_k write st / wflag / u_out / T only for rows with rowprob >= 0: problems in state ASM_WIDE, which
+  //      no kernel of the round touches (it works on ASM_RUN problems); the far-field form reads no x_unc beyond the window, so an
+  //      x_unc extension or the tail's gathered x_unc rows do not collide with it.  The dense, lazy and plain-GEMM forms of the pass
+  //      keep the serial order.
+  // The size-class lists, ranks and chunk totals (binlist, biglist, lrank, ctot) live from a round's bins to its multiplier kernels,
+  // all ordered on the main stream, and the pass reads none of them: both views share them.
+  auto set_view = [&](AsmDev& d, int v) {
+    const nnmpc_qp::AsmView& V = h->view[v];
+    d.lam = V.lam; d.xh = V.xh; d.xhw = V.xhw; d.T = V.xhw; d.tnorm = V.tnorm; d.tslack = V.tslack; d.lam32 = V.lam32; d.xh32 = V.xh32;
+    d.rowprob = V.rowprob; d.kblk = V.kblk; d.counters = V.counters;
+  };
+  const char* env_ovl = getenv("NNMPC_OVERLAP");         // (the variable: A/B runs, 0 = off; read per call)
+  const bool overlap_on = h->opts.asm_overlap >= 0 && h->view[1].rows > 0 && !(env_ovl && atoi(env_ovl) == 0);
+  int vW[2] = {h->np, h->np}, vrows[2] = {0, 0};         // per view: window and fp64 rows of the last round that ran in it
+  int pend = -1;                                         // the view whose settled rows await the full-width pass (-1: none)
+  bool tail_ran[2] = {false, false};
+  // the pass whose asm_wide_k ran last: its flops are counted from the scans of the next bins (they count what asm_wide_k marked)
+  // (wnext: the pass just launched -- beside a round its asm_wide_k comes after the bins that count the pass before it)
+  struct WideStat { bool open; int view, far_rp, skip, cols; double far_ksum; } wst = {false, 0, 0, 0, 0, 0.0}, wnext = wst;
+  int fft_prev[2] = {0, 0};
+  auto account = [&](const int* c) {                     // c: the counters of the bins pass just read back
+    if (!wst.open) return;
+    wst.open = false;
+    if (!h->profiling) return;
+    // (the problems asm_wide_k handled, the sum of their last active index + 1)
+    const double nw = c[ASM_CNT_WIDE + 1], ksum = c[ASM_CNT_WKSUM];
+    if (wst.far_rp) {
+      // far-field form: T = z V (k = n_aug + own k-range) and x = T U' (k = the column tile's share of the basis) -- over all
+      // columns, or (first-move calls) over the 128 x 128 tiles the certificate did not cover (device count of their k chunks, in
+      // the counters of the view the pass ran in)
+      const int fft = h->pin_cnt[wst.view * ASM_NCNT + ASM_CNT_FFTILES];
+      const double chunks = fft - fft_prev[wst.view];
+      fft_prev[wst.view] = fft;
+      h->stats.asm_gemm_flops += 2.0 * wst.far_rp * (ksum + nw * h->ka) +
+                                 (wst.skip ? 2.0 * G64_KC * 128.0 * 128.0 * chunks : 2.0 * 128.0 * wst.far_ksum * nw);
+    } else {
+      h->stats.asm_gemm_flops += 2.0 * wst.cols * (ksum + (lazy ? nw * h->ka : 0.0));   // (lazy: x_unc beyond the window is part of that pass)
+    }
+  };
   for (; !tail_only && rounds < 2 * a.max_rounds + 2; ++rounds) {
-    if (prev_rows) {
+    const int pv = pend;
+    bool inflight = false;                               // this iteration's pass runs on stream4: its asm_wide_k is still to come
+    AsmDev ap = a;                                       // the pass's arguments: the pending view, its round's window
+    int fused_c0 = -1;
+    if (pv >= 0) {
       // problems that settled inside last round's column window: all columns of x, once
+      const int prev_rows = vrows[pv];
+      set_view(ap, pv);
+      ap.W = vW[pv]; ap.wrows = prev_rows;
+      // (ap.W is that round's window: those columns are in that round's XH rows already)
+      const int c0 = (ap.W < h->np && (h->np - ap.W) % 128 == 0) ? ap.W : 0;
+      fused_c0 = ((h->np - c0) % 128 == 0 && !no_fuse) ? c0 : -1;     // the fused kernel's 128-column tiles fit: check in the GEMM's epilogue
+      const int ntm = (prev_rows + 127) / 128, ntn = (h->np - c0) / 128;
+      const nnmpc_qp::Far* ff = nullptr;
+      if (lazy && fused_c0 > 0 && !no_far) {
+        for (const auto& f : h->far) if (f.W == c0) ff = &f;
+        if (!ff && h->far_missing.size() < 16 && std::find(h->far_missing.begin(), h->far_missing.end(), c0) == h->far_missing.end())
+          h->far_missing.push_back(c0);                // (the host wrapper may add the factors for this window: nnmpc_qp_farfield_missing)
+      }
+      const bool ovl = ff && overlap_on && h->view[1 - pv].rows > 0;
+      if (!ovl && wst.open && h->profiling && h->view[1 - pv].rows > 0) {
+        // statistics only: a pass in sequence is about to mark its problems while those of an overlapped pass are still uncounted
+        // -- the two may be priced differently: count the marks now (scans of the bins in the free view; every list and row they
+        // write is written again by the bins that follow this pass)
+        AsmDev af = a;
+        set_view(af, 1 - pv);
+        hipLaunchKernelGGL(asm_bins_a_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, af);
+        hipLaunchKernelGGL(asm_bins_b_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, af);
+        HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(stream_sync(s));
+        account(h->pin_cnt + (1 - pv) * ASM_NCNT);
+      }
+      hipStream_t ps = ovl ? h->stream4 : s;
+      if (ovl) {
+        HIPCHK(hipEventRecord(h->ev_wfork, s));
+        HIPCHK(hipStreamWaitEvent(ps, h->ev_wfork, 0));
+      }
+      ap.ff_err = 0.0; ap.ff_efar = 0.0; ap.ff_skip = 0;
+      int far_rp = 0;
+      double far_ksum = 0.0;
       {
-        EvScope es(h, 5, 0.0);
-        // (a.W is still last round's window: those columns are in that round's XH rows already)
-        const int c0 = (a.W < h->np && (h->np - a.W) % 128 == 0) ? a.W : 0;
-        fused_c0 = ((h->np - c0) % 128 == 0 && !no_fuse) ? c0 : -1;     // the fused kernel's 128-column tiles fit: check in the GEMM's epilogue
-        const int ntm = (prev_rows + 127) / 128, ntn = (h->np - c0) / 128;
-        a.wrows = prev_rows;
-        const nnmpc_qp::Far* ff = nullptr;
-        if (lazy && fused_c0 > 0 && !no_far) {
-          for (const auto& f : h->far) if (f.W == c0) ff = &f;
-          if (!ff && h->far_missing.size() < 16 && std::find(h->far_missing.begin(), h->far_missing.end(), c0) == h->far_missing.end())
-            h->far_missing.push_back(c0);                // (the host wrapper may add the factors for this window: nnmpc_qp_farfield_missing)
-        }
-        a.ff_err = 0.0; a.ff_efar = 0.0; a.ff_skip = 0; wide_far_rp = 0;
+        EvScope es(h, 5, 0.0, ps);
         if (ff) {
           // far-field form: T = [x0 | lamw] V, x[c0:] = T U'; first-move calls skip the column tiles |U_j| |T_p| certifies
-          a.ffU = ff->U; a.ffVx = ff->Vx; a.ffVl = ff->Vl; a.ffcu = ff->cu; a.ffk = ff->kt; a.ffr = ff->rp; a.ffW = ff->W;
-          a.ff_err = h->p_inf * ff->efar; a.ff_efar = ff->efar;
-          a.ff_skip = h->nout <= c0 && h->nout < h->n;
-          wide_far_rp = ff->rp; wide_far_ksum = ff->ksum;
+          ap.ffU = ff->U; ap.ffVx = ff->Vx; ap.ffVl = ff->Vl; ap.ffcu = ff->cu; ap.ffk = ff->kt; ap.ffr = ff->rp; ap.ffW = ff->W;
+          ap.ff_err = h->p_inf * ff->efar; ap.ff_efar = ff->efar;
+          ap.ff_skip = h->nout <= c0 && h->nout < h->n;
+          far_rp = ff->rp; far_ksum = ff->ksum;
           h->stats.asm_far_passes += 1;
-          hipLaunchKernelGGL(asm_wide_t_k, dim3(g64_grid(ntm, ff->rp / 128)), dim3(256), G64_LDS, s, a, ntm, ff->rp / 128);
-          if (a.ff_skip) hipLaunchKernelGGL(asm_wide_tnorm_k, dim3((ntm * 128 + 3) / 4), dim3(256), 0, s, a, ntm);
-          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_FAR>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, a, c0, ntm, ntn);
+          hipLaunchKernelGGL(asm_wide_t_k, dim3(g64_grid(ntm, ff->rp / 128)), dim3(256), G64_LDS, ps, ap, ntm, ff->rp / 128);
+          if (ap.ff_skip) hipLaunchKernelGGL(asm_wide_tnorm_k, dim3((ntm * 128 + 3) / 4), dim3(256), 0, ps, ap, ntm);
+          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_FAR>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, ps, ap, c0, ntm, ntn);
         } else if (fused_c0 >= 0 && lazy) {              // (lazy: c0 = W >= the first window -- never 0 -- and x_unc exists up to Wx >= W)
-          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_LAZY>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, a, c0, ntm, ntn);
+          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_LAZY>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, ap, c0, ntm, ntn);
         } else if (fused_c0 >= 0) {
-          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_XUNC>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, a, c0, ntm, ntn);
+          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_XUNC>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, ap, c0, ntm, ntn);
         } else {
           // shapes the fused kernels' tiles do not fit: XHW = LAM Pinv beyond c0 by the plain GEMM, k-range per 64-row block
-          gemm64(h, h->asm_xhw + c0, h->np, h->asm_lam, h->np, h->H64 + (size_t)c0 * h->np, h->np, ((prev_rows + 127) / 128) * 128,
-                 h->np - c0, h->np, nullptr, 0, h->asm_kblk, nullptr, true);
+          gemm64(h, h->view[pv].xhw + c0, h->np, h->view[pv].lam, h->np, h->H64 + (size_t)c0 * h->np, h->np, ((prev_rows + 127) / 128) * 128,
+                 h->np - c0, h->np, nullptr, 0, h->view[pv].kblk, nullptr, true);
         }
-        wide_cols = h->np - c0;
       }
-      EvScope es(h, 6, 0.0);
-      hipLaunchKernelGGL(asm_wide_k, dim3((prev_rows + 3) / 4), dim3(256), 0, s, a, fused_c0);
+      wnext.view = pv; wnext.far_rp = far_rp; wnext.far_ksum = far_ksum; wnext.skip = ap.ff_skip; wnext.cols = h->np - c0; wnext.open = true;
+      if (ovl) {
+        HIPCHK(hipEventRecord(h->ev_wide, ps));
+        inflight = true;
+      } else {
+        EvScope es(h, 6, 0.0);
+        hipLaunchKernelGGL(asm_wide_k, dim3((prev_rows + 3) / 4), dim3(256), 0, s, ap, fused_c0);
+        wst = wnext;
+      }
+      pend = -1; vrows[pv] = 0;
     }
-    a.kref = kprev;
+    // the main stream joins the pass on stream4 and decides its problems (rule 1: after everything the round enqueued)
+    auto finish_pass = [&]() -> int {
+      HIPCHK(hipStreamWaitEvent(s, h->ev_wide, 0));
+      EvScope es(h, 6, 0.0);
+      hipLaunchKernelGGL(asm_wide_k, dim3((ap.wrows + 3) / 4), dim3(256), 0, s, ap, fused_c0);
+      wst = wnext;
+      inflight = false;
+      return 0;
+    };
     if (!a.pred_w) a.refine_later = 0;                   // (only behind predicted first sets: from other starts the f32 rounds are many and their sets still move)
     a.refine = a.refine_later && rounds >= 1;            // round 0 stays the plain f32 screen
-    {
-      EvScope es(h, 6, 0.0);                            // set bookkeeping: counted with asm_update_k
-      hipLaunchKernelGGL(asm_count_k, dim3((nprob + 3) / 4), dim3(256), 0, s, a);
-      hipLaunchKernelGGL(asm_bins_a_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, a);
-      hipLaunchKernelGGL(asm_bins_b_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, a);
+    a.kref = kprev;
+    // the round's view: beside a pass the one it does not occupy, view 0 otherwise
+    int rv = inflight ? 1 - pv : 0;
+    int n64 = 0, n32 = 0, nrun = 0;
+    for (;;) {
+      set_view(a, rv);
+      cnt = h->pin_cnt + rv * ASM_NCNT;
+      {
+        EvScope es(h, 6, 0.0);                            // set bookkeeping: counted with asm_update_k
+        hipLaunchKernelGGL(asm_count_k, dim3((nprob + 3) / 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(asm_bins_a_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, a);
+        hipLaunchKernelGGL(asm_bins_b_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, a);
+      }
+      HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));   // (both views' counters)
+      HIPCHK(stream_sync(s));
+      n64 = cnt[2]; n32 = cnt[ASM_CNT_ROWS32]; nrun = n64 + n32;   // solved in fp64 / f32 this round
+      account(cnt);                                       // flops of the last full-width pass asm_wide_k has decided
+      if (inflight && nrun > h->view[rv].rows) {
+        // more problems still running than the free view has rows (the early rounds of a call without predicted sets): the count was
+        // hidden behind the pass but is of no use -- finish the pass and count again, in view 0, as the serial order would have
+        // (the per-problem flop statistics of asm_count_k are not added a second time)
+        const int rcf = finish_pass();
+        if (rcf) return rcf;
+        rv = 0;
+        a.work = nullptr;
+        continue;
+      }
+      break;
     }
-    HIPCHK(hipMemcpyAsync(cnt, h->asm_counters, ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(stream_sync(s));
-    const int n64 = cnt[2], n32 = cnt[ASM_CNT_ROWS32], nrun = n64 + n32;   // solved in fp64 / f32 this round
-    if (h->profiling)                                   // flops of the full-width pass that opened this round
-    {
-        // (from the scans of this round's asm_bins: the problems asm_wide_k just handled, the sum of their last active index + 1)
-        const double nw = cnt[ASM_CNT_WIDE + 1], ksum = cnt[ASM_CNT_WKSUM];
-        if (wide_far_rp) {
-          // far-field form: T = z V (k = n_aug + own k-range) and x = T U' (k = the column tile's share of the basis) -- over all
-          // columns, or (first-move calls) over the 128 x 128 tiles the certificate did not cover (device count of their k chunks)
-          const double chunks = cnt[ASM_CNT_FFTILES] - fft_prev;
-          h->stats.asm_gemm_flops += 2.0 * wide_far_rp * (ksum + nw * h->ka) +
-                                     (a.ff_skip ? 2.0 * G64_KC * 128.0 * 128.0 * chunks : 2.0 * 128.0 * wide_far_ksum * nw);
-        } else {
-          h->stats.asm_gemm_flops += 2.0 * wide_cols * (ksum + (lazy ? nw * h->ka : 0.0));   // (lazy: x_unc beyond the window is part of that pass)
-        }
-        fft_prev = cnt[ASM_CNT_FFTILES];
-    }
+    a.work = h->asm_work;
     kprev = cnt[3];
     {
       static const bool trace = getenv("NNMPC_TRACE_ROUNDS") != nullptr;   // diagnostics: the populations of every round
       if (trace) {
-        fprintf(stderr, "asm round %d: fp64 %d f32 %d last-active %d wide-checked %d big %d big32 %d | fp64 classes", rounds, n64, n32, cnt[3],
+        fprintf(stderr, "asm round %d%s: fp64 %d f32 %d last-active %d wide-checked %d big %d big32 %d | fp64 classes", rounds, inflight ? " (beside the pass)" : "", n64, n32, cnt[3],
                 cnt[ASM_CNT_WIDE + 1], cnt[1], cnt[ASM_CNT_BIG32] + cnt[ASM_CNT_BIG32B]);
         for (int b = 0; b < ASM_NBIN; ++b) fprintf(stderr, " %d", cnt[4 + b]);
         fprintf(stderr, " | f32 classes");
@@ -1293,46 +1396,65 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
         fprintf(stderr, "\n");
       }
     }
-    if (nrun == 0) break;
+    if (nrun == 0) {
+      if (!inflight) break;
+      // nothing left to run beside the pass; asm_wide_k may still send problems back: the next count decides (this was no round)
+      const int rcf = finish_pass();
+      if (rcf) return rcf;
+      --rounds;
+      continue;
+    }
+    const nnmpc_qp::AsmView& V = h->view[rv];
     static const int tail_max = getenv("NNMPC_TAIL_MAX") ? atoi(getenv("NNMPC_TAIL_MAX")) : 256;   // (the variable: diagnostics)
     if (nrun <= std::min(h->asm_pool, tail_max) && (rounds >= (a.pred_w ? 2 : 6) || small)) {
       // the tail: a handful of stragglers (the bulk settles in 5-8 rounds) -- finish them on the device (asm_tail_k)
       // instead of paying eight launches and a read-back per round for them.  From round 6 on -- from round 2 when the first sets
       // were predicted (qp_predict.h: the bulk then settles in rounds 1-2, and rounds 3-4 were 0.9 ms for 130 problems) -- (12 before: at 100 000
       // problems per call the rounds 7..12 were launches for a few dozen problems, 5 % of the step)
-      EvScope es(h, 4, 0.0);
-      hipLaunchKernelGGL(asm_taillist_k, dim3((nprob + 255) / 256), dim3(256), 0, s, a);
-      if (Wx < h->np) {
-        // the tail evaluates all columns of its problems straight from Pinv: their x_unc rows beyond Wx, gathered by problem
-        gemm64(h, h->asm_xunc + Wx, h->np, h->x0_64, h->ka, h->Kunc64 + (size_t)Wx * h->ka, h->ka, ((nrun + 127) / 128) * 128, h->np - Wx, h->ka,
-               nullptr, 0, nullptr, h->asm_counters + ASM_CNT_TAIL, false, h->asm_biglist);
-        a.Wx = h->np;                                    // (for these problems)
-      }
-      const int lds_tail = (a.max_active + ASM_TS + ASM_TAIL_AREA) * 8 + ((h->n + 15) / 16) * 16 + ASM_TAIL_EXTRA;
-      hipLaunchKernelGGL(asm_tail_k, dim3(nrun), dim3(256), lds_tail, s, a, h->asm_tail_budget);
-      HIPCHK(hipMemcpyAsync(cnt, h->asm_counters, ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(stream_sync(s));
+      static const bool trace = getenv("NNMPC_TRACE_ROUNDS") != nullptr;   // diagnostics: iterations of the tail's problems
       {
-        static const bool trace = getenv("NNMPC_TRACE_ROUNDS") != nullptr;   // diagnostics: iterations of the tail's problems
-        if (trace) {
-          std::vector<int> rd(nprob), bl(nrun);
-          hipMemcpy(rd.data(), h->asm_rounds, nprob * sizeof(int), hipMemcpyDeviceToHost);
-          hipMemcpy(bl.data(), h->asm_biglist, nrun * sizeof(int), hipMemcpyDeviceToHost);
-          long sum = 0; int mx = 0;
-          for (int i = 0; i < nrun; ++i) { const int r = rd[bl[i]] - rounds; sum += r; mx = std::max(mx, r); }
-          fprintf(stderr, "asm tail after round %d: %d problems, iterations mean %.1f max %d\n", rounds, nrun, (double)sum / nrun, mx);
-#ifdef ASM_TAIL_PROF
-          unsigned long long tp[8];
-          hipMemcpyFromSymbol(tp, HIP_SYMBOL(asm_tail_prof), sizeof tp);
-          fprintf(stderr, "  tail clock sums (all workgroups): count/factor/solve %llu, substitutions %llu, x loop %llu, tests %llu, exchange %llu; iterations on the dense factor %llu, on a fresh factorisation %llu\n",
-                  tp[0], tp[1], tp[2], tp[3], tp[4], tp[5], tp[6]);
-          memset(tp, 0, sizeof tp); hipMemcpyToSymbol(HIP_SYMBOL(asm_tail_prof), tp, sizeof tp);
-#endif
+        EvScope es(h, 4, 0.0);
+        if (tail_ran[rv]) HIPCHK(hipMemsetAsync(V.counters + ASM_CNT_TAIL, 0, sizeof(int), s));   // (a second tail of a call, after problems came back from a pass: its own list)
+        hipLaunchKernelGGL(asm_taillist_k, dim3((nprob + 255) / 256), dim3(256), 0, s, a);
+        if (Wx < h->np) {
+          // the tail evaluates all columns of its problems straight from Pinv: their x_unc rows beyond Wx, gathered by problem
+          gemm64(h, h->asm_xunc + Wx, h->np, h->x0_64, h->ka, h->Kunc64 + (size_t)Wx * h->ka, h->ka, ((nrun + 127) / 128) * 128, h->np - Wx, h->ka,
+                 nullptr, 0, nullptr, V.counters + ASM_CNT_TAIL, false, h->asm_biglist);
+          a.Wx = h->np;                                    // (for these problems)
         }
+        const int lds_tail = (a.max_active + ASM_TS + ASM_TAIL_AREA) * 8 + ((h->n + 15) / 16) * 16 + ASM_TAIL_EXTRA;
+        hipLaunchKernelGGL(asm_tail_k, dim3(nrun), dim3(256), lds_tail, s, a, h->asm_tail_budget);
+        tail_ran[rv] = true;
+      }
+      if (!inflight || trace) {                           // (beside a pass the next iteration's count reads the counters)
+        HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(stream_sync(s));
+      }
+      if (trace) {
+        std::vector<int> rd(nprob), bl(nrun);
+        hipMemcpy(rd.data(), h->asm_rounds, nprob * sizeof(int), hipMemcpyDeviceToHost);
+        hipMemcpy(bl.data(), h->asm_biglist, nrun * sizeof(int), hipMemcpyDeviceToHost);
+        long sum = 0; int mx = 0;
+        for (int i = 0; i < nrun; ++i) { const int r = rd[bl[i]] - rounds; sum += r; mx = std::max(mx, r); }
+        fprintf(stderr, "asm tail after round %d: %d problems, iterations mean %.1f max %d\n", rounds, nrun, (double)sum / nrun, mx);
+#ifdef ASM_TAIL_PROF
+        unsigned long long tp[8];
+        hipMemcpyFromSymbol(tp, HIP_SYMBOL(asm_tail_prof), sizeof tp);
+        fprintf(stderr, "  tail clock sums (all workgroups): count/factor/solve %llu, substitutions %llu, x loop %llu, tests %llu, exchange %llu; iterations on the dense factor %llu, on a fresh factorisation %llu\n",
+                tp[0], tp[1], tp[2], tp[3], tp[4], tp[5], tp[6]);
+        memset(tp, 0, sizeof tp); hipMemcpyToSymbol(HIP_SYMBOL(asm_tail_prof), tp, sizeof tp);
+#endif
       }
       h->stats.asm_rounds += 1;
-      rounds = 0;                                         // (regular exit: the counters just read are final)
-      break;
+      if (!inflight) {
+        rounds = 0;                                       // (regular exit: the counters just read are final)
+        break;
+      }
+      a.Wx = Wx;                                          // (x_unc beyond Wx exists for the tail's problems only)
+      const int rcf = finish_pass();
+      if (rcf) return rcf;
+      h->stats.asm_overlapped_passes += 1;
+      continue;                                           // (the next count ends the loop, or finds what asm_wide_k sent back)
     }
     h->stats.asm_rounds += 1;
     // column window of this round: past the last active bound of any running problem plus one stage; a
@@ -1360,13 +1482,15 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       for (int b = 0; b < ASM_NREG; ++b) { nreg_wg += (cnt[4 + b] + 3) / 4; nreg32_wg += (cnt[ASM_CNT_F32 + b] + 3) / 4; }
       // three side streams: [slab kernel: few workgroups, long chains -- it starts first and runs beside everything else],
       // [four-wave kernels of the 12 .. 16-block sets], [single-wave kernels of the 10- and 11-block classes]
+      // (beside a pass stream4 carries the pass: the slab kernel then goes first on stream2)
       const bool side4 = cnt[1] > 0, side2 = nwg64 + nwg32 + nwg32b + nwg64r > 0 || (cnt[ASM_CNT_BIG32] && !a.use_wg), side3 = nreg2_wg + nreg32b_wg > 0;
+      hipStream_t st4 = inflight ? h->stream2 : h->stream4;
       if (nbig) {
         HIPCHK(hipEventRecord(h->ev_fork, s));
         if (side4) {
-          HIPCHK(hipStreamWaitEvent(h->stream4, h->ev_fork, 0));
-          { EvScope e9(h, 9, 0.0, h->stream4); hipLaunchKernelGGL((asm_lambda_tile_k<1>), dim3(std::min(cnt[1], h->asm_pool)), dim3(256), lds_big, h->stream4, a, 0); }
-          HIPCHK(hipEventRecord(h->ev_join4, h->stream4));
+          HIPCHK(hipStreamWaitEvent(st4, h->ev_fork, 0));
+          { EvScope e9(h, 9, 0.0, st4); hipLaunchKernelGGL((asm_lambda_tile_k<1>), dim3(std::min(cnt[1], h->asm_pool)), dim3(256), lds_big, st4, a, 0); }
+          HIPCHK(hipEventRecord(h->ev_join4, st4));
         }
         if (side2) {
           HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
@@ -1403,43 +1527,53 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       // algorithmic flops: 2 * window columns * (own last active bound + 1) per running problem (cnt[0] is their sum)
       EvScope es(h, 5, 2.0 * a.W * (double)cnt[0]);
       if (n64)
-        gemm64(h, h->asm_xh, h->np, h->asm_lam, h->np, h->H64, h->np, ((n64 + 127) / 128) * 128, a.W, h->np, nullptr, 0,
-               h->asm_kblk, nullptr, true);
+        gemm64(h, V.xh, h->np, V.lam, h->np, h->H64, h->np, ((n64 + 127) / 128) * 128, a.W, h->np, nullptr, 0,
+               V.kblk, nullptr, true);
       // (rows are ordered by their last active stage: every 64-row block has its own k-range, asm_bins_b_k)
       if (n32 && a.W % 128 == 0)
         hipLaunchKernelGGL((gemm_nt_f32_kdyn_k<128>), dim3(a.W / 128, (n32 + 127) / 128), dim3(256), TileCfg<128>::LDS_FLOATS * 4, s,
-                           h->asm_xh32, (size_t)h->np, h->asm_lam32, (size_t)h->np, h->H32, (size_t)h->np, h->np, h->asm_kblk + a.nkblk / 2, 2);
+                           V.xh32, (size_t)h->np, V.lam32, (size_t)h->np, h->H32, (size_t)h->np, h->np, V.kblk + a.nkblk / 2, 2);
       else if (n32)
         hipLaunchKernelGGL((gemm_nt_f32_kdyn_k<64>), dim3(a.W / 64, (n32 + 63) / 64), dim3(256), TileCfg<64>::LDS_FLOATS * 4, s,
-                           h->asm_xh32, (size_t)h->np, h->asm_lam32, (size_t)h->np, h->H32, (size_t)h->np, h->np, h->asm_kblk + a.nkblk / 2, 1);
+                           V.xh32, (size_t)h->np, V.lam32, (size_t)h->np, h->H32, (size_t)h->np, h->np, V.kblk + a.nkblk / 2, 1);
     }
     {
       EvScope es(h, 6, 0.0);
       // (rows of LAM whose problem settles inside the window are marked for the full-width pass that opens the next round)
-      if (n64) HIPCHK(hipMemsetAsync(h->asm_rowprob, 0xFF, (size_t)((n64 + 127) / 128) * 128 * sizeof(int), s));
+      if (n64) HIPCHK(hipMemsetAsync(V.rowprob, 0xFF, (size_t)((n64 + 127) / 128) * 128 * sizeof(int), s));
       hipLaunchKernelGGL(asm_update_k, dim3((nprob + 3) / 4), dim3(256), 0, s, a);
     }
-    prev_rows = a.W < h->n ? n64 : 0;
+    vW[rv] = a.W;
+    vrows[rv] = a.W < h->n ? n64 : 0;                    // fp64 rows of this round: the problems that settled in them await the full-width check
+    pend = vrows[rv] ? rv : -1;
+    if (inflight) {
+      const int rcf = finish_pass();
+      if (rcf) return rcf;
+      h->stats.asm_overlapped_passes += 1;
+    }
   }
   // certification with P itself (rows the inverse-error bound could not certify): q = tq x0 and px = x P
   if (rounds >= 2 * a.max_rounds + 2) {                  // left by the round cap: the last counters are not final
-    HIPCHK(hipMemcpyAsync(cnt, h->asm_counters, ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(stream_sync(s));
   }
   if (h->gemm_error) { h->gemm_error = false; return NNMPC_EINVAL; }
-  if (!defer_cnt) h->stats.asm_full_checks += cnt[ASM_CNT_DONE];
-  if (defer_cnt || cnt[ASM_CNT_DONE] > 0) {                // (row blocks without an ASM_DONE row leave these GEMMs at once)
+  set_view(a, 0);
+  cnt = h->pin_cnt;
+  auto ndone = [&]() { return h->pin_cnt[ASM_CNT_DONE] + h->pin_cnt[ASM_NCNT + ASM_CNT_DONE]; };   // (counted in the view a problem finished in)
+  if (!defer_cnt) h->stats.asm_full_checks += ndone();
+  if (defer_cnt || ndone() > 0) {                // (row blocks without an ASM_DONE row leave these GEMMs at once)
     gemm64(h, h->q64_all, h->np, h->x0_64, h->ka, h->tq64, h->ka, segp, h->np, h->ka, h->asm_state, ASM_DONE);
     gemm64(h, h->asm_xh, h->np, h->asm_x, h->np, h->P64, h->np, segp, h->np, h->np, h->asm_state, ASM_DONE);
   }
   hipLaunchKernelGGL(asm_certify_k, dim3(nprob), dim3(256), 0, s, a, h->pscale);
   int* st = h->pin_st;
   HIPCHK(hipMemcpyAsync(st, h->asm_status, (size_t)nprob * sizeof(int), hipMemcpyDeviceToHost, s));
-  int* pin_its = h->pin_cnt + ASM_NCNT;
+  int* pin_its = h->pin_cnt + 2 * ASM_NCNT;
   if (h->profiling && pred_flops_per_it > 0.0) HIPCHK(hipMemcpyAsync(pin_its, h->pred_cnt + 1, 4, hipMemcpyDeviceToHost, s));
-  if (defer_cnt) HIPCHK(hipMemcpyAsync(cnt, h->asm_counters, ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (defer_cnt) HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(stream_sync(s));
-  if (defer_cnt) h->stats.asm_full_checks += cnt[ASM_CNT_DONE];
+  if (defer_cnt) h->stats.asm_full_checks += ndone();
   if (h->profiling && pred_flops_per_it > 0.0) h->stats.asm_predict_flops += pred_flops_per_it * (double)*pin_its;
   HIPCHK(hipGetLastError());
   std::vector<int> fb;
@@ -1555,7 +1689,8 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   if (hipStreamCreate(&h->stream2) != hipSuccess || hipStreamCreate(&h->stream3) != hipSuccess || hipStreamCreate(&h->stream4) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->ev_join4, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&h->ev_wfork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->ev_wide, hipEventDisableTiming) != hipSuccess) {
     set_error("hipStreamCreate / hipEventCreate failed"); nnmpc_qp_destroy(h); return NNMPC_EHIP;
   }
   {
@@ -1611,7 +1746,7 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   A_(h->q64_all, G * np); A_(h->uunc_all, G * np);
   A_(h->lb_d, G * nu); A_(h->ub_d, G * nu);
   A_(h->in_stage, G * n_aug);
-  if (!rc && hipHostMalloc((void**)&h->pin_cnt, (ASM_NCNT + 4) * sizeof(int)) != hipSuccess) { set_error("nnmpc_qp_create: hipHostMalloc failed"); rc = NNMPC_EHIP; }
+  if (!rc && hipHostMalloc((void**)&h->pin_cnt, (2 * ASM_NCNT + 4) * sizeof(int)) != hipSuccess) { set_error("nnmpc_qp_create: hipHostMalloc failed"); rc = NNMPC_EHIP; }
   if (!rc && hipHostMalloc((void**)&h->pin_st, G * sizeof(int)) != hipSuccess) { set_error("nnmpc_qp_create: hipHostMalloc failed"); rc = NNMPC_EHIP; }
   A_(d.lb64, (size_t)S * nu); A_(d.ub64, (size_t)S * nu);
   A_(d.slot_prob, S); A_(d.age, S); A_(d.next_prob, 1);
@@ -1622,10 +1757,31 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   A_(h->asm_xunc, G * np); A_(h->asm_x, G * np); A_(h->asm_lam, G * np); A_(h->asm_xh, G * np);
   A_(h->asm_xhw, (G + 256) * np); A_(h->asm_rowprob, G + 256); A_(h->asm_wflag, G); A_(h->asm_wmark, G);
   A_(h->asm_tnorm, G + 128 * (ASM_NKG + 1)); A_(h->asm_tslack, G + 128 * (ASM_NKG + 1));
-  A_(h->asm_st, G * n); A_(h->asm_state, G); A_(h->asm_rounds, G); A_(h->asm_counters, ASM_NCNT);
+  A_(h->asm_st, G * n); A_(h->asm_state, G); A_(h->asm_rounds, G); A_(h->asm_counters, 2 * ASM_NCNT);
   A_(h->asm_biglist, G); A_(h->asm_status, G); A_(h->asm_binlist, (size_t)(ASM_NLIST + 4) * G);
   A_(h->asm_idxg, G * o.asm_max_active); A_(h->asm_mg, G); A_(h->asm_row, G); A_(h->asm_lrank, G); A_(h->asm_ctot, ((G + 1023) / 1024) * ASM_NSCAN); A_(h->asm_prec, G); A_(h->asm_redo, G); A_(h->asm_rowk, G); A_(h->asm_lam32, G * np); A_(h->asm_xh32, G * np); A_(h->asm_alpha, G); A_(h->asm_ninf, G); A_(h->asm_hi, G); A_(h->asm_kblk, 2 * (G / 64 + 2)); A_(h->asm_work, 3 * G);
   A_(h->asm_scratch, (size_t)h->asm_pool * ((size_t)(o.asm_max_active / 16) * (o.asm_max_active / 16 + 1) / 2 * ASM_TS));
+  {
+    // the second row space: a thirty-second of the segment, 1024 rows at least (the CDU batch of 100 000 at sx = 2 leaves ~1 300
+    // problems running after the round most sets settle in: 3 200 rows, 0.47 GB at np = 4608).  Its k-range array is as long as view
+    // 0's: asm_bins_b_k writes the entry of every row it hands out, also in a round that turns out not to fit these rows.
+    // (NNMPC_OVERLAP_ROWS: tests only -- a row count that forces the rounds back into view 0)
+    nnmpc_qp::AsmView& v0 = h->view[0];
+    v0.lam = h->asm_lam; v0.xh = h->asm_xh; v0.xhw = h->asm_xhw; v0.tnorm = h->asm_tnorm; v0.tslack = h->asm_tslack;
+    v0.lam32 = h->asm_lam32; v0.xh32 = h->asm_xh32; v0.rowprob = h->asm_rowprob; v0.kblk = h->asm_kblk; v0.counters = h->asm_counters;
+    v0.rows = (int)G;
+    long long R = std::max<long long>(1024, ((long long)G / 32 + 127) / 128 * 128);
+    if (const char* e = getenv("NNMPC_OVERLAP_ROWS")) R = std::max(0, atoi(e) / 128 * 128);
+    R = std::min<long long>(R, (long long)G);
+    if (o.asm_overlap >= 0 && R > 0) {
+      nnmpc_qp::AsmView& v1 = h->view[1];
+      const size_t Rr = (size_t)R;
+      A_(v1.lam, Rr * np); A_(v1.xh, Rr * np); A_(v1.xhw, (Rr + 256) * np); A_(v1.lam32, Rr * np); A_(v1.xh32, Rr * np);
+      A_(v1.tnorm, Rr + 128 * (ASM_NKG + 1)); A_(v1.tslack, Rr + 128 * (ASM_NKG + 1)); A_(v1.rowprob, Rr + 256); A_(v1.kblk, 2 * (G / 64 + 2));
+      v1.counters = h->asm_counters + ASM_NCNT;
+      if (!rc) v1.rows = (int)R;
+    }
+  }
 #undef A_
   if (rc) { nnmpc_qp_destroy(h); return rc; }
   d.n = n; d.np = np; d.nu = nu; d.slots = S; d.words = h->words;
@@ -1704,6 +1860,8 @@ int nnmpc_qp_destroy(nnmpc_qp* h) {
   if (h->ev_join) hipEventDestroy(h->ev_join);
   if (h->ev_join3) hipEventDestroy(h->ev_join3);
   if (h->ev_join4) hipEventDestroy(h->ev_join4);
+  if (h->ev_wfork) hipEventDestroy(h->ev_wfork);
+  if (h->ev_wide) hipEventDestroy(h->ev_wide);
   if (h->pin_cnt) hipHostFree(h->pin_cnt);
   if (h->pin_st) hipHostFree(h->pin_st);
   if (h->stream2) hipStreamDestroy(h->stream2);
