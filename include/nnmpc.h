@@ -239,6 +239,58 @@ int nnmpc_nn_last_ms(nnmpc_nn* h, double* gemm_ms, double* total_ms);
  * lib/controller_evaluation.py:849-860) */
 int nnmpc_nn_last_hidden_ms(nnmpc_nn* h, double* hidden_ms, int32_t* launches);
 
+/* ---- Training step of the structured network, device resident  <-  train_nn_controller (cdu_train.py:40-62): Keras
+ * RegulatorModel compiled with Adam + MSE and fit(batch_size, validation_split), here one handle that holds the f32 master
+ * weights, the Adam moments, the dataset and every workspace in HBM.  Arithmetic: f32 storage and accumulation on the exact-f32
+ * matrix pipes, losses summed in fp64;  pred = us + MLP(pass 1) - MLP(pass 2) without clip,  loss = mean over B nu of
+ * (pred - u)^2;  ReLU derivative 0 at 0;  Adam as torch.optim.Adam computes it:
+ *     m = m + (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;  W -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * with the bias-correction scalars computed on the host in double.  Every sum has one fixed order (no atomics): results are
+ * bit-identical from run to run, and the gradient a step applies is bit-identical to the one nnmpc_train_grad returns.
+ * dims / W / b: as nnmpc_nn_create (Keras layout, W_l: dims[l] x dims[l+1], b[nlayers-1] ignored); they become the initial
+ * weights and the initial snapshot.  Batches hold at most max_batch rows (the workspaces are sized for it rounded up to 128,
+ * the limit itself is not rounded).  lr > 0, 0 <= beta1, beta2 < 1, eps > 0 (NNMPC_EINVAL otherwise).
+ * Non-finite data are not rejected and not hidden: a NaN in a row gives a NaN loss and NaN weights, as in torch.
+ * Environment: NNMPC_TRAIN_DW_SLICES=n (read by create) forces n row slices of the weight-gradient reduction (tests). */
+typedef struct nnmpc_train nnmpc_train;
+int nnmpc_train_create(nnmpc_train** out, int32_t nlayers, const int32_t* dims,
+                       const double* const* W, const double* const* b, int32_t nx, int32_t nu,
+                       int32_t with_uprev, int32_t max_batch, double lr, double beta1, double beta2,
+                       double eps);
+int nnmpc_train_destroy(nnmpc_train* h);
+/* The dataset, n rows as _get_data_for_training leaves them (already scaled): x, xs n x nx; uprev (NULL unless with_uprev),
+ * us, u n x nu.  Converted to f32 and kept in HBM; replaces an earlier dataset.  A with-uprev network without uprev: NNMPC_EINVAL. */
+int nnmpc_train_set_data(nnmpc_train* h, int32_t n, const double* x, const double* uprev,
+                         const double* xs, const double* us, const double* u, int32_t ptr_kind);
+/* Loss and gradient of the batch made of dataset rows rows[0..B) (host pointer), no update.  gW[l]: dims[l] x dims[l+1],
+ * gb[l]: dims[l+1] for l < nlayers - 1 (Keras layout; NULL entries and NULL lists are skipped).  B > max_batch or a row
+ * index outside [0, n): NNMPC_EINVAL before any launch (also for step and epoch).  rows / perm are copied into a pinned
+ * buffer of the handle before the call returns: the caller may reuse or free them at once, also after a step without loss. */
+int nnmpc_train_grad(nnmpc_train* h, int32_t B, const int32_t* rows, double* loss,
+                     double* const* gW, double* const* gb);
+/* One Adam update on that batch.  loss == NULL: enqueued without waiting for the device. */
+int nnmpc_train_step(nnmpc_train* h, int32_t B, const int32_t* rows, double* loss);
+/* Every step of an epoch back to back: batches perm[0..batch), perm[batch..2 batch), ... (the last one is the short one),
+ * one upload of perm, one wait at the end; *loss = sum_i loss_i rows_i / nrows, accumulated on the device. */
+int nnmpc_train_epoch(nnmpc_train* h, int32_t nrows, const int32_t* perm, int32_t batch,
+                      double* loss);
+/* Forward only: mean squared error over dataset rows [first, first + count) (the validation loss). */
+int nnmpc_train_eval(nnmpc_train* h, int32_t first, int32_t count, double* mse);
+/* Keras layout, the f32 master weights as doubles; set_weights keeps the moments and the step count. */
+int nnmpc_train_get_weights(nnmpc_train* h, double* const* W, double* const* b);
+int nnmpc_train_set_weights(nnmpc_train* h, const double* const* W, const double* const* b);
+/* Device-side copy of the current weights (ModelCheckpoint(save_best_only=True)) / back; the moments are not part of it. */
+int nnmpc_train_snapshot(nnmpc_train* h);
+int nnmpc_train_restore(nnmpc_train* h);
+/* hipEvent times of the last grad / step / epoch / eval (waits for it): the whole call on the device, and the spans of its
+ * forward GEMMs and of its backward pass (dW, bias column sums, dA). */
+int nnmpc_train_last_ms(nnmpc_train* h, double* gemm_ms, double* total_ms);
+/* Row slices of the dW reduction per layer (nlayers entries) in the last backward pass. */
+int nnmpc_train_dw_slices(nnmpc_train* h, int32_t* slices);
+/* Largest |entry| over the padding rows and columns of every weight, bias and moment image (a NaN there: NaN).  The
+ * padding has zero gradients by construction and must stay exactly zero through updates; this is the check. */
+int nnmpc_train_padding_max(nnmpc_train* h, double* maxabs);
+
 /* ---- Lock-step closed-loop chains, device resident  <-  simulate_offline (lib/linearMPC.py:827-880), one OS process
  * per chain in the reference (:814-825).  All nc chains of a task advance together; per step (loop :845-866):
  *     x0 = [x - xs; uprev - us], bounds ulb - us / uub - us   (get_control_sequence :682-689)

@@ -55,6 +55,10 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_qp_first_moves", "nnmpc_qp_set_farfield", "nnmpc_qp_farfield_missing",
            "nnmpc_qp_set_profiling", "nnmpc_qp_get_stats", "nnmpc_qp_debug_factor_solve",
            "nnmpc_nn_create", "nnmpc_nn_destroy", "nnmpc_nn_forward", "nnmpc_nn_last_ms", "nnmpc_nn_last_hidden_ms",
+           "nnmpc_train_create", "nnmpc_train_destroy", "nnmpc_train_set_data", "nnmpc_train_grad", "nnmpc_train_step",
+           "nnmpc_train_epoch", "nnmpc_train_eval", "nnmpc_train_get_weights", "nnmpc_train_set_weights",
+           "nnmpc_train_snapshot", "nnmpc_train_restore", "nnmpc_train_last_ms", "nnmpc_train_dw_slices",
+           "nnmpc_train_padding_max",
            "nnmpc_chain_create", "nnmpc_chain_destroy", "nnmpc_chain_run", "nnmpc_chain_reset", "nnmpc_chain_last_ms",
            "nnmpc_ts_create", "nnmpc_ts_destroy", "nnmpc_ts_solve_batch",
            "nnmpc_cl_create", "nnmpc_cl_destroy", "nnmpc_cl_run", "nnmpc_cl_reset", "nnmpc_cl_last_ms",
@@ -116,6 +120,35 @@ def load():
     lib.nnmpc_nn_last_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.nnmpc_nn_last_hidden_ms.restype = i32
     lib.nnmpc_nn_last_hidden_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    f64, pf64, pi32, pdp = C.c_double, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(dp)
+    lib.nnmpc_train_create.restype = i32
+    lib.nnmpc_train_create.argtypes = [C.POINTER(vp), i32, pi32, pdp, pdp, i32, i32, i32, i32, f64, f64, f64, f64]
+    lib.nnmpc_train_destroy.restype = i32
+    lib.nnmpc_train_destroy.argtypes = [vp]
+    lib.nnmpc_train_set_data.restype = i32
+    lib.nnmpc_train_set_data.argtypes = [vp, i32, dp, dp, dp, dp, dp, i32]
+    lib.nnmpc_train_grad.restype = i32
+    lib.nnmpc_train_grad.argtypes = [vp, i32, dp, pf64, pdp, pdp]
+    lib.nnmpc_train_step.restype = i32
+    lib.nnmpc_train_step.argtypes = [vp, i32, dp, pf64]
+    lib.nnmpc_train_epoch.restype = i32
+    lib.nnmpc_train_epoch.argtypes = [vp, i32, dp, i32, pf64]
+    lib.nnmpc_train_eval.restype = i32
+    lib.nnmpc_train_eval.argtypes = [vp, i32, i32, pf64]
+    lib.nnmpc_train_get_weights.restype = i32
+    lib.nnmpc_train_get_weights.argtypes = [vp, pdp, pdp]
+    lib.nnmpc_train_set_weights.restype = i32
+    lib.nnmpc_train_set_weights.argtypes = [vp, pdp, pdp]
+    lib.nnmpc_train_snapshot.restype = i32
+    lib.nnmpc_train_snapshot.argtypes = [vp]
+    lib.nnmpc_train_restore.restype = i32
+    lib.nnmpc_train_restore.argtypes = [vp]
+    lib.nnmpc_train_last_ms.restype = i32
+    lib.nnmpc_train_last_ms.argtypes = [vp, pf64, pf64]
+    lib.nnmpc_train_dw_slices.restype = i32
+    lib.nnmpc_train_dw_slices.argtypes = [vp, pi32]
+    lib.nnmpc_train_padding_max.restype = i32
+    lib.nnmpc_train_padding_max.argtypes = [vp, pf64]
     u64 = C.c_uint64
     lib.nnmpc_qp_solve_batch_ex.restype = i32
     lib.nnmpc_qp_solve_batch_ex.argtypes = [vp, i32, dp, dp, dp, dp, dp, dp, dp, dp, i32, i32]

@@ -8,14 +8,20 @@ Counterpart of the reference's ``cdu_train.py`` / ``cstrs_train.py``
 Keras ``get_weights()`` list, which is exactly what ``nn.StructuredNN`` /
 ``LinearMPCLayers.RegulatorLayer*`` take for the HIP forward.
 
-This is the only place PyTorch does arithmetic (BASELINE.json north_star);
-it is not part of the accelerated hot path.
+``backend="torch"`` (the default) is the only place PyTorch does arithmetic
+(BASELINE.json north_star).  ``backend="hip"`` runs the same step -- forward,
+backward, Adam, the epoch loop -- in f32 on hand-written gfx950 kernels
+(csrc/nn_train.hip, ``HipTrainer``); the model object then only carries the
+trained weights.
 """
 import copy
+import ctypes as C
 import time
 
 import numpy as np
 import torch
+
+from . import _lib
 
 
 class RegulatorModel(torch.nn.Module):
@@ -70,12 +76,184 @@ class RegulatorModel(torch.nn.Module):
                     lin.bias.copy_(torch.as_tensor(np.asarray(next(it)), dtype=lin.bias.dtype))
 
 
+class HipTrainer:
+    """The native training step (C ABI ``nnmpc_train_*``): f32 master weights, Adam moments, dataset and workspaces
+    live on the device; ``weights`` is the Keras ``get_weights()`` list the network starts from.
+
+    Adam as ``torch.optim.Adam(lr, betas, eps)``.  There is no CPU fallback: without a device the constructor raises
+    ``_lib.NnmpcError``."""
+
+    def __init__(self, weights, nx, nu, *, nnwithuprev=True, max_batch=2048, lr=1e-3, betas=(0.9, 0.999), eps=1e-7):
+        lib = _lib.load()
+        Ws = [np.ascontiguousarray(w, np.float64) for w in weights[0:-1:2]] + \
+             [np.ascontiguousarray(weights[-1], np.float64)]
+        bs = [np.ascontiguousarray(b, np.float64).ravel() for b in weights[1::2]]
+        L = len(Ws)
+        if len(bs) != L - 1:
+            raise ValueError("weights must be [W1, b1, ..., W_{L-1}, b_{L-1}, Wout]")
+        self.dims = [Ws[0].shape[0]] + [w.shape[1] for w in Ws]
+        self.L, self.nx, self.nu, self.nnwithuprev, self.n = L, nx, nu, bool(nnwithuprev), 0
+        self._lib, self._h = lib, C.c_void_p()
+        _lib.check(lib.nnmpc_train_create(C.byref(self._h), L, (C.c_int32 * (L + 1))(*self.dims), self._plist(Ws),
+                                          self._plist(bs + [None]), nx, nu, int(self.nnwithuprev), int(max_batch),
+                                          lr, betas[0], betas[1], eps), "nnmpc_train_create")
+
+    @staticmethod
+    def _plist(arrays):
+        return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.nnmpc_train_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def set_data(self, data):
+        """dict(x, uprev, xs, us, u), rows = samples, already scaled; uploaded once as f32."""
+        c = lambda a, w: np.ascontiguousarray(a, np.float64).reshape(-1, w)
+        x, xs, us, u = c(data["x"], self.nx), c(data["xs"], self.nx), c(data["us"], self.nu), c(data["u"], self.nu)
+        up = c(data["uprev"], self.nu) if self.nnwithuprev and data.get("uprev") is not None else None
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_train_set_data(self._h, x.shape[0], p(x), p(up), p(xs), p(us), p(u), _lib.HOST),
+                   "nnmpc_train_set_data")
+        self.n = x.shape[0]
+
+    def set_data_device(self, n, x, uprev, xs, us, u):
+        """The same from HBM-resident f64 buffers (objects with data_ptr(); ``uprev`` None without uprev)."""
+        q = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+        _lib.check(self._lib.nnmpc_train_set_data(self._h, int(n), q(x), q(uprev), q(xs), q(us), q(u), _lib.DEVICE),
+                   "nnmpc_train_set_data")
+        self.n = int(n)
+
+    @staticmethod
+    def _rows(rows):
+        return np.ascontiguousarray(rows, np.int32).ravel()
+
+    def _empty(self):
+        d = self.dims
+        return [np.empty((d[l], d[l + 1])) for l in range(self.L)], [np.empty(d[l + 1]) for l in range(self.L - 1)]
+
+    @staticmethod
+    def _keras(Ws, bs):
+        out = []
+        for l, w in enumerate(Ws):
+            out.append(w)
+            if l < len(bs):
+                out.append(bs[l])
+        return out
+
+    def grad(self, rows):
+        """(loss, gradients in Keras order) of the batch of dataset rows ``rows``; no update."""
+        r, loss = self._rows(rows), C.c_double()
+        gW, gb = self._empty()
+        _lib.check(self._lib.nnmpc_train_grad(self._h, r.size, r.ctypes.data_as(C.c_void_p), C.byref(loss),
+                                              self._plist(gW), self._plist(gb + [None])), "nnmpc_train_grad")
+        return loss.value, self._keras(gW, gb)
+
+    def step(self, rows, want_loss=True):
+        """One Adam update; without ``want_loss`` the call does not wait for the device and returns None."""
+        r, loss = self._rows(rows), C.c_double()
+        _lib.check(self._lib.nnmpc_train_step(self._h, r.size, r.ctypes.data_as(C.c_void_p),
+                                              C.byref(loss) if want_loss else None), "nnmpc_train_step")
+        return loss.value if want_loss else None
+
+    def epoch(self, perm, batch):
+        """All steps of an epoch over the rows ``perm`` (the last batch is the short one); the row-weighted mean loss."""
+        r, loss = self._rows(perm), C.c_double()
+        _lib.check(self._lib.nnmpc_train_epoch(self._h, r.size, r.ctypes.data_as(C.c_void_p), int(batch), C.byref(loss)),
+                   "nnmpc_train_epoch")
+        return loss.value
+
+    def eval(self, first, count):
+        """Mean squared error over dataset rows [first, first + count), forward only."""
+        mse = C.c_double()
+        _lib.check(self._lib.nnmpc_train_eval(self._h, int(first), int(count), C.byref(mse)), "nnmpc_train_eval")
+        return mse.value
+
+    def get_weights(self):
+        Ws, bs = self._empty()
+        _lib.check(self._lib.nnmpc_train_get_weights(self._h, self._plist(Ws), self._plist(bs + [None])),
+                   "nnmpc_train_get_weights")
+        return self._keras(Ws, bs)
+
+    def set_weights(self, weights):
+        Ws = [np.ascontiguousarray(w, np.float64) for w in weights[0:-1:2]] + [np.ascontiguousarray(weights[-1], np.float64)]
+        bs = [np.ascontiguousarray(b, np.float64).ravel() for b in weights[1::2]]
+        if [Ws[0].shape[0]] + [w.shape[1] for w in Ws] != self.dims or len(bs) != self.L - 1:
+            raise ValueError("set_weights: shapes differ from the network's")
+        _lib.check(self._lib.nnmpc_train_set_weights(self._h, self._plist(Ws), self._plist(bs + [None])),
+                   "nnmpc_train_set_weights")
+
+    def snapshot(self):
+        _lib.check(self._lib.nnmpc_train_snapshot(self._h), "nnmpc_train_snapshot")
+
+    def restore(self):
+        _lib.check(self._lib.nnmpc_train_restore(self._h), "nnmpc_train_restore")
+
+    def last_ms(self):
+        """(hipEvent ms of the GEMM spans, of the whole last call)."""
+        g, t = C.c_double(), C.c_double()
+        _lib.check(self._lib.nnmpc_train_last_ms(self._h, C.byref(g), C.byref(t)), "nnmpc_train_last_ms")
+        return g.value, t.value
+
+    def dw_slices(self):
+        s = (C.c_int32 * self.L)()
+        _lib.check(self._lib.nnmpc_train_dw_slices(self._h, s), "nnmpc_train_dw_slices")
+        return list(s)
+
+    def padding_max(self):
+        m = C.c_double()
+        _lib.check(self._lib.nnmpc_train_padding_max(self._h, C.byref(m)), "nnmpc_train_padding_max")
+        return m.value
+
+
+def _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log):
+    """The "hip" backend of train_nn_controller: same Keras semantics, every step on the device in f32."""
+    tr = HipTrainer(model.get_weights(), model.Nx, model.Nu, nnwithuprev=model.nnwithuprev, max_batch=batch_size,
+                    lr=lr, eps=1e-7)
+    try:
+        tr.set_data(data)
+        n = tr.n
+        nval = int(n * validation_split)
+        ntr = n - nval
+        rng = np.random.default_rng(seed)
+        best, hist = float("inf"), []
+        t0 = time.time()
+        for ep in range(epochs):
+            run = tr.epoch(rng.permutation(ntr), batch_size)
+            vl = tr.eval(ntr, nval) if nval else run
+            hist.append((run, vl))
+            if vl < best:                                   # ModelCheckpoint(save_best_only=True)
+                best = vl
+                tr.snapshot()
+            if log:
+                log(f"epoch {ep + 1}/{epochs} loss {run:.3e} val_loss {vl:.3e}")
+        if best < float("inf"):
+            tr.restore()
+        ttime = time.time() - t0
+        model.set_weights(tr.get_weights())
+    finally:
+        tr.close()
+    if device:
+        model = model.to(device)
+    return model, ttime, hist
+
+
 def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation_split=0.05, lr=1e-3,
-                        device=None, seed=1, log=None):
+                        device=None, seed=1, log=None, backend="torch"):
     """Adam + MSE on ``data`` = dict(x, uprev, xs, us, u) (rows = samples, already scaled like
     the reference's _get_data_for_training).  Keras semantics: the LAST fraction of the rows is
     the validation set, the rest is reshuffled every epoch; the weights of the best validation
-    epoch are restored at the end.  Returns (model, training_time, history)."""
+    epoch are restored at the end.  Returns (model, training_time, history).
+
+    ``backend="torch"``: stock PyTorch ops in the model's dtype on ``device``.  ``backend="hip"``: the native f32
+    step (``HipTrainer``), shuffled by a numpy generator seeded with ``seed``; ``model`` comes back carrying the
+    trained weights.  No device: ``_lib.NnmpcError`` (no CPU fallback)."""
+    if backend == "hip":
+        return _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log)
+    if backend != "torch":
+        raise ValueError(f"unknown backend {backend!r}: 'torch' or 'hip'")
     torch.manual_seed(seed)
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     model = model.to(device)

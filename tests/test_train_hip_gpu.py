@@ -1,0 +1,381 @@
+"""The native training step (csrc/nn_train.hip, C ABI nnmpc_train_*, train.HipTrainer) against the project's own
+RegulatorModel in torch float64 ON THE CPU with autograd and torch.optim.Adam's formula -- never the code under test.
+
+Bars.  Gradients, per parameter tensor in Keras layout: max|g_hip - g64| / max|g64| <= max(8 x the same figure of the
+reference run in torch float32 on the CPU with the same weights and rows -- measured on every run; 8 because the summation
+orders differ and the error is statistical --, sqrt(2 Bp) 2^-24, the random-walk rounding of a length-2Bp f32 dot product).
+Loss: the same rule with floor 2^-20 relative.  A ReLU kink makes f32 and f64 legitimately disagree by O(1/B), so the batch
+is chosen by the reference alone: of 4B + 64 candidate rows, the first B whose smallest |pre-activation| (both passes, all
+hidden units, float64) exceeds 1e-4 x that row's largest.  Weights and data are rounded to f32 first, so every path starts
+from the same numbers.  The measured figures are printed (pytest -s)."""
+import functools
+import re
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+LR, B1, B2, EPS = 1e-3, 0.9, 0.999, 1e-7
+CASES = {                     # nx, nu, uprev, hidden widths, B
+    "a": (5, 3, True, [70, 130, 70], 200),
+    "b": (5, 3, True, [70, 130, 70], 1),
+    "c": (12, 6, True, [224, 240, 224], 129),       # one row in the second row tile
+    "d": (7, 4, False, [64, 128], 128),             # exact tile multiples, two hidden layers
+    "e": (5, 3, False, [70, 130, 70], 200),
+    "f": (5, 3, True, [70, 130, 70], 600),          # several dW slices (override)
+}
+FILL = 5                      # filler rows in front of the chosen ones: the step gathers by index
+
+
+def _f32(a):
+    return np.asarray(a, np.float32).astype(np.float64)
+
+
+def _weights(nx, nu, uprev, hidden, rng):
+    """Glorot-uniform weights, hidden biases 0.1 N(0,1); Keras order, f32-representable."""
+    dims = [2 * nx + (2 if uprev else 1) * nu] + list(hidden) + [nu]
+    out = []
+    for l in range(len(dims) - 1):
+        lim = np.sqrt(6.0 / (dims[l] + dims[l + 1]))
+        out.append(_f32(rng.uniform(-lim, lim, (dims[l], dims[l + 1]))))
+        if l < len(dims) - 2:
+            out.append(_f32(0.1 * rng.standard_normal(dims[l + 1])))
+    return out
+
+
+def _draw(n, nx, nu, rng):
+    x, xs = rng.standard_normal((n, nx)), 0.3 * rng.standard_normal((n, nx))
+    us = rng.uniform(-.5, .5, (n, nu))
+    up = us + rng.uniform(-.3, .3, (n, nu))
+    u = np.clip(us + 0.5 * rng.standard_normal((n, nu)), -1, 1)
+    return {k: _f32(v) for k, v in dict(x=x, uprev=up, xs=xs, us=us, u=u).items()}
+
+
+def _kink_margin(W, d, uprev):
+    """Per row: smallest / largest |pre-activation| over both passes and all hidden units (float64)."""
+    if uprev:
+        z1, z2 = np.hstack((d["x"], d["uprev"], d["xs"], d["us"])), np.hstack((d["xs"], d["us"], d["xs"], d["us"]))
+    else:
+        z1, z2 = np.hstack((d["x"], d["xs"], d["us"])), np.hstack((d["xs"], d["xs"], d["us"]))
+    lo, hi = np.full(z1.shape[0], np.inf), np.zeros(z1.shape[0])
+    for z in (z1, z2):
+        for l in range(0, len(W) - 1, 2):
+            p = np.abs(z @ W[l] + W[l + 1])
+            lo, hi = np.minimum(lo, p.min(1)), np.maximum(hi, p.max(1))
+            z = np.maximum(z @ W[l] + W[l + 1], 0.0)
+    return lo, hi
+
+
+def _kink_free(W, nx, nu, uprev, B, rng):
+    """Dataset of FILL + B rows whose rows FILL.. are the first B kink-free candidates of 4B + 64."""
+    d = _draw(4 * B + 64, nx, nu, rng)
+    lo, hi = _kink_margin(W, d, uprev)
+    keep = np.flatnonzero(lo > 1e-4 * hi)
+    assert keep.size >= B, (keep.size, B)
+    sel = np.concatenate((np.arange(FILL), keep[:B]))
+    return {k: v[sel] for k, v in d.items()}
+
+
+def _torch_grad(W, nx, nu, uprev, d, rows, dtype):
+    """(loss, Keras-order gradients) of train.RegulatorModel in torch ``dtype`` on the CPU, by autograd."""
+    import torch
+    from industrial_nnmpc_2021_amd.train import RegulatorModel
+    m = RegulatorModel(nx, nu, [None] + [w.shape[1] for w in W[0:-1:2]] + [nu], nnwithuprev=uprev, dtype=dtype)
+    m.set_weights(W)
+    t = lambda k: torch.as_tensor(d[k][rows], dtype=dtype)
+    loss = torch.mean((m(t("x"), t("uprev"), t("xs"), t("us")) - t("u")) ** 2)
+    loss.backward()
+    g = []
+    for lin in m.layers:
+        g.append(lin.weight.grad.double().numpy().T.copy())
+        if lin.bias is not None:
+            g.append(lin.bias.grad.double().numpy().copy())
+    return float(loss.detach()), g
+
+
+def _check_grad(tag, tr, W, nx, nu, uprev, d, rows):
+    """Check 1 at the weights W (those the handle holds): loss and every gradient tensor within their bars."""
+    import torch
+    B = len(rows)
+    Bp = (B + 127) // 128 * 128
+    l64, g64 = _torch_grad(W, nx, nu, uprev, d, rows, torch.float64)
+    l32, g32 = _torch_grad(W, nx, nu, uprev, d, rows, torch.float32)
+    lh, gh = tr.grad(rows)
+    rel = lambda a, ref: np.abs(a - ref).max() / np.abs(ref).max()
+    el, el32 = abs(lh - l64) / abs(l64), abs(l32 - l64) / abs(l64)
+    print(f"[{tag}] loss {l64:.6e}: hip {el:.2e}, torch f32 {el32:.2e}, bar {max(8 * el32, 2.0 ** -20):.2e}")
+    fails = []
+    if not el <= max(8 * el32, 2.0 ** -20):
+        fails.append(("loss", el))
+    for i, (a, r32, r64) in enumerate(zip(gh, g32, g64)):
+        assert a.shape == r64.shape
+        e, e32 = rel(a, r64), rel(r32, r64)
+        bar = max(8 * e32, np.sqrt(2 * Bp) * 2.0 ** -24)
+        print(f"[{tag}] tensor {i} {r64.shape}: hip {e:.2e}, torch f32 {e32:.2e}, bar {bar:.2e}")
+        if not e <= bar:
+            fails.append((i, e, bar))
+    assert not fails, fails
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    nx, nu, uprev, hidden, B = CASES[name]
+    rng = np.random.default_rng(100 + ord(name))
+    W = _weights(nx, nu, uprev, hidden, rng)
+    d = _kink_free(W, nx, nu, uprev, B, rng)
+    rows = FILL + rng.permutation(B)
+    return W, d, rows
+
+
+def _trainer(W, nx, nu, uprev, d, max_batch):
+    from industrial_nnmpc_2021_amd.train import HipTrainer
+    tr = HipTrainer(W, nx, nu, nnwithuprev=uprev, max_batch=max_batch, lr=LR, betas=(B1, B2), eps=EPS)
+    tr.set_data(d)
+    return tr
+
+
+@pytest.mark.parametrize("name", ["a", "b", "c", "d", "e"])
+def test_gradient_parity(name):
+    nx, nu, uprev, hidden, B = CASES[name]
+    W, d, rows = _case(name)
+    tr = _trainer(W, nx, nu, uprev, d, B)
+    try:
+        _check_grad(name, tr, W, nx, nu, uprev, d, rows)
+        if name == "a":
+            assert tr.dw_slices() == [1] * (len(hidden) + 1)         # what case (f) is compared with
+        assert tr.padding_max() == 0.0
+    finally:
+        tr.close()
+
+
+def test_gradient_parity_with_several_dw_slices(monkeypatch):
+    nx, nu, uprev, hidden, B = CASES["f"]
+    W, d, rows = _case("f")
+    monkeypatch.setenv("NNMPC_TRAIN_DW_SLICES", "3")                 # 2 Bp = 1280 rows = 40 chunks: slices of 14, 14, 12
+    tr = _trainer(W, nx, nu, uprev, d, B)
+    try:
+        _check_grad("f", tr, W, nx, nu, uprev, d, rows)
+        assert tr.dw_slices() == [3] * (len(hidden) + 1)
+    finally:
+        tr.close()
+
+
+def test_adam_steps_follow_torchs_formula():
+    """Three steps on the rows of case (a): after each, every entry is within 4 * 2^-24 * max(|W_ref|, lr) of torch's Adam
+    formula applied in numpy float64 to the weights read back before the step and the gradient ``grad`` returned for them
+    (a handful of f32 roundings of the update and of the subtraction).  Then check 1 again at the updated weights."""
+    nx, nu, uprev, hidden, B = CASES["a"]
+    W, d, rows = _case("a")
+    tr = _trainer(W, nx, nu, uprev, d, B)
+    try:
+        m = [np.zeros_like(w) for w in W]
+        v = [np.zeros_like(w) for w in W]
+        for t in (1, 2, 3):
+            W0 = tr.get_weights()
+            _, g = tr.grad(rows)
+            tr.step(rows)
+            W1 = tr.get_weights()
+            worst = 0.0
+            for i in range(len(W)):
+                m[i] = m[i] + (g[i] - m[i]) * (1 - B1)
+                v[i] = B2 * v[i] + (1 - B2) * g[i] * g[i]
+                ref = W0[i] - LR / (1 - B1 ** t) * m[i] / (np.sqrt(v[i]) / np.sqrt(1 - B2 ** t) + EPS)
+                ratio = np.abs(W1[i] - ref) / (4 * 2.0 ** -24 * np.maximum(np.abs(ref), LR))
+                worst = max(worst, ratio.max())
+                assert np.abs(W1[i] - W0[i]).max() > 0.1 * LR               # the step moved this tensor
+            print(f"[adam] step {t}: worst |W_hip - W_ref| / bar = {worst:.3f}")
+            assert worst <= 1.0
+        assert tr.padding_max() == 0.0                                       # padding of W, b, m, v still exactly zero
+        W3 = tr.get_weights()
+        lo, hi = _kink_margin(W3, d, uprev)                                  # the weights moved: the reference chooses again
+        rows3 = rows[(lo > 1e-4 * hi)[rows]]
+        assert len(rows3) >= B // 4, len(rows3)
+        _check_grad("a after 3 steps", tr, W3, nx, nu, uprev, d, rows3)
+    finally:
+        tr.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _epoch_data():
+    nx, nu, uprev, hidden = 5, 3, True, [70, 130, 70]
+    rng = np.random.default_rng(7)
+    return nx, nu, uprev, _weights(nx, nu, uprev, hidden, rng), _draw(1000, nx, nu, rng)
+
+
+def _bytes(weights):
+    return b"".join(np.ascontiguousarray(w).tobytes() for w in weights)
+
+
+def test_epoch_equals_its_steps():
+    """1000 rows, validation_split 0.05 -> 950 training rows, batch 256: three full batches and one of 182."""
+    nx, nu, uprev, W, d = _epoch_data()
+    ntr = 1000 - int(1000 * 0.05)
+    perm = np.random.default_rng(3).permutation(ntr)
+    a, b = _trainer(W, nx, nu, uprev, d, 256), _trainer(W, nx, nu, uprev, d, 256)
+    try:
+        parts = [perm[i:i + 256] for i in range(0, ntr, 256)]
+        assert [len(p) for p in parts] == [256, 256, 256, 182]
+        losses = [a.step(p) for p in parts]
+        le = b.epoch(perm, 256)
+        assert _bytes(a.get_weights()) == _bytes(b.get_weights())
+        want = sum(l * len(p) for l, p in zip(losses, parts)) / ntr
+        print(f"[epoch] loss {le:.9e}, from the steps {want:.9e}")
+        assert abs(le - want) <= 2.0 ** -20 * abs(want)
+        assert np.abs(np.concatenate([w.ravel() for w in a.get_weights()])
+                      - np.concatenate([w.ravel() for w in W])).max() > LR       # and it trained
+    finally:
+        a.close(); b.close()
+
+
+def test_steps_without_loss_equal_synced_steps():
+    """step(rows, want_loss=False) returns without waiting for the device; the caller's row buffer is overwritten right
+    after every call.  Mixed with synced steps it must leave the bytes of synced steps alone."""
+    nx, nu, uprev, W, d = _epoch_data()
+    perm = np.random.default_rng(5).permutation(950).astype(np.int32)
+    parts = [perm[i:i + 256] for i in range(0, 950, 256)] * 2
+    a, b = _trainer(W, nx, nu, uprev, d, 256), _trainer(W, nx, nu, uprev, d, 256)
+    try:
+        buf = np.empty(256, np.int32)
+        for i, p in enumerate(parts):
+            r = buf[:len(p)]
+            r[:] = p
+            if i % 3 == 2:
+                assert np.isfinite(a.step(r))
+            else:
+                assert a.step(r, want_loss=False) is None
+            buf[:] = 999                                                     # a valid row, but not the batch's
+            b.step(p)
+        assert _bytes(a.get_weights()) == _bytes(b.get_weights())
+    finally:
+        a.close(); b.close()
+
+
+def test_two_runs_give_identical_bytes():
+    nx, nu, uprev, W, d = _epoch_data()
+    out = []
+    for _ in range(2):
+        tr = _trainer(W, nx, nu, uprev, d, 256)
+        try:
+            rng = np.random.default_rng(11)
+            for _ep in range(2):
+                tr.epoch(rng.permutation(950), 256)
+            out.append(_bytes(tr.get_weights()))
+        finally:
+            tr.close()
+    assert out[0] == out[1]
+
+
+def test_fit_with_the_hip_backend_then_deploy_through_the_hip_forward():
+    """The scenario and thresholds of tests/test_train_gpu.py with backend="hip"; in addition the returned model's
+    validation loss in torch float64 equals min over hist (the best epoch's weights were restored)."""
+    import torch
+    from industrial_nnmpc_2021_amd.train import RegulatorModel, train_nn_controller
+    from industrial_nnmpc_2021_amd.nn import StructuredNN
+    from industrial_nnmpc_2021_amd import controller_evaluation as ce
+    rng = np.random.default_rng(1)
+    nx, nu, n = 6, 3, 8192
+    K = rng.standard_normal((nu, nx)) * 0.5
+    x, xs = 1.5 * rng.standard_normal((n, nx)), 0.2 * rng.standard_normal((n, nx))
+    us = rng.uniform(-.3, .3, (n, nu)); up = us + rng.uniform(-.2, .2, (n, nu))
+    u = np.clip(us + (x - xs) @ K.T, -1, 1)
+    raw = dict(x=x, uprev=up, xs=xs, us=us, u=u)
+    data, xscale = ce._get_data_for_training(data=raw, num_samples=n)
+    m = RegulatorModel(nx, nu, [None, 64, 64, nu], nnwithuprev=True)
+    m, ttime, hist = train_nn_controller(m, data, epochs=25, batch_size=512, backend="hip")
+    assert ttime > 0 and len(hist) == 25
+    assert hist[-1][1] < 0.25 * hist[0][1]                                     # it learns
+    W = m.get_weights()
+    net = StructuredNN(W, nx, nu, nnwithuprev=True, xscale=xscale, ulb=-np.ones(nu), uub=np.ones(nu), max_batch=1024)
+    k = 1000
+    got = net.forward(x[:k], up[:k], xs[:k], us[:k])
+    m = m.cpu()
+    t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
+    with torch.no_grad():
+        ref = m(t(data["x"][:k]), t(data["uprev"][:k]), t(data["xs"][:k]), t(data["us"][:k])).clamp(-1, 1).numpy()
+        nval = int(n * 0.05)
+        s = slice(n - nval, n)
+        val = lambda mod, tt: float(torch.mean((mod(tt(data["x"][s]), tt(data["uprev"][s]), tt(data["xs"][s]), tt(data["us"][s]))
+                                                - tt(data["u"][s])) ** 2))
+        val64 = val(m, t)
+        m32 = RegulatorModel(nx, nu, [None, 64, 64, nu], nnwithuprev=True, dtype=torch.float32)
+        m32.set_weights(W)
+        val32 = val(m32, lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32))
+    net.close()
+    assert np.abs(got - ref).max() < 1e-4
+    assert np.abs(got - u[:k]).mean() < 0.1
+    best = min(h[1] for h in hist)
+    e, e32 = abs(best - val64) / val64, abs(val32 - val64) / val64
+    print(f"[fit] val loss first {hist[0][1]:.3e} last {hist[-1][1]:.3e} best {best:.6e}, returned model in f64 {val64:.6e}: "
+          f"hip {e:.2e}, torch f32 {e32:.2e}")
+    assert e <= max(8 * e32, 2.0 ** -20)
+
+
+def test_device_resident_dataset_gives_the_same_bytes():
+    """set_data from f64 buffers already in HBM (NNMPC_DEVICE) converts to the same f32 dataset as the host path."""
+    from industrial_nnmpc_2021_amd import _lib
+    nx, nu, uprev, hidden, B = CASES["c"]
+    W, d, rows = _case("c")
+    a, b = _trainer(W, nx, nu, uprev, d, B), None
+    bufs = {k: _lib.DeviceArray.from_host(np.ascontiguousarray(v, np.float64)) for k, v in d.items()}
+    try:
+        from industrial_nnmpc_2021_amd.train import HipTrainer
+        b = HipTrainer(W, nx, nu, nnwithuprev=uprev, max_batch=B, lr=LR, betas=(B1, B2), eps=EPS)
+        b.set_data_device(d["x"].shape[0], bufs["x"], bufs["uprev"], bufs["xs"], bufs["us"], bufs["u"])
+        la, ga = a.grad(rows)
+        lb, gb = b.grad(rows)
+        assert la == lb and _bytes(ga) == _bytes(gb)
+    finally:
+        a.close()
+        if b is not None:
+            b.close()
+        for v in bufs.values():
+            v.free()
+
+
+def _einval(fn):
+    from industrial_nnmpc_2021_amd import _lib
+    with pytest.raises(_lib.NnmpcError) as ei:
+        fn()
+    assert re.search(r"\(code -1\): \S", str(ei.value)), str(ei.value)              # NNMPC_EINVAL with a message
+
+
+def test_edges_are_rejected_and_nan_is_not_hidden():
+    from industrial_nnmpc_2021_amd.train import HipTrainer
+    nx, nu, uprev, hidden, B = CASES["a"]
+    W, d, rows = _case("a")
+    n = d["x"].shape[0]
+    _einval(lambda: HipTrainer(W, nx + 1, nu, nnwithuprev=True, max_batch=128))      # dims[0] != 2 nx + 2 nu
+    _einval(lambda: HipTrainer(W, nx, nu + 1, nnwithuprev=True, max_batch=128))      # dims[L] != nu
+    _einval(lambda: HipTrainer(W, nx, nu, nnwithuprev=True, max_batch=128, eps=0.0))  # 0 / 0 on every zero-gradient entry
+    tr = _trainer(W, nx, nu, uprev, d, 200)                                           # the limit is not rounded up to the tile
+    try:
+        assert np.isfinite(tr.grad(rows[:200])[0])
+        _einval(lambda: tr.grad(np.concatenate((rows, rows[:1]))))
+        _einval(lambda: tr.step(np.concatenate((rows, rows[:1]))))
+    finally:
+        tr.close()
+    tr = _trainer(W, nx, nu, uprev, d, 128)
+    try:
+        before = _bytes(tr.get_weights())
+        _einval(lambda: tr.grad(rows[:129]))                                          # B > max_batch
+        _einval(lambda: tr.step(rows[:129]))
+        _einval(lambda: tr.epoch(rows[:100], 129))
+        for bad in (n, -1):
+            r = rows[:16].copy(); r[7] = bad
+            _einval(lambda: tr.grad(r))
+            _einval(lambda: tr.step(r))
+            _einval(lambda: tr.epoch(r, 8))
+        _einval(lambda: tr.eval(n - 3, 4))
+        _einval(lambda: tr.set_data({k: v for k, v in d.items() if k != "uprev"}))    # with-uprev network, no uprev
+        assert _bytes(tr.get_weights()) == before                                     # rejected before any launch
+        assert np.isfinite(tr.grad(rows[:16])[0])
+        bad = {k: v.copy() for k, v in d.items()}
+        bad["x"][rows[3], 1] = np.nan
+        tr.set_data(bad)
+        assert np.isnan(tr.grad(rows[:16])[0])                                        # not rejected, not hidden
+        assert np.isfinite(tr.grad(rows[4:20])[0])                                    # the other rows are unaffected
+        assert np.isnan(tr.step(rows[:16]))
+        assert np.isnan(tr.get_weights()[-1]).any()                                   # NaN weights, as in torch
+    finally:
+        tr.close()
