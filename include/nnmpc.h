@@ -47,7 +47,7 @@ extern "C" {
 
 /* per-problem status written by nnmpc_qp_solve_batch */
 #define NNMPC_ST_OPTIMAL 0   /* KKT conditions verified in fp64 */
-#define NNMPC_ST_MAXITER 1   /* round / polish budget exhausted, not certified */
+#define NNMPC_ST_MAXITER 1   /* round / polish budget exhausted (method 2: or an active set beyond asm_max_active), not certified */
 #define NNMPC_ST_NUMERIC 2   /* non-positive pivot or NaN; nnmpc_ts_*: also an infeasible or rank-deficient problem (see there) */
 
 typedef struct nnmpc_qp nnmpc_qp;
@@ -66,7 +66,10 @@ typedef struct {
   int32_t stale_cg_limit;    /* ... and refactor anyway after this many PCG steps; 0 = 16 */
   int32_t method;            /* 0 = auto: shared-inverse active-set pass (needs nnmpc_qp_set_inverse),
                                 PDIP for what it leaves; 1 = PDIP only; 2 = active-set pass only */
-  int32_t asm_max_active;    /* active-set pass: largest active set handled (<= 768); 0 = 768 */
+  int32_t asm_max_active;    /* active-set pass: largest active set handled (<= 768, rounded down to a multiple of 16, at least 16);
+                                0 = 768.  A set of exactly this many bounds is solved by the pass; a problem whose set is larger
+                                at ANY iteration (not only at the optimum) leaves it: method 0 solves it on the PDIP path, method 2
+                                reports NNMPC_ST_MAXITER for it -- its u and active rows are then not an answer */
   int32_t asm_max_rounds;    /* ... and its budget; 0 = 200 lock-step rounds (all-at-once exchanges settle in ~5) and 50 000
                                 iterations per problem in the device tail (the single-exchange fallback against cycling is
                                 finite but can take tens of thousands of ~30 us iterations on ill-conditioned Hessians with
@@ -122,7 +125,7 @@ typedef struct {
   int64_t asm_far_passes;    /* full-width passes that ran in the far-field form (nnmpc_qp_set_farfield) */
   double asm_side_ms;        /* hipEvent time of the multiplier kernels of the larger sets on the three side streams (they run
                                 beside asm_lambda_reg32_k / asm_lambda_reg_k; sum over the streams) */
-  int64_t asm_small_passes;  /* segments that went through the one-wave-per-problem kernel of small problems (asm_small_k: n <= 724) */
+  int64_t asm_small_passes;  /* segments that went through the one-wave-per-problem kernel of small problems (asm_small_k: padded n <= 724, i.e. n <= 704) */
   int64_t asm_predict_launches; /* launches of the first-set predictor (asm_predict_k) */
   double asm_predict_ms;     /* their hipEvent time (profiling on) */
   double asm_predict_flops;  /* bf16 MFMA flops they executed: 2 * 64 * 512 * (columns of Y in use) per workgroup and iteration */

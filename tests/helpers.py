@@ -407,3 +407,153 @@ def ts_reference(Pr, E, lb, ub, Q, Ee):
 def ts_kept(ref, q):
     """The margin rule: primal and dual margin of the certified reference > 1e-6 (dual: relative to max(1, |q|inf))."""
     return ref["primal_margin"] > TS_MARGIN and ref["dual_margin"] > TS_MARGIN * max(1.0, float(np.abs(q).max()))
+
+
+# ---- box QPs with an active set of a chosen size: tests/test_large_sets_gpu.py, tests/test_cpu_large_set_inputs.py ------------
+
+def kkt_check(P, tq, nu, N, x0, lb, ub, out, stat_tol):
+    """Independent fp64 check of every returned solution."""
+    Ps = np.tril(P) + np.tril(P, -1).T
+    U = out["u"]
+    G = U @ Ps + x0 @ tq.T                     # gradient rows
+    LB, UB = np.tile(lb, (1, N)), np.tile(ub, (1, N))
+    n = P.shape[0]
+    k, c = np.arange(n) // nu, np.arange(n) % nu
+    au, al = out["active"][:, k * 2 * nu + c], out["active"][:, k * 2 * nu + nu + c]
+    assert not (au & al).any()
+    assert (U <= UB + 1e-9).all() and (U >= LB - 1e-9).all()                 # primal feasibility
+    assert np.abs(np.where(au, U - UB, 0)).max() == 0 and np.abs(np.where(al, U - LB, 0)).max() == 0
+    scale = np.maximum(1.0, np.abs(x0 @ tq.T).max(axis=1, keepdims=True))
+    free = ~(au | al)
+    assert (np.abs(np.where(free, G, 0)) <= stat_tol * scale).all()            # stationarity on the free set
+    assert (np.where(au, -G, 1) > 0).all() and (np.where(al, G, 1) > 0).all()  # multiplier signs
+
+
+def kkt_stationarity(P, q, nu, out):
+    """Per row: max |gradient| over the free variables in units of max(1, |q|inf) -- the figure kkt_check bounds (tq = I)."""
+    n = P.shape[0]
+    k, c = np.arange(n) // nu, np.arange(n) % nu
+    free = ~(out["active"][:, k * 2 * nu + c] | out["active"][:, k * 2 * nu + nu + c])
+    G = out["u"] @ (np.tril(P) + np.tril(P, -1).T) + q
+    return np.abs(np.where(free, G, 0)).max(axis=1) / np.maximum(1.0, np.abs(q).max(axis=1))
+
+
+def state_to_active(state, nu):
+    """(B, n) uint8 bound states (0 free, 1 upper, 2 lower: the `guess` format) -> (B, 2n) bool rows of the reference's G."""
+    B, n = state.shape
+    k, c = np.arange(n) // nu, np.arange(n) % nu
+    act = np.zeros((B, 2 * n), bool)
+    act[:, k * 2 * nu + c] = state == 1
+    act[:, k * 2 * nu + nu + c] = state == 2
+    return act
+
+
+def active_to_state(active, nu):
+    """The inverse of state_to_active."""
+    n = active.shape[1] // 2
+    k, c = np.arange(n) // nu, np.arange(n) % nu
+    return active[:, k * 2 * nu + c].astype(np.uint8) + 2 * active[:, k * 2 * nu + nu + c].astype(np.uint8)
+
+
+def spd_logspectrum(n, seed, cond):
+    """Dense Q diag(exp(U(0, log cond))) Q' (the Hessian of tests/test_asm_gpu.py)."""
+    rng = np.random.default_rng(seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    ev = np.exp(rng.uniform(0.0, np.log(cond), n))
+    return (Q * ev) @ Q.T
+
+
+def large_set_hessian(n, seed):
+    """P = diag(U(1, 4)) + 0.15 (G + G'), G = N(0, 1) / sqrt(n): diagonally dominated, cond ~ 5 at n = 1024."""
+    rng = np.random.default_rng(seed)
+    G = rng.standard_normal((n, n)) / np.sqrt(n)
+    return np.diag(rng.uniform(1.0, 4.0, n)) + 0.15 * (G + G.T)
+
+
+def pushed_rows(P, nu, seed, sizes, lo, hi, exact=False):
+    """One problem per entry of ``sizes`` (tq = I, so q = x0; bounds -1 / +1 on every input): the unconstrained optimum x_unc is
+    0.05 N(0, 1), except on m indices drawn without replacement over the whole horizon, which sit at +-U(lo, hi) -- beyond a
+    bound -- and q = -P x_unc.  Returns q (B, n), lb, ub (nu,), the pushed bound states (B, n) uint8 (1 upper, 2 lower) and, with
+    ``exact``, the optimum x (B, n) in fp64.
+
+    exact: every row is CERTIFIED to have the pushed set as its optimal set -- the fp64 solve on that set (solve_on_set) keeps
+    every free variable within 0.9 of the origin and every multiplier above 1e-2 with the right sign, which for a positive definite
+    P makes it the optimum.  The couplings of hundreds of active bounds do now and then carry a pushed variable back inside the box
+    (seen at 768 bounds: x_unc = 1.64, optimum 0.84); such a row is drawn again (from the same generator: still a function of the
+    seed alone)."""
+    n = P.shape[0]
+    rng = np.random.default_rng(seed)
+    B = len(sizes)
+    Ps = np.tril(P) + np.tril(P, -1).T
+    lb, ub = -np.ones(nu), np.ones(nu)
+    xunc = 0.05 * rng.standard_normal((B, n))
+    q = np.empty((B, n))
+    state = np.zeros((B, n), np.uint8)
+    xref = np.empty((B, n)) if exact else None
+    for b, m in enumerate(sizes):
+        for attempt in range(50):
+            xu, st = xunc[b].copy(), np.zeros(n, np.uint8)
+            idx = rng.choice(n, int(m), replace=False)
+            sgn = rng.choice([-1.0, 1.0], int(m))
+            xu[idx] = sgn * rng.uniform(lo, hi, int(m))
+            st[idx] = np.where(sgn > 0, 1, 2)
+            qb = -Ps @ xu
+            if not exact:
+                break
+            x = solve_on_set(Ps, qb, lb, ub, st)
+            g = Ps @ x + qb
+            if np.abs(x[st == 0]).max(initial=0.0) <= 0.9 and (g[st == 1] < -1e-2).all() and (g[st == 2] > 1e-2).all():
+                xref[b] = x
+                break
+        else:
+            raise RuntimeError(f"no exact row of {m} bounds in 50 draws")
+        q[b], state[b] = qb, st
+    return q, lb, ub, state, xref
+
+
+def large_set_problem(n, nu, seed, sizes):
+    """Problems whose optimal active set has EXACTLY the sizes asked for: large_set_hessian with pushes of +-U(1.5, 3), rows
+    certified (pushed_rows, exact).  The optimum's set is the pushed set with the pushed signs, and so is the first set (the bounds
+    x_unc violates): a solver's f32 round and its fp64 solve both run at size m (tests/test_cpu_large_set_inputs.py holds the
+    oracle to this).  Returns P, q (B, n), lb, ub (nu,), expected bound states (B, n) uint8, the optimum x (B, n)."""
+    P = large_set_hessian(n, seed)
+    return (P,) + pushed_rows(P, nu, seed + 1, sizes, 1.5, 3.0, exact=True)
+
+
+# Numerical strain: the dense log-spectrum Hessian at cond 1e4 (below the 5e4 up to which method "auto" must solve everything),
+# pushes of +-U(1.2, 2): the couplings add bounds to the pushed ones, the free-block systems are ill conditioned.  The push counts
+# were chosen with the oracle so that its sets cover both large classes (tests/test_cpu_large_set_inputs.py asserts the shares).
+STRAIN_COND = 1e4
+STRAIN_SEED = 31
+STRAIN_PUSHES = [230, 250, 270, 300, 350, 400, 450, 500]        # oracle's sets: 264, 297, 335, 386, 429, 430, 479, 546 bounds
+
+
+def strain_problem(n=1024, nu=8):
+    """P, q, lb, ub of the strain family (the final sets are the oracle's to say)."""
+    P = spd_logspectrum(n, STRAIN_SEED, STRAIN_COND)
+    return (P,) + pushed_rows(P, nu, STRAIN_SEED + 1, STRAIN_PUSHES, 1.2, 2.0)[:3]
+
+
+def solve_on_set(Ps, q, lb, ub, state):
+    """fp64 optimum of ONE problem given its bound states (Ps: the full symmetric Hessian): x_A on the bounds,
+    P_FF x_F = -(q_F + P_FA x_A).  With a state that passes kkt_check this is the optimum itself (P is positive definite)."""
+    n = q.size
+    N = n // np.size(lb)
+    x = np.where(state == 1, np.tile(ub, N), np.where(state == 2, np.tile(lb, N), 0.0))
+    fr, ac = np.flatnonzero(state == 0), np.flatnonzero(state != 0)
+    if fr.size:
+        x[fr] = np.linalg.solve(Ps[np.ix_(fr, fr)], -(q[fr] + Ps[np.ix_(fr, ac)] @ x[ac]))
+    return x
+
+
+def oracle_rows(P, q, lb, ub, nu, rows):
+    """[(u*, active (2n,) bool)] of the listed rows by oracle.qp.solve_exact_box (tq = I)."""
+    n = P.shape[0]
+    out = []
+    for r in rows:
+        info = {"nu": nu}
+        x = oqp.solve_exact_box(P, q[r], np.tile(lb, n // nu), np.tile(ub, n // nu), info=info)
+        act = np.zeros(2 * n, bool)
+        act[info["active"]] = True
+        out.append((x, act))
+    return out

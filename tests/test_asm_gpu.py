@@ -1,8 +1,10 @@
 """GPU parity tests of the active-set fast path (qp_asm.h) on generic box QPs, through the C ABI.
 
-Every size class of the multiplier-system kernels (register-resident 4..9 blocks, LDS tiles 10..11
-blocks, the f32 LDS-tile workgroup kernel up to 16 blocks, the L2-slab kernel beyond) and the column-window / full-width re-entry logic get their own
-cases; the oracle is the fp64 interior-point + active-set restatement in oracle/qp.py.
+Sets of ~20 .. ~340 bounds at n = 512 (test_size_classes: push targets up to 230, the couplings add to them, and the exchange rule
+decides which kernel a round runs in -- the first sets hold nearly every bound) and the column-window / full-width re-entry logic
+get their own cases; the oracle is the fp64 interior-point + active-set restatement in oracle/qp.py.  This file does not reach
+the L2-slab kernel (385 .. 768 bounds), the hand-over at asm_max_active or the class edges on purpose:
+tests/test_large_sets_gpu.py puts sets of a chosen size, 16 .. 800 bounds, through every multiplier-system kernel.
 """
 import numpy as np
 import pytest

@@ -4,6 +4,8 @@ permutation invariance / determinism, trivial problems, ragged batch sizes."""
 import numpy as np
 import pytest
 
+from tests.helpers import kkt_check as _kkt          # (the independent fp64 check of every returned solution)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,24 +18,6 @@ def _setup(name, B, seed, sx, **kw):
     s = synthetic.samples(pl, B, seed, sx)
     x0 = np.concatenate((s["x"] - s["xs"], s["uprev"] - s["us"]), axis=1)
     return pl, P, tq, nu, x0, pl["ulb"].T - s["us"], pl["uub"].T - s["us"], BatchedBoxQP(P, tq, nu, **kw)
-
-
-def _kkt(P, tq, nu, N, x0, lb, ub, out, stat_tol):
-    """Independent fp64 check of every returned solution."""
-    Ps = np.tril(P) + np.tril(P, -1).T
-    U = out["u"]
-    G = U @ Ps + x0 @ tq.T                     # gradient rows
-    LB, UB = np.tile(lb, (1, N)), np.tile(ub, (1, N))
-    n = P.shape[0]
-    k, c = np.arange(n) // nu, np.arange(n) % nu
-    au, al = out["active"][:, k * 2 * nu + c], out["active"][:, k * 2 * nu + nu + c]
-    assert not (au & al).any()
-    assert (U <= UB + 1e-9).all() and (U >= LB - 1e-9).all()                 # primal feasibility
-    assert np.abs(np.where(au, U - UB, 0)).max() == 0 and np.abs(np.where(al, U - LB, 0)).max() == 0
-    scale = np.maximum(1.0, np.abs(x0 @ tq.T).max(axis=1, keepdims=True))
-    free = ~(au | al)
-    assert (np.abs(np.where(free, G, 0)) <= stat_tol * scale).all()            # stationarity on the free set
-    assert (np.where(au, -G, 1) > 0).all() and (np.where(al, G, 1) > 0).all()  # multiplier signs
 
 
 def test_cdu_size_kkt_symmetry_permutation():
