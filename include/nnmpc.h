@@ -294,6 +294,53 @@ int nnmpc_train_dw_slices(nnmpc_train* h, int32_t* slices);
  * padding has zero gradients by construction and must stay exactly zero through updates; this is the check. */
 int nnmpc_train_padding_max(nnmpc_train* h, double* maxabs);
 
+/* ---- A sweep of structured networks trained in lock step  <-  the loop `for (regulator_dim, num_sample) in
+ * itertools.product(regulator_dims, num_samples)` around train_nn_controller (cstrs_train.py / cdu_train.py main): G networks
+ * in ONE handle, every layer of every network in one launch (one per tile class present) instead of G.  All members share nx,
+ * nu, with_uprev, the depth, max_batch, the Adam parameters and one dataset; they differ in widths, weights, rows, step count
+ * and snapshot.  Arithmetic, padding, validation and error codes are nnmpc_train's, and so are the bytes: a member's weights
+ * and losses do not depend on the rest of the group and equal what an nnmpc_train handle computes from the same weights and
+ * rows (same tile functions, same summation orders, dW slices from the member's own shape).
+ * dims: G x (nlayers + 1), member after member; W, b: G x nlayers pointers (b of a member's last layer is ignored).  Replaces
+ * G calls of nnmpc_train_create.  G < 1, or a member whose dims[0] / dims[L] disagree with nx, nu: NNMPC_EINVAL. */
+typedef struct nnmpc_train_group nnmpc_train_group;
+int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers, const int32_t* dims,
+                             const double* const* W, const double* const* b, int32_t nx, int32_t nu,
+                             int32_t with_uprev, int32_t max_batch, double lr, double beta1,
+                             double beta2, double eps);
+int nnmpc_train_group_destroy(nnmpc_train_group* h);
+/* The shared dataset, as nnmpc_train_set_data takes it (what _get_data_for_training(num_samples = the largest) hands the
+ * sweep; member g then uses rows [0, n_g)).  Replaces G uploads. */
+int nnmpc_train_group_set_data(nnmpc_train_group* h, int32_t n, const double* x,
+                               const double* uprev, const double* xs, const double* us,
+                               const double* u, int32_t ptr_kind);
+/* One epoch of every member, replacing G calls of nnmpc_train_epoch: perm holds the members' row lists one after another,
+ * nrows[g] entries for member g.  Member g runs ceil(nrows[g] / batch) lock-step steps (its last batch is the short one) and
+ * then sits out; nrows[g] == 0: the member skips the epoch (weights, moments and step count untouched, loss[g] = NaN).
+ * loss[g]: the row-weighted mean of the member's step losses, accumulated on the device.  One upload, one wait.
+ * batch > max_batch, a row index outside [0, n), no dataset: NNMPC_EINVAL before any launch. */
+int nnmpc_train_group_epoch(nnmpc_train_group* h, const int32_t* nrows, const int32_t* perm,
+                            int32_t batch, double* loss);
+/* Forward only, replacing G calls of nnmpc_train_eval: mse[g] over dataset rows [first[g], first[g] + count[g]) in chunks
+ * of max_batch rows; count[g] == 0: skipped (mse[g] = NaN). */
+int nnmpc_train_group_eval(nnmpc_train_group* h, const int32_t* first, const int32_t* count,
+                           double* mse);
+/* Member g's weights as nnmpc_train_get_weights / nnmpc_train_set_weights exchange them. */
+int nnmpc_train_group_get_weights(nnmpc_train_group* h, int32_t g, double* const* W,
+                                  double* const* b);
+int nnmpc_train_group_set_weights(nnmpc_train_group* h, int32_t g, const double* const* W,
+                                  const double* const* b);
+/* nnmpc_train_snapshot / nnmpc_train_restore for the members with mask[g] != 0 (per-member
+ * ModelCheckpoint(save_best_only=True)); one device-side copy per member. */
+int nnmpc_train_group_snapshot(nnmpc_train_group* h, const int32_t* mask);
+int nnmpc_train_group_restore(nnmpc_train_group* h, const int32_t* mask);
+/* nnmpc_train_padding_max over every member. */
+int nnmpc_train_group_padding_max(nnmpc_train_group* h, double* maxabs);
+/* nnmpc_train_last_ms for the last epoch / eval of the group. */
+int nnmpc_train_group_last_ms(nnmpc_train_group* h, double* gemm_ms, double* total_ms);
+/* Kernel launches the last epoch / eval enqueued (counted where they are launched): what a loop over G handles multiplies by G. */
+int nnmpc_train_group_last_launches(nnmpc_train_group* h, int64_t* n);
+
 /* ---- Lock-step closed-loop chains, device resident  <-  simulate_offline (lib/linearMPC.py:827-880), one OS process
  * per chain in the reference (:814-825).  All nc chains of a task advance together; per step (loop :845-866):
  *     x0 = [x - xs; uprev - us], bounds ulb - us / uub - us   (get_control_sequence :682-689)

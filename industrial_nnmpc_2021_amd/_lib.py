@@ -59,6 +59,10 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_train_epoch", "nnmpc_train_eval", "nnmpc_train_get_weights", "nnmpc_train_set_weights",
            "nnmpc_train_snapshot", "nnmpc_train_restore", "nnmpc_train_last_ms", "nnmpc_train_dw_slices",
            "nnmpc_train_padding_max",
+           "nnmpc_train_group_create", "nnmpc_train_group_destroy", "nnmpc_train_group_set_data",
+           "nnmpc_train_group_epoch", "nnmpc_train_group_eval", "nnmpc_train_group_get_weights",
+           "nnmpc_train_group_set_weights", "nnmpc_train_group_snapshot", "nnmpc_train_group_restore",
+           "nnmpc_train_group_padding_max", "nnmpc_train_group_last_ms", "nnmpc_train_group_last_launches",
            "nnmpc_chain_create", "nnmpc_chain_destroy", "nnmpc_chain_run", "nnmpc_chain_reset", "nnmpc_chain_last_ms",
            "nnmpc_ts_create", "nnmpc_ts_destroy", "nnmpc_ts_solve_batch",
            "nnmpc_cl_create", "nnmpc_cl_destroy", "nnmpc_cl_run", "nnmpc_cl_reset", "nnmpc_cl_last_ms",
@@ -149,6 +153,31 @@ def load():
     lib.nnmpc_train_dw_slices.argtypes = [vp, pi32]
     lib.nnmpc_train_padding_max.restype = i32
     lib.nnmpc_train_padding_max.argtypes = [vp, pf64]
+    # the sweep in one handle: each entry replaces G calls of the nnmpc_train_* function named beside it
+    lib.nnmpc_train_group_create.restype = i32                    # nnmpc_train_create
+    lib.nnmpc_train_group_create.argtypes = [C.POINTER(vp), i32, i32, pi32, pdp, pdp, i32, i32, i32, i32, f64, f64, f64, f64]
+    lib.nnmpc_train_group_destroy.restype = i32                   # nnmpc_train_destroy
+    lib.nnmpc_train_group_destroy.argtypes = [vp]
+    lib.nnmpc_train_group_set_data.restype = i32                  # nnmpc_train_set_data (one shared dataset)
+    lib.nnmpc_train_group_set_data.argtypes = [vp, i32, dp, dp, dp, dp, dp, i32]
+    lib.nnmpc_train_group_epoch.restype = i32                     # nnmpc_train_epoch
+    lib.nnmpc_train_group_epoch.argtypes = [vp, dp, dp, i32, dp]
+    lib.nnmpc_train_group_eval.restype = i32                      # nnmpc_train_eval
+    lib.nnmpc_train_group_eval.argtypes = [vp, dp, dp, dp]
+    lib.nnmpc_train_group_get_weights.restype = i32               # nnmpc_train_get_weights
+    lib.nnmpc_train_group_get_weights.argtypes = [vp, i32, pdp, pdp]
+    lib.nnmpc_train_group_set_weights.restype = i32               # nnmpc_train_set_weights
+    lib.nnmpc_train_group_set_weights.argtypes = [vp, i32, pdp, pdp]
+    lib.nnmpc_train_group_snapshot.restype = i32                  # nnmpc_train_snapshot, by mask
+    lib.nnmpc_train_group_snapshot.argtypes = [vp, dp]
+    lib.nnmpc_train_group_restore.restype = i32                   # nnmpc_train_restore, by mask
+    lib.nnmpc_train_group_restore.argtypes = [vp, dp]
+    lib.nnmpc_train_group_padding_max.restype = i32               # nnmpc_train_padding_max
+    lib.nnmpc_train_group_padding_max.argtypes = [vp, pf64]
+    lib.nnmpc_train_group_last_ms.restype = i32                   # nnmpc_train_last_ms
+    lib.nnmpc_train_group_last_ms.argtypes = [vp, pf64, pf64]
+    lib.nnmpc_train_group_last_launches.restype = i32             # (new: launches of the last epoch / eval)
+    lib.nnmpc_train_group_last_launches.argtypes = [vp, C.POINTER(C.c_int64)]
     u64 = C.c_uint64
     lib.nnmpc_qp_solve_batch_ex.restype = i32
     lib.nnmpc_qp_solve_batch_ex.argtypes = [vp, i32, dp, dp, dp, dp, dp, dp, dp, dp, i32, i32]

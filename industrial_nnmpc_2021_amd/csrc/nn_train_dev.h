@@ -1,0 +1,261 @@
+// What one workgroup of the training step's kernels does, as __device__ functions of its block coordinates, and the shape
+// rules of the step.  nn_train.hip (one network per handle) and nn_train_group.hip (a sweep of networks per launch) both
+// build their kernels from these, so a network's bytes are the same whichever of the two trains it: same tile functions,
+// same summation orders, same slice rule.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include "tile_gemm.h"
+#include "tile_gemm_tn.h"
+
+namespace nnmpc {
+
+// Row slices of the dW reduction over M = 2 Bp rows for a layer with `tiles` output tiles: as many as keep tiles x slices
+// within the device's CUs (num_cus: the device property, 256 on MI355X) (one workgroup each: a second round would cost a
+// whole slice time), at least 512 rows per slice, whole 32-row chunks.  Depends on the shape alone (and on the override
+// force > 0, read once at create), never on timing.  Integer arithmetic only: host and device agree.
+__host__ __device__ inline int dw_slices_wanted(int force, int num_cus, int M, int tiles) {   // non-decreasing in M
+  const int a = num_cus / tiles > 1 ? num_cus / tiles : 1, b = M / 512 > 1 ? M / 512 : 1;
+  const int S = force > 0 ? force : (a < b ? a : b);
+  const int c = S < M / KC ? S : M / KC;
+  return c > 1 ? c : 1;
+}
+__host__ __device__ inline int dw_slices(int force, int num_cus, int M, int tiles, int* slice_rows) {
+  const int chunks = M / KC, S = dw_slices_wanted(force, num_cus, M, tiles);
+  const int per = (chunks + S - 1) / S;
+  *slice_rows = per * KC;
+  return (chunks + per - 1) / per;
+}
+
+// nn_assemble_k's row layout (nn_forward.hip) from an f32 dataset, row b of the batch = dataset row idx[b] (idx == nullptr:
+// first + b), for b = b_first, b_first + b_step, ... < Bp.  Samples b >= B and the pad columns are zero.
+__device__ __forceinline__ void train_gather_rows(float* __restrict__ in, int ldk, int Bp, int B, int nx, int nu,
+                                                  int with_uprev, const float* __restrict__ x,
+                                                  const float* __restrict__ uprev, const float* __restrict__ xs,
+                                                  const float* __restrict__ us, const int* __restrict__ idx, int first,
+                                                  int b_first, int b_step) {
+  const int o2 = nx + (with_uprev ? nu : 0);               // first column of the xs block
+  const int din = o2 + nx + nu;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int b = b_first; b < Bp; b += b_step) {
+    float* d1 = in + (size_t)b * ldk;
+    float* d2 = in + (size_t)(Bp + b) * ldk;
+    if (b >= B) {
+      for (int k = tid; k < ldk; k += nt) { d1[k] = 0.f; d2[k] = 0.f; }
+      continue;
+    }
+    const size_t row = idx ? (size_t)idx[b] : (size_t)first + b;
+    const float* xa = x + row * nx;
+    const float* xb = xs + row * nx;
+    const float* ub = us + row * nu;
+    for (int k = tid; k < nx; k += nt) {
+      const float xv = xa[k], sv = xb[k];
+      d1[k] = xv; d1[o2 + k] = sv;
+      d2[k] = sv; d2[o2 + k] = sv;
+    }
+    for (int k = tid; k < nu; k += nt) {
+      const float uv = ub[k];
+      d1[o2 + nx + k] = uv; d2[o2 + nx + k] = uv;
+      if (with_uprev) { d1[nx + k] = uprev[row * nu + k]; d2[nx + k] = uv; }
+    }
+    for (int k = din + tid; k < ldk; k += nt) { d1[k] = 0.f; d2[k] = 0.f; }
+  }
+}
+
+// Head output o [2Bp][ldo] -> pred = us + (o1 - o2), the squared error of the 64 samples of block `blk` as one fp64 partial
+// (lanes add their elements in index order, then a fixed LDS tree), and, with dz != nullptr, the head-output gradient
+// +g on pass-1 rows, -g on pass-2 rows, g = gscale (pred - u), exactly zero on padding rows and pad columns.  256 threads.
+__device__ __forceinline__ void train_output_block(float* __restrict__ dz, const float* __restrict__ o, int ldo, int Bp,
+                                                   int B, int nu, const float* __restrict__ us,
+                                                   const float* __restrict__ u, const int* __restrict__ idx, int first,
+                                                   float gscale, double* __restrict__ partial, int blk) {
+  __shared__ double red[256];
+  const int b0 = blk * 64, tid = threadIdx.x;
+  double acc = 0.0;
+  for (int e = tid; e < 64 * ldo; e += 256) {
+    const int b = b0 + e / ldo, c = e % ldo;
+    float g = 0.f;
+    if (b < B && c < nu) {
+      const size_t row = idx ? (size_t)idx[b] : (size_t)first + b;
+      const float pred = us[row * nu + c] + (o[(size_t)b * ldo + c] - o[(size_t)(Bp + b) * ldo + c]);
+      const float d = pred - u[row * nu + c];
+      acc += (double)d * (double)d;
+      g = gscale * d;
+    }
+    if (dz) {
+      dz[(size_t)b * ldo + c] = g;
+      dz[(size_t)(Bp + b) * ldo + c] = 0.f - g;
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) partial[blk] = red[0];
+}
+
+// One thread adds the workgroup partials in index order: loss = scale * sum; acc += w * loss (the epoch's running sum).
+__device__ __forceinline__ void train_loss_finish(const double* __restrict__ partial, int np, double scale, double w,
+                                                  double* __restrict__ loss, double* __restrict__ acc) {
+  double s = 0.0;
+  for (int i = 0; i < np; ++i) s += partial[i];
+  const double l = s * scale;
+  *loss = l;
+  *acc += w * l;
+}
+
+// Forward tile (tm, tn) of C = act(A B' + bias): gemm_nt_f32_k's tile (gemm_kernels.h) and epilogue.
+template <int NB, bool RELU, bool BIAS>
+__device__ __forceinline__ void train_fwd_tile(float* __restrict__ C, size_t ldc, const float* __restrict__ A, size_t lda,
+                                               const float* __restrict__ B, size_t ldb, int K,
+                                               const float* __restrict__ bias, int tm, int tn, float* lds) {
+  using Cf = TileCfg<NB>;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int m0 = tm * NB, n0 = tn * NB;
+  f32x16 acc[Cf::MT][Cf::MT];
+  zero_acc<NB>(acc);
+  PlainOp a{A + (size_t)m0 * lda, lda};
+  PlainOp b{B + (size_t)n0 * ldb, ldb};
+  tile_gemm_nt<NB>(acc, a, b, K, lds, false);
+#pragma unroll
+  for (int mi = 0; mi < Cf::MT; ++mi)
+#pragma unroll
+    for (int mj = 0; mj < Cf::MT; ++mj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wr * Cf::WT + mi * 32 + acc_row(r, lane);
+        const int col = n0 + wc * Cf::WT + mj * 32 + acc_col(lane);
+        float v = acc[mi][mj][r];
+        if (BIAS) v += bias[col];
+        if (RELU) v = relu_nan(v);
+        C[(size_t)row * ldc + col] = v;
+      }
+}
+
+// dW planes: P[z][m][n] = sum over the rows r of slice z of A[r][m] * B[r][n]  (A = dZ_l, B = A_{l-1}); tile (by, bx) of slice bz.
+template <int NB>
+__device__ __forceinline__ void train_tn_tile(float* __restrict__ P, size_t plane, size_t ldp, const float* __restrict__ A,
+                                              size_t lda, const float* __restrict__ B, size_t ldb, int rows, int slice_rows,
+                                              int bx, int by, int bz, float* lds) {
+  using Cf = TileCfg<NB>;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int m0 = by * NB, n0 = bx * NB;
+  const int r0 = bz * slice_rows, r1 = min(rows, r0 + slice_rows);
+  f32x16 acc[Cf::MT][Cf::MT];
+  zero_acc<NB>(acc);
+  if (r1 > r0) tile_gemm_tn<NB>(acc, A + (size_t)r0 * lda + m0, lda, B + (size_t)r0 * ldb + n0, ldb, r1 - r0, lds);
+  float* Pz = P + (size_t)bz * plane;
+#pragma unroll
+  for (int mi = 0; mi < Cf::MT; ++mi)
+#pragma unroll
+    for (int mj = 0; mj < Cf::MT; ++mj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wr * Cf::WT + mi * 32 + acc_row(r, lane);
+        const int col = n0 + wc * Cf::WT + mj * 32 + acc_col(lane);
+        Pz[(size_t)row * ldp + col] = acc[mi][mj][r];
+      }
+}
+
+// dZ_{l-1} = (dZ_l W_l) * relu'(A_{l-1}):  C = A B' with B = the [in][out] copy of W_l, masked in the epilogue by the
+// activation tile of the layer below (same shape and stride as C).  The derivative at 0 is 0 (a NaN passes), as in torch.
+template <int NB>
+__device__ __forceinline__ void train_nt_mask_tile(float* __restrict__ C, size_t ldc, const float* __restrict__ A,
+                                                   size_t lda, const float* __restrict__ B, size_t ldb, int K,
+                                                   const float* __restrict__ act, int bx, int by, float* lds) {
+  using Cf = TileCfg<NB>;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int m0 = by * NB, n0 = bx * NB;
+  f32x16 acc[Cf::MT][Cf::MT];
+  zero_acc<NB>(acc);
+  PlainOp a{A + (size_t)m0 * lda, lda};
+  PlainOp b{B + (size_t)n0 * ldb, ldb};
+  tile_gemm_nt<NB>(acc, a, b, K, lds, false);
+#pragma unroll
+  for (int mi = 0; mi < Cf::MT; ++mi)
+#pragma unroll
+    for (int mj = 0; mj < Cf::MT; ++mj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wr * Cf::WT + mi * 32 + acc_row(r, lane);
+        const int col = n0 + wc * Cf::WT + mj * 32 + acc_col(lane);
+        const size_t at = (size_t)row * ldc + col;
+        C[at] = act[at] <= 0.f ? 0.f : acc[mi][mj][r];
+      }
+}
+
+// Bias-gradient partials: P[s][c] = sum of dZ[r][c] over the 128 rows of block s = by.  Thread (c, q) adds rows q, q+4, ...
+// in order, then the four q are added in order.  64 columns per block bx, 256 threads.
+__device__ __forceinline__ void train_colsum_block(float* __restrict__ P, const float* __restrict__ dz, int ld, int bx, int by) {
+  __shared__ float red[4][64];
+  const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
+  const int col = bx * 64 + c;
+  const float* p = dz + (size_t)by * 128 * ld + col;
+  float s = 0.f;
+  for (int r = q; r < 128; r += 4) s += p[(size_t)r * ld];
+  red[q][c] = s;
+  __syncthreads();
+  if (q == 0) P[(size_t)by * ld + col] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+}
+
+// THE gradient of an entry: its partial planes added in plane order.  train_adam_* and train_plane_sum_k (what
+// nnmpc_train_grad returns) both call it, so the gradient a step applies is the one grad reports, bit for bit.
+__device__ __forceinline__ float plane_sum(const float* __restrict__ P, size_t plane, int S, size_t at) {
+  float g = P[at];
+  for (int s = 1; s < S; ++s) g += P[(size_t)s * plane + at];
+  return g;
+}
+
+struct AdamCoef { double omb1, b2, omb2, step, bc2s, eps; };   // 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1^t), sqrt(1 - beta2^t), eps
+
+// The scalars of Adam step t (t >= 1), in double on the host.
+inline AdamCoef adam_coef(double lr, double beta1, double beta2, double eps, long t) {
+  AdamCoef k;
+  k.omb1 = 1.0 - beta1; k.b2 = beta2; k.omb2 = 1.0 - beta2;
+  k.step = lr / (1.0 - pow(beta1, (double)t));
+  k.bc2s = sqrt(1.0 - pow(beta2, (double)t));
+  k.eps = eps;
+  return k;
+}
+
+// torch.optim.Adam's update of one entry: m, v, w are f32 in memory, the arithmetic in between is fp64 (about two
+// million entries per step at the widest network: not measurable), so an entry carries the rounding of its three stores only.
+__device__ __forceinline__ float adam_entry(float g, float* m, float* v, float w, const AdamCoef& k) {
+  const double gd = g;
+  const double mn = (double)*m + (gd - (double)*m) * k.omb1;
+  const double vn = k.b2 * (double)*v + k.omb2 * gd * gd;
+  *m = (float)mn; *v = (float)vn;
+  return (float)((double)w - k.step * (mn / (sqrt(vn) / k.bc2s + k.eps)));
+}
+
+// One 64 x 64 tile (bx: in, by: out) of W per workgroup: Wt [out][in] (the forward's operand) is updated in place and the
+// same values go, through an LDS transpose, to Wk [in][out] (the dA GEMM's operand) -- no transpose pass.  256 threads.
+__device__ __forceinline__ void train_adam_w_tile(float* __restrict__ Wt, float* __restrict__ Wk, float* __restrict__ m,
+                                                  float* __restrict__ v, const float* __restrict__ P, size_t plane, int S,
+                                                  int kpad, int npad, const AdamCoef& k, int bx, int by) {
+  __shared__ float t[64][65];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int i0 = bx * 64, o0 = by * 64;
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int ol = ty + 4 * j;
+    const size_t at = (size_t)(o0 + ol) * kpad + i0 + tx;
+    const float w = adam_entry(plane_sum(P, plane, S, at), m + at, v + at, Wt[at], k);
+    Wt[at] = w;
+    t[ol][tx] = w;
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int il = ty + 4 * j;
+    Wk[(size_t)(i0 + il) * npad + o0 + tx] = t[tx][il];
+  }
+}
+
+}  // namespace nnmpc

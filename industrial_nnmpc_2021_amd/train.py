@@ -12,7 +12,8 @@ Keras ``get_weights()`` list, which is exactly what ``nn.StructuredNN`` /
 (BASELINE.json north_star).  ``backend="hip"`` runs the same step -- forward,
 backward, Adam, the epoch loop -- in f32 on hand-written gfx950 kernels
 (csrc/nn_train.hip, ``HipTrainer``); the model object then only carries the
-trained weights.
+trained weights.  ``train_nn_controllers`` trains a whole sweep of networks in
+one lock-step launch group (csrc/nn_train_group.hip, ``HipGroupTrainer``).
 """
 import copy
 import ctypes as C
@@ -206,6 +207,216 @@ class HipTrainer:
         m = C.c_double()
         _lib.check(self._lib.nnmpc_train_padding_max(self._h, C.byref(m)), "nnmpc_train_padding_max")
         return m.value
+
+
+def group_schedule(nrows, batch):
+    """Per member the batch sizes of its lock-step steps: ``ceil(nrows[g] / batch)`` steps, the last one the short one;
+    a member without rows has none.  Step k of the group runs the members that have a k-th entry."""
+    out = []
+    for n in nrows:
+        n = int(n)
+        out.append([min(batch, n - i) for i in range(0, n, batch)])
+    return out
+
+
+class HipGroupTrainer:
+    """A sweep of networks in one handle (C ABI ``nnmpc_train_group_*``): what a list of ``HipTrainer`` does, with every
+    layer of every member in one launch.  ``weights`` is a list of Keras ``get_weights()`` lists, one per member; the
+    members share nx, nu, nnwithuprev, the depth, max_batch, Adam's parameters and one dataset, of which each uses the rows
+    it is given.  A member's weights and losses are, byte for byte, those of a ``HipTrainer`` fed the same rows.
+
+    No device: ``_lib.NnmpcError`` (no CPU fallback)."""
+
+    def __init__(self, weights, nx, nu, *, nnwithuprev=True, max_batch=2048, lr=1e-3, betas=(0.9, 0.999), eps=1e-7):
+        lib = _lib.load()
+        self.G = len(weights)
+        Ws, bs, self.dims = [], [], []
+        for w in weights:
+            Wg = [np.ascontiguousarray(a, np.float64) for a in w[0:-1:2]] + [np.ascontiguousarray(w[-1], np.float64)]
+            bg = [np.ascontiguousarray(a, np.float64).ravel() for a in w[1::2]]
+            if len(bg) != len(Wg) - 1:
+                raise ValueError("weights must be [W1, b1, ..., W_{L-1}, b_{L-1}, Wout]")
+            Ws.append(Wg); bs.append(bg + [None])
+            self.dims.append([Wg[0].shape[0]] + [a.shape[1] for a in Wg])
+        L = len(Ws[0]) if Ws else 1
+        if any(len(Wg) != L for Wg in Ws):
+            raise ValueError("the members of a group have the same depth")
+        self.L, self.nx, self.nu, self.nnwithuprev, self.n = L, nx, nu, bool(nnwithuprev), 0
+        self.max_batch = int(max_batch)
+        self._lib, self._h = lib, C.c_void_p()
+        flat = lambda ll: [a for l in ll for a in l]
+        _lib.check(lib.nnmpc_train_group_create(C.byref(self._h), self.G, L,
+                                                (C.c_int32 * max(1, self.G * (L + 1)))(*flat(self.dims)),
+                                                HipTrainer._plist(flat(Ws)), HipTrainer._plist(flat(bs)), nx, nu,
+                                                int(self.nnwithuprev), self.max_batch, lr, betas[0], betas[1], eps),
+                   "nnmpc_train_group_create")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.nnmpc_train_group_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def set_data(self, data):
+        """dict(x, uprev, xs, us, u), rows = samples, already scaled; uploaded once as f32 for all members."""
+        c = lambda a, w: np.ascontiguousarray(a, np.float64).reshape(-1, w)
+        x, xs, us, u = c(data["x"], self.nx), c(data["xs"], self.nx), c(data["us"], self.nu), c(data["u"], self.nu)
+        up = c(data["uprev"], self.nu) if self.nnwithuprev and data.get("uprev") is not None else None
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_train_group_set_data(self._h, x.shape[0], p(x), p(up), p(xs), p(us), p(u), _lib.HOST),
+                   "nnmpc_train_group_set_data")
+        self.n = x.shape[0]
+
+    def set_data_device(self, n, x, uprev, xs, us, u):
+        """The same from HBM-resident f64 buffers (objects with data_ptr(); ``uprev`` None without uprev)."""
+        q = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+        _lib.check(self._lib.nnmpc_train_group_set_data(self._h, int(n), q(x), q(uprev), q(xs), q(us), q(u), _lib.DEVICE),
+                   "nnmpc_train_group_set_data")
+        self.n = int(n)
+
+    def _i32(self, values, what):
+        a = np.ascontiguousarray(values, np.int32).ravel()
+        if a.size != self.G:
+            raise ValueError(f"{what}: {a.size} entries for a group of {self.G}")
+        return a
+
+    def epoch(self, perms, batch):
+        """One epoch of every member over its own row list ``perms[g]`` (empty or None: the member sits the epoch out);
+        member g takes ``len(group_schedule(...)[g])`` lock-step steps.  Returns the members' row-weighted mean losses
+        (NaN for a member without rows)."""
+        if len(perms) != self.G:
+            raise ValueError(f"epoch: {len(perms)} row lists for a group of {self.G}")
+        lists = [np.empty(0, np.int32) if p is None else HipTrainer._rows(p) for p in perms]
+        nrows = self._i32([p.size for p in lists], "epoch")
+        self.steps = max((len(s) for s in group_schedule(nrows, int(batch))), default=0)
+        rows = np.ascontiguousarray(np.concatenate(lists)) if self.G else np.empty(0, np.int32)
+        if rows.size == 0:
+            rows = np.zeros(1, np.int32)
+        loss = np.empty(max(1, self.G))
+        _lib.check(self._lib.nnmpc_train_group_epoch(self._h, nrows.ctypes.data_as(C.c_void_p),
+                                                     rows.ctypes.data_as(C.c_void_p), int(batch),
+                                                     loss.ctypes.data_as(C.c_void_p)), "nnmpc_train_group_epoch")
+        return [float(v) for v in loss[:self.G]]
+
+    def eval(self, first, count):
+        """Per member the mean squared error over dataset rows [first[g], first[g] + count[g]), forward only
+        (count 0: skipped, NaN)."""
+        f, c = self._i32(first, "eval"), self._i32(count, "eval")
+        mse = np.empty(max(1, self.G))
+        _lib.check(self._lib.nnmpc_train_group_eval(self._h, f.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
+                                                    mse.ctypes.data_as(C.c_void_p)), "nnmpc_train_group_eval")
+        return [float(v) for v in mse[:self.G]]
+
+    def _empty(self, g):
+        d = self.dims[g]
+        return [np.empty((d[l], d[l + 1])) for l in range(self.L)], [np.empty(d[l + 1]) for l in range(self.L - 1)]
+
+    def get_weights(self, g):
+        Ws, bs = self._empty(g)
+        _lib.check(self._lib.nnmpc_train_group_get_weights(self._h, int(g), HipTrainer._plist(Ws),
+                                                           HipTrainer._plist(bs + [None])), "nnmpc_train_group_get_weights")
+        return HipTrainer._keras(Ws, bs)
+
+    def set_weights(self, g, weights):
+        Ws = [np.ascontiguousarray(w, np.float64) for w in weights[0:-1:2]] + [np.ascontiguousarray(weights[-1], np.float64)]
+        bs = [np.ascontiguousarray(b, np.float64).ravel() for b in weights[1::2]]
+        if [Ws[0].shape[0]] + [w.shape[1] for w in Ws] != self.dims[g] or len(bs) != self.L - 1:
+            raise ValueError("set_weights: shapes differ from the member's")
+        _lib.check(self._lib.nnmpc_train_group_set_weights(self._h, int(g), HipTrainer._plist(Ws),
+                                                           HipTrainer._plist(bs + [None])), "nnmpc_train_group_set_weights")
+
+    def snapshot(self, mask):
+        m = self._i32([1 if v else 0 for v in mask], "snapshot")
+        _lib.check(self._lib.nnmpc_train_group_snapshot(self._h, m.ctypes.data_as(C.c_void_p)), "nnmpc_train_group_snapshot")
+
+    def restore(self, mask):
+        m = self._i32([1 if v else 0 for v in mask], "restore")
+        _lib.check(self._lib.nnmpc_train_group_restore(self._h, m.ctypes.data_as(C.c_void_p)), "nnmpc_train_group_restore")
+
+    def last_ms(self):
+        """(hipEvent ms of the GEMM spans, of the whole last epoch / eval)."""
+        g, t = C.c_double(), C.c_double()
+        _lib.check(self._lib.nnmpc_train_group_last_ms(self._h, C.byref(g), C.byref(t)), "nnmpc_train_group_last_ms")
+        return g.value, t.value
+
+    def last_launches(self):
+        """Kernel launches the last epoch / eval enqueued."""
+        n = C.c_int64()
+        _lib.check(self._lib.nnmpc_train_group_last_launches(self._h, C.byref(n)), "nnmpc_train_group_last_launches")
+        return n.value
+
+    def padding_max(self):
+        m = C.c_double()
+        _lib.check(self._lib.nnmpc_train_group_padding_max(self._h, C.byref(m)), "nnmpc_train_group_padding_max")
+        return m.value
+
+
+def train_nn_controllers(models, data, *, num_samples=None, epochs=1500, batch_size=2048, validation_split=0.05,
+                         lr=1e-3, seed=1, log=None, backend="hip"):
+    """``train_nn_controller`` for a sweep: member i is ``models[i]`` trained on the first ``num_samples[i]`` rows of
+    ``data`` (default: all), which is what the reference's loop over ``itertools.product(regulator_dims, num_samples)``
+    hands each of its calls.  Keras semantics per member: the last ``int(n_i * validation_split)`` of its rows are its
+    validation set, the rest is reshuffled every epoch by the member's own ``np.random.default_rng(seed)`` -- the row
+    order a separate ``train_nn_controller(..., backend="hip", seed=seed)`` would give it -- and the weights of its best
+    validation epoch are restored at the end.  Returns (models, training_time, hists), hists[i] as that call's history.
+
+    ``backend="hip"``: one ``HipGroupTrainer``, all members in lock step; the models must agree in Nx, Nu, nnwithuprev
+    and depth (``ValueError`` otherwise; build one group per depth).  ``backend="torch"``: a loop over
+    ``train_nn_controller``."""
+    models = list(models)
+    if backend not in ("hip", "torch"):
+        raise ValueError(f"unknown backend {backend!r}: 'torch' or 'hip'")
+    if not models:
+        raise ValueError("train_nn_controllers: no models")
+    n = int(np.asarray(data["x"]).shape[0])
+    ns = [n] * len(models) if num_samples is None else [int(v) for v in num_samples]
+    if len(ns) != len(models) or any(v < 1 or v > n for v in ns):
+        raise ValueError(f"num_samples: one entry per model, each in [1, {n}]")
+    if backend == "torch":
+        t0, hists = time.time(), []
+        for i, m in enumerate(models):
+            part = {k: (None if data.get(k) is None else np.asarray(data[k])[:ns[i]]) for k in ("x", "uprev", "xs", "us", "u")}
+            models[i], _, h = train_nn_controller(m, part, epochs=epochs, batch_size=batch_size,
+                                                  validation_split=validation_split, lr=lr, seed=seed, log=log)
+            hists.append(h)
+        return models, time.time() - t0, hists
+    m0 = models[0]
+    for m in models[1:]:
+        if (m.Nx, m.Nu, bool(m.nnwithuprev), len(m.layers)) != (m0.Nx, m0.Nu, bool(m0.nnwithuprev), len(m0.layers)):
+            raise ValueError("train_nn_controllers: the models of a group agree in Nx, Nu, nnwithuprev and depth")
+    G = len(models)
+    tr = HipGroupTrainer([m.get_weights() for m in models], m0.Nx, m0.Nu, nnwithuprev=m0.nnwithuprev,
+                         max_batch=batch_size, lr=lr, eps=1e-7)
+    try:
+        tr.set_data(data)
+        nval = [int(v * validation_split) for v in ns]
+        ntr = [v - w for v, w in zip(ns, nval)]
+        rngs = [np.random.default_rng(seed) for _ in range(G)]
+        best, hists = [float("inf")] * G, [[] for _ in range(G)]
+        t0 = time.time()
+        for ep in range(epochs):
+            run = tr.epoch([rngs[g].permutation(ntr[g]) for g in range(G)], batch_size)
+            vl = tr.eval(ntr, nval) if any(nval) else run
+            better = []
+            for g in range(G):
+                v = vl[g] if nval[g] else run[g]
+                hists[g].append((run[g], v))
+                better.append(v < best[g])                  # ModelCheckpoint(save_best_only=True), per member
+                if better[g]:
+                    best[g] = v
+            if any(better):
+                tr.snapshot(better)
+            if log:
+                log(f"epoch {ep + 1}/{epochs} " + " ".join(f"[{g}] loss {hists[g][-1][0]:.3e} val_loss {hists[g][-1][1]:.3e}"
+                                                          for g in range(G)))
+        tr.restore([b < float("inf") for b in best])
+        ttime = time.time() - t0
+        for g, m in enumerate(models):
+            m.set_weights(tr.get_weights(g))
+    finally:
+        tr.close()
+    return models, ttime, hists
 
 
 def _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log):

@@ -13,6 +13,18 @@ fraction of the 157.3 TF f32 MFMA peak on its own flop count
 2 (2B) (3 sum_{l>=1} d_l d_{l+1} + 2 d_0 d_1).  One JSON line per (shape, path).
 
     python scripts/train_bench.py [--rows 100000] [--batch 2048] [--epochs 5] [--repeats 5] [--paths torch64,torch32,hip] [--shapes cdu,small]
+
+--sweep cstrs|cdu times a whole sweep of the reference (cstrs_train.py: [36, w, w, w, 6], w in 224 .. 272, 40 000 .. 150 000
+rows, batch 1024, validation_split 0.1: 48 networks; cdu_train.py: [536, w, w, w, 32], w in 832 .. 1024, 20 000 .. 357 600
+rows, batch 2048, validation_split 0.05: 52 networks) two ways with the same protocol and clock convention:
+
+  loop   the networks one after another, each a HipTrainer: epoch + eval per epoch
+  group  one HipGroupTrainer (csrc/nn_train_group.hip): one grouped epoch + one grouped eval per epoch
+
+and prints one JSON line per way: ms per sweep epoch (min / median / max over the runs), and for the group the hipEvent
+time, the launches per lock-step step and the fraction of the f32 MFMA peak on the sweep's own flop count.
+
+    python scripts/train_bench.py --sweep cstrs [--epochs 5] [--repeats 5] [--ways loop,group]
 """
 import argparse
 import json
@@ -96,6 +108,72 @@ def run_hip_events(dims, uprev, data, batch, epochs, repeats):
     return dict(epoch_event_ms=spread(tot), epoch_gemm_event_ms=spread(gemm), dw_slices=slices)
 
 
+SWEEPS = {
+    "cstrs": dict(dims=[[36, w, w, w, 6] for w in (224, 240, 256, 272)], uprev=True, rows=list(range(40000, 150001, 10000)),
+                  batch=1024, validation_split=0.1),
+    "cdu": dict(dims=[[536, w, w, w, 32] for w in (832, 896, 960, 1024)], uprev=False,
+                rows=[20000] + list(range(30000, 330001, 30000)) + [357600], batch=2048, validation_split=0.05),
+}
+
+
+def run_sweep(name, epochs, repeats, ways):
+    import itertools
+    import time
+    from industrial_nnmpc_2021_amd.train import HipGroupTrainer, HipTrainer, RegulatorModel, group_schedule
+    sw = SWEEPS[name]
+    uprev, batch, vs = sw["uprev"], sw["batch"], sw["validation_split"]
+    members = list(itertools.product(sw["dims"], sw["rows"]))                 # the reference's loop order
+    nx, nu = geometry(members[0][0], uprev)
+    data = synthetic(max(sw["rows"]), nx, nu)
+    weights = [RegulatorModel(nx, nu, d, nnwithuprev=uprev).get_weights() for d, _ in members]
+    nval = [int(n * vs) for _, n in members]
+    ntr = [n - v for (_, n), v in zip(members, nval)]
+    sched = group_schedule(ntr, batch)
+    flop = sum(step_flop(d, B) for (d, _), s in zip(members, sched) for B in s)
+    common = dict(sweep=name, members=len(members), batch=batch, epochs=epochs, repeats=repeats,
+                  member_steps_per_epoch=sum(len(s) for s in sched), lockstep_steps_per_epoch=max(len(s) for s in sched))
+    if "loop" in ways:
+        runs = [0.0] * repeats
+        for (d, n), w, a, v in zip(members, weights, ntr, nval):
+            tr = HipTrainer(w, nx, nu, nnwithuprev=uprev, max_batch=batch)
+            tr.set_data({k: x[:n] for k, x in data.items()})
+            rng = np.random.default_rng(1)
+            tr.epoch(rng.permutation(a), batch)                               # warm-up
+            tr.eval(a, v)
+            for r in range(repeats):
+                t0 = time.time()
+                for _ep in range(epochs):
+                    tr.epoch(rng.permutation(a), batch)
+                    tr.eval(a, v)
+                runs[r] += time.time() - t0
+            tr.close()
+        print(json.dumps(dict(common, way="loop", epoch_ms=spread([1e3 * t / epochs for t in runs]))), flush=True)
+    if "group" in ways:
+        tr = HipGroupTrainer(weights, nx, nu, nnwithuprev=uprev, max_batch=batch)
+        tr.set_data(data)
+        rngs = [np.random.default_rng(1) for _ in members]
+        tr.epoch([g.permutation(a) for g, a in zip(rngs, ntr)], batch)        # warm-up
+        tr.eval(ntr, nval)
+        runs, ev, gemm = [], [], []
+        for r in range(repeats):
+            t0, e, ge = time.time(), 0.0, 0.0
+            for _ep in range(epochs):
+                tr.epoch([g.permutation(a) for g, a in zip(rngs, ntr)], batch)
+                launches = tr.last_launches()
+                g_ms, t_ms = tr.last_ms()
+                e += t_ms
+                ge += g_ms
+                tr.eval(ntr, nval)
+            runs.append(1e3 * (time.time() - t0) / epochs)
+            ev.append(e / epochs)
+            gemm.append(ge / epochs)
+        tr.close()
+        steps = common["lockstep_steps_per_epoch"]
+        print(json.dumps(dict(common, way="group", epoch_ms=spread(runs), epoch_event_ms=spread(ev),
+                              epoch_gemm_event_ms=spread(gemm), launches_per_lockstep_step=launches / steps,
+                              f32_mfma_peak_fraction=flop / (spread(ev)["median"] * 1e-3) / PEAK_F32_MFMA)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100000)
@@ -104,7 +182,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--paths", default="torch64,torch32,hip")
     ap.add_argument("--shapes", default="cdu,small")
+    ap.add_argument("--sweep", default="", help="cstrs or cdu: time the whole sweep, looped and grouped, instead of the shapes")
+    ap.add_argument("--ways", default="loop,group")
     a = ap.parse_args()
+    if a.sweep:
+        for name in a.sweep.split(","):
+            run_sweep(name, a.epochs, a.repeats, a.ways.split(","))
+        return
     for sname in a.shapes.split(","):
         dims, uprev = SHAPES[sname]
         nx, nu = geometry(dims, uprev)
