@@ -58,7 +58,8 @@ typedef struct {
   int32_t nb;                /* Cholesky block 64 | 128; 0 = auto */
   int32_t max_ipm_iters;     /* 0 = 40 */
   int32_t max_polish_rounds; /* 0 = 150 (the single-exchange fallback against cycling may take one round per bound) */
-  int32_t max_refine;        /* PCG steps per active set; 0 = 60 */
+  int32_t max_refine;        /* PCG steps per active set and factor; 0 = 60.  On a fresh factor the cap ends the refinement (the KKT check judges
+                                what it reached); on a reused factor (stale_max_changes) it asks for the factor of the current set first */
   int32_t max_rounds;        /* lock-step rounds a problem may stay resident; 0 = 1000 */
   int32_t sub_steps;         /* solve sub-steps (PCG steps / KKT check) per round; 0 = 8 */
   int32_t stale_max_changes; /* polish: reuse the previous factor as PCG preconditioner when at most
@@ -215,6 +216,10 @@ int nnmpc_qp_get_stats(nnmpc_qp* h, nnmpc_qp_stats* out, int32_t reset);
  * solve K_b sol_b = rhs_b for b < B <= max_batch (all B x n, host pointers). */
 int nnmpc_qp_debug_factor_solve(nnmpc_qp* h, int32_t B, const float* dvec, const float* mask,
                                 const float* rhs, float* sol);
+/* ... and the per-problem flags of that call (B host int32): 1 = the factorisation of K_b met a non-positive pivot (the pivot is
+ * replaced by 1e-30 and the kernels run on: sol_b is then finite or not, but never an answer), 0 otherwise.  In a solve the same
+ * flag makes the problem's status NNMPC_ST_NUMERIC. */
+int nnmpc_qp_debug_factor_fail(nnmpc_qp* h, int32_t B, int32_t* fail);
 
 /* Structured NN controller.  dims = [d_in, h1, ..., h_{L-1}, nu]; W[l] is
  * dims[l] x dims[l+1] row-major (Keras kernel layout), b[l] has dims[l+1]

@@ -279,14 +279,17 @@ __device__ int cg_alpha(const QpDev& d, int p, double* shd) {
   xm = block_maxd(xm, shd);
   const int rc = d.rcnt[p] + 1;
   const bool nan = !(a == a) || !(xm == xm);
-  const bool conv = !ok || nan || (fabs(a) * pm <= d.refine_tol * fmax(1.0, xm)) || rc >= d.max_refine;
+  // (the step cap ends the PCG on a FRESH factor only: on a reused one it asks for the factor of the current set first, like
+  // stale_cg_limit -- otherwise max_refine < stale_cg_limit gives up a slot with the right set as MAXITER)
+  const bool capped = rc >= d.max_refine;
+  const bool conv = !ok || nan || (fabs(a) * pm <= d.refine_tol * fmax(1.0, xm)) || (capped && !d.stale[p]);
   if (conv) {
     for (int r = tid; r < d.n; r += 256) d.v64[o + r] = d.x[o + r];
   } else {
     for (int r = tid; r < d.n; r += 256) d.rhs[o + r] = d.st[o + r] ? 0.f : (float)d.r64[o + r];
   }
   // PCG on a stale preconditioner that does not converge quickly: factor the current set instead
-  const bool refac = !conv && d.stale[p] && rc >= d.stale_cg_limit;
+  const bool refac = !conv && d.stale[p] && (capped || rc >= d.stale_cg_limit);
   if (refac) for (int r = tid; r < d.n; r += 256) d.v64[o + r] = d.x[o + r];
   __syncthreads();
   if (tid == 0) {
@@ -2183,6 +2186,14 @@ int nnmpc_qp_debug_factor_solve(nnmpc_qp* h, int32_t B, const float* dvec, const
   for (int p = 0; p < B; ++p)
     for (int r = 0; r < h->n; ++r) sol[(size_t)p * h->n + r] = so[(size_t)p * h->np + r];
   if (h->profiling) { stream_sync(h->stream); ev_collect(h); }
+  return NNMPC_OK;
+}
+
+int nnmpc_qp_debug_factor_fail(nnmpc_qp* h, int32_t B, int32_t* fail) {
+  if (!h || B <= 0 || B > h->slots || !fail) { set_error("debug_factor_fail: bad arguments"); return NNMPC_EINVAL; }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(stream_sync(h->stream));
+  HIPCHK(hipMemcpy(fail, h->d.fail, (size_t)B * 4, hipMemcpyDeviceToHost));
   return NNMPC_OK;
 }
 

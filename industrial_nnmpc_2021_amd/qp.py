@@ -259,3 +259,10 @@ class BatchedBoxQP:
             self._h, B, *(a.ctypes.data_as(C.c_void_p) for a in (dvec, mask, rhs, sol))),
             "nnmpc_qp_debug_factor_solve")
         return sol
+
+    def debug_factor_fail(self, B):
+        """(B,) int32: 1 where the last debug_factor_solve met a non-positive pivot in that row's factorisation."""
+        fail = np.empty(B, np.int32)
+        _lib.check(self._lib.nnmpc_qp_debug_factor_fail(self._h, B, fail.ctypes.data_as(C.c_void_p)),
+                   "nnmpc_qp_debug_factor_fail")
+        return fail

@@ -557,3 +557,159 @@ def oracle_rows(P, q, lb, ub, nu, rows):
         act[info["active"]] = True
         out.append((x, act))
     return out
+
+
+# ---- PDIP path: tests/test_pdip_factor_gpu.py, tests/test_pdip_paths_gpu.py, tests/test_cpu_pdip_inputs.py --------------------
+
+PDIP_FACTOR_COND = 1e2
+# (n, nb): every n sits on a tile or a 32-row sub-block edge of chol_diag_k / chol_panel_k / trsv_k
+PDIP_FACTOR_SHAPES = ([(n, 64) for n in (2, 31, 33, 64)] + [(n, nb) for n in (65, 127, 128, 129) for nb in (64, 128)]
+                      + [(449, 64), (449, 128)])
+PDIP_FACTOR_ROWS = 6
+PDIP_PIVOT_SHAPE = (129, 64)
+PDIP_PIVOT_AT = (5, 40, 70)       # sub-block 0 of tile 0, sub-block 1 of tile 0, tile 1 (nb = 64)
+PDIP_PIVOT_ROW = 2
+
+
+def pdip_unit_spd(n, seed, cond=PDIP_FACTOR_COND):
+    """Dense SPD matrix with random orthogonal eigenvectors (every tile couples with every other) and log-uniform eigenvalues
+    whose extremes are 1 and ``cond`` exactly, then rescaled to a unit diagonal (D^-1/2 P D^-1/2, diagonal set to exactly 1): the
+    library's normalisation by the upper median of the diagonal is then exactly 1.  Returns (P, the matrix before rescaling)."""
+    rng = np.random.default_rng(seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    ev = np.exp(rng.uniform(0.0, np.log(cond), n))
+    ev[0], ev[-1] = 1.0, cond
+    P0 = (Q * ev) @ Q.T
+    P0 = 0.5 * (P0 + P0.T)
+    s = 1.0 / np.sqrt(np.diag(P0))
+    P = P0 * s[:, None] * s[None, :]
+    P = np.tril(P) + np.tril(P, -1).T
+    np.fill_diagonal(P, 1.0)
+    return P, P0
+
+
+def pdip_factor_case(n, seed=None):
+    """P (unit diagonal), tq (n x 1, unused by the factor hook) and the six rows of a factor / solve case: dvec, mask, rhs (f32).
+    Row 0: dvec = 0, mask all ones.  Row 1: dvec = 1e-6.  Row 2: IPM-like, dvec = exp(U(-3, 3)).  Row 3: polish-like, a random
+    30 % of the variables masked, dvec = 1 there and 1e-6 elsewhere.  Row 4: all but three variables masked (same dvec rule).
+    Row 5: one whole tile masked (rows 64 .. 127) when n >= 128, otherwise another draw of row 3."""
+    seed = 7000 + n if seed is None else seed
+    P, _ = pdip_unit_spd(n, seed)
+    rng = np.random.default_rng(seed + 1)
+    B = PDIP_FACTOR_ROWS
+    dvec = np.zeros((B, n), np.float32)
+    mask = np.ones((B, n), np.float32)
+    dvec[1] = 1e-6
+    dvec[2] = np.exp(rng.uniform(-3.0, 3.0, n))
+
+    def masked(r, off):
+        mask[r, off] = 0.0
+        dvec[r] = np.where(off, 1.0, 1e-6)
+    masked(3, rng.random(n) < 0.3)
+    off = np.ones(n, bool)
+    off[rng.choice(n, min(3, n), replace=False)] = False
+    masked(4, off)
+    draw = rng.random(n) < 0.3
+    masked(5, (np.arange(n) // 64 == 1) if n >= 128 else draw)
+    rhs = rng.standard_normal((B, n)).astype(np.float32)
+    return dict(P=P, tq=np.ones((n, 1)), dvec=dvec, mask=mask, rhs=rhs)
+
+
+def pdip_second_call(case, seed=99):
+    """Another (dvec, mask, rhs) for the same P: what the second call on one handle factors (the Dacc invariant)."""
+    n = case["P"].shape[0]
+    rng = np.random.default_rng(seed)
+    B = PDIP_FACTOR_ROWS
+    off = rng.random((B, n)) < 0.2
+    mask = np.where(off, 0.0, 1.0).astype(np.float32)
+    dvec = np.where(off, 1.0, np.exp(rng.uniform(-4.0, 1.0, (B, n)))).astype(np.float32)
+    return dvec, mask, rng.standard_normal((B, n)).astype(np.float32)
+
+
+def pdip_K(P, dvec_row, mask_row):
+    """K = mask mask' o P32 + diag(dvec) in float64 from the f32-rounded P: the matrix the kernels factor."""
+    P32 = P.astype(np.float32).astype(np.float64)
+    m = mask_row.astype(np.float64)
+    return m[:, None] * m[None, :] * P32 + np.diag(dvec_row.astype(np.float64))
+
+
+def pdip_solve_errors(P, dvec, mask, rhs, sol):
+    """Per row (e, e32): max|sol - ref| / max|ref| of the kernels' solution and of LAPACK's f32 Cholesky (cho_factor / cho_solve
+    on the float32 K), both against np.linalg.solve on the float64 K."""
+    import scipy.linalg as sla
+    out = []
+    for b in range(dvec.shape[0]):
+        K = pdip_K(P, dvec[b], mask[b])
+        ref = np.linalg.solve(K, rhs[b].astype(np.float64))
+        s32 = sla.cho_solve(sla.cho_factor(K.astype(np.float32), lower=True), rhs[b])
+        assert s32.dtype == np.float32
+        rm = np.abs(ref).max()
+        out.append((float(np.abs(sol[b].astype(np.float64) - ref).max() / rm), float(np.abs(s32.astype(np.float64) - ref).max() / rm)))
+    return out
+
+
+def pdip_pivot_rows(case, at):
+    """The case's rows with row PDIP_PIVOT_ROW replaced by one whose K has a negative diagonal entry at index ``at``
+    (dvec = -3 against P_ii = 1): a non-positive pivot whatever came before it."""
+    dvec, mask = case["dvec"].copy(), case["mask"].copy()
+    dvec[PDIP_PIVOT_ROW] = 0.0
+    mask[PDIP_PIVOT_ROW] = 1.0
+    dvec[PDIP_PIVOT_ROW, at] = -3.0
+    return dvec, mask
+
+
+# The family of tests/test_pdip_paths_gpu.py: the generic SPD construction of tests/test_random_shapes_gpu.py at n = 130 (nu = 2,
+# N = 65: T = 3 tiles of 64 with 62 pad rows), cond(P) = 1e3, 24 problems; PDIP_FAMILY_SCALE was chosen with the oracle so that
+# every row's set holds 10 - 50 % of the variables (tests/test_cpu_pdip_inputs.py asserts it); row 1 is the empty set.
+PDIP_FAMILY_SEED = 4100
+PDIP_FAMILY_SCALE = 0.3
+PDIP_FAMILY_B = 24
+
+
+def pdip_family(seed=PDIP_FAMILY_SEED, scale=PDIP_FAMILY_SCALE, n=130, nu=2, cond=1e3, B=PDIP_FAMILY_B, n_aug=6):
+    rng = np.random.default_rng(seed)
+    P = spd_logspectrum(n, seed + 1, cond)
+    tq = rng.standard_normal((n, n_aug)) * np.sqrt(np.diag(P))[:, None] * scale
+    x0 = rng.standard_normal((B, n_aug))
+    x0[1] = 0.0
+    lb = -rng.uniform(0.2, 2.0, (B, nu))
+    ub = rng.uniform(0.2, 2.0, (B, nu))
+    return dict(P=P, tq=tq, nu=nu, N=n // nu, n=n, x0=x0, lb=lb, ub=ub, cond=cond)
+
+
+def pdip_family_oracle(fam):
+    """(U* (B, n), active (B, 2n) bool) of the family by oracle.qp.solve_exact_box."""
+    B, n = fam["x0"].shape[0], fam["n"]
+    U, act = np.empty((B, n)), np.zeros((B, 2 * n), bool)
+    for b in range(B):
+        info = {"nu": fam["nu"]}
+        U[b] = oqp.solve_exact_box(fam["P"], fam["tq"] @ fam["x0"][b], np.tile(fam["lb"][b], fam["N"]), np.tile(fam["ub"][b], fam["N"]),
+                                   info=info)
+        act[b, info["active"]] = True
+    return U, act
+
+
+def pdip_flipped_guess(state, seed=5):
+    """The bound states with a random 10 % of every row's variables flipped: a free one put on a random bound, a held one freed."""
+    rng = np.random.default_rng(seed)
+    g = state.copy()
+    B, n = g.shape
+    for b in range(B):
+        idx = rng.choice(n, max(1, n // 10), replace=False)
+        g[b, idx] = np.where(g[b, idx] == 0, rng.integers(1, 3, idx.size), 0)
+    return g
+
+
+def pdip_indefinite(n=64, seed=11):
+    """Unit diagonal, eigenvalues in [1, 10] but one negative: the diagonal is positive (the handle is created), no Cholesky exists."""
+    rng = np.random.default_rng(seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    ev = rng.uniform(1.0, 10.0, n)
+    ev[0] = -5.0
+    P0 = (Q * ev) @ Q.T
+    P0 = 0.5 * (P0 + P0.T)
+    s = 1.0 / np.sqrt(np.diag(P0))
+    P = P0 * s[:, None] * s[None, :]
+    P = np.tril(P) + np.tril(P, -1).T
+    np.fill_diagonal(P, 1.0)
+    return P

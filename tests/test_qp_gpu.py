@@ -30,7 +30,7 @@ def test_factor_solve_kernels(name, nb):
     rhs = rng.standard_normal((B, n)).astype(np.float32)
     sol = qp.debug_factor_solve(dvec, mask, rhs)
     Ps = np.tril(reg.P) + np.tril(reg.P, -1).T
-    Ps = Ps / np.median(np.diag(Ps))   # the f32 path works on P / median(diag P)
+    Ps = Ps / np.sort(np.diag(Ps))[n // 2]   # the f32 path works on P / the upper median of diag P (nnmpc_qp_create: nth_element at n / 2)
     for b in range(B):
         K = (mask[b][:, None] * mask[b][None, :]).astype(np.float64) * Ps + np.diag(dvec[b].astype(np.float64))
         ref = np.linalg.solve(K, rhs[b].astype(np.float64))

@@ -7,6 +7,9 @@ status 0 must be the exact optimum with the exact active set.
   * method "auto" (the default path): every problem must come back solved (status 0) while cond(P) < 5e4; beyond -- with half
     the bounds active the documented limit of both paths, DESIGN.md section 9 -- a problem may exhaust its budget (status 1);
   * method "asm" (no PDIP path behind the active-set pass): a problem may exhaust its budget at any conditioning;
+  * method "pdip" (the PDIP path alone, which under "auto" sees only what the active-set pass leaves over): the same rule as
+    "asm" on these seeds; on a second family of 12 seeds with cond(P) <= 1e3 it must finish every problem with status 0 -- a path that
+    finishes nothing does not pass;
   * never, in any mode, a status 0 with a wrong answer or a wrong active set.
 """
 import numpy as np
@@ -21,7 +24,7 @@ def _spd(n, rng, cond):
     return (Q * ev) @ Q.T
 
 
-def _case(seed):
+def _case(seed, log10_cond_max=6):
     rng = np.random.default_rng(seed)
     nu = int(rng.choice([1, 2, 3, 4, 5, 6, 8, 16]))
     N = int(rng.integers(2, 60))
@@ -29,7 +32,7 @@ def _case(seed):
     if n > 420:
         N = 420 // nu
         n = nu * N
-    cond = float(10 ** rng.uniform(0, 6))
+    cond = float(10 ** rng.uniform(0, log10_cond_max))
     P = _spd(n, rng, cond)
     n_aug = int(rng.integers(1, 12))
     tq = rng.standard_normal((n, n_aug)) * np.sqrt(np.diag(P))[:, None] * rng.uniform(0.1, 3.0)
@@ -44,12 +47,11 @@ def _case(seed):
     return P, tq, nu, N, n, cond, x0, lb, ub, f32, tail
 
 
-@pytest.mark.parametrize("method", ["auto", "asm"])
-@pytest.mark.parametrize("seed", list(range(100, 112)))
-def test_random_shape(seed, method):
+def _check(seed, method, log10_cond_max=6):
+    """Solves the case; every status 0 must be the exact optimum with the exact set.  Returns (rows not finished, cond)."""
     from industrial_nnmpc_2021_amd.qp import BatchedBoxQP
     from oracle import qp as oqp
-    P, tq, nu, N, n, cond, x0, lb, ub, f32, tail = _case(seed)
+    P, tq, nu, N, n, cond, x0, lb, ub, f32, tail = _case(seed, log10_cond_max)
     qp = BatchedBoxQP(P, tq, nu, max_batch=128, method=method, asm_f32_rounds=f32, asm_tail_batch=tail)
     out = qp.solve_batch(x0, lb, ub)
     qp.close()
@@ -58,7 +60,7 @@ def test_random_shape(seed, method):
     for b in range(x0.shape[0]):
         st = int(out["status"][b])
         if st != 0:
-            assert st == 1 and (method == "asm" or cond >= 5e4), (seed, b, st, cond)   # budget exhausted: see the docstring
+            assert st == 1 and (method in ("asm", "pdip") or cond >= 5e4), (seed, b, st, cond)   # budget exhausted: see the docstring
             unsolved += 1
             continue
         info = {"nu": nu}
@@ -68,5 +70,20 @@ def test_random_shape(seed, method):
         err = np.abs(out["u"][b] - xe).max() / max(1.0, np.abs(xe).max())
         assert err <= tol, (seed, b, err, cond)
         assert (out["active"][b] == act).all(), (seed, b, int((out["active"][b] != act).sum()), int(act.sum()))
+    return unsolved, cond
+
+
+@pytest.mark.parametrize("method", ["auto", "asm", "pdip"])
+@pytest.mark.parametrize("seed", list(range(100, 112)))
+def test_random_shape(seed, method):
+    unsolved, cond = _check(seed, method)
+    print(f"\nseed {seed} method {method} cond {cond:.3g}: {unsolved} rows not finished")
     if method == "auto" and cond < 5e4:
         assert unsolved == 0
+
+
+@pytest.mark.parametrize("seed", list(range(200, 212)))
+def test_pdip_finishes_every_row_up_to_cond_1e3(seed):
+    unsolved, cond = _check(seed, "pdip", log10_cond_max=3)
+    assert cond <= 1e3
+    assert unsolved == 0, (seed, cond, unsolved)
