@@ -418,7 +418,8 @@ int nnmpc_ts_solve_batch(nnmpc_ts* h, int32_t B, const double* q, const double* 
  *            started on the instance's previous active set shifted by one stage;  NN: clip(us + NN(x^, uprev, xs, us) -
  *            NN(xs, us, xs, us)) (:863-892);  SATDLQR: clip(Kaug [x^ - xs; uprev - us] + us) (:1003-1005);  US: us (:1076)
  *   cost     z = [x^ - xs; uprev - us], w = u - us, ell = z'Qaug z + w'Raug w + z'Maug w + w'Maug'z,
- *            avg_{t+1} = (avg_t t + ell) / (t + 1)                                                             (:691-701)
+ *            avg_{t+1} = (avg_t t + ell) / (t + 1), t counted from create / reset (not from this call: a chunked run
+ *            continues the mean of the chunks before it)                                                       (:691-701)
  *   plant    uprev = u,  x = A x + B u + Bp p_t,  y_{t+1} = C x + sigma o v_{t+1}                               (:87-131)
  * Nothing random runs on the device: v holds the standard-normal draws of every instance. */
 typedef struct nnmpc_cl nnmpc_cl;
@@ -432,7 +433,8 @@ typedef struct nnmpc_cl nnmpc_cl;
  *   target  tb nb_ x (ny + nd), Qb nu x nb_, Qy nu x ny, q0 nu, Cd ny x nd, Eb nz x nb_, Xb nx x nb_, Xu nx x nu
  *           (target.ReducedTargetProblem; the QP itself is the borrowed nnmpc_ts handle, created with nu, nz)
  *   cost    Qaug (nx + nu)^2, Raug nu x nu, Maug (nx + nu) x nu
- *   bounds  ulb, uub (nu);  initial values x0 (nx), xhat0 (na), uprev0 (nu) shared by every instance */
+ *   bounds  ulb, uub (nu);  initial values x0 (nx), xhat0 (na), uprev0 (nu) shared by every instance
+ * Bp and Cd may be NULL when nd = 0, Eb when nz = 0 (dist of nnmpc_cl_run too when nd = 0); every other pointer is required. */
 typedef struct {
   int32_t nx, nu, ny, nd, nz;
   const double *A, *B, *C, *Bp;
@@ -476,7 +478,8 @@ int nnmpc_cl_reset(nnmpc_cl* h);
  * and controller inputs (incl. SATDLQR / US), grouped NN forward, MPC solves (to the last slot's end), clip + cost + plant;
  * slot_step_ms (T x nslots, may be NULL): each step's controller phase of each slot for the whole batch (MPC: its solve,
  * NN: the grouped forward, SATDLQR / US: the expansion kernel).  The phase events of at most 256 steps are alive at a time: a
- * longer run drains its stream once per 256 steps to add them up, so the handle holds (7 + MPC slots) x 256 + 2 events at most. */
+ * longer run drains its stream once per 256 steps to add them up, so the handle holds (7 + MPC slots, + 1 with the nonlinear
+ * plant) x 256 + 2 events at most. */
 int nnmpc_cl_last_ms(nnmpc_cl* h, double* total_ms, double* phase_ms, double* slot_step_ms);
 /* ---- Nonlinear plant of the closed loop: the CSTRs-with-flash plant of the reference's study (cstrs_parameters.py,
  * NonlinearPlantSimulator, lib/nonlinearMPC.py:11-48).  Its 12-state ODE is integrated over each sample by classical RK4 with

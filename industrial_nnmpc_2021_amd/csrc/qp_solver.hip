@@ -1916,7 +1916,9 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
   {
     const int kap = ((n_aug + 63) / 64) * 64;
     double *tmp = nullptr, *kt = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, (size_t)np * np * 8));
+    // tmp holds P Pinv (np x np), then P Kunc (np x kap): kap exceeds np when the horizon is short beside the state (n < n_aug)
+    const size_t ntmp = (size_t)np * std::max(np, kap);
+    HIPCHK(hipMalloc((void**)&tmp, ntmp * 8));
     HIPCHK(hipMalloc((void**)&kt, (size_t)kap * np * 8));
     std::vector<double> ktr((size_t)kap * np, 0.0);
     for (int r = 0; r < n; ++r)
@@ -1924,8 +1926,8 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
     HIPCHK(hipMemcpy(kt, ktr.data(), ktr.size() * 8, hipMemcpyHostToDevice));
     gemm64(h, tmp, np, h->P64, np, h->H64, np, np, np, np);                 // P Pinv (Pinv symmetric)
     HIPCHK(stream_sync(h->stream));
-    std::vector<double> c((size_t)np * np);
-    HIPCHK(hipMemcpy(c.data(), tmp, c.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<double> c(ntmp);
+    HIPCHK(hipMemcpy(c.data(), tmp, (size_t)np * np * 8, hipMemcpyDeviceToHost));
     double e2 = 0.0;
     for (int r = 0; r < n; ++r)
       for (int cc = 0; cc < n; ++cc) e2 = std::max(e2, std::fabs(c[(size_t)r * np + cc] - (r == cc ? 1.0 : 0.0)));

@@ -713,3 +713,381 @@ def pdip_indefinite(n=64, seed=11):
     P = np.tril(P) + np.tril(P, -1).T
     np.fill_diagonal(P, 1.0)
     return P
+
+
+# ---- closed-loop and chain step kernels (csrc/closed_loop.hip, chain half of csrc/chain.hip): tests/test_cl_step_gpu.py,
+# tests/test_chain_step_gpu.py, tests/test_cpu_cl_step_inputs.py ------------------------------------------------------------------
+# Nothing below imports the package: the model is a bag of matrices in the fields of nnmpc_cl_model (include/nnmpc.h), the
+# reference is numpy in np.longdouble on the RECORDED inputs of a step, and every fp64 identity comes with its own bound
+#     |kernel - reference| <= 2 gamma_n (the identity with every matrix and vector replaced by its absolute value and every
+#                                        subtraction by an addition),       gamma_n = n eps / (1 - n eps),
+# n = the additions along the longest path through the identity: the forward bound of a dot product in any summation order
+# (Higham, Accuracy and Stability, section 3.5); the factor 2 covers nesting and FMA contraction.
+
+# case -> (nx, nu, ny, nd, nz); the boundary each one puts into play (all loops of the kernels stride by 256 threads):
+CL_STEP_CASES = {
+    "a": (1, 1, 1, 0, 0),        # every dimension 1, nd = 0, nz = 0: Bp / Cd / Eb NULL
+    "b": (3, 2, 2, 1, 1),        # smallest with every term present
+    "c": (254, 3, 7, 5, 1),      # nx < 256 < na = 259: bin[ny + k - nx] on a second trip; nx + nu = 257; nbv = 255
+    "d": (255, 2, 5, 1, 1),      # na = nbv = 256 exactly; nx + nu = 257
+    "e": (257, 5, 12, 0, 2),     # nx on a second trip with nd = 0; nbv = 259
+    "f": (300, 4, 257, 3, 2),    # ny > 256 (r, bin, y); nx, na, nbv all on a second trip
+    "g": (40, 6, 300, 2, 3),     # ny >> nx
+    "h": (520, 2, 3, 2, 1),      # three trips
+}
+CL_STEP_T = 12
+CL_STEP_N = 4                    # horizon of the MPC slot
+CL_STEP_MPC_COND = 1e2
+CL_STEP_HIDDEN = [64, 70]        # one full and one ragged column tile of cl_nn_layer_k
+CL_STEP_KINDS = ("us", "satdlqr", "nn_u", "nn", "mpc")
+CL_STEP_COUNTS = (3, 4, 2, 3, 4)  # instances per slot: nb = 16
+CL_STEP_NSCEN = 3
+CL_STEP_NN_TOL = 1e-4            # the bar of cl_assert_one_step_identity (f32 sums)
+# Gaussian scales on top of 1 / sqrt(fan-in).  L: with a gain of the order of 1 the estimator matrix (I - L Caug) Aaug of a
+# random draw has a norm of the order of sqrt(na) + sqrt(ny) and the estimate leaves every bound within 12 steps; entries of
+# 0.3 / (sqrt(na) + sqrt(ny)) keep |L|_2 near 0.3 (tests/test_cpu_cl_step_inputs.py holds the records below 1e3).
+# Qaug: G with entries 0.5 / sqrt(nx + nu) keeps the running cost of the largest case below 1e3.
+CL_STEP_SCALES = dict(Qb=0.8, Qy=0.8, Eb=0.05, Kaug=0.3, L=0.3, Qaug=0.5, q0=0.1, x0=0.3, sigma=0.05, p=0.5)
+# Seeds: 9000 + 10 * (index of the case).  Aaug has nd eigenvalues 1 and a small random L moves them either way; case b also
+# carries the 513-step runs across the event blocks, so its seed was chosen with the reference alone among 9010 .. 9019 for an
+# estimator matrix (I - L Caug) Aaug of spectral radius 0.954 (asserted on the CPU, like every share figure).
+CL_STEP_SEEDS = dict({c: 9000 + 10 * i for i, c in enumerate(sorted(CL_STEP_CASES))}, b=9012)
+CL_STEP_LONG_T = (257, 513)      # one and two crossings of the 256-step event block
+
+
+def cl_step_model(seed, nx, nu, ny, nd, nz, scales=CL_STEP_SCALES):
+    """A synthetic model in the fields of nnmpc_cl_model (plus Pr, E of the target handle, Kaug of a SATDLQR slot and sigma): A
+    with spectral radius 0.9, Gaussian B, Bp, C, Cd, L, tb, Qb, Qy, Xb, Xu, Maug, Kaug scaled by 1 / sqrt(fan-in), Qaug = G G',
+    Raug SPD, Pr / E / ulb / uub from ts_matrices(seed, nu, nz, 10), Eb small enough that E u = e stays feasible inside the
+    box.  Aaug, Baug, Caug: the augmented matrices of A, B, Bp, C, Cd (constant disturbance model).  No Riccati equation, no
+    reduction of a target problem: the kernels are linear maps and are tested as such.  Bp / Cd are None for nd = 0, Eb for
+    nz = 0 (the NULL pointers nnmpc_cl_create allows)."""
+    rng = np.random.default_rng(seed)
+    g = lambda r, c, s=1.0: s * rng.standard_normal((r, c)) / np.sqrt(max(c, 1))
+    na, nbv, nzz = nx + nd, nx + nz, nx + nu
+    W = rng.standard_normal((nx, nx))
+    A = 0.9 * W / np.abs(np.linalg.eigvals(W)).max()
+    B, Bp, C, Cd = g(nx, nu), g(nx, nd), g(ny, nx), g(ny, nd)
+    L = g(na, ny, scales["L"] * np.sqrt(ny) / (np.sqrt(na) + np.sqrt(ny)))
+    tb, Qb, Qy = g(nbv, ny + nd), g(nu, nbv, scales["Qb"]), g(nu, ny, scales["Qy"])
+    Eb, Xb, Xu = g(nz, nbv, scales["Eb"]), g(nx, nbv), g(nx, nu)
+    Maug, Kaug = g(nzz, nu), g(nu, nzz, scales["Kaug"])
+    G = g(nzz, nzz, scales["Qaug"])
+    Gr = g(nu, nu)
+    q0 = scales["q0"] * rng.standard_normal(nu)
+    x0, xhat0 = scales["x0"] * rng.standard_normal(nx), scales["x0"] * rng.standard_normal(na)
+    sigma = scales["sigma"] * rng.uniform(0.5, 1.5, ny)
+    Pr, E, ulb, uub = ts_matrices(seed, nu, nz, 10.0)
+    uprev0 = 0.5 * (ulb + rng.uniform(0.0, 1.0, nu) * (uub - ulb))
+    Aaug = np.block([[A, Bp], [np.zeros((nd, nx)), np.eye(nd)]])
+    Baug = np.vstack((B, np.zeros((nd, nu))))
+    Caug = np.hstack((C, Cd))
+    return dict(nx=nx, nu=nu, ny=ny, nd=nd, nz=nz, A=A, B=B, C=C, Bp=Bp if nd else None, Aaug=Aaug, Baug=Baug, Caug=Caug, L=L,
+                tb=tb, Qb=Qb, Qy=Qy, q0=q0, Cd=Cd if nd else None, Eb=Eb if nz else None, Xb=Xb, Xu=Xu, Qaug=G @ G.T,
+                Raug=Gr @ Gr.T + 0.1 * np.eye(nu), Maug=Maug, ulb=ulb, uub=uub, x0=x0, xhat0=xhat0, uprev0=uprev0,
+                Pr=Pr, E=E, Kaug=Kaug, sigma=sigma)
+
+
+def cl_step_batch(case, seed=None, kinds=CL_STEP_KINDS, counts=CL_STEP_COUNTS, T=CL_STEP_T):
+    """Everything one run of a case needs but the device: the model, one slot spec per kind (dicts in the form DeviceClosedLoop
+    takes; the MPC spec carries P, tq, nu, N in place of a solver), the slot and scenario of every instance, setpoints in +-1
+    and disturbances in +-0.5 of three scenarios (a fresh draw at every step: every step is its own test vector), the noise."""
+    nx, nu, ny, nd, nz = CL_STEP_CASES[case]
+    seed = CL_STEP_SEEDS[case] if seed is None else seed
+    M = cl_step_model(seed, nx, nu, ny, nd, nz)
+    rng = np.random.default_rng(seed + 1)
+    slots = []
+    for k in kinds:
+        if k == "us":
+            slots.append(dict(kind="us"))
+        elif k == "satdlqr":
+            slots.append(dict(kind="satdlqr", Kaug=M["Kaug"]))
+        elif k in ("nn_u", "nn"):
+            wu = k == "nn_u"
+            slots.append(dict(kind="nn", weights=cl_nn_weights(seed + (2 if wu else 3), 2 * nx + (2 if wu else 1) * nu, CL_STEP_HIDDEN, nu),
+                              with_uprev=wu, xscale=np.random.default_rng(seed + 4).uniform(0.5, 2.0, nx)))
+        else:
+            n = CL_STEP_N * nu
+            slots.append(dict(kind="mpc", P=spd_logspectrum(n, seed + 5, CL_STEP_MPC_COND), nu=nu, N=CL_STEP_N,
+                              tq=np.random.default_rng(seed + 6).standard_normal((n, nx + nu)) / np.sqrt(nx + nu)))
+    inst_slot = np.repeat(np.arange(len(kinds)), counts[:len(kinds)]).astype(np.int32)
+    nb = inst_slot.size
+    scen = ((np.arange(nb) + 1) % CL_STEP_NSCEN).astype(np.int32)
+    SP = rng.uniform(-1.0, 1.0, (CL_STEP_NSCEN, T, ny))
+    DS = CL_STEP_SCALES["p"] * rng.uniform(-1.0, 1.0, (CL_STEP_NSCEN, T, nd))
+    V = rng.standard_normal((T + 1, nb, ny))
+    return dict(case=case, M=M, slots=slots, inst_slot=inst_slot, scen=scen, SP=SP, DS=DS, V=V, sigma=M["sigma"], T=T)
+
+
+def cl_gamma(n):
+    return n * TS_EPS / (1.0 - n * TS_EPS)
+
+
+def _cl_ld(M):
+    """np.longdouble copies of the model's matrices and their absolute values (cached in the dict)."""
+    if "_ld" not in M:
+        nx, nu, ny, nd, nz = (M[k] for k in ("nx", "nu", "ny", "nd", "nz"))
+        shape = dict(Bp=(nx, nd), Cd=(ny, nd), Eb=(nz, nx + nz), E=(nz, nu))
+        ld, ab = {}, {}
+        for k in ("A", "B", "C", "Bp", "Aaug", "Baug", "Caug", "L", "tb", "Qb", "Qy", "q0", "Cd", "Eb", "Xb", "Xu", "Qaug", "Raug",
+                  "Maug", "ulb", "uub"):
+            a = np.zeros(shape[k]) if M.get(k) is None else np.asarray(M[k], np.float64)
+            ld[k] = a.astype(np.longdouble)
+            ab[k] = np.abs(ld[k])
+        M["_ld"] = (ld, ab)
+    return M["_ld"]
+
+
+def _ld(a):
+    return np.asarray(a, np.longdouble)
+
+
+def cl_ref_filter(M, xhat, uprev, y):
+    """xp = Aaug xhat + Baug uprev, xhat' = xp + L (y - Caug xp); rows.  -> (xhat', bound)."""
+    m, a = _cl_ld(M)
+    xhat, uprev, y = _ld(xhat), _ld(uprev), _ld(y)
+    xp = xhat @ m["Aaug"].T + uprev @ m["Baug"].T
+    axp = np.abs(xhat) @ a["Aaug"].T + np.abs(uprev) @ a["Baug"].T
+    out = xp + (y - xp @ m["Caug"].T) @ m["L"].T
+    mag = axp + (np.abs(y) + axp @ a["Caug"].T) @ a["L"].T
+    na = M["nx"] + M["nd"]
+    return out, 2.0 * cl_gamma(na + M["nu"] + na + M["ny"] + 2) * mag
+
+
+def cl_ref_reduce(M, xhat1, ysp):
+    """dhat = xhat'[nx:], b = tb [ysp; dhat], q = Qb b + Qy (ysp - Cd dhat) + q0, e = Eb b.  -> (b, |b| bound form, q, e)."""
+    m, a = _cl_ld(M)
+    xhat1, ysp = _ld(xhat1), _ld(ysp)
+    dhat = xhat1[:, M["nx"]:]
+    bin_ = np.concatenate((ysp, dhat), axis=1)
+    b = bin_ @ m["tb"].T
+    q = b @ m["Qb"].T + (ysp - dhat @ m["Cd"].T) @ m["Qy"].T + m["q0"]
+    return b, np.abs(bin_) @ a["tb"].T, q, b @ m["Eb"].T
+
+
+def cl_ref_expand(M, b, babs, us):
+    """xs = Xb b + Xu us.  -> (xs, bound)."""
+    m, a = _cl_ld(M)
+    us = _ld(us)
+    n = M["ny"] + M["nd"] + M["nx"] + M["nz"] + M["nu"] + 2
+    return b @ m["Xb"].T + us @ m["Xu"].T, 2.0 * cl_gamma(n) * (babs @ a["Xb"].T + np.abs(us) @ a["Xu"].T)
+
+
+def cl_ref_z(xhat1, xs, uprev, us, nx):
+    """z = [xhat'[:nx] - xs; uprev - us] and its absolute-value form."""
+    xh, xs, uprev, us = _ld(xhat1)[:, :nx], _ld(xs), _ld(uprev), _ld(us)
+    return (np.concatenate((xh - xs, uprev - us), axis=1),
+            np.concatenate((np.abs(xh) + np.abs(xs), np.abs(uprev) + np.abs(us)), axis=1))
+
+
+def cl_ref_satdlqr(M, Kaug, z, zabs, us):
+    """clip(Kaug z + us).  -> (u, bound): the clip is 1-Lipschitz, so the bound of the unclipped value holds."""
+    m, a = _cl_ld(M)
+    K, us = _ld(Kaug), _ld(us)
+    u = np.minimum(np.maximum(z @ K.T + us, m["ulb"]), m["uub"])
+    return u, 2.0 * cl_gamma(M["nx"] + M["nu"] + 3) * (zabs @ np.abs(K).T + np.abs(us))
+
+
+def cl_ref_cost(M, z, zabs, u, us, avg0, tg):
+    """ell = z'Qaug z + w'Raug w + z'Maug w + w'Maug'z with w = u - us; avg' = (avg tg + ell) / (tg + 1).  -> (ell, avg', bound of avg')."""
+    m, a = _cl_ld(M)
+    u, us, avg0, tg = _ld(u), _ld(us), _ld(avg0), _ld(tg)
+    w, wabs = u - us, np.abs(u) + np.abs(us)
+    zM = z @ m["Maug"]
+    ell = ((z @ m["Qaug"].T) * z).sum(axis=1) + ((w @ m["Raug"].T) * w).sum(axis=1) + 2.0 * (zM * w).sum(axis=1)
+    mag = ((zabs @ a["Qaug"].T) * zabs).sum(axis=1) + ((wabs @ a["Raug"].T) * wabs).sum(axis=1) + 2.0 * ((zabs @ a["Maug"]) * wabs).sum(axis=1)
+    n = 2 * (M["nx"] + M["nu"]) + M["nu"] + 8 + 4
+    return ell, (avg0 * tg + ell) / (tg + 1.0), 2.0 * cl_gamma(n) * (np.abs(avg0) * tg + mag) / (tg + 1.0)
+
+
+def cl_ref_plant(M, x, u, p):
+    """x' = A x + B u + Bp p.  -> (x', bound)."""
+    m, a = _cl_ld(M)
+    x, u, p = _ld(x), _ld(u), _ld(p)
+    x1 = x @ m["A"].T + u @ m["B"].T + p @ m["Bp"].T
+    return x1, 2.0 * cl_gamma(M["nx"] + M["nu"] + M["nd"] + 2) * (np.abs(x) @ a["A"].T + np.abs(u) @ a["B"].T + np.abs(p) @ a["Bp"].T)
+
+
+def cl_ref_measure(M, x1, v1, sigma):
+    """y = C x + sigma o v.  -> (y, bound)."""
+    m, a = _cl_ld(M)
+    x1, v1, sigma = _ld(x1), _ld(v1), _ld(sigma)
+    return x1 @ m["C"].T + sigma * v1, 2.0 * cl_gamma(M["nx"] + 2) * (np.abs(x1) @ a["C"].T + sigma * np.abs(v1))
+
+
+def cl_ref_targets(M, q, e):
+    """The certified target optimum of every row (ts_reference: the enumeration of all bound states, nu <= 7).
+    -> (us (R, nu) float64, kept (R,) bool under ts_kept, cond (R,), number of inputs on a bound (R,))."""
+    q = np.asarray(q, np.float64)
+    e = np.asarray(e, np.float64).reshape(q.shape[0], M["nz"])
+    refs = ts_reference(M["Pr"], M["E"], M["ulb"], M["uub"], q, e)
+    return (np.array([r["us"] for r in refs]), np.array([ts_kept(r, q[i]) for i, r in enumerate(refs)]),
+            np.array([r["cond"] for r in refs]), np.array([int((r["state"] != 0).sum()) for r in refs]))
+
+
+def cl_ref_mpc(spec, z, us, ulb, uub):
+    """First move of v* = argmin 1/2 v'P v + (tq z)'v, ulb - us <= v <= uub - us (every stage), by oracle.qp.solve_exact_box.
+    -> (v*[:nu] (R, nu), max |v*| (R,))."""
+    nu, N = spec["nu"], spec["N"]
+    z, us = np.asarray(z, np.float64), np.asarray(us, np.float64)
+    first, vmax = np.empty((z.shape[0], nu)), np.empty(z.shape[0])
+    for r in range(z.shape[0]):
+        v = oqp.solve_exact_box(spec["P"], spec["tq"] @ z[r], np.tile(ulb - us[r], N), np.tile(uub - us[r], N))
+        first[r], vmax[r] = v[:nu], np.abs(v).max()
+    return first, vmax
+
+
+def cl_mpc_tol(cond=CL_STEP_MPC_COND):
+    """The bar of tests/test_random_shapes_gpu.py for status-0 rows."""
+    return 1e-7 * max(1.0, cond / 1e3)
+
+
+def cl_step_reference(b, rec, tg0=0, uprev_in=None, want=None):
+    """Every identity of one step, for every instance and step of a run, each from the RECORDED inputs of that step (errors do
+    not compound).  ``b``: a cl_step_batch (its SP / DS / V are this call's tables), ``rec``: the records of the run (T + 1 rows
+    of y, x, xhat, avg; T rows of u, xs, us), ``tg0``: steps since create / reset before this call, ``uprev_in``: (nb, nu) the
+    previous input of every instance at the start of the call (default: the model's uprev0).
+    Returns {identity: dict(got, ref, bound, mask)} with (T, nb, .) arrays; fp64 identities carry the derived ``bound``, "us" the
+    TS_ERR_FACTOR bar (mask: ts_kept), "u_mpc" the bar of test_random_shapes_gpu.py, "u_us" must be equal bit for bit (bound 0); the NN
+    moves are judged by cl_one_step_reference (not here)."""
+    M = b["M"]
+    nx, nu, ny, nd, nz = (M[k] for k in ("nx", "nu", "ny", "nd", "nz"))
+    T, nb = rec["u"].shape[0], rec["u"].shape[1]
+    fl = lambda a: np.ascontiguousarray(a).reshape(T * nb, a.shape[2] if a.ndim == 3 else 1)
+    up = np.concatenate(((np.tile(M["uprev0"], (nb, 1)) if uprev_in is None else uprev_in)[None], rec["u"][:-1]), axis=0)
+    ysp = np.swapaxes(b["SP"][b["scen"]], 0, 1)
+    p = np.swapaxes(b["DS"][b["scen"]], 0, 1)
+    tg = np.repeat(tg0 + np.arange(T), nb).astype(np.float64)
+    out = {}
+    put = lambda name, got, ref, bound, mask=None: out.__setitem__(name, dict(
+        got=np.asarray(got).reshape(T, nb, -1), ref=np.asarray(ref).reshape(T, nb, -1), bound=np.asarray(bound).reshape(T, nb, -1),
+        mask=np.ones((T, nb), bool) if mask is None else np.asarray(mask).reshape(T, nb)))
+    xh1, bnd = cl_ref_filter(M, fl(rec["xhat"][:-1]), fl(up), fl(rec["y"][:-1]))
+    put("xhat", rec["xhat"][1:], xh1, bnd)
+    bb, babs, q, e = cl_ref_reduce(M, fl(rec["xhat"][1:]), fl(ysp))
+    us, kept, cond, nact = cl_ref_targets(M, q, e)
+    put("us", rec["us"], us, (TS_ERR_FACTOR * TS_EPS * cond * np.maximum(1.0, np.abs(us).max(axis=1)))[:, None] * np.ones((1, nu)), kept)
+    out["us"]["on_bound"] = nact.reshape(T, nb)
+    xs, bnd = cl_ref_expand(M, bb, babs, fl(rec["us"]))
+    put("xs", rec["xs"], xs, bnd)
+    z, zabs = cl_ref_z(fl(rec["xhat"][1:]), fl(rec["xs"]), fl(up), fl(rec["us"]), nx)
+    for s, spec in enumerate(b["slots"]):
+        rows = np.flatnonzero(np.tile(b["inst_slot"] == s, T))
+        m = np.tile(b["inst_slot"] == s, T).reshape(T, nb)
+        if spec["kind"] == "us":
+            put("u_us", rec["u"], rec["us"], np.zeros((T * nb, nu)), m)
+        elif spec["kind"] == "satdlqr":
+            u, bnd = cl_ref_satdlqr(M, spec["Kaug"], z, zabs, fl(rec["us"]))
+            put("u_satdlqr", rec["u"], u, bnd, m)
+        elif spec["kind"] == "mpc" and (want is None or "u_mpc" in want):
+            first = np.zeros((T * nb, nu))
+            vmax = np.ones(T * nb)
+            first[rows], vmax[rows] = cl_ref_mpc(spec, z[rows], fl(rec["us"])[rows], M["ulb"], M["uub"])
+            put("u_mpc", rec["u"], first + fl(rec["us"]), (cl_mpc_tol() * np.maximum(1.0, vmax))[:, None] * np.ones((1, nu)), m)
+            out["u_mpc"]["first"] = first.reshape(T, nb, nu)
+    ell, avg1, bnd = cl_ref_cost(M, z, zabs, fl(rec["u"]), fl(rec["us"]), fl(rec["avg"][:-1])[:, 0], tg)
+    put("avg", rec["avg"][1:], avg1, bnd)
+    x1, bnd = cl_ref_plant(M, fl(rec["x"][:-1]), fl(rec["u"]), fl(p))
+    put("x", rec["x"][1:], x1, bnd)
+    y1, bnd = cl_ref_measure(M, fl(rec["x"][1:]), fl(b["V"][1:]), b["sigma"])
+    put("y", rec["y"][1:], y1, bnd)
+    return out
+
+
+def cl_identity_ratios(idn):
+    """Largest |got - ref| / bound of every identity over its masked rows (0 / 0 = 0; anything over a zero bound = inf)."""
+    out = {}
+    for name, d in idn.items():
+        err = np.abs(_ld(d["got"]) - _ld(d["ref"]))[d["mask"]]
+        bnd = _ld(d["bound"])[d["mask"]]
+        if err.size == 0:
+            out[name] = 0.0
+            continue
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(err == 0, 0.0, err / bnd)
+        out[name] = float(np.nanmax(np.where(np.isnan(r), np.inf, r)))
+    return out
+
+
+def cl_step_simulate(b, T=None):
+    """The reference ALONE, state carried in float64 from step to step (us from the certified target oracle, NN moves from
+    oracle.nn, MPC moves from oracle.qp): the records a faultless device run would give, up to rounding.  What
+    tests/test_cpu_cl_step_inputs.py judges the inputs of the GPU tests with.  Also returns ``kept`` / ``on_bound`` (T, nb)."""
+    from oracle import nn as onn
+    M = b["M"]
+    nx, nu = M["nx"], M["nu"]
+    T = b["T"] if T is None else T
+    nb = b["inst_slot"].size
+    f8 = lambda a: np.asarray(a, np.float64)
+    x, xhat, up = np.tile(M["x0"], (nb, 1)), np.tile(M["xhat0"], (nb, 1)), np.tile(M["uprev0"], (nb, 1))
+    y = f8(cl_ref_measure(M, x, b["V"][0], b["sigma"])[0])
+    avg = np.zeros(nb)
+    rec = dict(y=[y], x=[x], xhat=[xhat], avg=[avg], u=[], xs=[], us=[], kept=[], on_bound=[])
+    for t in range(T):
+        xhat = f8(cl_ref_filter(M, xhat, up, y)[0])
+        bb, babs, q, e = cl_ref_reduce(M, xhat, b["SP"][b["scen"], t])
+        us, kept, _, nact = cl_ref_targets(M, q, e)
+        xs = f8(cl_ref_expand(M, bb, babs, us)[0])
+        z, zabs = cl_ref_z(xhat, xs, up, us, nx)
+        u = np.empty((nb, nu))
+        for s, spec in enumerate(b["slots"]):
+            r = np.flatnonzero(b["inst_slot"] == s)
+            if spec["kind"] == "us":
+                u[r] = us[r]
+            elif spec["kind"] == "satdlqr":
+                u[r] = f8(cl_ref_satdlqr(M, spec["Kaug"], z[r], zabs[r], us[r])[0])
+            elif spec["kind"] == "nn":
+                u[r] = onn.control_input(spec["weights"], xhat[r, :nx], up[r], xs[r], us[r], spec["xscale"], M["ulb"], M["uub"], spec["with_uprev"])
+            else:
+                u[r] = cl_ref_mpc(spec, f8(z[r]), us[r], M["ulb"], M["uub"])[0] + us[r]
+        avg = f8(cl_ref_cost(M, z, zabs, u, us, avg, np.full(nb, float(t)))[1])
+        x = f8(cl_ref_plant(M, x, u, b["DS"][b["scen"], t])[0])
+        y = f8(cl_ref_measure(M, x, b["V"][t + 1], b["sigma"])[0])
+        up = u
+        for k, v in (("y", y), ("x", x), ("xhat", xhat), ("avg", avg), ("u", u), ("xs", xs), ("us", us), ("kept", kept), ("on_bound", nact)):
+            rec[k].append(v)
+    return {k: np.array(v) for k, v in rec.items()}
+
+
+# ---- chains (chain_pre_k / chain_post_k) and nnmpc_qp_first_moves -----------------------------------------------------------------
+CHAIN_STEP_SHAPES = [(1, 1, 0), (3, 2, 1), (255, 2, 3), (257, 3, 0), (300, 5, 3), (520, 2, 2)]     # (nx, nu, nd); the last: nx + nu + nd > 512
+CHAIN_STEP_T = 8
+FIRST_MOVES_CASES = [(1, 1, 1, True), (7, 3, 11, False), (7, 3, 11, True), (70000, 16, 20, True)]  # (B, nu, ldu, us given); the last: 1 120 000 elements
+
+
+def chain_step_case(nx, nu, nd, nc, seed=None, T=CHAIN_STEP_T):
+    """A, B, Bd as in cl_step_model, the regulator's P / tq as in cl_step_batch's MPC slot, asymmetric bounds, and the target
+    pairs / disturbances of T steps of nc chains (xs small beside x, us well inside the box)."""
+    seed = 9500 + nx if seed is None else seed
+    rng = np.random.default_rng(seed)
+    g = lambda r, c: rng.standard_normal((r, c)) / np.sqrt(max(c, 1))
+    W = rng.standard_normal((nx, nx))
+    A = 0.9 * W / np.abs(np.linalg.eigvals(W)).max()
+    B, Bd = g(nx, nu), g(nx, nd)
+    ulb, uub = -rng.uniform(0.2, 1.5, nu), rng.uniform(0.2, 1.5, nu)
+    n = CL_STEP_N * nu
+    spec = dict(P=spd_logspectrum(n, seed + 5, CL_STEP_MPC_COND), nu=nu, N=CL_STEP_N, tq=rng.standard_normal((n, nx + nu)) / np.sqrt(nx + nu))
+    return dict(nx=nx, nu=nu, nd=nd, nc=nc, A=A, B=B, Bd=Bd, ulb=ulb, uub=uub, spec=spec, x0=0.5 * rng.standard_normal(nx),
+                uprev0=0.5 * (ulb + rng.uniform(0, 1, nu) * (uub - ulb)), Xs=0.3 * rng.standard_normal((T, nc, nx)),
+                Us=0.5 * (ulb + rng.uniform(0, 1, (T, nc, nu)) * (uub - ulb)), D=0.5 * rng.uniform(-1, 1, (T, nc, nd)), T=T)
+
+
+def chain_step_reference(c, rec, Xs, Us, D):
+    """The chain identities from the recorded x, uprev, u of a call: u[t] = v*[:nu] + us[t] with z = [x[t] - xs[t]; uprev[t] - us[t]]
+    (bar of test_random_shapes_gpu.py), x[t + 1] = A x[t] + B u[t] + Bd d[t] (derived bound, rows t < T - 1), uprev[t + 1] = u[t]
+    (bit for bit).  -> {identity: dict(got, ref, bound, mask)}."""
+    nx, nu, nd, nc = c["nx"], c["nu"], c["nd"], c["nc"]
+    T = rec["u"].shape[0]
+    fl = lambda a: np.ascontiguousarray(a).reshape(-1, a.shape[-1])
+    z = np.concatenate((fl(rec["x"]) - fl(Xs), fl(rec["uprev"]) - fl(Us)), axis=1)
+    first, vmax = cl_ref_mpc(c["spec"], z, fl(Us), c["ulb"], c["uub"])
+    one = np.ones((T, nc), bool)
+    out = dict(u=dict(got=rec["u"], ref=(first + fl(Us)).reshape(T, nc, nu), first=first.reshape(T, nc, nu), mask=one,
+                      bound=((cl_mpc_tol() * np.maximum(1.0, vmax))[:, None] * np.ones((1, nu))).reshape(T, nc, nu)))
+    A, B, Bd = _ld(c["A"]), _ld(c["B"]), _ld(c["Bd"])
+    x, u, d = _ld(fl(rec["x"][:-1])), _ld(fl(rec["u"][:-1])), _ld(np.asarray(D[:T - 1]).reshape((T - 1) * nc, nd))
+    x1 = x @ A.T + u @ B.T + d @ Bd.T
+    bnd = 2.0 * cl_gamma(nx + nu + nd + 2) * (np.abs(x) @ np.abs(A).T + np.abs(u) @ np.abs(B).T + np.abs(d) @ np.abs(Bd).T)
+    out["x"] = dict(got=rec["x"][1:], ref=x1.reshape(T - 1, nc, nx), bound=bnd.reshape(T - 1, nc, nx), mask=one[1:])
+    out["uprev"] = dict(got=rec["uprev"][1:], ref=rec["u"][:-1], bound=np.zeros((T - 1, nc, nu)), mask=one[1:])
+    return out
