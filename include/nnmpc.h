@@ -19,6 +19,9 @@
  *                             (lib/LinearMPCLayers.py:40-61, :91-112) ==
  *                             NeuralNetworkController._get_control_input
  *                             (lib/controller_evaluation.py:863-892).
+ *   nnmpc_nn_create_ex     <- the same, or UnstdRegulatorLayer (lib/LinearMPCLayers.py:135-159) /
+ *                             NeuralNetworkControllerUnstd (lib/controller_evaluation.py:895-916)
+ *                             by its `form`; nnmpc_nn_forward serves every form.
  *
  * Conventions: plain pointers and sizes only; all matrices row-major; the
  * caller owns every buffer it passes; a handle owns its device copies and
@@ -234,6 +237,18 @@ int nnmpc_nn_create(nnmpc_nn** out, int32_t nlayers, const int32_t* dims,
                     const double* const* W, const double* const* b, int32_t nx, int32_t nu,
                     int32_t with_uprev, const double* xscale, const double* ulb,
                     const double* uub, int32_t use_bf16, int32_t max_batch);
+/* The same with the controller's form.  NNMPC_NN_STRUCTURED: nnmpc_nn_create.  NNMPC_NN_UNSTD: the unstructured controller
+ * u = clip(MLP([x / xscale, (uprev), xs / xscale, us])) -- ONE pass, no us +, hidden layers relu(W'z + b), linear head WITH a
+ * bias: b[nlayers - 1] (nu entries) is required (NeuralNetworkControllerUnstd, lib/controller_evaluation.py:895-916).
+ * NNMPC_NN_UNSTD_RELU: the same with relu on the head as well, which is what the Keras UnstdRegulatorLayer computes
+ * (lib/LinearMPCLayers.py:147-148).  dims as above (dims[0] = 2 nx + (2 | 1) nu, dims[L] = nu); any other form: NNMPC_EINVAL. */
+#define NNMPC_NN_STRUCTURED 0
+#define NNMPC_NN_UNSTD 1
+#define NNMPC_NN_UNSTD_RELU 2
+int nnmpc_nn_create_ex(nnmpc_nn** out, int32_t nlayers, const int32_t* dims,
+                       const double* const* W, const double* const* b, int32_t nx, int32_t nu,
+                       int32_t with_uprev, const double* xscale, const double* ulb,
+                       const double* uub, int32_t use_bf16, int32_t max_batch, int32_t form);
 int nnmpc_nn_destroy(nnmpc_nn* h);
 /* x, xs: B x nx; uprev (ignored when !with_uprev), us: B x nu; u: B x nu.
  * Non-finite inputs are not rejected and not laundered: a NaN (or an Inf that meets an opposite Inf) in a row of x, uprev, xs
@@ -416,7 +431,8 @@ int nnmpc_ts_solve_batch(nnmpc_ts* h, int32_t B, const double* q, const double* 
  *            xs = Xb b + Xu us                                                                                 (:298-311)
  *   control  MPC: first move of the regulator QP at [x^ - xs; uprev - us], bounds ulb - us / uub - us, + us (:682-689), warm-
  *            started on the instance's previous active set shifted by one stage;  NN: clip(us + NN(x^, uprev, xs, us) -
- *            NN(xs, us, xs, us)) (:863-892);  SATDLQR: clip(Kaug [x^ - xs; uprev - us] + us) (:1003-1005);  US: us (:1076)
+ *            NN(xs, us, xs, us)) (:863-892);  SATDLQR: clip(Kaug [x^ - xs; uprev - us] + us) (:1003-1005);  US: us (:1076);
+ *            NN_UNSTD: clip(NN(x^, uprev, xs, us)), one pass, head with a bias (:895-916)
  *   cost     z = [x^ - xs; uprev - us], w = u - us, ell = z'Qaug z + w'Raug w + z'Maug w + w'Maug'z,
  *            avg_{t+1} = (avg_t t + ell) / (t + 1), t counted from create / reset (not from this call: a chunked run
  *            continues the mean of the chunks before it)                                                       (:691-701)
@@ -427,6 +443,7 @@ typedef struct nnmpc_cl nnmpc_cl;
 #define NNMPC_CL_NN 1
 #define NNMPC_CL_SATDLQR 2
 #define NNMPC_CL_US 3
+#define NNMPC_CL_NN_UNSTD 4     /* clip(NN(x^, uprev, xs, us)): one pass, head with a bias (lib/controller_evaluation.py:895-916) */
 /* Shared model data (fp64, row-major, host), na = nx + nd, nb_ = nx + nz:
  *   plant   A nx x nx, B nx x nu, C ny x nx, Bp nx x nd
  *   filter  Aaug na x na, Baug na x nu, Caug ny x na, L na x ny (steady-state gain, dlqe)
@@ -445,7 +462,7 @@ typedef struct {
 } nnmpc_cl_model;
 /* One controller of the evaluation.  MPC: qp = the borrowed regulator handle (n_aug = nx + nu; any horizon).  NN: dims / W / b
  * as nnmpc_nn_create (copied to HBM in f32; hidden widths <= 2048), with_uprev, xscale (nx, NULL = ones).  SATDLQR: Kaug
- * (nu x (nx + nu)).  US: nothing. */
+ * (nu x (nx + nu)).  US: nothing.  NN_UNSTD: the fields of NN; b has nlayers entries, all required (the head's bias too). */
 typedef struct {
   int32_t kind;
   nnmpc_qp* qp;

@@ -35,7 +35,8 @@ class QpStats(C.Structure):
                 ("asm_predict_flops", C.c_double), ("asm_overlapped_passes", C.c_int64)]
 
 
-CL_MPC, CL_NN, CL_SATDLQR, CL_US = 0, 1, 2, 3
+CL_MPC, CL_NN, CL_SATDLQR, CL_US, CL_NN_UNSTD = 0, 1, 2, 3, 4
+NN_STRUCTURED, NN_UNSTD, NN_UNSTD_RELU = 0, 1, 2
 CL_PLANT_LINEAR, CL_PLANT_CSTRS_FLASH, CSTRS_NPAR = 0, 1, 51
 
 
@@ -54,7 +55,7 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_qp_solve_batch_warm", "nnmpc_qp_solve_batch_ex", "nnmpc_qp_set_inverse", "nnmpc_qp_dims",
            "nnmpc_qp_first_moves", "nnmpc_qp_set_farfield", "nnmpc_qp_farfield_missing",
            "nnmpc_qp_set_profiling", "nnmpc_qp_get_stats", "nnmpc_qp_debug_factor_solve", "nnmpc_qp_debug_factor_fail",
-           "nnmpc_nn_create", "nnmpc_nn_destroy", "nnmpc_nn_forward", "nnmpc_nn_last_ms", "nnmpc_nn_last_hidden_ms",
+           "nnmpc_nn_create", "nnmpc_nn_create_ex", "nnmpc_nn_destroy", "nnmpc_nn_forward", "nnmpc_nn_last_ms", "nnmpc_nn_last_hidden_ms",
            "nnmpc_train_create", "nnmpc_train_destroy", "nnmpc_train_set_data", "nnmpc_train_grad", "nnmpc_train_step",
            "nnmpc_train_epoch", "nnmpc_train_eval", "nnmpc_train_get_weights", "nnmpc_train_set_weights",
            "nnmpc_train_snapshot", "nnmpc_train_restore", "nnmpc_train_last_ms", "nnmpc_train_dw_slices",
@@ -118,6 +119,8 @@ def load():
     lib.nnmpc_nn_create.restype = i32
     lib.nnmpc_nn_create.argtypes = [C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(dp), C.POINTER(dp),
                                     i32, i32, i32, dp, dp, dp, i32, i32]
+    lib.nnmpc_nn_create_ex.restype = i32
+    lib.nnmpc_nn_create_ex.argtypes = lib.nnmpc_nn_create.argtypes + [i32]
     lib.nnmpc_nn_destroy.restype = i32
     lib.nnmpc_nn_destroy.argtypes = [vp]
     lib.nnmpc_nn_forward.restype = i32

@@ -33,11 +33,12 @@ class DeviceClosedLoop:
     model: dict with nx, nu, ny, nd, nz and the matrices of nnmpc_cl_model (A, B, C, Bp, Aaug, Baug, Caug, L, tb, Qb, Qy,
     q0, Cd, Eb, Xb, Xu, Qaug, Raug, Maug, ulb, uub, x0, xhat0, uprev0); target: the ``target.BatchedTargetSelector`` whose
     handle solves the reduced target problems; slots: dicts with ``kind`` ("mpc" + ``qp`` (qp.BatchedBoxQP), "nn" + ``weights``,
-    ``with_uprev``, ``xscale``, "satdlqr" + ``Kaug``, "us"); inst_slot: slot of every instance, non-decreasing.  The QP and
+    ``with_uprev``, ``xscale``, "nn_unstd" + the same with the even-length list [W1, b1, ..., WL, bL], "satdlqr" + ``Kaug``,
+    "us"); inst_slot: slot of every instance, non-decreasing.  The QP and
     target handles are borrowed: they must outlive this object.
     """
 
-    KINDS = {"mpc": _lib.CL_MPC, "nn": _lib.CL_NN, "satdlqr": _lib.CL_SATDLQR, "us": _lib.CL_US}
+    KINDS = {"mpc": _lib.CL_MPC, "nn": _lib.CL_NN, "satdlqr": _lib.CL_SATDLQR, "us": _lib.CL_US, "nn_unstd": _lib.CL_NN_UNSTD}
 
     def __init__(self, model, target, slots, inst_slot):
         lib = _lib.load()
@@ -63,14 +64,18 @@ class DeviceClosedLoop:
                 cs[j].qp = s["qp"]._h.value
             elif s["kind"] == "satdlqr":
                 cs[j].Kaug = arr(s["Kaug"])
-            elif s["kind"] == "nn":
+            elif s["kind"] in ("nn", "nn_unstd"):
                 w = s["weights"]
-                Ws = [_f(a) for a in w[0:-1:2]] + [_f(w[-1])]
-                bs = [_f(a).ravel() for a in w[1::2]]
+                if s["kind"] == "nn_unstd":                      # every layer has a bias; a missing one reaches the library as NULL
+                    Ws = [_f(a) for a in w[0::2]]
+                    bs = [None if a is None else _f(a).ravel() for a in w[1::2]]
+                else:
+                    Ws = [_f(a) for a in w[0:-1:2]] + [_f(w[-1])]
+                    bs = [_f(a).ravel() for a in w[1::2]] + [None]
                 L = len(Ws)
                 dims = (C.c_int32 * (L + 1))(*([Ws[0].shape[0]] + [a.shape[1] for a in Ws]))
                 Wp = (C.c_void_p * L)(*[a.ctypes.data for a in Ws])
-                bp = (C.c_void_p * L)(*([a.ctypes.data for a in bs] + [None]))
+                bp = (C.c_void_p * L)(*[None if a is None else a.ctypes.data for a in bs])
                 keep += [Ws, bs, dims, Wp, bp]
                 cs[j].nlayers, cs[j].dims = L, C.addressof(dims)
                 cs[j].W, cs[j].b = C.addressof(Wp), C.addressof(bp)
@@ -149,8 +154,11 @@ class DeviceClosedLoop:
 
 
 def _kind(ctl):
-    from .controller_evaluation import NeuralNetworkController, SatDlqrController, SteadyStateController
+    from .controller_evaluation import (NeuralNetworkController, NeuralNetworkControllerUnstd, SatDlqrController,
+                                        SteadyStateController)
     from .linearMPC import LinearMPCController
+    if isinstance(ctl, NeuralNetworkControllerUnstd):            # before its base class
+        return "nn_unstd"
     if isinstance(ctl, NeuralNetworkController):
         return "nn"
     if isinstance(ctl, SatDlqrController):
@@ -198,6 +206,9 @@ def _validate(plant, controllers, scenarios, Nsim, seeds, instances, record):
                 raise ValueError(f"simulate_closed_loop_batch: controller {j} differs from controller 0 in {k}; all controllers "
                                  "of one evaluation share the filter, target, cost and plant data")
     Nu, Ny, Nd = ref.B.shape[1], ref.C.shape[0], ref.Bd.shape[1]
+    for j, (c, k) in enumerate(zip(controllers, kinds)):
+        if k == "nn_unstd":
+            _check_unstd_weights(j, c, ref.B.shape[0], Nu)
     if _plant_dims(plant) != (Nu, Ny, Nd):
         raise ValueError("simulate_closed_loop_batch: plant and controllers disagree on Nu / Ny / Nd (the plant's Np must "
                          "equal the filter's Nd)")
@@ -227,6 +238,21 @@ def _validate(plant, controllers, scenarios, Nsim, seeds, instances, record):
     return kinds, instances
 
 
+def _check_unstd_weights(j, ctl, Nx, Nu):
+    """The unstructured controller's list [W1, b1, ..., WL, bL]: even length, kernels that chain from the input width
+    2 Nx + (2 | 1) Nu to Nu, a bias of its kernel's width on every layer."""
+    from .nn import split_unstd_weights
+    who = f"simulate_closed_loop_batch: controller {j} (unstructured NN)"
+    try:
+        Ws, _ = split_unstd_weights(ctl.regulator_weights)
+    except ValueError as e:
+        raise ValueError(f"{who}: {e}") from None
+    din = 2 * Nx + (2 if ctl.nnwithuprev else 1) * Nu
+    if Ws[0].shape[0] != din or Ws[-1].shape[1] != Nu:
+        raise ValueError(f"{who}: the network maps {Ws[0].shape[0]} inputs to {Ws[-1].shape[1]} outputs, "
+                         f"the plant needs {din} -> {Nu}")
+
+
 def _model(plant, ctl):
     from .target import ReducedTargetProblem
     red = ReducedTargetProblem(ctl.A, ctl.B, ctl.C, ctl.H, ctl.Bd, ctl.Cd, ctl.Qs, ctl.Rs, ctl.usp)
@@ -248,7 +274,7 @@ def simulate_closed_loop_batch(plant, controllers, *, scenarios, Nsim, seeds, in
     ``nonlinearMPC.NonlinearPlantSimulator`` of the CSTRs-with-flash model (``cstrs_parameters._get_cstrs_plant(linear=False)``:
     the ODE is integrated on the device with the host simulator's RK4 scheme, y = C x + noise with C = hx.C; any other
     nonlinear model raises ``TypeError``); controllers:
-    ``LinearMPCController`` (any horizon), ``NeuralNetworkController``, ``SatDlqrController``, ``SteadyStateController`` in
+    ``LinearMPCController`` (any horizon), ``NeuralNetworkController``, ``NeuralNetworkControllerUnstd``, ``SatDlqrController``, ``SteadyStateController`` in
     their initial state, sharing the filter, target, cost and plant data (``ValueError`` otherwise, before any device work);
     scenarios: (setpoints (>= Nsim, Ny), disturbances (>= Nsim, Nd)) pairs; seeds: noise seeds.  ``instances`` defaults to
     controllers x scenarios x seeds as (controller, scenario, seed) triples.  ``chunk``: steps per device call (the state
@@ -282,8 +308,8 @@ def simulate_closed_loop_batch(plant, controllers, *, scenarios, Nsim, seeds, in
         ctl, k = controllers[c], kinds[c]
         if k == "mpc":
             slots.append(dict(kind="mpc", qp=ctl.regulator._solver()))
-        elif k == "nn":
-            slots.append(dict(kind="nn", weights=ctl.regulator_weights, with_uprev=ctl.nnwithuprev, xscale=np.ravel(ctl.xscale)))
+        elif k in ("nn", "nn_unstd"):
+            slots.append(dict(kind=k, weights=ctl.regulator_weights, with_uprev=ctl.nnwithuprev, xscale=np.ravel(ctl.xscale)))
         elif k == "satdlqr":
             slots.append(dict(kind="satdlqr", Kaug=ctl.Kaug))
         else:

@@ -1,5 +1,5 @@
 """Counterparts of the hot-path pieces of the reference's lib/controller_evaluation.py:
-the NN controller (forward on the GPU) and the PRBS sampler / training-data scaling
+the NN controllers, structured and unstructured (forward on the GPU), and the PRBS sampler / training-data scaling
 that sit either side of the offline data-generation path."""
 import itertools
 import time
@@ -8,7 +8,7 @@ import numpy as np
 
 from .linearMPC import LinearMPCController, _save_training_data
 from .linearMPC_build import dlqr
-from .nn import StructuredNN
+from .nn import StructuredNN, UnstructuredNN
 
 
 def _sample_repeats(num_change, num_simulation_steps, mean_change, sigma_change):
@@ -136,6 +136,15 @@ class NeuralNetworkController(LinearMPCController):
         return self._net.forward(X, Uprev if self.nnwithuprev else None, Xs, Us)
 
 
+class NeuralNetworkControllerUnstd(NeuralNetworkController):
+    """The unstructured comparison controller (reference :895-916): u = clip(NN(x/xscale, (uprev), xs/xscale, us)), one pass,
+    linear head with a bias; ``regulator_weights`` is the even-length Keras list [W1, b1, ..., WL, bL]."""
+
+    def _make_net(self):
+        return UnstructuredNN(self.regulator_weights, self.Nx, self.Nu, nnwithuprev=self.nnwithuprev,
+                              ulb=self.ulb, uub=self.uub, max_batch=1024, head_relu=False)
+
+
 class _BaselineController(LinearMPCController):
     """Filter + target selector + stage cost of LinearMPCController without a regulator: the common part of the reference's
     SatDlqrController and SteadyStateController (lib/controller_evaluation.py:918-1087)."""
@@ -206,6 +215,12 @@ def _get_nn_controller(optimal_controller, regulator_weights, xscale, nnwithupre
     """(reference :656-682)"""
     return NeuralNetworkController(regulator_weights=regulator_weights, xscale=xscale, nnwithuprev=nnwithuprev,
                                    **_shared(optimal_controller))
+
+
+def _get_nn_controller_unstd(optimal_controller, regulator_weights, xscale, nnwithuprev):
+    """(reference :684-710)"""
+    return NeuralNetworkControllerUnstd(regulator_weights=regulator_weights, xscale=xscale, nnwithuprev=nnwithuprev,
+                                        **_shared(optimal_controller))
 
 
 def _get_satdlqr_controller(optimal_controller):
@@ -283,3 +298,28 @@ def simulate_neural_networks(*, plant, mpc_controller, online_test_scenarios, tr
     return dict(plants=res["plants"], controllers=res["controllers"], performance_loss=performance_loss,
                 average_comp_time=average_comp_time, worst_case_comp_time=worst_case_comp_time,
                 average_speedups=sp[..., 0], worst_case_speedups=sp[..., 1])
+
+
+def simulate_neural_network_unstd(*, plant, mpc_controller, online_test_scenarios, regulator_weights, xscale, Nsim,
+                                  nnwithuprev=True, seed=0, **kw):
+    """_simulate_neural_network_unstd (reference :525-625): the ONE trained unstructured network on every scenario, with the
+    MPC's instances in the same device run (the reference reads the MPC's costs from an earlier run's pickle).  Returns
+    performance_loss = 100 (ell_nn - ell_mpc) / ell_mpc, average_comp_time, worst_case_comp_time, average_speedups,
+    worst_case_speedups, each (1, num_scenarios) like the reference's arrays, and plants, controllers (the network's).
+    Computation times are per-step device times of the whole lock-step batch; noise in the reference script's order
+    (simulate_closed_loop_batch, plant_y0=True)."""
+    from .closed_loop import simulate_closed_loop_batch
+    kw.setdefault("plant_y0", True)
+    ns = len(online_test_scenarios)
+    nn = NeuralNetworkControllerUnstd(regulator_weights=regulator_weights, xscale=xscale, nnwithuprev=nnwithuprev,
+                                      build_forward=False, **_shared(mpc_controller))
+    res = simulate_closed_loop_batch(plant, [nn, mpc_controller], scenarios=online_test_scenarios, Nsim=Nsim, seeds=[seed],
+                                     return_objects=True, **kw)
+    ell = res["avg"][:, -1].reshape(2, ns)
+    ct = res["computation_times"].reshape(2, ns, -1)
+    performance_loss = 100 * (ell[:1] - ell[1:]) / ell[1:]
+    sp = np.array([_speedups(ct[1, s], ct[0, s]) for s in range(ns)])
+    return dict(plants=res["plants"][:ns], controllers=res["controllers"][:ns], performance_loss=performance_loss,
+                average_comp_time=ct[0].mean(axis=1)[None, :], worst_case_comp_time=ct[0].max(axis=1)[None, :],
+                average_speedups=sp[None, :, 0], worst_case_speedups=sp[None, :, 1],
+                mpc_plants=res["plants"][ns:], mpc_controllers=res["controllers"][ns:])

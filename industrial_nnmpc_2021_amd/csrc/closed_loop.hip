@@ -2,10 +2,10 @@
 // noise seed) instance of an evaluation at once -- see include/nnmpc.h (nnmpc_cl_*).  Per step:
 //   cl_filter_k    filter update and the target problem's reduction (one workgroup per instance)
 //   ts_solve_k     the reduced target QPs of all instances (nnmpc_ts_launch_internal, one wave per instance)
-//   cl_expand_k    xs, the regulator's inputs (MPC), Kaug z + us (SATDLQR), us (US), the two NN input rows (NN)
-//   cl_nn_layer_k  grouped structured-NN forward: ONE launch per layer index for all networks (workgroup = network x 64 columns)
+//   cl_expand_k    xs, the regulator's inputs (MPC), Kaug z + us (SATDLQR), us (US), the two NN input rows (NN) or the one (NN_UNSTD)
+//   cl_nn_layer_k  grouped NN forward: ONE launch per layer index for all networks, structured and unstructured (workgroup = network x 64 columns)
 //   nnmpc_qp_solve_batch_ex per MPC slot on the borrowed handle's stream (first moves, warm-started), beside the NN layers
-//   cl_post_k      u (NN combine + clip, SATDLQR clip, MPC first move + us), stage cost, running mean, plant step, records
+//   cl_post_k      u (NN combine + clip, NN_UNSTD clip, SATDLQR clip, MPC first move + us), stage cost, running mean, plant step, records
 // Shared matrices are read by all instances from L2; a thread owns one output element and walks a stored transpose so that
 // the lanes of a wave read consecutive doubles.
 #include <hip/hip_runtime.h>
@@ -40,7 +40,7 @@ struct SlotDev {                  // per slot, device copy
 
 struct NNLayer {                  // one layer of one network
   const float* W;                 // [K][N] (Keras kernel layout)
-  const float* bias;              // [N] or null (output layer)
+  const float* bias;              // [N] or null (output layer of a structured network)
   int K, N, row0, rows, last;
 };
 
@@ -184,6 +184,17 @@ __global__ __launch_bounds__(CL_THREADS) void cl_expand_k(ExpandArgs a, const in
     for (int k = tid; k < nu; k += CL_THREADS) ctl_u[(size_t)i * nu + k] = colsum(s.Kt, nx + nu, nu, zz, k) + su[k];
   } else if (s.kind == NNMPC_CL_US) {
     for (int k = tid; k < nu; k += CL_THREADS) ctl_u[(size_t)i * nu + k] = su[k];
+  } else if (s.kind == NNMPC_CL_NN_UNSTD) {              // the one row [x^, (uprev), xs^, us] of an unstructured network
+    const int wu = s.with_uprev, o2 = nx + (wu ? nu : 0);
+    float* d1 = act + (size_t)nn_row[i] * a.ldA;
+    for (int k = tid; k < nx; k += CL_THREADS) {
+      const double sc = s.xscale[k];
+      d1[k] = (float)(xhat[(size_t)i * a.na + k] / sc); d1[o2 + k] = (float)(xsv[k] / sc);
+    }
+    for (int k = tid; k < nu; k += CL_THREADS) {
+      d1[o2 + nx + k] = (float)su[k];
+      if (wu) d1[nx + k] = (float)uprev[(size_t)i * nu + k];
+    }
   } else {                                               // NN rows: pass 1 [x^, (uprev), xs^, us], pass 2 [xs^, (us), xs^, us]
     const int wu = s.with_uprev, o2 = nx + (wu ? nu : 0);
     float* d1 = act + (size_t)nn_row[i] * a.ldA;
@@ -205,7 +216,8 @@ __global__ __launch_bounds__(CL_THREADS) void cl_expand_k(ExpandArgs a, const in
 // ---- grouped structured-NN layer: one launch per layer index for ALL networks.  Workgroup = (network, 64 output columns);
 // the 4 waves take 4 contiguous K slices, every thread one column and NN_RB rows in registers, the activation rows in LDS.
 // A row's sum runs over k in a fixed order inside each slice and the slices are added in a fixed order: its value does not
-// depend on how many rows or networks share the launch.  Bias + ReLU fused; the output layer writes o (rows x nu) for cl_post_k.
+// depend on how many rows or networks share the launch.  Bias + ReLU fused; the output layer writes o (rows x nu) for cl_post_k:
+// v itself for a structured network (it has no head bias), v + bias for an unstructured one.
 __global__ __launch_bounds__(256) void cl_nn_layer_k(const NNLayer* __restrict__ desc, const int2* __restrict__ tiles,
                                                      const float* __restrict__ in, float* __restrict__ out, float* __restrict__ o,
                                                      int ldA, int nu) {
@@ -246,7 +258,7 @@ __global__ __launch_bounds__(256) void cl_nn_layer_k(const NNLayer* __restrict__
       for (int r = 0; r < nr; ++r) {
         float v = ((acc[r] + red[0][r][lane]) + red[1][r][lane]) + red[2][r][lane];
         const size_t row = (size_t)(d.row0 + r0 + r);
-        if (d.last) o[row * nu + col] = v;
+        if (d.last) o[row * nu + col] = d.bias ? v + bb : v;
         else out[row * ldA + col] = __builtin_elementwise_maximum(v + bb, 0.f);   // IEEE 754-2019 maximum: a NaN stays a NaN (fmaxf returns 0)
       }
     }
@@ -295,8 +307,9 @@ __global__ __launch_bounds__(CL_THREADS) void cl_post_k(PostArgs a, int t, int t
     else if (s.kind == NNMPC_CL_NN) {
       const int r1 = nn_row[i], r2 = r1 + s.count;
       u = sk + ((double)o[(size_t)r1 * nu + k] - (double)o[(size_t)r2 * nu + k]);
-    } else u = ctl_u[(size_t)i * nu + k];
-    if (s.kind == NNMPC_CL_NN || s.kind == NNMPC_CL_SATDLQR) {   // _clip_control_input
+    } else if (s.kind == NNMPC_CL_NN_UNSTD) u = (double)o[(size_t)nn_row[i] * nu + k];
+    else u = ctl_u[(size_t)i * nu + k];
+    if (s.kind == NNMPC_CL_NN || s.kind == NNMPC_CL_NN_UNSTD || s.kind == NNMPC_CL_SATDLQR) {   // _clip_control_input
       u = u > a.uub[k] ? a.uub[k] : u;
       u = u < a.ulb[k] ? a.ulb[k] : u;
     }
@@ -618,15 +631,16 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
         set_error("nnmpc_cl_create: slot %d (MPC) needs a regulator handle with nu=%d n_aug=%d", k, nu, nx + nu);
         return NNMPC_EINVAL;
       }
-    } else if (s.kind == NNMPC_CL_NN) {
+    } else if (s.kind == NNMPC_CL_NN || s.kind == NNMPC_CL_NN_UNSTD) {
+      const bool un = s.kind == NNMPC_CL_NN_UNSTD;
       const int din = 2 * nx + (s.with_uprev ? 2 : 1) * nu;
       if (s.nlayers < 1 || !s.dims || !s.W || !s.b || s.dims[0] != din || s.dims[s.nlayers] != nu) {
         set_error("nnmpc_cl_create: slot %d (NN) needs dims [%d, ..., %d] with weights and biases", k, din, nu);
         return NNMPC_EINVAL;
       }
       for (int l = 0; l < s.nlayers; ++l)
-        if (s.dims[l] <= 0 || s.dims[l] > NN_MAXK || s.dims[l + 1] <= 0 || !s.W[l] || (l < s.nlayers - 1 && !s.b[l])) {
-          set_error("nnmpc_cl_create: slot %d (NN) layer %d: widths 1..%d, weights and (hidden) biases required", k, l, NN_MAXK);
+        if (s.dims[l] <= 0 || s.dims[l] > NN_MAXK || s.dims[l + 1] <= 0 || !s.W[l] || ((un || l < s.nlayers - 1) && !s.b[l])) {
+          set_error("nnmpc_cl_create: slot %d (NN) layer %d: widths 1..%d, weights and (hidden; unstructured: all) biases required", k, l, NN_MAXK);
           return NNMPC_EINVAL;
         }
     } else if (s.kind == NNMPC_CL_SATDLQR) {
@@ -689,7 +703,9 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
       double* kt = nullptr;
       upT(&kt, s.Kaug, nu, nzz);
       d.Kt = kt;
-    } else if (s.kind == NNMPC_CL_NN) {
+    } else if (s.kind == NNMPC_CL_NN || s.kind == NNMPC_CL_NN_UNSTD) {
+      const bool un = s.kind == NNMPC_CL_NN_UNSTD;
+      const int rows = un ? d.count : 2 * d.count;       // unstructured: one pass, one row per instance
       d.with_uprev = s.with_uprev ? 1 : 0;
       d.row0 = h->nn_rows;
       std::vector<double> xsc(nx, 1.0);
@@ -703,17 +719,17 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
         std::vector<float> wf((size_t)K * N), bf(N, 0.f);
         for (size_t j = 0; j < wf.size(); ++j) wf[j] = (float)s.W[l][j];
         const bool last = l == s.nlayers - 1;
-        if (!last) for (int j = 0; j < N; ++j) bf[j] = (float)s.b[l][j];
+        if (!last || un) for (int j = 0; j < N; ++j) bf[j] = (float)s.b[l][j];
         float *wd = nullptr, *bd = nullptr;
         if (!rc) rc = cl_upload(h, &wd, wf.data(), wf.size());
-        if (!rc && !last) rc = cl_upload(h, &bd, bf.data(), bf.size());
-        layers[k].push_back(NNLayer{wd, bd, K, N, h->nn_rows, 2 * d.count, last ? 1 : 0});
+        if (!rc && (!last || un)) rc = cl_upload(h, &bd, bf.data(), bf.size());
+        layers[k].push_back(NNLayer{wd, bd, K, N, h->nn_rows, rows, last ? 1 : 0});
         h->maxK = std::max(h->maxK, K);
         if (!last) h->ldA = std::max(h->ldA, N);
       }
       h->ldA = std::max(h->ldA, s.dims[0]);
       h->nn_layers = std::max(h->nn_layers, s.nlayers);
-      h->nn_rows += 2 * d.count;
+      h->nn_rows += rows;
     }
   }
   if (!rc) rc = cl_upload(h, &h->slots_d, h->sd.data(), h->sd.size());
@@ -856,7 +872,7 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
       if (nl) h->plant_ms += el(E[6 + nm], E[7 + nm]);
       for (int k = 0, j = 0; k < h->nslots; ++k) {
         double v_ = xp;
-        if (h->kind[k] == NNMPC_CL_NN) v_ = nn;
+        if (h->kind[k] == NNMPC_CL_NN || h->kind[k] == NNMPC_CL_NN_UNSTD) v_ = nn;
         else if (h->kind[k] == NNMPC_CL_MPC) v_ = h->count[k] ? ms[j++] : 0.0;
         h->slot_ms[(size_t)t * h->nslots + k] = v_;
       }

@@ -10,6 +10,12 @@
 // kernel is the same NT tile GEMM the QP path uses); bias + ReLU are fused in
 // the GEMM epilogue, concat/scale in the assemble kernel and us + (o1 - o2) +
 // clip in the combine kernel.
+//
+// Unstructured controller (nnmpc_nn_create_ex, form NNMPC_NN_UNSTD / NNMPC_NN_UNSTD_RELU):
+//   u = clip( MLP([x/xs_scale, (uprev), xs/xs_scale, us]) )
+// Reference: NeuralNetworkControllerUnstd (lib/controller_evaluation.py:895-916; linear head with a bias) and
+// UnstdRegulatorLayer.call (lib/LinearMPCLayers.py:135-156; relu on the head too).  ONE row per sample through the same
+// tile GEMMs; the head's bias (+ ReLU) sits in its GEMM epilogue and nn_clip_k replaces the combine kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -101,6 +107,68 @@ __global__ __launch_bounds__(256) void nn_assemble_split_k(__bf16* __restrict__ 
   }
 }
 
+// Single-pass rows of the unstructured forms: rows [0, Mp) = [x^, (uprev), xs^, us], rows b >= B and the pad columns zero.
+template <class T>
+__global__ __launch_bounds__(256) void nn_assemble1_k(T* __restrict__ in, int ldk, int Mp, int B, int nx, int nu,
+                              int with_uprev, const double* __restrict__ x,
+                              const double* __restrict__ uprev, const double* __restrict__ xs,
+                              const double* __restrict__ us, const float* __restrict__ inv_scale) {
+  const int o2 = nx + (with_uprev ? nu : 0);
+  const int din = o2 + nx + nu;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int b = blockIdx.x; b < Mp; b += gridDim.x) {
+    T* d1 = in + (size_t)b * ldk;
+    if (b >= B) {
+      for (int k = tid; k < ldk; k += nt) d1[k] = (T)0.f;
+      continue;
+    }
+    const double* xa = x + (size_t)b * nx;
+    const double* xb = xs + (size_t)b * nx;
+    const double* ub = us + (size_t)b * nu;
+    for (int k = tid; k < nx; k += nt) {
+      const float sc = inv_scale[k];
+      d1[k] = (T)((float)xa[k] * sc); d1[o2 + k] = (T)((float)xb[k] * sc);
+    }
+    for (int k = tid; k < nu; k += nt) {
+      d1[o2 + nx + k] = (T)(float)ub[k];
+      if (with_uprev) d1[nx + k] = (T)(float)uprev[(size_t)b * nu + k];
+    }
+    for (int k = din + tid; k < ldk; k += nt) d1[k] = (T)0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void nn_assemble1_split_k(__bf16* __restrict__ in, int ldk, int Mp, int B, int nx, int nu,
+                              int with_uprev, const double* __restrict__ x,
+                              const double* __restrict__ uprev, const double* __restrict__ xs,
+                              const double* __restrict__ us, const float* __restrict__ inv_scale) {
+  const int o2 = nx + (with_uprev ? nu : 0);
+  const int din = o2 + nx + nu;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  auto put = [&](__bf16* row, int k, float v) {
+    const __bf16 h = (__bf16)v, l = (__bf16)(v - (float)h);
+    row[k] = h; row[ldk + k] = l;
+  };
+  for (int b = blockIdx.x; b < Mp; b += gridDim.x) {
+    __bf16* d1 = in + (size_t)b * 2 * ldk;
+    if (b >= B) {
+      for (int k = tid; k < 2 * ldk; k += nt) d1[k] = (__bf16)0.f;
+      continue;
+    }
+    const double* xa = x + (size_t)b * nx;
+    const double* xb = xs + (size_t)b * nx;
+    const double* ub = us + (size_t)b * nu;
+    for (int k = tid; k < nx; k += nt) {
+      const float sc = inv_scale[k];
+      put(d1, k, (float)xa[k] * sc); put(d1, o2 + k, (float)xb[k] * sc);
+    }
+    for (int k = tid; k < nu; k += nt) {
+      put(d1, o2 + nx + k, (float)ub[k]);
+      if (with_uprev) put(d1, nx + k, (float)uprev[(size_t)b * nu + k]);
+    }
+    for (int k = din + tid; k < ldk; k += nt) put(d1, k, 0.f);
+  }
+}
+
 __global__ void nn_combine_k(double* __restrict__ u, const float* __restrict__ o, int ldo, int Bp,
                              int B, int nu, const double* __restrict__ us,
                              const double* __restrict__ ulb, const double* __restrict__ uub,
@@ -111,6 +179,20 @@ __global__ void nn_combine_k(double* __restrict__ u, const float* __restrict__ o
   for (; i < total; i += stride) {
     const int b = (int)(i / nu), c = (int)(i % nu);
     double v = us[i] + ((double)o[(size_t)b * ldo + c] - (double)o[(size_t)(Bp + b) * ldo + c]);
+    if (clip) { v = v > uub[c] ? uub[c] : v; v = v < ulb[c] ? ulb[c] : v; }
+    u[i] = v;
+  }
+}
+
+// Unstructured forms: u = clip(o) (the head's bias and ReLU are in its GEMM epilogue); a NaN passes the clip like above.
+__global__ void nn_clip_k(double* __restrict__ u, const float* __restrict__ o, int ldo, int B, int nu,
+                          const double* __restrict__ ulb, const double* __restrict__ uub, int clip) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t total = (size_t)B * nu;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < total; i += stride) {
+    const int b = (int)(i / nu), c = (int)(i % nu);
+    double v = (double)o[(size_t)b * ldo + c];
     if (clip) { v = v > uub[c] ? uub[c] : v; v = v < ulb[c] ? ulb[c] : v; }
     u[i] = v;
   }
@@ -131,6 +213,7 @@ struct nnmpc_nn {
   int split;               // use_bf16 == 2: activation rows [hi | lo], walked hi, hi, lo against weights stacked [hi ; lo ; hi] along K
   std::vector<float*> bias;  // [npad]
   int nx, nu, with_uprev, clip, max_batch;
+  int form;                // NNMPC_NN_STRUCTURED, NNMPC_NN_UNSTD, NNMPC_NN_UNSTD_RELU
   float* inv_scale;
   double *ulb, *uub;
   float* act[2];           // ping-pong activations [2*max_batch][maxw] (f32; the bf16 path uses them as bf16 storage, head output f32)
@@ -196,10 +279,20 @@ int nnmpc_nn_create(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, const 
                     const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev,
                     const double* xscale, const double* ulb, const double* uub, int32_t use_bf16,
                     int32_t max_batch) {
+  return nnmpc_nn_create_ex(out, nlayers, dims, W, b, nx, nu, with_uprev, xscale, ulb, uub, use_bf16, max_batch,
+                            NNMPC_NN_STRUCTURED);
+}
+
+int nnmpc_nn_create_ex(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, const double* const* W,
+                       const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev,
+                       const double* xscale, const double* ulb, const double* uub, int32_t use_bf16,
+                       int32_t max_batch, int32_t form) {
   if (!out || nlayers < 1 || !dims || !W || !b || nx <= 0 || nu <= 0) { set_error("nnmpc_nn_create: bad arguments"); return NNMPC_EINVAL; }
   const int din = 2 * nx + (with_uprev ? 2 : 1) * nu;
   if (dims[0] != din || dims[nlayers] != nu) { set_error("nnmpc_nn_create: dims[0]=%d (want %d), dims[L]=%d (want %d)", dims[0], din, dims[nlayers], nu); return NNMPC_EINVAL; }
   if ((ulb == nullptr) != (uub == nullptr)) { set_error("nnmpc_nn_create: ulb and uub must both be given or both NULL"); return NNMPC_EINVAL; }
+  if (form != NNMPC_NN_STRUCTURED && form != NNMPC_NN_UNSTD && form != NNMPC_NN_UNSTD_RELU) { set_error("nnmpc_nn_create_ex: unknown form %d", form); return NNMPC_EINVAL; }
+  if (form != NNMPC_NN_STRUCTURED && !b[nlayers - 1]) { set_error("nnmpc_nn_create_ex: the unstructured forms need the head's bias b[%d]", nlayers - 1); return NNMPC_EINVAL; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("nnmpc_nn_create: no HIP device available (no CPU fallback)"); return NNMPC_EHIP; }
   nnmpc_nn* h = new nnmpc_nn();
@@ -207,6 +300,7 @@ int nnmpc_nn_create(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, const 
   h->use_bf16 = use_bf16 == 2 ? 2 : (use_bf16 != 0);
   h->split = h->use_bf16 == 2;
   h->nlayers = nlayers; h->nx = nx; h->nu = nu; h->with_uprev = with_uprev; h->clip = ulb != nullptr;
+  h->form = form;
   h->max_batch = ((std::max(max_batch, 1) + 127) / 128) * 128;
   h->gemm_ms = h->total_ms = h->hidden_ms = 0; h->hidden_launches = 0;
   h->dims.assign(dims, dims + nlayers + 1);
@@ -216,6 +310,11 @@ int nnmpc_nn_create(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, const 
   hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4);
   hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES);
   hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES);
+  if (form != NNMPC_NN_STRUCTURED) {                        // the head with its bias (+ ReLU) in the epilogue
+    hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4);
+    hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, false, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES);
+    hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES);
+  }
   hipFuncSetAttribute((const void*)gemm_nt_bf16_wide_k<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES);
   hipFuncSetAttribute((const void*)gemm_nt_bf16_wide_k<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES);
   h->maxw = 0;
@@ -229,7 +328,7 @@ int nnmpc_nn_create(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, const 
     std::vector<float> wt((size_t)np_ * kp, 0.f), bb(np_, 0.f);
     for (int i = 0; i < dims[l]; ++i)
       for (int o = 0; o < dims[l + 1]; ++o) wt[(size_t)o * kp + i] = (float)W[l][(size_t)i * dims[l + 1] + o];
-    if (l < nlayers - 1) {
+    if (l < nlayers - 1 || form != NNMPC_NN_STRUCTURED) {
       if (!b[l]) { set_error("nnmpc_nn_create: missing bias for hidden layer %d", l); rc = NNMPC_EINVAL; break; }
       for (int o = 0; o < dims[l + 1]; ++o) bb[o] = (float)b[l][o];
     }
@@ -242,7 +341,7 @@ int nnmpc_nn_create(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, const 
     if (h->use_bf16) {
       const bool lastl = l == nlayers - 1;
       const int k16 = ((dims[l] + 63) / 64) * 64;
-      const int ldc = lastl ? np_ : ((dims[l + 1] + 63) / 64) * 64;   // head: the row length nn_combine_k reads (128 per 128 columns once nu > 64)
+      const int ldc = lastl ? np_ : ((dims[l + 1] + 63) / 64) * 64;   // head: the row length nn_combine_k / nn_clip_k read (128 per 128 columns once nu > 64)
       const int nb = (!lastl && ldc >= 2 * WBN) ? WBN : (dims[l + 1] > 64 ? 128 : 64);   // WBN: the wide-tile kernel
       const int n16 = ((ldc + nb - 1) / nb) * nb;
       h->k16.push_back(k16); h->n16.push_back(n16); h->ldc16.push_back(ldc);
@@ -327,7 +426,20 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
       dx = x + (size_t)b0 * nx; dxs = xs + (size_t)b0 * nx; dus = us + (size_t)b0 * nu;
       dup = h->with_uprev ? uprev + (size_t)b0 * nu : nullptr; du = u + (size_t)b0 * nu;
     }
-    if (h->split)
+    // Unstructured forms: one row per sample.  The wide-tile kernel works in panels of WBM = 256 rows, so the bf16 paths pad the
+    // row count to 256 (the activation buffers hold 2 max_batch rows); the pad rows are zero inputs nobody reads back.
+    const bool un = h->form != NNMPC_NN_STRUCTURED, hrelu = h->form == NNMPC_NN_UNSTD_RELU;
+    const int M = !un ? 2 * Bp : (h->use_bf16 ? ((Bp + WBM - 1) / WBM) * WBM : Bp);
+    if (un && h->split)
+      hipLaunchKernelGGL(nn_assemble1_split_k, dim3(8192), dim3(256), 0, s, reinterpret_cast<__bf16*>(h->act[0]),
+                         h->kpad[0], M, nb, nx, nu, h->with_uprev, dx, dup, dxs, dus, h->inv_scale);
+    else if (un && h->use_bf16)
+      hipLaunchKernelGGL(nn_assemble1_k<__bf16>, dim3(8192), dim3(256), 0, s, reinterpret_cast<__bf16*>(h->act[0]),
+                         h->kpad[0], M, nb, nx, nu, h->with_uprev, dx, dup, dxs, dus, h->inv_scale);
+    else if (un)
+      hipLaunchKernelGGL(nn_assemble1_k<float>, dim3(8192), dim3(256), 0, s, h->act[0], h->kpad[0], M, nb, nx, nu,
+                         h->with_uprev, dx, dup, dxs, dus, h->inv_scale);
+    else if (h->split)
       hipLaunchKernelGGL(nn_assemble_split_k, dim3(8192), dim3(256), 0, s, reinterpret_cast<__bf16*>(h->act[0]),
                          h->kpad[0], Bp, nb, nx, nu, h->with_uprev, dx, dup, dxs, dus, h->inv_scale);
     else if (h->use_bf16)
@@ -338,7 +450,6 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
                          h->with_uprev, dx, dup, dxs, dus, h->inv_scale);
     hipEventRecord(h->eg[3 * nsub], s);
     int cur = 0;
-    const int M = 2 * Bp;
     for (int l = 0; l < h->nlayers; ++l) {
       const int K = h->kpad[l], N = h->npad[l];
       float* C = h->act[cur ^ 1];
@@ -355,26 +466,36 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
           if (h->split) launch_layer16_wide<true, true, true>(s, reinterpret_cast<__bf16*>(C), ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l]);
           else launch_layer16_wide<true, true, false>(s, reinterpret_cast<__bf16*>(C), ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l]);
         } else if (h->n16[l] % 128 == 0) {
-          if (last) launch_layer16<128, false, false, 0>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, nullptr, nk0);
+          if (last && un && hrelu) launch_layer16<128, true, true, 0>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l], nk0);
+          else if (last && un) launch_layer16<128, false, true, 0>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l], nk0);
+          else if (last) launch_layer16<128, false, false, 0>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, nullptr, nk0);
           else if (h->split) launch_layer16<128, true, true, 2>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l], nk0);
           else launch_layer16<128, true, true, 1>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l]);
         } else {
-          if (last) launch_layer16<64, false, false, 0>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, nullptr, nk0);
+          if (last && un && hrelu) launch_layer16<64, true, true, 0>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l], nk0);
+          else if (last && un) launch_layer16<64, false, true, 0>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l], nk0);
+          else if (last) launch_layer16<64, false, false, 0>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, nullptr, nk0);
           else if (h->split) launch_layer16<64, true, true, 2>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l], nk0);
           else launch_layer16<64, true, true, 1>(s, C, ldc, A16, lda, h->Wt16[l], K16, M, K16, h->bias[l]);
         }
       } else if (N % 128 == 0) {
-        if (last) launch_layer<128, false, false>(s, C, N, A, K, h->Wt[l], K, M, N, K, nullptr);
+        if (last && un && !hrelu) launch_layer<128, false, true>(s, C, N, A, K, h->Wt[l], K, M, N, K, h->bias[l]);
+        else if (last && !un) launch_layer<128, false, false>(s, C, N, A, K, h->Wt[l], K, M, N, K, nullptr);
         else launch_layer<128, true, true>(s, C, N, A, K, h->Wt[l], K, M, N, K, h->bias[l]);
       } else {
-        if (last) launch_layer<64, false, false>(s, C, N, A, K, h->Wt[l], K, M, N, K, nullptr);
+        if (last && un && !hrelu) launch_layer<64, false, true>(s, C, N, A, K, h->Wt[l], K, M, N, K, h->bias[l]);
+        else if (last && !un) launch_layer<64, false, false>(s, C, N, A, K, h->Wt[l], K, M, N, K, nullptr);
         else launch_layer<64, true, true>(s, C, N, A, K, h->Wt[l], K, M, N, K, h->bias[l]);
       }
       cur ^= 1;
     }
     hipEventRecord(h->eg[3 * nsub + 2], s);
-    hipLaunchKernelGGL(nn_combine_k, dim3(1024), dim3(256), 0, s, du, h->act[cur], h->npad[h->nlayers - 1], Bp,
-                       nb, nu, dus, h->ulb, h->uub, h->clip);
+    if (un)
+      hipLaunchKernelGGL(nn_clip_k, dim3(1024), dim3(256), 0, s, du, h->act[cur], h->npad[h->nlayers - 1], nb, nu, h->ulb,
+                         h->uub, h->clip);
+    else
+      hipLaunchKernelGGL(nn_combine_k, dim3(1024), dim3(256), 0, s, du, h->act[cur], h->npad[h->nlayers - 1], Bp,
+                         nb, nu, dus, h->ulb, h->uub, h->clip);
     if (ptr_kind == NNMPC_HOST) {                           // the staging buffers are reused by the next sub-batch
       HIPCHK(hipMemcpyAsync(u + (size_t)b0 * nu, h->su, (size_t)nb * nu * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(stream_sync(s));

@@ -1,10 +1,15 @@
-"""Structured NN controller forward on the GPU (host wrapper over the C ABI).
+"""NN controller forwards on the GPU (host wrappers over the C ABI).
 
+Structured:
     u = clip(us + NN(x/xscale, [uprev], xs/xscale, us) - NN(xs/xscale, [us], xs/xscale, us))
-
 Reference: RegulatorLayerWithUprev / RegulatorLayerWithoutUprev.call
 (lib/LinearMPCLayers.py:40-61, :91-112) and NeuralNetworkController
 ._get_control_input (lib/controller_evaluation.py:863-892).
+
+Unstructured:
+    u = clip(NN(x/xscale, [uprev], xs/xscale, us))
+Reference: NeuralNetworkControllerUnstd (lib/controller_evaluation.py:895-916) and
+UnstdRegulatorLayer.call (lib/LinearMPCLayers.py:135-156).
 """
 import ctypes as C
 import numpy as np
@@ -12,35 +17,38 @@ import numpy as np
 from . import _lib
 
 
-class StructuredNN:
-    """``weights``: Keras get_weights() order [W1 (in x h), b1, ..., Wout (h x nu)].
+class _DeviceNN:
+    """What the two forwards share: the handle's life, ``forward``, ``forward_device`` and the timers.  A subclass splits the
+    Keras list into kernels and biases (``_split``) and names its form (``_form``)."""
 
-    ``use_bf16``: False -- f32 MFMA GEMMs; True -- bf16 operands, f32 accumulation (~2e-2 relative error on the CDU
-    architecture); "split" (or 2) -- activations and weights as bf16 pairs hi + lo, every layer ONE bf16 GEMM of three times
-    the depth (hi hi' + hi lo' + lo hi'): f32-grade results (~1e-5) from the bf16 matrix pipes."""
+    def _split(self, weights):
+        raise NotImplementedError
 
-    def __init__(self, weights, nx, nu, *, nnwithuprev=True, xscale=None, ulb=None, uub=None,
-                 max_batch=65536, use_bf16=False):
+    def _form(self):
+        raise NotImplementedError
+
+    def _create(self, weights, nx, nu, nnwithuprev, xscale, ulb, uub, max_batch, use_bf16):
+        Ws, bs = self._split(weights)                          # bs: one entry per layer, None where the layer has no bias
         lib = _lib.load()
-        Ws = [np.ascontiguousarray(w, np.float64) for w in weights[0:-1:2]] + \
-             [np.ascontiguousarray(weights[-1], np.float64)]
-        bs = [np.ascontiguousarray(b, np.float64).ravel() for b in weights[1::2]]
         L = len(Ws)
-        if len(bs) != L - 1:
-            raise ValueError("weights must be [W1, b1, ..., W_{L-1}, b_{L-1}, Wout]")
         dims = [Ws[0].shape[0]] + [w.shape[1] for w in Ws]
         self.nx, self.nu, self.nnwithuprev = nx, nu, bool(nnwithuprev)
         dims_c = (C.c_int32 * (L + 1))(*dims)
         Wp = (C.c_void_p * L)(*[w.ctypes.data for w in Ws])
-        bp = (C.c_void_p * L)(*([b.ctypes.data for b in bs] + [None]))
+        bp = (C.c_void_p * L)(*[None if b is None else b.ctypes.data for b in bs])
         opt = lambda a: None if a is None else np.ascontiguousarray(np.ravel(a), np.float64)
         xs_, lb_, ub_ = opt(xscale), opt(ulb), opt(uub)
         self._keep = (Ws, bs, xs_, lb_, ub_)
         p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         self._h = C.c_void_p()
-        _lib.check(lib.nnmpc_nn_create(C.byref(self._h), L, dims_c, Wp, bp, nx, nu, int(nnwithuprev),
-                                       p(xs_), p(lb_), p(ub_), 2 if use_bf16 in ("split", 2) else int(bool(use_bf16)), max_batch),
-                   "nnmpc_nn_create")
+        mode = 2 if use_bf16 in ("split", 2) else int(bool(use_bf16))
+        form = self._form()
+        if form == _lib.NN_STRUCTURED:
+            _lib.check(lib.nnmpc_nn_create(C.byref(self._h), L, dims_c, Wp, bp, nx, nu, int(nnwithuprev),
+                                           p(xs_), p(lb_), p(ub_), mode, max_batch), "nnmpc_nn_create")
+        else:
+            _lib.check(lib.nnmpc_nn_create_ex(C.byref(self._h), L, dims_c, Wp, bp, nx, nu, int(nnwithuprev),
+                                              p(xs_), p(lb_), p(ub_), mode, max_batch, form), "nnmpc_nn_create_ex")
         self._lib = lib
 
     def close(self):
@@ -78,3 +86,61 @@ class StructuredNN:
         g, k = C.c_double(), C.c_int32()
         self._lib.nnmpc_nn_last_hidden_ms(self._h, C.byref(g), C.byref(k))
         return g.value, k.value
+
+
+class StructuredNN(_DeviceNN):
+    """``weights``: Keras get_weights() order [W1 (in x h), b1, ..., Wout (h x nu)].
+
+    ``use_bf16``: False -- f32 MFMA GEMMs; True -- bf16 operands, f32 accumulation (~2e-2 relative error on the CDU
+    architecture); "split" (or 2) -- activations and weights as bf16 pairs hi + lo, every layer ONE bf16 GEMM of three times
+    the depth (hi hi' + hi lo' + lo hi'): f32-grade results (~1e-5) from the bf16 matrix pipes."""
+
+    def __init__(self, weights, nx, nu, *, nnwithuprev=True, xscale=None, ulb=None, uub=None,
+                 max_batch=65536, use_bf16=False):
+        self._create(weights, nx, nu, nnwithuprev, xscale, ulb, uub, max_batch, use_bf16)
+
+    def _form(self):
+        return _lib.NN_STRUCTURED
+
+    def _split(self, weights):
+        Ws = [np.ascontiguousarray(w, np.float64) for w in weights[0:-1:2]] + \
+             [np.ascontiguousarray(weights[-1], np.float64)]
+        bs = [np.ascontiguousarray(b, np.float64).ravel() for b in weights[1::2]]
+        if len(bs) != len(Ws) - 1:
+            raise ValueError("weights must be [W1, b1, ..., W_{L-1}, b_{L-1}, Wout]")
+        return Ws, bs + [None]
+
+
+def split_unstd_weights(weights):
+    """The Keras get_weights() list of UnstdRegulatorModel, [W1, b1, ..., WL, bL], as (kernels, biases) in fp64;
+    ``ValueError`` for a list of odd length, a bias that does not fit its kernel or kernels that do not chain."""
+    weights = list(weights)
+    if not weights or len(weights) % 2:
+        raise ValueError("unstructured weights must be [W1, b1, ..., WL, bL] (every layer has a bias: an even-length list), "
+                         f"got {len(weights)} arrays")
+    Ws = [np.ascontiguousarray(w, np.float64) for w in weights[0::2]]
+    bs = [np.ascontiguousarray(b, np.float64).ravel() for b in weights[1::2]]
+    for l, (w, b) in enumerate(zip(Ws, bs)):
+        if w.ndim != 2 or b.size != w.shape[1] or (l and w.shape[0] != Ws[l - 1].shape[1]):
+            raise ValueError(f"unstructured weights: layer {l} has kernel {w.shape} and bias ({b.size},)")
+    return Ws, bs
+
+
+class UnstructuredNN(_DeviceNN):
+    """u = clip(MLP([x / xscale, (uprev), xs / xscale, us])): one pass, hidden layers relu(W'z + b), the head with a bias.
+
+    ``weights``: Keras get_weights() order of UnstdRegulatorModel, [W1, b1, ..., WL, bL] (an odd-length list: ``ValueError``).
+    ``head_relu``: False -- linear head, what NeuralNetworkControllerUnstd computes (lib/controller_evaluation.py:907-908);
+    True -- relu on the head as well, what the Keras UnstdRegulatorLayer computes (lib/LinearMPCLayers.py:147-148).
+    ``use_bf16`` as for ``StructuredNN``."""
+
+    def __init__(self, weights, nx, nu, *, nnwithuprev=True, xscale=None, ulb=None, uub=None,
+                 max_batch=65536, use_bf16=False, head_relu=False):
+        self.head_relu = bool(head_relu)
+        self._create(weights, nx, nu, nnwithuprev, xscale, ulb, uub, max_batch, use_bf16)
+
+    def _form(self):
+        return _lib.NN_UNSTD_RELU if self.head_relu else _lib.NN_UNSTD
+
+    def _split(self, weights):
+        return split_unstd_weights(weights)

@@ -77,6 +77,60 @@ class RegulatorModel(torch.nn.Module):
                     lin.bias.copy_(torch.as_tensor(np.asarray(next(it)), dtype=lin.bias.dtype))
 
 
+class UnstdRegulatorModel(torch.nn.Module):
+    """u = MLP(x, [uprev], xs, us): the reference's unstructured comparison network (lib/LinearMPCLayers.py:135-174,
+    trained by cstrs_train_unstd.py).  One pass, a bias on every Dense, ``regulator_dims[0]`` ignored like there.
+
+    ``head_relu``: the Keras layer builds every Dense with activation='relu', the output one included (:147-148), while the
+    numpy controller that runs the trained weights ends in a linear head (lib/controller_evaluation.py:907-908).  True
+    (the default) is the Keras code as written, False the controller's form.  Trains through
+    ``train_nn_controller(backend="torch")``; the native backends take structured networks only."""
+
+    unstructured = True
+
+    def __init__(self, Nx, Nu, regulator_dims, nnwithuprev=True, head_relu=True, dtype=torch.float64):
+        super().__init__()
+        self.Nx, self.Nu, self.nnwithuprev, self.head_relu = Nx, Nu, nnwithuprev, bool(head_relu)
+        widths = [2 * Nx + (2 if nnwithuprev else 1) * Nu] + list(regulator_dims[1:])
+        self.layers = torch.nn.ModuleList([torch.nn.Linear(widths[i], widths[i + 1], bias=True, dtype=dtype)
+                                           for i in range(len(widths) - 1)])
+        for lin in self.layers:                       # Keras Dense default: glorot_uniform, zero bias
+            torch.nn.init.xavier_uniform_(lin.weight)
+            torch.nn.init.zeros_(lin.bias)
+
+    def forward(self, x, uprev, xs, us):
+        z = torch.cat((x, uprev, xs, us), -1) if self.nnwithuprev else torch.cat((x, xs, us), -1)
+        for lin in self.layers[:-1]:
+            z = torch.relu(lin(z))
+        z = self.layers[-1](z)
+        return torch.relu(z) if self.head_relu else z
+
+    def get_weights(self):
+        """Keras order: [W1 (in x h), b1, ..., WL (h x Nu), bL] as float64 numpy arrays."""
+        out = []
+        for lin in self.layers:
+            out.append(lin.weight.detach().cpu().double().numpy().T.copy())
+            out.append(lin.bias.detach().cpu().double().numpy().copy())
+        return out
+
+    def set_weights(self, weights):
+        weights = list(weights)
+        if len(weights) != 2 * len(self.layers):
+            raise ValueError(f"set_weights: {len(weights)} arrays for {len(self.layers)} layers with a bias each")
+        with torch.no_grad():
+            for l, lin in enumerate(self.layers):
+                lin.weight.copy_(torch.as_tensor(np.asarray(weights[2 * l]).T, dtype=lin.weight.dtype))
+                lin.bias.copy_(torch.as_tensor(np.asarray(weights[2 * l + 1]), dtype=lin.bias.dtype))
+
+
+def _refuse_unstructured(model, who):
+    """The native training kernels compute the structured form (two passes, bias-free head) and would misread the
+    unstructured weight list."""
+    if getattr(model, "unstructured", False):
+        raise ValueError(f"{who}: the native HIP training step takes structured networks only; train an "
+                         "UnstdRegulatorModel with train_nn_controller(..., backend=\"torch\")")
+
+
 class HipTrainer:
     """The native training step (C ABI ``nnmpc_train_*``): f32 master weights, Adam moments, dataset and workspaces
     live on the device; ``weights`` is the Keras ``get_weights()`` list the network starts from.
@@ -381,6 +435,8 @@ def train_nn_controllers(models, data, *, num_samples=None, epochs=1500, batch_s
                                                   validation_split=validation_split, lr=lr, seed=seed, log=log)
             hists.append(h)
         return models, time.time() - t0, hists
+    for m in models:
+        _refuse_unstructured(m, "train_nn_controllers(backend=\"hip\")")
     m0 = models[0]
     for m in models[1:]:
         if (m.Nx, m.Nu, bool(m.nnwithuprev), len(m.layers)) != (m0.Nx, m0.Nu, bool(m0.nnwithuprev), len(m0.layers)):
@@ -462,6 +518,7 @@ def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation
     step (``HipTrainer``), shuffled by a numpy generator seeded with ``seed``; ``model`` comes back carrying the
     trained weights.  No device: ``_lib.NnmpcError`` (no CPU fallback)."""
     if backend == "hip":
+        _refuse_unstructured(model, "train_nn_controller(backend=\"hip\")")
         return _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log)
     if backend != "torch":
         raise ValueError(f"unknown backend {backend!r}: 'torch' or 'hip'")

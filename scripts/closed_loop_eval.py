@@ -10,6 +10,9 @@ online_simulation on a few instances for comparison.  One JSON line per size at 
 
     python scripts/closed_loop_eval.py --size both --steps 2880 --seeds 1
 
+``--unstd K`` adds K unstructured networks (controller_evaluation.NeuralNetworkControllerUnstd: one pass, a bias on the head)
+of the same widths to the batch; they share the grouped forward's launches with the structured ones.
+
 ``--size cstrs-flash`` is the reference's real CSTRs study instead: its linearised model and controllers, both online test
 scenarios for 4320 steps, 48 random networks of its widths, the nonlinear plant integrated on the device (run_cstrs_flash).
 """
@@ -66,6 +69,11 @@ def networks(size, Nx, Nu, nets, rng):
     return out
 
 
+def unstd_networks(size, Nx, Nu, nets, rng):
+    """``networks`` with a head bias: the even-length list [W1, b1, ..., WL, bL] of the unstructured controller."""
+    return [W + [0.1 * rng.standard_normal(Nu)] for W in networks(size, Nx, Nu, nets, rng)]
+
+
 def run(size, args):
     from industrial_nnmpc_2021_amd import linearMPC as lm, controller_evaluation as ce
     from industrial_nnmpc_2021_amd.closed_loop import simulate_closed_loop_batch
@@ -80,6 +88,13 @@ def run(size, args):
                                       **ce._shared(mpc)) for W in Ws]          # the batch run uploads the weights itself
     base = [mpc, ce._get_short_horizon_controller(mpc, SHORT_N[size]), ce._get_satdlqr_controller(mpc), ce._get_us_controller(mpc)]
     ctls = nns + base
+    uns = []
+    if args.unstd:                                          # after the baselines: the instance order of the rest is unchanged
+        Wu = unstd_networks(size, Nx, Nu, args.unstd, np.random.default_rng(6))
+        uns = [ce.NeuralNetworkControllerUnstd(regulator_weights=W, xscale=xscale, nnwithuprev=WITH_UPREV[size],
+                                               build_forward=False, **ce._shared(mpc)) for W in Wu]
+        ctls = ctls + uns
+        Ws = Ws + Wu
     nn_bytes = sum(4 * sum(np.asarray(a).size for a in W) for W in Ws)
     # one short run first: the regulators' one-time setup (inverse, far-field factors) and the kernels' first launches
     simulate_closed_loop_batch(plant, ctls, scenarios=scen, Nsim=4, seeds=[0], record=("avg",))
@@ -90,14 +105,16 @@ def run(size, args):
     ph = {k: v / T for k, v in res["phase_ms"].items()}
     nn_bound_ms = nn_bytes / (HBM_TBPS * 1e12) * 1e3
     frac = nn_bound_ms / ph["nn"] if ph["nn"] > 0 else float("nan")
-    print(f"[{size}] {len(nns)} networks ({nn_bytes / 1e6:.1f} MB f32) + 4 baselines, {len(scen)} scenario x {args.seeds} seed(s) = "
+    if uns:
+        print(f"[{size}] of the networks below, {len(uns)} are unstructured (one pass, one row per instance)")
+    print(f"[{size}] {len(nns) + len(uns)} networks ({nn_bytes / 1e6:.1f} MB f32) + 4 baselines, {len(scen)} scenario x {args.seeds} seed(s) = "
           f"{nb} instances, {T} steps (setup {setup_s:.1f} s)")
     print(f"[{size}] wall {res['wall_s']:.3f} s, device {res['device_ms'] / 1e3:.3f} s, {1e3 * res['wall_s'] / T:.3f} ms per step")
     print(f"[{size}] per step (ms): " + ", ".join(f"{k} {v:.4f}" for k, v in ph.items()))
     print(f"[{size}] grouped NN forward: {ph['nn'] * 1e3:.1f} us per step vs HBM bound {nn_bound_ms * 1e3:.1f} us -> {frac:.2f} of the bound")
     # host online_simulation on a few instances (one network, the MPC) for comparison
     host = {}
-    for name, mk in (("nn", lambda: ce._get_nn_controller(mpc, Ws[-1], xscale, WITH_UPREV[size])),
+    for name, mk in (("nn", lambda: ce._get_nn_controller(mpc, Ws[len(nns) - 1], xscale, WITH_UPREV[size])),
                      ("mpc", lambda: lm.LinearMPCController(N=pl["N"], **common))):
         ctl = mk()
         np.random.seed(0)
@@ -108,12 +125,18 @@ def run(size, args):
             lm.online_simulation(hp, ctl, setpoints=scen[0][0][:args.host_steps], disturbances=scen[0][1][:args.host_steps],
                                  Nsim=args.host_steps)
         host[name] = (time.time() - t0) / args.host_steps
-    host_est = (len(nns) * args.seeds * host["nn"] + 2 * args.seeds * host["mpc"] + 2 * args.seeds * host["nn"]) * T
+    host_est = ((len(nns) + len(uns)) * args.seeds * host["nn"] + 2 * args.seeds * host["mpc"] + 2 * args.seeds * host["nn"]) * T
     print(f"[{size}] host online_simulation: {1e3 * host['nn']:.2f} ms per NN step, {1e3 * host['mpc']:.2f} ms per MPC step "
           f"-> ~{host_est:.1f} s for the same instances (estimate; baselines priced as NN steps), speed-up {host_est / res['wall_s']:.1f}x")
     loss = 100 * (res["avg"][:len(nns) * args.seeds, -1] - res["avg"][len(nns) * args.seeds, -1]) / res["avg"][len(nns) * args.seeds, -1]
     print(f"[{size}] performance loss of the (random) networks vs MPC: median {np.median(loss):.1f} %")
-    return dict(size=size, networks=len(nns), instances=nb, steps=T, wall_s=res["wall_s"], device_s=res["device_ms"] / 1e3,
+    extra = {}
+    if uns:
+        k0 = (len(nns) + len(base)) * args.seeds
+        uloss = 100 * (res["avg"][k0:, -1] - res["avg"][len(nns) * args.seeds, -1]) / res["avg"][len(nns) * args.seeds, -1]
+        print(f"[{size}] performance loss of the (random) unstructured networks vs MPC: median {np.median(uloss):.1f} %")
+        extra = dict(unstd_networks=len(uns))
+    return dict(extra, size=size, networks=len(nns), instances=nb, steps=T, wall_s=res["wall_s"], device_s=res["device_ms"] / 1e3,
                 phase_ms_per_step=ph, nn_bytes=nn_bytes, nn_bound_us=nn_bound_ms * 1e3, nn_fraction_of_bound=frac,
                 host_ms_per_step=dict((k, 1e3 * v) for k, v in host.items()), host_estimate_s=host_est,
                 speedup=host_est / res["wall_s"], setup_s=setup_s)
@@ -175,6 +198,7 @@ def main():
     ap.add_argument("--steps", type=int, default=2880)
     ap.add_argument("--seeds", type=int, default=1)
     ap.add_argument("--nets", type=int, default=52)
+    ap.add_argument("--unstd", type=int, default=0, help="unstructured networks added to the batch (sizes cstrs / cdu)")
     ap.add_argument("--chunk", type=int, default=None, help="steps per device call (records stream back per chunk)")
     ap.add_argument("--host-steps", type=int, default=30)
     ap.add_argument("--json", default=None)
