@@ -1,7 +1,7 @@
 // What one workgroup of the training step's kernels does, as __device__ functions of its block coordinates, and the shape
 // rules of the step.  nn_train.hip (one network per handle) and nn_train_group.hip (a sweep of networks per launch) both
 // build their kernels from these, so a network's bytes are the same whichever of the two trains it: same tile functions,
-// same summation orders, same slice rule.
+// same summation orders, same slice rule.  The host side the two share (layout, uploads, dataset, events) is nn_train_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,5 @@
-"""The native training step (csrc/nn_train.hip, C ABI nnmpc_train_*, train.HipTrainer) against the project's own
+"""The native training step (csrc/nn_train.hip on the host side of csrc/nn_train_host.h, C ABI nnmpc_train_*,
+train.HipTrainer) against the project's own
 RegulatorModel in torch float64 ON THE CPU with autograd and torch.optim.Adam's formula -- never the code under test.
 
 Bars.  Gradients, per parameter tensor in Keras layout: max|g_hip - g64| / max|g64| <= max(8 x the same figure of the
@@ -266,6 +267,57 @@ def test_two_runs_give_identical_bytes():
     assert out[0] == out[1]
 
 
+def test_grad_leaves_no_trace():
+    """grad and eval between two steps change neither the weights, the moments nor the Adam count: step(p0), grad(p1),
+    eval, step(p2) leaves the bytes of step(p0), step(p2), p2 being the 182-row batch; and grad(p1) twice gives the same
+    loss and gradient bytes."""
+    nx, nu, uprev, W, d = _epoch_data()
+    perm = np.random.default_rng(13).permutation(950)
+    p0, p1, p2 = perm[:256], perm[256:512], perm[768:]
+    assert len(p2) == 182
+    a, b = _trainer(W, nx, nu, uprev, d, 256), _trainer(W, nx, nu, uprev, d, 256)
+    try:
+        a.step(p0)
+        l1, g1 = a.grad(p1)
+        l2, g2 = a.grad(p1)
+        assert l1 == l2 and _bytes(g1) == _bytes(g2)
+        assert np.isfinite(a.eval(950, 50))
+        la = a.step(p2)
+        b.step(p0)
+        lb = b.step(p2)
+        assert la == lb
+        assert _bytes(a.get_weights()) == _bytes(b.get_weights())
+        assert a.padding_max() == 0.0
+    finally:
+        a.close(); b.close()
+
+
+def test_step_applies_the_gradient_grad_reports_with_several_dw_slices(monkeypatch):
+    """600 rows with three slices forced: grad reports the slices it ran, and the step on the same rows moves every entry
+    by Adam's first update of that gradient, to the bar of test_adam_steps_follow_torchs_formula."""
+    monkeypatch.setenv("NNMPC_TRAIN_DW_SLICES", "3")
+    nx, nu, uprev, W, d = _epoch_data()
+    rows = np.random.default_rng(17).permutation(1000)[:600]
+    tr = _trainer(W, nx, nu, uprev, d, 600)
+    try:
+        W0 = tr.get_weights()
+        _, g = tr.grad(rows)
+        assert tr.dw_slices() == [3] * 4
+        tr.step(rows)
+        W1 = tr.get_weights()
+        worst = 0.0
+        for i in range(len(W)):
+            m, v = g[i] * (1 - B1), (1 - B2) * g[i] * g[i]
+            ref = W0[i] - LR / (1 - B1) * m / (np.sqrt(v) / np.sqrt(1 - B2) + EPS)
+            worst = max(worst, (np.abs(W1[i] - ref) / (4 * 2.0 ** -24 * np.maximum(np.abs(ref), LR))).max())
+            assert np.abs(W1[i] - W0[i]).max() > 0.1 * LR                   # the step moved this tensor
+        print(f"[adam, 3 slices] worst |W_hip - W_ref| / bar = {worst:.3f}")
+        assert worst <= 1.0
+        assert tr.dw_slices() == [3] * 4
+    finally:
+        tr.close()
+
+
 def test_fit_with_the_hip_backend_then_deploy_through_the_hip_forward():
     """The scenario and thresholds of tests/test_train_gpu.py with backend="hip"; in addition the returned model's
     validation loss in torch float64 equals min over hist (the best epoch's weights were restored)."""
@@ -338,6 +390,7 @@ def _einval(fn):
     with pytest.raises(_lib.NnmpcError) as ei:
         fn()
     assert re.search(r"\(code -1\): \S", str(ei.value)), str(ei.value)              # NNMPC_EINVAL with a message
+    assert "nnmpc_train_" in str(ei.value) and "nnmpc_train_group" not in str(ei.value), str(ei.value)   # of the ABI that was called
 
 
 def test_edges_are_rejected_and_nan_is_not_hidden():
