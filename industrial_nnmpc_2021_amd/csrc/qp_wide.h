@@ -38,7 +38,9 @@ __device__ __forceinline__ int wide_tile_k(const AsmDev& d, int tm) {
 }
 
 // ---- epilogue shared by the three forms: x, feasibility of the free variables, u out.  All loads of a row are issued
-// unconditionally and together (a branch per element would turn the epilogue into a chain of dependent round trips).
+// unconditionally and together (a branch per element would turn the epilogue into a chain of dependent round trips) -- within
+// a row: the 16 row groups still follow each other, which is why the far-field and lazy kernels use wide_epilogue_image below
+// whenever the bounds of a tile fit LDS.
 // BEYOND: every column of the tile lies beyond the window the rows settled in (c0 > 0): all of them are free variables -- no
 // bound state to load -- and, nu dividing 32 or 16, a lane's four columns (16 apart) see two inputs at most.
 template <bool XUNC, bool BEYOND>
@@ -102,18 +104,127 @@ __device__ __forceinline__ void wide_epilogue(const AsmDev& d, const f64x4 (&acc
     }
 }
 
+// ---- BEYOND epilogue of the far-field and lazy forms with the bounds in LDS.  The epilogue above, compiled for these two kernels,
+// is 16 row groups one after the other, each with its own rowprob -> lb / ub loads and, behind them, its predicated stores: loads and
+// stores share vmcnt, so every group waits for its loads AND for the previous group's stores -- 16 dependent round trips through a
+// memory system busy with the write-out, per tile.  Nothing in them depends on the accumulators.  Here a tile's epilogue is ONE
+// batch of loads and one wait: the row map comes from the kernel's LDS copy (rowp), the bounds of the tile's 128 problems go
+// through the LDS the K loop has left free, and the 16 row groups then compare and store from registers and LDS alone.
+//   image: row r of the tile at r * 16 nu bytes, entry k = {lb[k], ub[k]} of the row's problem (problem 0 for rows without one):
+//   one ds_read_b128 per bound pair.  16 lanes walk 16 consecutive entries, so every lane group of a ds_read_b128 (4 x 16 lanes,
+//   MI355X: {0-3, 12-15, 20-27}, ...) covers one whole 256-byte bank row whatever the row stride: conflict-free for nu = 16, 32.
+//   It holds nu <= 32 (128 rows x 32 entries x 16 B = G64_LDS); wider, odd or unaligned inputs keep the epilogue above.
+#ifndef WIDE_EPILOGUE_IMAGE
+#define WIDE_EPILOGUE_IMAGE 1      // (scripts/micro/wide_micro.hip builds the epilogue above with 0 for its A/B)
+#endif
+constexpr int WIDE_IMG_NU = G64_LDS / (128 * 16);
+
+// phase stamps of wave 0 of workgroup ASM_STAMP_WG (scripts/micro only, see qp_asm.h): compiles to nothing otherwise
+#ifdef ASM_STAMPS
+#define WIDE_STAMP(i) do { if (blockIdx.x == ASM_STAMP_WG && threadIdx.x < 64) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (threadIdx.x == 0) asm_stamp_buf[i] = t_; } } while (0)
+#else
+#define WIDE_STAMP(i) do { } while (0)
+#endif
+
+__device__ __forceinline__ bool wide_image_fits(const AsmDev& d) {
+  return WIDE_EPILOGUE_IMAGE && d.nu <= WIDE_IMG_NU && (d.nu & 1) == 0 &&
+         ((reinterpret_cast<size_t>(d.lb) | reinterpret_cast<size_t>(d.ub)) & 15) == 0;      // (16-byte loads of input pairs)
+}
+
+// rowp (LDS): rowprob of the tile's 128 rows; sm: the GEMM's LDS, free (every wave is past the K loop's last barrier).
+__device__ __forceinline__ void wide_epilogue_image(const AsmDev& d, const f64x4 (&acc)[4][4], int m0, int n0, const int* rowp, double* sm) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  char* img = reinterpret_cast<char*>(sm);
+  const int stride = d.nu * 16;
+  {
+    // thread (lr, kp): inputs 2 kp, 2 kp + 1 of the rows lr + 16 it -- 16 lanes per row, 16 loads of 16 bytes in flight per thread.
+    // ds_write_b128 works in groups of 8 lanes over 32 banks: the lanes kp and kp + 4 of a group write the two entries in opposite
+    // order, so that the group covers 8 distinct 16-byte slots of 128 bytes
+    const int lr = tid >> 4, kp = tid & 15, flip = (kp >> 2) & 1;
+    if (2 * kp < d.nu) {
+      f64x2 vl[8], vu[8];
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const size_t o = (size_t)max(rowp[lr + 16 * it], 0) * d.nu + 2 * kp;
+        vl[it] = *reinterpret_cast<const f64x2*>(d.lb + o);
+        vu[it] = *reinterpret_cast<const f64x2*>(d.ub + o);
+      }
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        char* e = img + (lr + 16 * it) * stride + kp * 32;
+        const f64x2 e0{vl[it][0], vu[it][0]}, e1{vl[it][1], vu[it][1]};
+        *reinterpret_cast<f64x2*>(e + 16 * flip) = flip ? e1 : e0;
+        *reinterpret_cast<f64x2*>(e + 16 * (flip ^ 1)) = flip ? e0 : e1;
+      }
+    }
+  }
+  int colj[4];
+  bool incol[4];
+  const char* rb[4];                                               // entry of column j in the first of this lane's 16 rows
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = n0 + wc * 64 + j * 16 + (lane & 15);
+    colj[j] = min(col, d.n - 1);                                   // (clamped: columns >= n are padding, never stored)
+    incol[j] = col < d.n;
+    rb[j] = img + (wr * 64 + (lane >> 4)) * stride + (colj[j] % d.nu) * 16;
+  }
+  int prow[16];
+#pragma unroll
+  for (int g = 0; g < 16; ++g) prow[g] = rowp[wr * 64 + (g >> 2) * 16 + (lane >> 4) + 4 * (g & 3)];
+  __syncthreads();                                                 // the image is complete
+  WIDE_STAMP(2);
+  // row group g = 4 i + r: row 16 i + 4 r + (lane >> 4) of the wave's 64.  The bounds of group g + 1 are read before the stores
+  // of group g are issued; between the first store and the last there is no global load and nothing to wait for but LDS
+  f64x2 b[2][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) b[0][j] = *reinterpret_cast<const f64x2*>(rb[j]);
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int i = g >> 2, r = g & 3;
+    if (g + 1 < 16) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        b[(g + 1) & 1][j] = *reinterpret_cast<const f64x2*>(rb[j] + (((g + 1) >> 2) * 16 + 4 * ((g + 1) & 3)) * stride);
+    }
+    const int p = prow[g];
+    const int pc = max(p, 0);
+    int ns[4], viol = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double x = acc[i][j][r];
+      ns[j] = x > b[g & 1][j][1] + d.bound_tol ? 1 : (x < b[g & 1][j][0] - d.bound_tol ? 2 : 0);
+      viol |= (p >= 0 && incol[j]) ? ns[j] : 0;
+      if (p >= 0 && incol[j] && colj[j] < d.nout) d.u_out[(size_t)pc * d.ldu + colj[j]] = x;     // final if nothing changes
+    }
+    if (viol) {                                                    // (rare: the problem goes back into the rounds)
+      unsigned char* st = d.st + (size_t)pc * d.n;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (incol[j] && ns[j] != 0) st[colj[j]] = (unsigned char)ns[j];
+      d.wflag[pc] = 1;                                             // (same value from every writer)
+    }
+  }
+}
+
 // columns: c0 + 128 tn ...; 1-D grid of g64_grid(ntm, ntn) workgroups, ntm = row tiles of AsmDev::wrows.
 template <int MODE>
 static __global__ __launch_bounds__(256, 2) void asm_wide_gemm_k(AsmDev d, int c0, int ntm, int ntn) {
   extern __shared__ __attribute__((aligned(16))) double g64_sm[];
   __shared__ long long rowoff[128];
+  __shared__ int rowp[128];                                  // rowprob of the tile's rows (the image epilogue's row map)
   int tm, tn;
   if (!g64_tile_of(blockIdx.x, ntm, ntn, tm, tn)) return;
   const int m0 = tm * 128, n0 = c0 + tn * 128, tid = threadIdx.x;
-  {                                                          // a tile without a settled problem has nothing to do
+  if (MODE == WIDE_XUNC) {                                   // a tile without a settled problem has nothing to do
     const int any = tid < 128 && d.rowprob[m0 + tid] >= 0;
     if (!__syncthreads_or(any)) return;
+  } else {
+    const int rp = tid < 128 ? d.rowprob[m0 + tid] : -1;
+    if (tid < 128) rowp[tid] = rp;
+    if (!__syncthreads_or(rp >= 0)) return;
   }
+  WIDE_STAMP(0);
   f64x4 acc[4][4];
   g64_zero(acc);
   if (MODE == WIDE_FAR) {
@@ -133,7 +244,14 @@ static __global__ __launch_bounds__(256, 2) void asm_wide_gemm_k(AsmDev d, int c
       const G64Seg s1{d.T, 0, d.ffU, 0, 0};
       g64_tile<false>(acc, st, s1, g64_sm);
     }
-    wide_epilogue<false, true>(d, acc, m0, n0);
+    WIDE_STAMP(1);
+    if (wide_image_fits(d)) wide_epilogue_image(d, acc, m0, n0, rowp, g64_sm);
+    else wide_epilogue<false, true>(d, acc, m0, n0);
+    WIDE_STAMP(3);                                           // (stores issued ...
+#ifdef ASM_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    WIDE_STAMP(4);                                           // ... and acknowledged)
+#endif
     return;
   }
   const int K1 = min(d.np, wide_tile_k(d, tm));
@@ -143,7 +261,8 @@ static __global__ __launch_bounds__(256, 2) void asm_wide_gemm_k(AsmDev d, int c
     __syncthreads();
     const G64Seg sx{d.x0, (size_t)d.ka, d.Kunc + (size_t)n0 * d.ka, (size_t)d.ka, d.ka / G64_KC};
     g64_tile<true>(acc, sx, sl, g64_sm, rowoff);             // acc = x0 Kunc' - lam Pinv'
-    wide_epilogue<false, true>(d, acc, m0, n0);
+    if (wide_image_fits(d)) wide_epilogue_image(d, acc, m0, n0, rowp, g64_sm);
+    else wide_epilogue<false, true>(d, acc, m0, n0);
   } else {
     const G64Seg s1{d.lam, 0, d.H, 0, 0};
     g64_tile<false>(acc, sl, s1, g64_sm);                    // acc = lam Pinv'
