@@ -223,6 +223,17 @@ int nnmpc_qp_debug_factor_solve(nnmpc_qp* h, int32_t B, const float* dvec, const
  * replaced by 1e-30 and the kernels run on: sol_b is then finite or not, but never an answer), 0 otherwise.  In a solve the same
  * flag makes the problem's status NNMPC_ST_NUMERIC. */
 int nnmpc_qp_debug_factor_fail(nnmpc_qp* h, int32_t B, int32_t* fail);
+/* Kernel-level test hook: the first-set predictor alone.  Does what a solve does up to and including the predictor's launch -- x_unc for
+ * the window's columns, the bound states cleared, the extent kernel if asked, the launch itself through the solve's own launch code --
+ * whether or not a solve of this size would run the predictor, and hands back the bound states it wrote.  Host pointers,
+ * 1 <= B <= the segment size.  NNMPC_EINVAL when the handle has no inverse, no predictor window (n < 512, nu < 4 or > 64,
+ * asm_predict_iters < 0), or wide = 1 without the 1024-column window (n < 1024 or nu not a multiple of 4). */
+int nnmpc_qp_debug_predict(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub,
+                           int32_t iters,   /* as opts.asm_predict_iters: 0 adaptive, 1 .. 64 fixed */
+                           int32_t wide,    /* 0: 512-column window, 1: 1024-column window, -1: chosen by the extent kernel as a call does */
+                           uint8_t* state,  /* out [B][n]: 0 free, 1 upper, 2 lower */
+                           int32_t* info,   /* out [4]: W, problems per workgroup, the extent kernel's count (-1 if not run), window chosen (0 / 1) */
+                           double* L);      /* out: the step constant of that window, 1.05 lambda_max(D^-1/2 Pinv_WW D^-1/2) */
 
 /* Structured NN controller.  dims = [d_in, h1, ..., h_{L-1}, nu]; W[l] is
  * dims[l] x dims[l+1] row-major (Keras kernel layout), b[l] has dims[l+1]

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(64 * PRED_NW, 2) void asm_predict_k(AsmDev d, PredA
       const double* xr = d.xunc + p * d.np + 16 * (w * NT + jt) + 4 * lq;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        // (f16 range; a NaN stays a NaN: that problem is rejected elsewhere)
+        // (f16 range; a NaN becomes -60000 -- fmaxf returns the operand that is a number: that problem is rejected elsewhere)
         const pf32x2 xu = {fminf(fmaxf((float)xr[2 * h], -60000.f), 60000.f), fminf(fmaxf((float)xr[2 * h + 1], -60000.f), 60000.f)};
         sx[jt][pt][h] = __builtin_bit_cast(unsigned, __builtin_convertvector(xu, pf16x2));
         sm[jt][pt][h] = 0u;

@@ -1001,7 +1001,10 @@ int build_predictor(nnmpc_qp* h, const std::vector<double>& hh, int np, nnmpc_qp
   std::vector<double> v(W, 1.0), u(W), isd(W);
   for (int j = 0; j < W; ++j) isd[j] = 1.0 / std::sqrt(dg[j]);
   double lam = 0.0;
-  for (int itp = 0; itp < 200; ++itp) {
+  // (the change per step is no error bound: with the two largest eigenvalues a factor r apart the Rayleigh quotient still lacks
+  // ~ change r^2 / (1 - r^2).  Stopping at a change of 1e-6 left L short by 2e-5 on the CDU plant and, at the old cap of 200 steps,
+  // by 2.3e-3 on a plant with r = 0.9988 -- inside the 5 % margin, but not the lambda_max the step is documented to be)
+  for (int itp = 0; itp < 5000; ++itp) {
     double nv = 0.0;
     for (int i = 0; i < W; ++i) nv += v[i] * v[i];
     nv = std::sqrt(nv);
@@ -1014,7 +1017,7 @@ int build_predictor(nnmpc_qp* h, const std::vector<double>& hh, int np, nnmpc_qp
     }
     double num = 0.0;
     for (int i = 0; i < W; ++i) num += u[i] * v[i] / isd[i];
-    const bool conv = std::fabs(num - lam) <= 1e-6 * std::fabs(num);
+    const bool conv = std::fabs(num - lam) <= 1e-9 * std::fabs(num);
     lam = num;
     v = u;
     if (conv && itp > 8) break;
@@ -1035,6 +1038,46 @@ int build_predictor(nnmpc_qp* h, const std::vector<double>& hh, int np, nnmpc_qp
   if (!pw.Hf) { int rc = dev_alloc(h, (unsigned short**)&pw.Hf, hf.size()); if (rc) return rc; }
   HIPCHK(hipMemcpy(pw.Hf, hf.data(), hf.size() * 2, hipMemcpyHostToDevice));
   pw.L = L;
+  return 0;
+}
+
+// asm_extent_k over the last quarter of the 512-column window: *count = problems with a bound x_unc violates there (one 4-byte read-back).
+int predictor_extent(nnmpc_qp* h, const AsmDev& a, int nprob, int* count) {
+  hipStream_t s = h->stream;
+  HIPCHK(hipMemsetAsync(h->pred_cnt, 0, 4, s));
+  hipLaunchKernelGGL(asm_extent_k, dim3((nprob + 63) / 64), dim3(256), 0, s, a, PRED_W - PRED_W / 4, PRED_W, h->pred_cnt);
+  HIPCHK(hipMemcpyAsync(h->pin_cnt, h->pred_cnt, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(stream_sync(s));
+  *count = h->pin_cnt[0];
+  h->pin_cnt[0] = 0;
+  return 0;
+}
+
+// The one launch of asm_predict_k (solve_segment_asm and nnmpc_qp_debug_predict): its arguments -- the beta schedule, the adaptive
+// rule -- and the instance and grid that go with the window and nu.  iters_req: 0 adaptive (every workgroup between 8 and PRED_MAXIT),
+// 1 .. PRED_MAXIT fixed.  a: n, np, nu, nseg, lb, ub, xunc (the window's columns formed) and st (zeroed) are read.  *W_out, *MR_out:
+// the window, the problems per workgroup; *flops_per_it: the dense count of one iteration of one workgroup.
+int launch_predictor(nnmpc_qp* h, const AsmDev& a, int nprob, int iters_req, int wide, int* W_out, int* MR_out, double* flops_per_it) {
+  hipStream_t s = h->stream;
+  const int iters = iters_req == 0 ? (int)PRED_MAXIT : iters_req;
+  PredArgs pa;
+  { static const int f10 = getenv("NNMPC_PRED_FACTOR") ? atoi(getenv("NNMPC_PRED_FACTOR")) : 3; pa.fac10 = f10; }   // (the variable: diagnostics)
+  pa.iters = iters; pa.adaptive = iters_req == 0; pa.itsum = h->profiling ? h->pred_cnt + 1 : nullptr;
+  if (h->profiling) HIPCHK(hipMemsetAsync(h->pred_cnt + 1, 0, 4, s));
+  double t = 1.0;
+  for (int k = 0; k < iters; ++k) { const double tn = 0.5 * (1.0 + std::sqrt(1.0 + 4.0 * t * t)); pa.beta[k] = (float)((t - 1.0) / tn); t = tn; }
+  for (int k = iters; k < PRED_MAXIT; ++k) pa.beta[k] = 0.f;
+  const bool nu4 = h->nu % 4 == 0;
+  const int W = wide ? PRED_W2 : PRED_W, MR = (wide || !nu4) ? 32 : 64;
+  pa.Hf = h->pred[wide].Hf;
+  // (flops: the dense count -- every k-step of every iteration after the first; the iterations are summed on the device)
+  *flops_per_it = 2.0 * W * (double)W * MR;
+  *W_out = W; *MR_out = MR;
+  h->stats.asm_predict_launches += 1;
+  EvScope es(h, 10, 0.0);
+  if (wide) hipLaunchKernelGGL((asm_predict_k<8, 2>), dim3((nprob + 31) / 32), dim3(64 * PRED_NW), (pred_lds_bytes<8, 2>(h->nu)), s, a, pa);
+  else if (nu4) hipLaunchKernelGGL((asm_predict_k<4, 4>), dim3((nprob + 63) / 64), dim3(64 * PRED_NW), (pred_lds_bytes<4, 4>(h->nu)), s, a, pa);
+  else hipLaunchKernelGGL((asm_predict_k<4, 2, false>), dim3((nprob + 31) / 32), dim3(64 * PRED_NW), (pred_lds_bytes<4, 2>(h->nu)), s, a, pa);
   return 0;
 }
 
@@ -1104,13 +1147,6 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
     // the prediction takes the mean iteration count from 5.5 to 2, but a launch of asm_small_k lasts as long as its SLOWEST problem, and
     // that one keeps its ~25 iterations: 1.76 ms per step without, 1.94 with the predictor)
     if (iters > 0 && h->pred[0].L > 0.0 && !guess_dev && !small && !tail_only && Wx >= PRED_W) {
-      PredArgs pa;
-      { static const int f10 = getenv("NNMPC_PRED_FACTOR") ? atoi(getenv("NNMPC_PRED_FACTOR")) : 3; pa.fac10 = f10; }   // (the variable: diagnostics)
-      pa.iters = iters; pa.adaptive = iters_req == 0; pa.itsum = h->profiling ? h->pred_cnt + 1 : nullptr;
-      if (h->profiling) HIPCHK(hipMemsetAsync(h->pred_cnt + 1, 0, 4, s));
-      double t = 1.0;
-      for (int k = 0; k < iters; ++k) { const double tn = 0.5 * (1.0 + std::sqrt(1.0 + 4.0 * t * t)); pa.beta[k] = (float)((t - 1.0) / tn); t = tn; }
-      for (int k = iters; k < PRED_MAXIT; ++k) pa.beta[k] = 0.f;
       // Which window: the optimum's active bounds reach further along the horizon than the bounds x_unc violates.  When more than a
       // quarter of the problems already violate a bound in the last quarter of the 512-column window (CDU plant: 0.05 % at sx = 2,
       // 8 % at sx = 4, 46 % at sx = 6), the 1024-column instance names the sets -- four times the L2 traffic per problem and x_unc
@@ -1122,12 +1158,10 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       if (h->pred[1].L > 0.0 && lazy) {
         if (force_w >= 0) wide = force_w;
         else {
-          HIPCHK(hipMemsetAsync(h->pred_cnt, 0, 4, s));
-          hipLaunchKernelGGL(asm_extent_k, dim3((nprob + 63) / 64), dim3(256), 0, s, a, PRED_W - PRED_W / 4, PRED_W, h->pred_cnt);
-          HIPCHK(hipMemcpyAsync(h->pin_cnt, h->pred_cnt, 4, hipMemcpyDeviceToHost, s));
-          HIPCHK(stream_sync(s));
-          wide = h->pin_cnt[0] * 4 > nprob;
-          h->pin_cnt[0] = 0;
+          int count = 0;
+          const int rc = predictor_extent(h, a, nprob, &count);
+          if (rc) return rc;
+          wide = count * 4 > nprob;
         }
       }
       if (wide && Wx < PRED_W2) {
@@ -1135,16 +1169,9 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
         gemm64(h, h->asm_xunc + Wx, h->np, h->x0_64, h->ka, h->Kunc64 + (size_t)Wx * h->ka, h->ka, segp, PRED_W2 - Wx, h->ka);
         Wx = PRED_W2; a.Wx = Wx;
       }
-      const bool nu4 = h->nu % 4 == 0;
-      const int W = wide ? PRED_W2 : PRED_W, MR = (wide || !nu4) ? 32 : 64;
-      pa.Hf = h->pred[wide].Hf;
-      // (flops: the dense count -- every k-step of every iteration after the first; the iterations are summed on the device)
-      pred_flops_per_it = 2.0 * W * (double)W * MR;
-      h->stats.asm_predict_launches += 1;
-      EvScope es(h, 10, 0.0);
-      if (wide) hipLaunchKernelGGL((asm_predict_k<8, 2>), dim3((nprob + 31) / 32), dim3(64 * PRED_NW), (pred_lds_bytes<8, 2>(h->nu)), s, a, pa);
-      else if (nu4) hipLaunchKernelGGL((asm_predict_k<4, 4>), dim3((nprob + 63) / 64), dim3(64 * PRED_NW), (pred_lds_bytes<4, 4>(h->nu)), s, a, pa);
-      else hipLaunchKernelGGL((asm_predict_k<4, 2, false>), dim3((nprob + 31) / 32), dim3(64 * PRED_NW), (pred_lds_bytes<4, 2>(h->nu)), s, a, pa);
+      int W = 0, MR = 0;
+      const int rc = launch_predictor(h, a, nprob, iters_req, wide, &W, &MR, &pred_flops_per_it);
+      if (rc) return rc;
       a.pred_w = W;
       { static const int pf = getenv("NNMPC_PRED_F64") ? atoi(getenv("NNMPC_PRED_F64")) : 0; a.pred_f64 = pf; }   // (the variable: diagnostics, A/B)
     }
@@ -2196,6 +2223,55 @@ int nnmpc_qp_debug_factor_fail(nnmpc_qp* h, int32_t B, int32_t* fail) {
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(stream_sync(h->stream));
   HIPCHK(hipMemcpy(fail, h->d.fail, (size_t)B * 4, hipMemcpyDeviceToHost));
+  return NNMPC_OK;
+}
+
+int nnmpc_qp_debug_predict(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub, int32_t iters, int32_t wide,
+                           uint8_t* state, int32_t* info, double* L) {
+  if (!h || B <= 0 || B > h->seg_max || !x0 || !lb || !ub || !state || !info || !L || iters < 0 || iters > PRED_MAXIT || wide < -1 || wide > 1) {
+    set_error("debug_predict: bad arguments"); return NNMPC_EINVAL;
+  }
+  if (!h->have_inverse) { set_error("debug_predict: needs nnmpc_qp_set_inverse first"); return NNMPC_EINVAL; }
+  if (!(h->pred[0].L > 0.0)) { set_error("debug_predict: the handle has no predictor window (n = %d, nu = %d)", h->n, h->nu); return NNMPC_EINVAL; }
+  if (wide == 1 && !(h->pred[1].L > 0.0)) { set_error("debug_predict: the handle has no 1024-column window (n = %d, nu = %d)", h->n, h->nu); return NNMPC_EINVAL; }
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const int nprob = B, segp = ((nprob + 127) / 128) * 128;
+  HIPCHK(hipMemcpyAsync(h->in_stage, x0, (size_t)nprob * h->n_aug * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->lb_d, lb, (size_t)nprob * h->nu * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->ub_d, ub, (size_t)nprob * h->nu * 8, hipMemcpyHostToDevice, s));
+  // what solve_segment_asm does up to the predictor's launch: x0 padded, x_unc for the window's columns, the bound states cleared
+  hipLaunchKernelGGL(pad_x0_k, dim3(512), dim3(256), 0, s, h->x0_64, h->x0_32, h->in_stage, nprob, h->n_aug, h->ka, segp);
+  int Wx = PRED_W;
+  gemm64(h, h->asm_xunc, h->np, h->x0_64, h->ka, h->Kunc64, h->ka, segp, Wx, h->ka);
+  AsmDev a;
+  memset(&a, 0, sizeof(a));
+  a.n = h->n; a.np = h->np; a.nu = h->nu; a.nseg = nprob; a.Wx = Wx;
+  a.lb = h->lb_d; a.ub = h->ub_d; a.xunc = h->asm_xunc; a.st = h->asm_st;
+  HIPCHK(hipMemsetAsync(h->asm_st, 0, (size_t)nprob * h->n, s));
+  int count = -1;
+  if (wide < 0) {
+    wide = 0;
+    if (h->pred[1].L > 0.0) {
+      const int rc = predictor_extent(h, a, nprob, &count);
+      if (rc) return rc;
+      wide = count * 4 > nprob;
+    }
+  }
+  if (wide) {
+    gemm64(h, h->asm_xunc + Wx, h->np, h->x0_64, h->ka, h->Kunc64 + (size_t)Wx * h->ka, h->ka, segp, PRED_W2 - Wx, h->ka);
+    Wx = PRED_W2; a.Wx = Wx;
+  }
+  int W = 0, MR = 0;
+  double flops_per_it = 0.0;
+  const int rc = launch_predictor(h, a, nprob, iters, wide, &W, &MR, &flops_per_it);
+  if (rc) return rc;
+  HIPCHK(stream_sync(s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(state, h->asm_st, (size_t)nprob * h->n, hipMemcpyDeviceToHost));
+  info[0] = W; info[1] = MR; info[2] = count; info[3] = wide;
+  *L = h->pred[wide].L;
+  if (h->profiling) ev_collect(h);
   return NNMPC_OK;
 }
 

@@ -260,6 +260,23 @@ class BatchedBoxQP:
             "nnmpc_qp_debug_factor_solve")
         return sol
 
+    def debug_predict(self, x0, lb, ub, iters=0, wide=0):
+        """Kernel-level hook: the first-set predictor alone (csrc/qp_predict.h), through the launch code of a solve.
+        iters: 0 adaptive, 1 .. 64 fixed; wide: 0 the 512-column window, 1 the 1024-column one, -1 chosen by the extent kernel.
+        Returns dict(state (B, n) uint8 -- 0 free, 1 upper, 2 lower --, W, MR (problems per workgroup), count (the extent kernel's,
+        -1 if it did not run), wide (the window chosen), L (that window's step constant))."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, self.n_aug)
+        B = x0.shape[0]
+        lb = np.ascontiguousarray(np.broadcast_to(np.asarray(lb, np.float64).reshape(-1, self.nu), (B, self.nu)))
+        ub = np.ascontiguousarray(np.broadcast_to(np.asarray(ub, np.float64).reshape(-1, self.nu), (B, self.nu)))
+        state = np.full((B, self.n), 255, np.uint8)
+        info = np.full(4, -9, np.int32)
+        L = C.c_double(0.0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_qp_debug_predict(self._h, B, p(x0), p(lb), p(ub), int(iters), int(wide), p(state), p(info),
+                                                    C.byref(L)), "nnmpc_qp_debug_predict")
+        return dict(state=state, W=int(info[0]), MR=int(info[1]), count=int(info[2]), wide=int(info[3]), L=float(L.value))
+
     def debug_factor_fail(self, B):
         """(B,) int32: 1 where the last debug_factor_solve met a non-positive pivot in that row's factorisation."""
         fail = np.empty(B, np.int32)

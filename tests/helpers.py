@@ -1091,3 +1091,399 @@ def chain_step_reference(c, rec, Xs, Us, D):
     out["x"] = dict(got=rec["x"][1:], ref=x1.reshape(T - 1, nc, nx), bound=bnd.reshape(T - 1, nc, nx), mask=one[1:])
     out["uprev"] = dict(got=rec["uprev"][1:], ref=rec["u"][:-1], bound=np.zeros((T - 1, nc, nu)), mask=one[1:])
     return out
+
+
+# ---- first-set predictor (csrc/qp_predict.h) through nnmpc_qp_debug_predict: tests/test_predict_kernel_gpu.py,
+# tests/test_cpu_predict_inputs.py ------------------------------------------------------------------------------------------------
+# pred_reference reproduces what asm_predict_k STORES (bf16 H', f16 x_unc, f32 bounds, bf16 y and nu between iterations, the restart
+# and the adaptive count by group of MR rows) and nothing of how it computes; it imports nothing from the package.
+
+PRED_COUNTS = (1, 2, 3, 8, 24, 64, 0)          # iterations: fixed, and 0 = adaptive
+PRED_FAC10 = 3
+# case -> (nu, N); n = nu N.  Plants of the form synthetic.plant returns: Nx = 12, Ny = 6, rho 0.97, the CDU tuning (Q = 2 C'C, R = 0.1 I, S = 0)
+PRED_CASES = {
+    "a": (8, 64),       # <4,4>: n = W exactly; per32 bound reuse
+    "b": (32, 16),      # <4,4>: ldb = 36; one stage per 32 columns
+    "c": (4, 128),      # <4,4>: the smallest nu; every lane one whole stage
+    "d": (12, 43),      # <4,4>: NU4 but 32 % nu != 0 (no reuse across column tiles); n = 516 > W: columns 512 .. 515 stay 0
+    "e": (64, 8),       # <4,4>: the largest nu; the largest LDS image
+    "f": (6, 86),       # <4,2,false>: the per-column bound lookup with its wrap; MR = 32
+    "g": (5, 103),      # <4,2,false>: n = 515 is no multiple of 4: the byte-store path of the states
+    "h": (7, 74),       # <4,2,false>: wrap at an odd nu
+    "i": (16, 64),      # n = 1024: <8,2> (wide = 1) and <4,4>
+}
+# plant seeds 300 + index; cases e and i moved on by 10: chosen with the reference alone so that no restart sum that decides a kb within
+# the first 24 iterations is smaller than 1e-3 of its terms and the two arithmetic variants agree at every count but 64
+PRED_SEEDS = dict({c: 300 + k for k, c in enumerate(sorted(PRED_CASES))}, e=314, i=318)
+PRED_MIX_SX = (0.5, 2.0, 4.0)                  # state spread of the three groups of the 2 MR + 2 batch
+PRED_SX = 6.0                                  # state spread of the B = 1, MR - 1, MR + 1 batches
+PRED_TIGHT_B = 2
+PRED_TIGHT = 0.05                              # box scale of the "tight" batch
+PRED_SPECIAL = dict(tiny=3, wide=5, steady=7)  # rows of the MR + 1 batch: a box of +-0.02, one of +-50, x0 = 0 with two inputs exactly on a bound
+
+
+def pred_instance(nu, wide):
+    """(W, MR) of the instance the library launches."""
+    return (1024, 32) if wide else (512, 64 if nu % 4 == 0 else 32)
+
+
+def pred_plant(nu, N, seed, rho=0.97):
+    """synthetic.plant's construction at Nx = 12, Ny = 6 with the CDU tuning."""
+    rng = np.random.default_rng(seed)
+    Nx, Ny = 12, 6
+    W = rng.standard_normal((Nx, Nx)) / np.sqrt(Nx)
+    A = rho * W / np.max(np.abs(np.linalg.eigvals(W)))
+    B = rng.standard_normal((Nx, nu)) / np.sqrt(Nx)
+    Cm = rng.standard_normal((Ny, Nx)) / np.sqrt(Nx)
+    return dict(A=A, B=B, C=Cm, Q=2.0 * Cm.T @ Cm, R=0.1 * np.eye(nu), S=0.0 * np.eye(nu), N=N, ulb=-np.ones((nu, 1)), uub=np.ones((nu, 1)))
+
+
+_PRED_CASE_CACHE = {}
+
+
+def pred_case(name):
+    """Plant, (P, tq, nu) of build_regulator_matrices and Pinv, Kunc exactly as BatchedBoxQP forms them for Kunc="auto"."""
+    if name not in _PRED_CASE_CACHE:
+        import scipy.linalg as sla
+        from industrial_nnmpc_2021_amd.linearMPC_build import build_regulator_matrices
+        nu, N = PRED_CASES[name]
+        pl = pred_plant(nu, N, PRED_SEEDS[name])
+        P, tq, nu2 = build_regulator_matrices(pl)
+        assert nu2 == nu and P.shape[0] == nu * N
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        tq = np.ascontiguousarray(tq, dtype=np.float64)
+        Ps = np.tril(P) + np.tril(P, -1).T
+        cf = sla.cho_factor(Ps, lower=True)
+        Kunc = -sla.cho_solve(cf, tq)
+        Pinv = sla.cho_solve(cf, np.eye(nu * N))
+        _PRED_CASE_CACHE[name] = dict(name=name, pl=pl, P=P, Ps=Ps, tq=tq, nu=nu, N=N, n=nu * N, Kunc=Kunc, Pinv=Pinv)
+    return _PRED_CASE_CACHE[name]
+
+
+def pred_batches(c, MR):
+    """name -> (x0, lb, ub): B = 1, MR - 1, MR + 1 (with the PRED_SPECIAL rows; its second group is one real row and MR - 1 clones)
+    at sx = PRED_SX, 2 MR + 2 with sx = 0.5 / 2 / 4 by group, and B = 2 at sx = 4 with both boxes scaled by PRED_TIGHT: on this small
+    plant the bounds x_unc violates stay within the first stages whatever sx is (at most ~40 per problem at sx = 4), so that the adaptive
+    count of every group of the other batches is at or near its floor of 8; the tight boxes take it well above (the one group of that batch is two problems and MR - 2 clones of the second,
+    which count like problems; only two rows, because next to a tight box most of a row's w lies within PRED_TAU max|w| of a bound)."""
+    pl, seed = c["pl"], 10 * PRED_SEEDS[c["name"]]
+    out = {}
+    for k, (tag, B) in enumerate((("b1", 1), ("mr-1", MR - 1), ("mr+1", MR + 1))):
+        _, x0, lb, ub = batch_inputs(pl, B, seed + k, PRED_SX)
+        if tag == "mr+1":
+            t, w, s = PRED_SPECIAL["tiny"], PRED_SPECIAL["wide"], PRED_SPECIAL["steady"]
+            lb[t], ub[t] = -0.02, 0.02
+            lb[w], ub[w] = -50.0, 50.0
+            x0[s] = 0.0
+            ub[s, 0] = 0.0                     # us on its upper bound for input 0, on its lower bound for input 1
+            lb[s, 1] = 0.0
+        out[tag] = (x0, lb, ub)
+    parts = [batch_inputs(pl, b, seed + 3 + g, sx)[1:] for g, (b, sx) in enumerate(zip((MR, MR, 2), PRED_MIX_SX))]
+    out["mix"] = tuple(np.ascontiguousarray(np.concatenate([p[i] for p in parts], axis=0)) for i in range(3))
+    _, x0, lb, ub = batch_inputs(pl, PRED_TIGHT_B, seed + 6, PRED_MIX_SX[2])
+    out["tight"] = (x0, PRED_TIGHT * lb, PRED_TIGHT * ub)
+    return out
+
+
+def pred_beta(iters=64):
+    """beta[k] of the t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2 recursion, as floats."""
+    beta, t = np.zeros(64, np.float32), 1.0
+    for k in range(iters):
+        tn = 0.5 * (1.0 + np.sqrt(1.0 + 4.0 * t * t))
+        beta[k] = np.float32((t - 1.0) / tn)
+        t = tn
+    return beta
+
+
+def pred_hprime(Pinv, W, L):
+    """H'[j][k] = bf16_rne(float(Pinv[j][k] / (L dg[k]))) over the window, as float32 (Pinv symmetrised as nnmpc_qp_set_inverse does)."""
+    hh = 0.5 * (Pinv[:W, :W] + Pinv[:W, :W].T)
+    return bf16_round((hh / (L * np.diag(hh))[None, :]).astype(np.float32))
+
+
+def pred_xunc_f16(xunc):
+    """x_unc as the kernel keeps it: f32, clamped to +-60000 by fminf(fmaxf(x, -60000), 60000) -- C's fmaxf returns the other operand
+    for a NaN, so a NaN becomes -60000 --, then f16.  Returned as float32."""
+    x = np.asarray(xunc, np.float64).astype(np.float32)
+    x = np.fmin(np.fmax(x, np.float32(-60000.0)), np.float32(60000.0))
+    return x.astype(np.float16).astype(np.float32)
+
+
+def pred_reference(Pinv, xunc, lb, ub, nu, W, MR, L, counts=PRED_COUNTS, fac10=PRED_FAC10, variant="f64"):
+    """The iteration of asm_predict_k on B problems with its storage roundings; xunc (B, >= W) = Kunc x0 in fp64, lb / ub (B, nu).
+
+    Per iteration  w = y + (x_unc - H' y),  nu+ = w - clip(w, lb, ub),  y+ = nu+ + beta[kb] (nu+ - nu),  y and nu rounded to bf16
+    where the kernel stores them.  By group of MR consecutive rows (the last group filled with clones of the last problem, which
+    count like problems): kb goes back to 0 at iteration it when sum (y - nu+)(nu+ - nu) of iteration it - 1 was positive; the
+    adaptive count is min(64, max(8, fac10 nviol / (10 MR))) with nviol the non-zeros of the bf16 nu after iteration 0.
+    A fixed count of k iterations is the first k of the same trajectory (the beta table does not depend on the count).
+
+    variant "f64": H' y and the elementwise part in fp64 (the reference); "f32": H' y accumulated in f32 in ascending k-steps of
+    32, elementwise part in f32 (only measures how much arithmetic freedom the comparison must tolerate).
+
+    Returns {count: dict(state (B, W) uint8, margin (B, W))} -- margin = min(|w - lb|, |w - ub|) / max(1, max_j |w_pj|) of the
+    last iteration -- plus "nit" (groups,), "nviol" (groups,), "rsum_rel" (groups, 64): restart sum of every iteration over the sum
+    of its terms' absolute values (1 where every term is zero; NaN beyond the 64 iterations run)."""
+    B = xunc.shape[0]
+    ft = np.float64 if variant == "f64" else np.float32
+    Hp = pred_hprime(Pinv, W, L)
+    HpT = np.ascontiguousarray(Hp.T.astype(ft))
+    cols = np.arange(W) % nu
+    xu_all = pred_xunc_f16(xunc[:, :W]).astype(ft)
+    lb_all = np.asarray(lb, np.float64).astype(np.float32)[:, cols].astype(ft)
+    ub_all = np.asarray(ub, np.float64).astype(np.float32)[:, cols].astype(ft)
+    beta = pred_beta(64).astype(ft)
+    ng = -(-B // MR)
+    fixed = sorted(k for k in counts if k > 0)
+    out = {k: dict(state=np.zeros((B, W), np.uint8), margin=np.zeros((B, W))) for k in counts}
+    nits, nviols, rrel = np.zeros(ng, int), np.zeros(ng, int), np.full((ng, 64), np.nan)
+    for g in range(ng):
+        rows = np.minimum(np.arange(g * MR, (g + 1) * MR), B - 1)           # min(p0 + r, nseg - 1)
+        real = np.arange(g * MR, min((g + 1) * MR, B)) - g * MR
+        xu, lbg, ubg = xu_all[rows], lb_all[rows], ub_all[rows]
+        y = np.zeros((MR, W), ft)
+        nuv = np.zeros((MR, W), ft)
+        kb, rprev, nit = 0, 0.0, 64
+        for it in range(64):
+            if it > 0:
+                if variant == "f64":
+                    acc = y @ HpT
+                else:
+                    acc = np.zeros((MR, W), np.float32)
+                    for ks in range(0, W, 32):
+                        acc += y[:, ks:ks + 32] @ HpT[ks:ks + 32]
+                kb = 0 if rprev > 0.0 else kb + 1
+            else:
+                acc = np.zeros((MR, W), ft)
+            w = y + (xu - acc)
+            nun = w - np.minimum(np.maximum(w, lbg), ubg)
+            dn = nun - nuv
+            yn = beta[kb] * dn + nun
+            terms = ((y - nun) * dn).astype(np.float64)
+            rprev = float(terms.sum())
+            den = float(np.abs(terms).sum())
+            rrel[g, it] = rprev / den if den > 0 else 1.0
+            y = bf16_round(yn).astype(ft)
+            nuv = bf16_round(nun).astype(ft)
+            if it == 0:
+                nviols[g] = int((nuv != 0).sum())
+                nit = min(64, max(8, (fac10 * nviols[g]) // (10 * MR)))
+                nits[g] = nit
+            for k in ([it + 1] if it + 1 in fixed else []) + ([0] if 0 in counts and it + 1 == nit else []):
+                st = np.where(nuv > 0, 1, np.where(nuv < 0, 2, 0)).astype(np.uint8)
+                wd = w.astype(np.float64)
+                mg = np.minimum(np.abs(wd - lbg), np.abs(wd - ubg)) / np.maximum(1.0, np.abs(wd).max(axis=1, keepdims=True))
+                out[k]["state"][g * MR + real] = st[real]
+                out[k]["margin"][g * MR + real] = mg[real]
+    out["nit"], out["nviol"], out["rsum_rel"] = nits, nviols, rrel
+    return out
+
+
+# The entrywise comparison: an entry is DECIDED when the reference's margin exceeds PRED_TAU; on every decided entry the kernel's
+# state equals the reference's.  PRED_TAU_MEASURED is the smallest power of two at which the reference's two arithmetic variants
+# name the same state on every decided entry of every case, batch and count (tests/test_cpu_predict_inputs.py measures it again and
+# asserts it has not grown); the factor 4 is for the MFMA's internal summation order, a third variant nobody has observed.
+PRED_TAU_MEASURED = 2.0 ** -12
+PRED_TAU_FACTOR = 4.0
+PRED_TAU = PRED_TAU_FACTOR * PRED_TAU_MEASURED
+PRED_MAX_UNDECIDED = 0.02           # caps on the inputs, asserted on the reference alone
+PRED_MIN_NONFREE = 0.03
+PRED_MIN_RSUM_REL = 1e-3
+
+
+# (case, wide, count) -> the caps of the entrywise comparison the pair misses on the reference alone (pred_failed_conditions), whatever
+# the seed: on this small plant the bounds that matter sit in the first few stages, so that fewer than 3 % of a window are non-free
+# in the first iterations ("nonfree"), and the iterates of rows far from the origin come to rest within PRED_TAU max|w| of many bounds
+# ("und").  Those pairs are compared entry by entry all the same AND by the quality of their sets.  At 64 iterations the two
+# arithmetic variants of the reference differ on decided entries ("variants") or a restart sum is too close to zero ("rsum"): those are
+# compared by quality alone.  tests/test_cpu_predict_inputs.py asserts the list entry for entry.
+PRED_FALLBACK = {
+    ('a', 0, 64): ('variants', 'rsum', 'und'),
+    ('b', 0, 1): ('nonfree',),
+    ('b', 0, 2): ('nonfree',),
+    ('b', 0, 64): ('variants', 'rsum'),
+    ('c', 0, 1): ('nonfree',),
+    ('c', 0, 2): ('nonfree',),
+    ('c', 0, 3): ('nonfree',),
+    ('c', 0, 64): ('variants', 'und'),
+    ('d', 0, 64): ('variants', 'und'),
+    ('e', 0, 1): ('nonfree',),
+    ('e', 0, 2): ('nonfree',),
+    ('e', 0, 3): ('nonfree',),
+    ('e', 0, 8): ('nonfree',),
+    ('e', 0, 0): ('nonfree',),
+    ('f', 0, 1): ('nonfree',),
+    ('f', 0, 2): ('nonfree',),
+    ('f', 0, 3): ('nonfree',),
+    ('f', 0, 24): ('und',),
+    ('f', 0, 64): ('und',),
+    ('f', 0, 0): ('und',),
+    ('g', 0, 1): ('nonfree',),
+    ('g', 0, 2): ('nonfree',),
+    ('g', 0, 3): ('nonfree',),
+    ('g', 0, 8): ('und', 'nonfree'),
+    ('g', 0, 24): ('und',),
+    ('g', 0, 64): ('und',),
+    ('g', 0, 0): ('und', 'nonfree'),
+    ('h', 0, 24): ('und',),
+    ('h', 0, 64): ('variants', 'und'),
+    ('h', 0, 0): ('und',),
+    ('i', 0, 1): ('nonfree',),
+    ('i', 0, 64): ('variants', 'rsum', 'und'),
+    ('i', 1, 1): ('nonfree',),
+    ('i', 1, 2): ('nonfree',),
+    ('i', 1, 3): ('nonfree',),
+    ('i', 1, 8): ('nonfree',),
+    ('i', 1, 24): ('und', 'nonfree'),
+    ('i', 1, 64): ('variants', 'und'),
+    ('i', 1, 0): ('und', 'nonfree'),
+}
+
+
+def pred_hamming(state, ref_state):
+    """Per row: entries in which two sets of bound states differ."""
+    return (np.asarray(state) != np.asarray(ref_state)).sum(axis=1)
+
+
+def pred_windows():
+    """[(case name, wide)] of every instance the tests launch."""
+    return [(name, w) for name in sorted(PRED_CASES) for w in ((0, 1) if name == "i" else (0,))]
+
+
+def pred_lambda(Pinv, W):
+    """lambda_max(D^-1/2 Pinv_WW D^-1/2) by eigvalsh."""
+    hh = 0.5 * (Pinv[:W, :W] + Pinv[:W, :W].T)
+    isd = 1.0 / np.sqrt(np.diag(hh))
+    return float(np.linalg.eigvalsh(hh * isd[:, None] * isd[None, :]).max())
+
+
+def pred_power_iteration(Pinv, W):
+    """build_predictor's loop, step for step: L = 1.05 lam."""
+    hh = 0.5 * (Pinv[:W, :W] + Pinv[:W, :W].T)
+    isd = 1.0 / np.sqrt(np.diag(hh))
+    v, lam = np.ones(W), 0.0
+    for itp in range(5000):
+        v = v * isd / np.sqrt((v * v).sum())
+        u = (hh @ v) * isd
+        num = float((u * v / isd).sum())
+        conv = abs(num - lam) <= 1e-9 * abs(num)
+        lam, v = num, u
+        if conv and itp > 8:
+            break
+    return 1.05 * lam
+
+
+def pred_references(c, wide, L, variant="f64", batches=None):
+    """{batch: pred_reference of it} of one case and window."""
+    W, MR = pred_instance(c["nu"], wide)
+    out = {}
+    for tag, (x0, lb, ub) in pred_batches(c, MR).items():
+        if batches is None or tag in batches:
+            out[tag] = pred_reference(c["Pinv"], x0 @ c["Kunc"].T, lb, ub, c["nu"], W, MR, L, variant=variant)
+    return out
+
+
+def pred_deciding_rsum(ref, k):
+    """Smallest |restart sum| / sum |terms| among the sums that decide a kb when k iterations run (0: each group's adaptive count):
+    the sums of the iterations 0 .. k - 2."""
+    return min(float(np.abs(ref["rsum_rel"][g, :max((k if k else ref["nit"][g]) - 1, 0)]).min(initial=1.0)) for g in range(len(ref["nit"])))
+
+
+def pred_pair_conditions(r64, r32, k, tau=None, tau_measured=None):
+    """The conditions of one (case, window, count) over all batches of the case, on the reference alone.  r64 / r32: pred_references
+    of the two variants.  Returns dict(und, nonfree, up, lo, empty, rsum, need, vdiff): undecided share; non-free share, upper / lower
+    counts of the decided entries; rows with an empty set; smallest deciding restart sum of either variant; largest margin of an
+    entry on which the variants differ; entries decided under tau_measured on which they differ."""
+    tau = PRED_TAU if tau is None else tau
+    tau_measured = PRED_TAU_MEASURED if tau_measured is None else tau_measured
+    cat = lambda r, key: np.concatenate([r[t][k][key] for t in r64])
+    s, m, s2 = cat(r64, "state"), cat(r64, "margin"), cat(r32, "state")
+    dec, diff = m > tau, s != s2
+    return dict(und=float(1.0 - dec.mean()), nonfree=float((s[dec] != 0).mean()), up=int((s[dec] == 1).sum()), lo=int((s[dec] == 2).sum()),
+                empty=int(((s != 0).sum(axis=1) == 0).sum()),
+                rsum=min(min(pred_deciding_rsum(r[t], k) for t in r64) for r in (r64, r32)),
+                need=float(m[diff].max()) if diff.any() else 0.0, vdiff=int((diff & (m > tau_measured)).sum()))
+
+
+def pred_failed_conditions(cond):
+    """Names of the conditions a pair misses: "variants" and "rsum" make the entrywise comparison itself unsound (the pair is compared
+    by quality alone); "und", "nonfree", "signs", "empty" only thin it out (the pair is compared entry by entry AND by quality)."""
+    f = []
+    if cond["vdiff"]:
+        f.append("variants")
+    if cond["rsum"] < PRED_MIN_RSUM_REL:
+        f.append("rsum")
+    if cond["und"] > PRED_MAX_UNDECIDED:
+        f.append("und")
+    if cond["nonfree"] < PRED_MIN_NONFREE:
+        f.append("nonfree")
+    if not (cond["up"] and cond["lo"]):
+        f.append("signs")
+    if not cond["empty"]:
+        f.append("empty")
+    return f
+
+
+PRED_QUALITY_BATCH = "mix"          # the fallback rule's eight rows: the first eight of this batch's second group (sx = 2: what the figures of
+                                    # csrc/qp_predict.h were measured at; from sx = 6 the iteration takes 64 steps to come as close)
+PRED_QUALITY_ROWS = 8
+PRED_GOLDEN = "predict_oracle_sets.npz"
+
+
+def pred_oracle_states(c, wide):
+    """(8, W) uint8 bound states of the optimum inside the window for the fallback rule's rows, by oracle.qp.solve_exact_box."""
+    W, MR = pred_instance(c["nu"], wide)
+    x0, lb, ub = pred_batches(c, MR)[PRED_QUALITY_BATCH]
+    n = c["n"]
+    act = np.zeros((PRED_QUALITY_ROWS, 2 * n), bool)
+    for r, (_, a) in enumerate(oracle_box_rows(c["Ps"], c["tq"], c["nu"], c["N"], x0, lb, ub, range(MR, MR + PRED_QUALITY_ROWS))):
+        act[r, a] = True
+    return active_to_state(act, c["nu"])[:, :W]
+
+
+def pred_golden_states(name, wide):
+    """The same states from tests/golden (tests/test_cpu_predict_inputs.py holds the file to the oracle)."""
+    import os
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", PRED_GOLDEN)) as f:
+        return f[f"{name}{wide}"]
+
+
+def pred_quality(state, opt, MR):
+    """Mean Hamming distance of predicted sets from the optimum's sets inside the window over the fallback rule's rows."""
+    return float(pred_hamming(state[MR:MR + PRED_QUALITY_ROWS, :opt.shape[1]], opt).mean())
+
+
+def pred_quality_allowance(q64, q32):
+    """What the kernel's figure may exceed the worse variant's by: twice the variants' own difference, one bound per four problems at least."""
+    return max(2.0 * abs(q64 - q32), 0.25)
+
+
+def pred_nonfinite_batch(c, MR):
+    """The MR - 1 batch (one group) with row 2 given a NaN in x0 and row 4 scaled so that |x_unc| passes 60000."""
+    x0, lb, ub = (a.copy() for a in pred_batches(c, MR)["mr-1"])
+    x0[2, 1] = np.nan
+    x0[4] *= 2.0e5 / np.abs(x0[4] @ c["Kunc"].T).max()
+    return x0, lb, ub
+
+
+PRED_NONFINITE_COUNTS = (1, 3, 8)
+PRED_NONFINITE_ROWS = (2, 4)
+
+
+def pred_extent_batches(c):
+    """Case i: two batches of 8 rows on either side of asm_extent_k's threshold count 4 > B.  On this plant no ordinary row violates a
+    bound in the columns [384, 512) -- x_unc is 0 that far out --; a row whose box [-2, -0.5] does not hold 0 does in every column.
+    -> {"narrow": 2 such rows, "wide": 3}."""
+    out = {}
+    for tag, k in (("narrow", 2), ("wide", 3)):
+        _, x0, lb, ub = batch_inputs(c["pl"], 8, 10 * PRED_SEEDS[c["name"]] + 8, 2.0)
+        lb[1:1 + k], ub[1:1 + k] = -2.0, -0.5
+        out[tag] = (x0, lb, ub)
+    return out
+
+
+def pred_extent_count(c, x0, lb, ub):
+    """Rows with a violated bound in the columns [384, 512) of x_unc (fp64)."""
+    cols = np.arange(384, 512)
+    xu = (x0 @ c["Kunc"].T)[:, cols]
+    return int(((xu > ub[:, cols % c["nu"]]) | (xu < lb[:, cols % c["nu"]])).any(axis=1).sum())

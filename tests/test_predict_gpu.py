@@ -42,7 +42,9 @@ def test_predictor_changes_rounds_not_results_mid_size():
 
 
 def test_predictor_is_skipped_where_it_does_not_apply():
-    """A caller's guess, a call that goes to the device tail, a small problem (n < 512) and nu not a multiple of 4 run without it."""
+    """A caller's guess, a call that goes to the device tail and a small problem (n < 512) run without it.  (nu >= 4 that is no
+    multiple of 4 runs WITH it, through asm_predict_k<4, 2, false>, once n is past the one-wave path of small problems:
+    tests/test_predict_kernel_gpu.py::test_production_launch_of_the_per_column_instance.)"""
     from industrial_nnmpc_2021_amd.qp import BatchedBoxQP
     pl, P, tq, nu = _plant("mid_cdu")
     s, x0, lb, ub = batch_inputs(pl, 64, 5, 2.0)
