@@ -13,12 +13,9 @@
 #include <chrono>
 #include <cmath>
 #include <vector>
-#include "../../include/nnmpc.h"
-#include "common.h"
+#include "dev_res.h"
 
 using namespace nnmpc;
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(e_)); return NNMPC_EHIP; } } while (0)
 
 namespace {
 
@@ -335,35 +332,8 @@ struct nnmpc_chain {
   hipStream_t stream = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   double total_ms = 0.0, solve_ms = 0.0;
-  std::vector<void*> allocs;
-  // grow-only staging for host-pointer runs
-  void* stage[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t stage_cap[7] = {0, 0, 0, 0, 0, 0, 0};
+  DevRes res{7};                                            // owns all of it; its slots: staging for host-pointer runs
 };
-
-namespace {
-template <class T>
-int chain_alloc(nnmpc_chain* c, T** p, size_t count) {
-  void* q = nullptr;
-  const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-  if (e != hipSuccess) { set_error("hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e)); return NNMPC_ENOMEM; }
-  hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(T));
-  c->allocs.push_back(q);
-  *p = (T*)q;
-  return 0;
-}
-template <class T>
-int chain_stage(nnmpc_chain* c, int which, T** out, size_t bytes) {
-  if (c->stage_cap[which] < bytes) {
-    if (c->stage[which]) { hipFree(c->stage[which]); c->stage[which] = nullptr; c->stage_cap[which] = 0; }
-    const hipError_t e = hipMalloc(&c->stage[which], bytes + 256);
-    if (e != hipSuccess) { c->stage[which] = nullptr; set_error("hipMalloc(%zu bytes of staging): %s", bytes, hipGetErrorString(e)); return NNMPC_ENOMEM; }
-    c->stage_cap[which] = bytes + 256;
-  }
-  *out = (T*)c->stage[which];
-  return 0;
-}
-}  // namespace
 
 extern "C" {
 
@@ -380,48 +350,42 @@ int nnmpc_chain_create(nnmpc_chain** out, nnmpc_qp* qp, int32_t nc, int32_t nx, 
     set_error("nnmpc_chain_create: regulator has nu=%d n_aug=%d, chains need nu=%d n_aug=nx+nu=%d", qnu, qnaug, nu, nx + nu);
     return NNMPC_EINVAL;
   }
-  nnmpc_chain* c = new nnmpc_chain();
+  GUARD_BEGIN
+  Building<nnmpc_chain, nnmpc_chain_destroy> guard(new nnmpc_chain());   // released into *out at the end; destroyed on any other way out
+  nnmpc_chain* c = guard.get();
+  DevRes& res = c->res;
   c->qp = qp; c->nc = nc; c->nx = nx; c->nu = nu; c->nd = nd; c->n = n; c->words = (2 * n + 31) / 32;
-  if (hipGetDevice(&c->device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess ||
-      hipEventCreate(&c->e0) != hipSuccess || hipEventCreate(&c->e1) != hipSuccess) {
-    set_error("nnmpc_chain_create: no HIP device / stream"); nnmpc_chain_destroy(c); return NNMPC_EHIP;
-  }
+  HIPCHK(hipGetDevice(&c->device));
+  res.device = c->device;
+  if (int rc = res.stream(&c->stream)) return rc;
+  if (int rc = res.event(&c->e0)) return rc;
+  if (int rc = res.event(&c->e1)) return rc;
   const int nzz = nx + nu + nd;
-  int rc = 0;
-#define A_(ptr, cnt) if (!rc) rc = chain_alloc(c, &(ptr), (size_t)(cnt))
-  A_(c->Mt, (size_t)nzz * nx); A_(c->ulb, nu); A_(c->uub, nu); A_(c->x0, nx); A_(c->uprev0, nu);
-  A_(c->x, (size_t)nc * nx); A_(c->uprev, (size_t)nc * nu);
-  A_(c->qx0, (size_t)nc * (nx + nu)); A_(c->lb, (size_t)nc * nu); A_(c->ub, (size_t)nc * nu); A_(c->first, (size_t)nc * nu);
-  A_(c->act, (size_t)nc * c->words); A_(c->status, nc); A_(c->guess, (size_t)nc * n);
-#undef A_
-  if (rc) { nnmpc_chain_destroy(c); return rc; }
   std::vector<double> mt((size_t)nzz * nx);
   for (int i = 0; i < nx; ++i) {
     for (int j = 0; j < nx; ++j) mt[(size_t)j * nx + i] = A[(size_t)i * nx + j];
     for (int j = 0; j < nu; ++j) mt[(size_t)(nx + j) * nx + i] = B[(size_t)i * nu + j];
     for (int j = 0; j < nd; ++j) mt[(size_t)(nx + nu + j) * nx + i] = Bd[(size_t)i * nd + j];
   }
-  hipError_t e = hipMemcpy(c->Mt, mt.data(), mt.size() * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(c->ulb, ulb, nu * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(c->uub, uub, nu * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(c->x0, x0, nx * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(c->uprev0, uprev0, nu * 8, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { set_error("nnmpc_chain_create: upload failed: %s", hipGetErrorString(e)); nnmpc_chain_destroy(c); return NNMPC_EHIP; }
-  rc = nnmpc_chain_reset(c);
-  if (rc) { nnmpc_chain_destroy(c); return rc; }
-  *out = c;
+  if (int rc = res.upload(&c->Mt, mt.data(), mt.size())) return rc;
+  if (int rc = res.upload(&c->ulb, ulb, nu)) return rc;
+  if (int rc = res.upload(&c->uub, uub, nu)) return rc;
+  if (int rc = res.upload(&c->x0, x0, nx)) return rc;
+  if (int rc = res.upload(&c->uprev0, uprev0, nu)) return rc;
+#define A_(ptr, cnt) if (int rc = res.alloc(&(ptr), (size_t)(cnt))) return rc
+  A_(c->x, (size_t)nc * nx); A_(c->uprev, (size_t)nc * nu);
+  A_(c->qx0, (size_t)nc * (nx + nu)); A_(c->lb, (size_t)nc * nu); A_(c->ub, (size_t)nc * nu); A_(c->first, (size_t)nc * nu);
+  A_(c->act, (size_t)nc * c->words); A_(c->status, nc); A_(c->guess, (size_t)nc * n);
+#undef A_
+  if (int rc = nnmpc_chain_reset(c)) return rc;
+  *out = guard.release();
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_chain_destroy(nnmpc_chain* c) {
   if (!c) return NNMPC_OK;
-  hipSetDevice(c->device);
-  hipDeviceSynchronize();
-  for (void* p : c->allocs) hipFree(p);
-  for (void* p : c->stage) if (p) hipFree(p);
-  if (c->e0) hipEventDestroy(c->e0);
-  if (c->e1) hipEventDestroy(c->e1);
-  if (c->stream) hipStreamDestroy(c->stream);
+  c->res.release();
   delete c;
   return NNMPC_OK;
 }
@@ -454,14 +418,14 @@ int nnmpc_chain_run(nnmpc_chain* c, int32_t T, const double* xs, const double* u
   int* st_d = status;
   if (ptr_kind == NNMPC_HOST) {
     double *a = nullptr, *b = nullptr, *cc = nullptr;
-    int rc = chain_stage(c, 0, &a, sx * 8);
-    if (!rc) rc = chain_stage(c, 1, &b, su * 8);
-    if (!rc) rc = chain_stage(c, 2, &cc, std::max<size_t>(sd, 1) * 8);
-    if (!rc) rc = chain_stage(c, 3, &xr_d, sx * 8);
-    if (!rc) rc = chain_stage(c, 4, &ur_d, su * 8);
-    if (!rc) rc = chain_stage(c, 5, &uu_d, su * 8);
-    if (!rc) rc = chain_stage(c, 6, &st_d, ss * 4);
-    if (rc) return rc;
+    DevRes& res = c->res;
+    if (int rc = res.slot(0, &a, sx * 8)) return rc;
+    if (int rc = res.slot(1, &b, su * 8)) return rc;
+    if (int rc = res.slot(2, &cc, std::max<size_t>(sd, 1) * 8)) return rc;
+    if (int rc = res.slot(3, &xr_d, sx * 8)) return rc;
+    if (int rc = res.slot(4, &ur_d, su * 8)) return rc;
+    if (int rc = res.slot(5, &uu_d, su * 8)) return rc;
+    if (int rc = res.slot(6, &st_d, ss * 4)) return rc;
     HIPCHK(hipMemcpy(a, xs, sx * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b, us, su * 8, hipMemcpyHostToDevice));
     if (sd) HIPCHK(hipMemcpy(cc, d, sd * 8, hipMemcpyHostToDevice));
@@ -535,23 +499,8 @@ struct nnmpc_ts {
   double *Pr = nullptr, *E = nullptr, *esc = nullptr, *lb = nullptr, *ub = nullptr;   // E: rows scaled by esc
   double dsc = 1.0;
   hipStream_t stream = nullptr;
-  void* stage[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t stage_cap[6] = {0, 0, 0, 0, 0, 0};
+  DevRes res{6};                                            // owns all of it; its slots: staging for host-pointer calls
 };
-
-namespace {
-template <class T>
-int ts_stage(nnmpc_ts* h, int which, T** out, size_t bytes) {
-  if (h->stage_cap[which] < bytes) {
-    if (h->stage[which]) { hipFree(h->stage[which]); h->stage[which] = nullptr; h->stage_cap[which] = 0; }
-    const hipError_t e = hipMalloc(&h->stage[which], bytes + bytes / 4 + 256);
-    if (e != hipSuccess) { h->stage[which] = nullptr; set_error("hipMalloc(%zu bytes of staging): %s", bytes, hipGetErrorString(e)); return NNMPC_ENOMEM; }
-    h->stage_cap[which] = bytes + bytes / 4 + 256;
-  }
-  *out = (T*)h->stage[which];
-  return 0;
-}
-}  // namespace
 
 extern "C" {
 
@@ -561,11 +510,8 @@ int nnmpc_ts_create(nnmpc_ts** out, int32_t nu, int32_t nz, const double* Pr, co
     set_error("nnmpc_ts_create: bad arguments (nu=%d nz=%d; nu + nz <= 64)", nu, nz);
     return NNMPC_EINVAL;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("nnmpc_ts_create: no HIP device available (this library has no CPU fallback)");
-    return NNMPC_EHIP;
-  }
+  GUARD_BEGIN
+  if (int rc = check_device(__func__)) return rc;
   // Equilibration, by powers of two (exact): every row of E is brought to the size of Pr, and the unit rows of held inputs
   // too (dsc).  Without it the pivot test of ts_ge_solve -- relative to the largest entry of the WHOLE KKT matrix -- refused
   // every problem with max|Pr| / max|E| beyond about 1e6, and partial pivoting mixed rows of very different size.
@@ -582,36 +528,30 @@ int nnmpc_ts_create(nnmpc_ts** out, int32_t nu, int32_t nz, const double* Pr, co
     esc[k] = pmax > 0.0 && emax > 0.0 ? pow2_near(pmax / emax) : 1.0;
     for (int c = 0; c < nu; ++c) Es[(size_t)k * nu + c] = esc[k] * E[(size_t)k * nu + c];
   }
-  nnmpc_ts* h = new nnmpc_ts();
+  Building<nnmpc_ts, nnmpc_ts_destroy> guard(new nnmpc_ts());   // released into *out at the end; destroyed on any other way out
+  nnmpc_ts* h = guard.get();
+  DevRes& res = h->res;
   h->nu = nu; h->nz = nz;
   h->dsc = pow2_near(pmax);
-  hipGetDevice(&h->device);
-  hipError_t e = hipStreamCreate(&h->stream);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->Pr, (size_t)nu * nu * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->E, std::max<size_t>((size_t)nz * nu, 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->esc, std::max<size_t>((size_t)nz, 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->lb, nu * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->ub, nu * 8);
-  if (e == hipSuccess) e = hipMemcpy(h->Pr, Pr, (size_t)nu * nu * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && nz) e = hipMemcpy(h->E, Es.data(), (size_t)nz * nu * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->esc, esc.data(), std::max<size_t>((size_t)nz, 1) * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->lb, lb, nu * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->ub, ub, nu * 8, hipMemcpyHostToDevice);
+  HIPCHK(hipGetDevice(&h->device));
+  res.device = h->device;
+  if (int rc = res.stream(&h->stream)) return rc;
+  if (int rc = res.upload(&h->Pr, Pr, (size_t)nu * nu)) return rc;
+  if (int rc = res.upload(&h->E, Es.data(), (size_t)nz * nu)) return rc;
+  if (int rc = res.upload(&h->esc, esc.data(), esc.size())) return rc;
+  if (int rc = res.upload(&h->lb, lb, nu)) return rc;
+  if (int rc = res.upload(&h->ub, ub, nu)) return rc;
   const int N = nu + nz;
   const size_t lds = ((size_t)N * (N + 2) + N) * sizeof(double);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ts_solve_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { set_error("nnmpc_ts_create: %s", hipGetErrorString(e)); nnmpc_ts_destroy(h); return NNMPC_EHIP; }
-  *out = h;
+  HIPCHK(hipFuncSetAttribute((const void*)ts_solve_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  *out = guard.release();
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_ts_destroy(nnmpc_ts* h) {
   if (!h) return NNMPC_OK;
-  hipSetDevice(h->device);
-  hipDeviceSynchronize();
-  for (void* p : {(void*)h->Pr, (void*)h->E, (void*)h->esc, (void*)h->lb, (void*)h->ub}) if (p) hipFree(p);
-  for (void* p : h->stage) if (p) hipFree(p);
-  if (h->stream) hipStreamDestroy(h->stream);
+  h->res.release();
   delete h;
   return NNMPC_OK;
 }
@@ -648,13 +588,13 @@ int nnmpc_ts_solve_batch(nnmpc_ts* h, int32_t B, const double* q, const double* 
   int* sd = status;
   if (ptr_kind == NNMPC_HOST) {
     double *a = nullptr, *b = nullptr;
-    int rc = ts_stage(h, 0, &a, (size_t)B * nu * 8);
-    if (!rc) rc = ts_stage(h, 1, &b, std::max<size_t>((size_t)B * nz, 1) * 8);
-    if (!rc) rc = ts_stage(h, 2, &ud, (size_t)B * nu * 8);
-    if (!rc && lam_eq) rc = ts_stage(h, 3, &ld, std::max<size_t>((size_t)B * nz, 1) * 8);
-    if (!rc && active) rc = ts_stage(h, 4, &ad, (size_t)B * nu);
-    if (!rc) rc = ts_stage(h, 5, &sd, (size_t)B * 4);
-    if (rc) return rc;
+    DevRes& res = h->res;
+    if (int rc = res.slot(0, &a, (size_t)B * nu * 8)) return rc;
+    if (int rc = res.slot(1, &b, std::max<size_t>((size_t)B * nz, 1) * 8)) return rc;
+    if (int rc = res.slot(2, &ud, (size_t)B * nu * 8)) return rc;
+    if (lam_eq) if (int rc = res.slot(3, &ld, std::max<size_t>((size_t)B * nz, 1) * 8)) return rc;
+    if (active) if (int rc = res.slot(4, &ad, (size_t)B * nu)) return rc;
+    if (int rc = res.slot(5, &sd, (size_t)B * 4)) return rc;
     HIPCHK(hipMemcpyAsync(a, q, (size_t)B * nu * 8, hipMemcpyHostToDevice, h->stream));
     if (nz) HIPCHK(hipMemcpyAsync(b, e, (size_t)B * nz * 8, hipMemcpyHostToDevice, h->stream));
     qd = a; ed = b;

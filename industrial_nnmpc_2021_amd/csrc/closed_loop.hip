@@ -13,12 +13,9 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
-#include "../../include/nnmpc.h"
-#include "common.h"
+#include "dev_res.h"
 
 using namespace nnmpc;
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(e_)); return NNMPC_EHIP; } } while (0)
 
 namespace {
 
@@ -554,7 +551,6 @@ struct nnmpc_cl {
   bool fresh = true;
   int64_t tglob = 0;
   hipStream_t stream = nullptr;
-  std::vector<hipEvent_t> ev;
   double total_ms = 0.0, phase_ms[6] = {0, 0, 0, 0, 0, 0};
   int plant = NNMPC_CL_PLANT_LINEAR;                // nnmpc_cl_set_plant
   CstrsPar cstrs = {};
@@ -562,42 +558,8 @@ struct nnmpc_cl {
   int plant_substeps = 0;
   std::vector<double> slot_ms;                      // [T][nslots] of the last run
   int last_T = 0;
-  std::vector<void*> allocs;
-  void* stage[16] = {};
-  size_t stage_cap[16] = {};
+  DevRes res{15};                                   // owns all of it; its slots: staging of host-pointer runs; its pool: the phase events
 };
-
-namespace {
-template <class T>
-int cl_alloc(nnmpc_cl* h, T** p, size_t count) {
-  void* q = nullptr;
-  const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-  if (e != hipSuccess) { set_error("hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e)); return NNMPC_ENOMEM; }
-  hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(T));
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  return 0;
-}
-template <class T>
-int cl_upload(nnmpc_cl* h, T** p, const T* src, size_t count) {
-  int rc = cl_alloc(h, p, count);
-  if (!rc && count && hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("nnmpc_cl_create: upload failed"); rc = NNMPC_EHIP;
-  }
-  return rc;
-}
-template <class T>
-int cl_stage(nnmpc_cl* h, int which, T** out, size_t bytes) {
-  if (h->stage_cap[which] < bytes) {
-    if (h->stage[which]) { hipFree(h->stage[which]); h->stage[which] = nullptr; h->stage_cap[which] = 0; }
-    const hipError_t e = hipMalloc(&h->stage[which], bytes + 256);
-    if (e != hipSuccess) { h->stage[which] = nullptr; set_error("hipMalloc(%zu bytes of staging): %s", bytes, hipGetErrorString(e)); return NNMPC_ENOMEM; }
-    h->stage_cap[which] = bytes + 256;
-  }
-  *out = (T*)h->stage[which];
-  return 0;
-}
-}  // namespace
 
 extern "C" {
 
@@ -650,27 +612,28 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
       return NNMPC_EINVAL;
     }
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("nnmpc_cl_create: no HIP device available (no CPU fallback)"); return NNMPC_EHIP; }
-  nnmpc_cl* h = new nnmpc_cl();
+  GUARD_BEGIN
+  if (int rc = check_device(__func__)) return rc;
+  Building<nnmpc_cl, nnmpc_cl_destroy> guard(new nnmpc_cl());   // released into *out at the end; destroyed on any other way out
+  nnmpc_cl* h = guard.get();
+  DevRes& res = h->res;
   h->nx = nx; h->nu = nu; h->ny = ny; h->nd = nd; h->nz = nz; h->na = nx + nd; h->nbv = nx + nz; h->nb = nb; h->nslots = nslots;
   h->ts = ts;
-  if (hipGetDevice(&h->device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
-    set_error("nnmpc_cl_create: no HIP device / stream"); nnmpc_cl_destroy(h); return NNMPC_EHIP;
-  }
+  HIPCHK(hipGetDevice(&h->device));
+  res.device = h->device;
+  if (int rc = res.stream(&h->stream)) return rc;
   const int na = h->na, nbv = h->nbv, nzz = nx + nu;
-  int rc = 0;
-  std::vector<double> zero1(1, 0.0);
-  auto up = [&](double** p, const std::vector<double>& v) { if (!rc) rc = cl_upload(h, p, v.data(), v.size()); };
-  auto upT = [&](double** p, const double* M, int r, int c) { if (!rc) rc = (M && r * c) ? cl_upload(h, p, transpose(M, r, c).data(), (size_t)r * c) : cl_alloc(h, p, 1); };
-  auto upD = [&](double** p, const double* M, size_t cnt) { if (!rc) rc = (M && cnt) ? cl_upload(h, p, M, cnt) : cl_alloc(h, p, 1); };
-  upT(&h->At, m->A, nx, nx); upT(&h->Bt, m->B, nx, nu); upT(&h->Bpt, m->Bp, nx, nd); upT(&h->Ct, m->C, ny, nx);
-  upT(&h->Aat, m->Aaug, na, na); upT(&h->Bat, m->Baug, na, nu); upT(&h->Cat, m->Caug, ny, na); upT(&h->Lt, m->L, na, ny);
-  upT(&h->tbt, m->tb, nbv, ny + nd); upT(&h->Qbt, m->Qb, nu, nbv); upT(&h->Qyt, m->Qy, nu, ny); upD(&h->q0, m->q0, nu);
-  upT(&h->Cdt, m->Cd, ny, nd); upT(&h->Ebt, m->Eb, nz, nbv); upT(&h->Xbt, m->Xb, nx, nbv); upT(&h->Xut, m->Xu, nx, nu);
-  upD(&h->Qaug, m->Qaug, (size_t)nzz * nzz); upD(&h->Raug, m->Raug, (size_t)nu * nu); upD(&h->Maug, m->Maug, (size_t)nzz * nu);
-  upD(&h->ulb, m->ulb, nu); upD(&h->uub, m->uub, nu); upD(&h->x0, m->x0, nx); upD(&h->xhat0, m->xhat0, na); upD(&h->uprev0, m->uprev0, nu);
-#define A_(ptr, cnt) if (!rc) rc = cl_alloc(h, &(ptr), (size_t)(cnt))
+  // a matrix transposed, or as it is; an absent or empty one is one zero
+  auto upT = [&](double** p, const double* M, int r, int c) { return (M && r * c) ? res.upload(p, transpose(M, r, c).data(), (size_t)r * c) : res.alloc(p, 1); };
+  auto upD = [&](double** p, const double* M, size_t cnt) { return (M && cnt) ? res.upload(p, M, cnt) : res.alloc(p, 1); };
+#define OK_(x) if (int rc = (x)) return rc
+#define A_(ptr, cnt) OK_(res.alloc(&(ptr), (size_t)(cnt)))
+  OK_(upT(&h->At, m->A, nx, nx)); OK_(upT(&h->Bt, m->B, nx, nu)); OK_(upT(&h->Bpt, m->Bp, nx, nd)); OK_(upT(&h->Ct, m->C, ny, nx));
+  OK_(upT(&h->Aat, m->Aaug, na, na)); OK_(upT(&h->Bat, m->Baug, na, nu)); OK_(upT(&h->Cat, m->Caug, ny, na)); OK_(upT(&h->Lt, m->L, na, ny));
+  OK_(upT(&h->tbt, m->tb, nbv, ny + nd)); OK_(upT(&h->Qbt, m->Qb, nu, nbv)); OK_(upT(&h->Qyt, m->Qy, nu, ny)); OK_(upD(&h->q0, m->q0, nu));
+  OK_(upT(&h->Cdt, m->Cd, ny, nd)); OK_(upT(&h->Ebt, m->Eb, nz, nbv)); OK_(upT(&h->Xbt, m->Xb, nx, nbv)); OK_(upT(&h->Xut, m->Xu, nx, nu));
+  OK_(upD(&h->Qaug, m->Qaug, (size_t)nzz * nzz)); OK_(upD(&h->Raug, m->Raug, (size_t)nu * nu)); OK_(upD(&h->Maug, m->Maug, (size_t)nzz * nu));
+  OK_(upD(&h->ulb, m->ulb, nu)); OK_(upD(&h->uub, m->uub, nu)); OK_(upD(&h->x0, m->x0, nx)); OK_(upD(&h->xhat0, m->xhat0, na)); OK_(upD(&h->uprev0, m->uprev0, nu));
   A_(h->x, (size_t)nb * nx); A_(h->xhat, (size_t)nb * na); A_(h->uprev, (size_t)nb * nu); A_(h->y, (size_t)nb * ny); A_(h->avg, nb);
   A_(h->b, (size_t)nb * nbv); A_(h->q, (size_t)nb * nu); A_(h->e, (size_t)nb * std::max(nz, 1)); A_(h->us, (size_t)nb * nu);
   A_(h->xs, (size_t)nb * nx); A_(h->qx0, (size_t)nb * nzz); A_(h->lb, (size_t)nb * nu); A_(h->ub, (size_t)nb * nu);
@@ -682,7 +645,7 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
   for (int k = 1; k < nslots; ++k) h->base[k] = h->base[k - 1] + h->count[k - 1];
   std::vector<int> nn_row(nb, 0);
   std::vector<std::vector<NNLayer>> layers(nslots);
-  for (int k = 0; k < nslots && !rc; ++k) {
+  for (int k = 0; k < nslots; ++k) {
     const nnmpc_cl_slot& s = slots[k];
     SlotDev& d = h->sd[k];
     memset(&d, 0, sizeof(d));
@@ -701,7 +664,7 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
       d.act = act; d.guess = g;
     } else if (s.kind == NNMPC_CL_SATDLQR) {
       double* kt = nullptr;
-      upT(&kt, s.Kaug, nu, nzz);
+      OK_(upT(&kt, s.Kaug, nu, nzz));
       d.Kt = kt;
     } else if (s.kind == NNMPC_CL_NN || s.kind == NNMPC_CL_NN_UNSTD) {
       const bool un = s.kind == NNMPC_CL_NN_UNSTD;
@@ -711,18 +674,18 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
       std::vector<double> xsc(nx, 1.0);
       if (s.xscale) for (int j = 0; j < nx; ++j) xsc[j] = s.xscale[j];
       double* xd = nullptr;
-      up(&xd, xsc);
+      OK_(res.upload(&xd, xsc.data(), xsc.size()));
       d.xscale = xd;
       for (int j = 0; j < d.count; ++j) nn_row[d.base + j] = h->nn_rows + j;
-      for (int l = 0; l < s.nlayers && !rc; ++l) {
+      for (int l = 0; l < s.nlayers; ++l) {
         const int K = s.dims[l], N = s.dims[l + 1];
         std::vector<float> wf((size_t)K * N), bf(N, 0.f);
         for (size_t j = 0; j < wf.size(); ++j) wf[j] = (float)s.W[l][j];
         const bool last = l == s.nlayers - 1;
         if (!last || un) for (int j = 0; j < N; ++j) bf[j] = (float)s.b[l][j];
         float *wd = nullptr, *bd = nullptr;
-        if (!rc) rc = cl_upload(h, &wd, wf.data(), wf.size());
-        if (!rc && (!last || un)) rc = cl_upload(h, &bd, bf.data(), bf.size());
+        OK_(res.upload(&wd, wf.data(), wf.size()));
+        if (!last || un) OK_(res.upload(&bd, bf.data(), bf.size()));
         layers[k].push_back(NNLayer{wd, bd, K, N, h->nn_rows, rows, last ? 1 : 0});
         h->maxK = std::max(h->maxK, K);
         if (!last) h->ldA = std::max(h->ldA, N);
@@ -732,10 +695,10 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
       h->nn_rows += rows;
     }
   }
-  if (!rc) rc = cl_upload(h, &h->slots_d, h->sd.data(), h->sd.size());
-  if (!rc) rc = cl_upload(h, &h->inst_slot, (const int*)inst_slot, (size_t)nb);
-  if (!rc) rc = cl_upload(h, &h->nn_row, nn_row.data(), nn_row.size());
-  if (!rc && h->nn_rows) {
+  OK_(res.upload(&h->slots_d, h->sd.data(), h->sd.size()));
+  OK_(res.upload(&h->inst_slot, (const int*)inst_slot, (size_t)nb));
+  OK_(res.upload(&h->nn_row, nn_row.data(), nn_row.size()));
+  if (h->nn_rows) {
     // layer-major descriptor table and the (network, column tile) list of every layer index
     std::vector<NNLayer> desc;
     std::vector<int2> tiles;
@@ -750,30 +713,22 @@ int nnmpc_cl_create(nnmpc_cl** out, const nnmpc_cl_model* m, nnmpc_ts* ts, int32
       }
       h->tile_cnt.push_back((int)tiles.size() - h->tile_off.back());
     }
-    if (!rc) rc = cl_upload(h, &h->desc_d, desc.data(), desc.size());
-    if (!rc) rc = cl_upload(h, &h->tiles_d, tiles.data(), tiles.size());
+    OK_(res.upload(&h->desc_d, desc.data(), desc.size()));
+    OK_(res.upload(&h->tiles_d, tiles.data(), tiles.size()));
     A_(h->act[0], (size_t)h->nn_rows * h->ldA); A_(h->act[1], (size_t)h->nn_rows * h->ldA); A_(h->o, (size_t)h->nn_rows * nu);
-    if (!rc && hipFuncSetAttribute((const void*)cl_nn_layer_k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   NN_RB * NN_MAXK * (int)sizeof(float)) != hipSuccess) {
-      set_error("nnmpc_cl_create: hipFuncSetAttribute(cl_nn_layer_k) failed"); rc = NNMPC_EHIP;
-    }
+    HIPCHK(hipFuncSetAttribute((const void*)cl_nn_layer_k, hipFuncAttributeMaxDynamicSharedMemorySize, NN_RB * NN_MAXK * (int)sizeof(float)));
   }
 #undef A_
-  if (rc) { nnmpc_cl_destroy(h); return rc; }
-  rc = nnmpc_cl_reset(h);
-  if (rc) { nnmpc_cl_destroy(h); return rc; }
-  *out = h;
+#undef OK_
+  if (int rc = nnmpc_cl_reset(h)) return rc;
+  *out = guard.release();
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_cl_destroy(nnmpc_cl* h) {
   if (!h) return NNMPC_OK;
-  hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* p : h->allocs) hipFree(p);
-  for (void* p : h->stage) if (p) hipFree(p);
-  for (hipEvent_t e : h->ev) hipEventDestroy(e);
-  if (h->stream) hipStreamDestroy(h->stream);
+  h->res.release();
   delete h;
   return NNMPC_OK;
 }
@@ -800,7 +755,9 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
     return NNMPC_EINVAL;
   }
   if (T == 0) return NNMPC_OK;
+  GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
+  DevRes& res = h->res;
   const int nb = h->nb, nx = h->nx, nu = h->nu, ny = h->ny, nd = h->nd, na = h->na, nbv = h->nbv;
   // scenario indices are checked on the host before anything is launched (device pointers: one copy of nb ints)
   std::vector<int32_t> sc(nb);
@@ -822,16 +779,15 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
   if (ptr_kind == NNMPC_HOST) {
     double *a = nullptr, *b = nullptr, *c = nullptr, *s = nullptr;
     int* si = nullptr;
-    int rc = cl_stage(h, 0, &a, n_sp * 8);
-    if (!rc) rc = cl_stage(h, 1, &b, std::max<size_t>(n_d, 1) * 8);
-    if (!rc) rc = cl_stage(h, 2, &c, n_v * 8);
-    if (!rc) rc = cl_stage(h, 3, &s, (size_t)ny * 8);
-    if (!rc) rc = cl_stage(h, 4, &si, (size_t)nb * 4);
+    if (int rc = res.slot(0, &a, n_sp * 8)) return rc;
+    if (int rc = res.slot(1, &b, std::max<size_t>(n_d, 1) * 8)) return rc;
+    if (int rc = res.slot(2, &c, n_v * 8)) return rc;
+    if (int rc = res.slot(3, &s, (size_t)ny * 8)) return rc;
+    if (int rc = res.slot(4, &si, (size_t)nb * 4)) return rc;
     double* yy = nullptr;
-    if (!rc && y0) rc = cl_stage(h, 14, &yy, (size_t)nb * ny * 8);
-    for (int k = 0; k < 7 && !rc; ++k) if (rd[k]) rc = cl_stage(h, 5 + k, &rdd[k], rsz[k] * 8);
-    for (int k = 0; k < 2 && !rc; ++k) if (rs[k]) rc = cl_stage(h, 12 + k, &rsd[k], (size_t)T * nb * 4);
-    if (rc) return rc;
+    if (y0) if (int rc = res.slot(14, &yy, (size_t)nb * ny * 8)) return rc;
+    for (int k = 0; k < 7; ++k) if (rd[k]) if (int rc = res.slot(5 + k, &rdd[k], rsz[k] * 8)) return rc;
+    for (int k = 0; k < 2; ++k) if (rs[k]) if (int rc = res.slot(12 + k, &rsd[k], (size_t)T * nb * 4)) return rc;
     HIPCHK(hipMemcpy(a, setpoints, n_sp * 8, hipMemcpyHostToDevice));
     if (n_d) HIPCHK(hipMemcpy(b, dist, n_d * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c, v, n_v * 8, hipMemcpyHostToDevice));
@@ -847,8 +803,9 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
   // phase events of at most CL_EV_BLOCK steps are alive at a time: after each block the stream is drained once and the block's
   // times are added up, so the pool is bounded whatever T is
   const int blk = std::min(T, CL_EV_BLOCK);
-  while (h->ev.size() < (size_t)blk * ne + 2) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev.push_back(e); }
-  hipEvent_t ev_t0 = h->ev[(size_t)blk * ne], ev_t1 = h->ev[(size_t)blk * ne + 1];
+  hipEvent_t ev_t0, ev_t1;
+  if (int rc = res.pool_event((size_t)blk * ne + 1, &ev_t1)) return rc;
+  if (int rc = res.pool_event((size_t)blk * ne, &ev_t0)) return rc;
   hipStream_t s = h->stream;
   FilterArgs fa{nx, nu, ny, nd, h->nz, na, nbv, T, h->Aat, h->Bat, h->Cat, h->Lt, h->tbt, h->Qbt, h->Qyt, h->q0, h->Cdt, h->Ebt};
   ExpandArgs xa{nx, nu, na, nbv, h->ldA, h->Xbt, h->Xut, h->ulb, h->uub};
@@ -863,7 +820,7 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
   std::vector<double> ms(nm);
   auto collect = [&](int t0, int t1) {                   // steps [t0, t1) of the current block, stream drained
     for (int t = t0; t < t1; ++t) {
-      hipEvent_t* E = h->ev.data() + (size_t)(t - t0) * ne;
+      hipEvent_t* E = res.pool.data() + (size_t)(t - t0) * ne;
       const double f = el(E[0], E[1]), tg = el(E[1], E[2]), xp = el(E[2], E[3]), nn = el(E[3], E[4]);
       double mp = 0.0;
       for (int j = 0; j < nm; ++j) { ms[j] = el(E[3], E[5 + j]); mp = std::max(mp, ms[j]); }
@@ -888,7 +845,7 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
       collect(tb, t);
       tb = t;
     }
-    hipEvent_t* E = h->ev.data() + (size_t)(t - tb) * ne;
+    hipEvent_t* E = res.pool.data() + (size_t)(t - tb) * ne;
     hipEventRecord(E[0], s);
     hipLaunchKernelGGL(cl_filter_k, dim3(nb), dim3(CL_THREADS), lds_f, s, fa, t, sc_d, sp_d, h->xhat, h->uprev, h->y, h->b, h->q, h->e);
     hipEventRecord(E[1], s);
@@ -951,6 +908,7 @@ int nnmpc_cl_run(nnmpc_cl* h, int32_t T, int32_t nscen, const double* setpoints,
     for (int k = 0; k < 2; ++k) if (rs[k]) HIPCHK(hipMemcpy(rs[k], rsd[k], (size_t)T * nb * 4, hipMemcpyDeviceToHost));
   }
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_cl_last_ms(nnmpc_cl* h, double* total_ms, double* phase_ms, double* slot_step_ms) {
@@ -995,31 +953,30 @@ int nnmpc_cstrs_flow(int32_t nb, const double* par, int32_t npar, double sample_
   const int rc = cstrs_check(par, npar, sample_time, substeps, &q, "nnmpc_cstrs_flow");
   if (rc) return rc;
   if (nb == 0) return NNMPC_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("nnmpc_cstrs_flow: no HIP device available (no CPU fallback)"); return NNMPC_EHIP; }
+  GUARD_BEGIN
+  if (int rc = check_device(__func__)) return rc;
   const size_t bx = (size_t)nb * 12 * 8, bu = (size_t)nb * 6 * 8, bp = (size_t)nb * 5 * 8;
   const double *xd = x, *ud = u, *pd = p;
   double* od = x_out;
-  void* buf = nullptr;
+  DevRes work;                                            // the staging of a host-pointer call: freed on every way out
+  HIPCHK(hipGetDevice(&work.device));
   if (ptr_kind == NNMPC_HOST) {
-    HIPCHK(hipMalloc(&buf, 2 * bx + bu + bp));
-    char* b = (char*)buf;
+    char* b = nullptr;
+    if (int rc = work.alloc(&b, 2 * bx + bu + bp)) return rc;
     double *xh = (double*)b, *uh = (double*)(b + bx), *ph = (double*)(b + bx + bu);
     od = (double*)(b + bx + bu + bp);
-    hipError_t e = hipMemcpy(xh, x, bx, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(uh, u, bu, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ph, p, bp, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(buf); set_error("nnmpc_cstrs_flow: upload: %s", hipGetErrorString(e)); return NNMPC_EHIP; }
+    HIPCHK(hipMemcpy(xh, x, bx, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(uh, u, bu, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ph, p, bp, hipMemcpyHostToDevice));
     xd = xh; ud = uh; pd = ph;
   }
   hipLaunchKernelGGL(cstrs_flow_k, dim3((nb + CSTRS_THREADS - 1) / CSTRS_THREADS), dim3(CSTRS_THREADS), 0, 0, q, sample_time / substeps,
                      substeps, nb, xd, ud, pd, od);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess && ptr_kind == NNMPC_HOST) e = hipMemcpy(x_out, od, bx, hipMemcpyDeviceToHost);
-  if (buf) hipFree(buf);
-  if (e != hipSuccess) { set_error("nnmpc_cstrs_flow: %s", hipGetErrorString(e)); return NNMPC_EHIP; }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  if (ptr_kind == NNMPC_HOST) HIPCHK(hipMemcpy(x_out, od, bx, hipMemcpyDeviceToHost));
   return NNMPC_OK;
+  GUARD_END
 }
 
 }  // extern "C"

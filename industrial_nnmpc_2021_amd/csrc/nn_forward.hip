@@ -23,10 +23,9 @@
 #include <algorithm>
 #include <chrono>
 #include <stdlib.h>
-#include "../../include/nnmpc.h"
 #include "gemm_kernels.h"
 #include "tile_gemm_bf16.h"
-#include "common.h"
+#include "dev_res.h"
 
 using namespace nnmpc;
 
@@ -221,25 +220,12 @@ struct nnmpc_nn {
   double *sx, *suprev, *sxs, *sus, *su;  // staging for host pointers
   hipStream_t stream;
   hipEvent_t e0, e1;
-  std::vector<hipEvent_t> eg;   // (start, end of the hidden layers, end) of the GEMMs of every sub-batch of a call
   double hidden_ms; int hidden_launches;
   double gemm_ms, total_ms;
-  std::vector<void*> allocs;
+  DevRes res;              // owns all of it; its pool: (start, end of the hidden layers, end) of the GEMMs of every sub-batch of a call
 };
 
 namespace {
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(e_)); return NNMPC_EHIP; } } while (0)
-
-template <class T>
-int nn_alloc(nnmpc_nn* h, T** p, size_t count) {
-  void* q = nullptr;
-  if (hipMalloc(&q, count * sizeof(T)) != hipSuccess) { set_error("hipMalloc(%zu) failed", count * sizeof(T)); return NNMPC_ENOMEM; }
-  hipMemset(q, 0, count * sizeof(T));
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  return 0;
-}
-
 template <int NB, bool RELU, bool BIAS>
 void launch_layer(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda, const float* Wt,
                   size_t ldb, int M, int N, int K, const float* bias) {
@@ -293,10 +279,13 @@ int nnmpc_nn_create_ex(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, con
   if ((ulb == nullptr) != (uub == nullptr)) { set_error("nnmpc_nn_create: ulb and uub must both be given or both NULL"); return NNMPC_EINVAL; }
   if (form != NNMPC_NN_STRUCTURED && form != NNMPC_NN_UNSTD && form != NNMPC_NN_UNSTD_RELU) { set_error("nnmpc_nn_create_ex: unknown form %d", form); return NNMPC_EINVAL; }
   if (form != NNMPC_NN_STRUCTURED && !b[nlayers - 1]) { set_error("nnmpc_nn_create_ex: the unstructured forms need the head's bias b[%d]", nlayers - 1); return NNMPC_EINVAL; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("nnmpc_nn_create: no HIP device available (no CPU fallback)"); return NNMPC_EHIP; }
-  nnmpc_nn* h = new nnmpc_nn();
-  hipGetDevice(&h->device);
+  GUARD_BEGIN
+  if (int rc = check_device("nnmpc_nn_create")) return rc;
+  Building<nnmpc_nn, nnmpc_nn_destroy> guard(new nnmpc_nn());   // released into *out at the end; destroyed on any other way out
+  nnmpc_nn* h = guard.get();
+  DevRes& res = h->res;
+  HIPCHK(hipGetDevice(&h->device));
+  res.device = h->device;
   h->use_bf16 = use_bf16 == 2 ? 2 : (use_bf16 != 0);
   h->split = h->use_bf16 == 2;
   h->nlayers = nlayers; h->nx = nx; h->nu = nu; h->with_uprev = with_uprev; h->clip = ulb != nullptr;
@@ -304,22 +293,22 @@ int nnmpc_nn_create_ex(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, con
   h->max_batch = ((std::max(max_batch, 1) + 127) / 128) * 128;
   h->gemm_ms = h->total_ms = h->hidden_ms = 0; h->hidden_launches = 0;
   h->dims.assign(dims, dims + nlayers + 1);
-  hipStreamCreate(&h->stream);
-  hipEventCreate(&h->e0); hipEventCreate(&h->e1);
-  hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4);
-  hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4);
-  hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES);
-  hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES);
+  if (int rc = res.stream(&h->stream)) return rc;
+  if (int rc = res.event(&h->e0)) return rc;
+  if (int rc = res.event(&h->e1)) return rc;
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES));
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES));
   if (form != NNMPC_NN_STRUCTURED) {                        // the head with its bias (+ ReLU) in the epilogue
-    hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4);
-    hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, false, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES);
+    HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+    HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, false, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_bf16_k<128, true, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg16<128>::LDS_BYTES));
   }
-  hipFuncSetAttribute((const void*)gemm_nt_bf16_wide_k<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES);
-  hipFuncSetAttribute((const void*)gemm_nt_bf16_wide_k<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES);
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_bf16_wide_k<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES));
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_bf16_wide_k<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES));
   h->maxw = 0;
-  int rc = 0;
-  for (int l = 0; l < nlayers && !rc; ++l) {
+  for (int l = 0; l < nlayers; ++l) {
     const int kp = l == 0 ? ((dims[0] + 63) / 64) * 64 : h->npad[l - 1];
     // wide layers use 128-wide tiles (pad to 128), narrow ones (the Nu-wide head) 64
     const int np_ = dims[l + 1] > 64 ? ((dims[l + 1] + 127) / 128) * 128 : 64;
@@ -329,14 +318,12 @@ int nnmpc_nn_create_ex(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, con
     for (int i = 0; i < dims[l]; ++i)
       for (int o = 0; o < dims[l + 1]; ++o) wt[(size_t)o * kp + i] = (float)W[l][(size_t)i * dims[l + 1] + o];
     if (l < nlayers - 1 || form != NNMPC_NN_STRUCTURED) {
-      if (!b[l]) { set_error("nnmpc_nn_create: missing bias for hidden layer %d", l); rc = NNMPC_EINVAL; break; }
+      if (!b[l]) { set_error("nnmpc_nn_create: missing bias for hidden layer %d", l); return NNMPC_EINVAL; }
       for (int o = 0; o < dims[l + 1]; ++o) bb[o] = (float)b[l][o];
     }
     float *dw = nullptr, *db = nullptr;
-    rc = nn_alloc(h, &dw, wt.size()); if (rc) break;
-    rc = nn_alloc(h, &db, bb.size()); if (rc) break;
-    hipMemcpy(dw, wt.data(), wt.size() * 4, hipMemcpyHostToDevice);
-    hipMemcpy(db, bb.data(), bb.size() * 4, hipMemcpyHostToDevice);
+    if (int rc = res.upload(&dw, wt.data(), wt.size())) return rc;
+    if (int rc = res.upload(&db, bb.data(), bb.size())) return rc;
     h->Wt.push_back(dw); h->bias.push_back(db);
     if (h->use_bf16) {
       const bool lastl = l == nlayers - 1;
@@ -358,43 +345,36 @@ int nnmpc_nn_create_ex(nnmpc_nn** out, int32_t nlayers, const int32_t* dims, con
           if (h->split) { w16[(size_t)o * kw + k16 + i] = rne(f - tof(hi)); w16[(size_t)o * kw + 2 * k16 + i] = hi; }
         }
       bf16raw* d16 = nullptr;
-      rc = nn_alloc(h, &d16, w16.size()); if (rc) break;
-      hipMemcpy(d16, w16.data(), w16.size() * 2, hipMemcpyHostToDevice);
+      if (int rc = res.upload(&d16, w16.data(), w16.size())) return rc;
       h->Wt16.push_back(d16);
     }
   }
   std::vector<float> is(nx, 1.f);
   if (xscale) for (int i = 0; i < nx; ++i) is[i] = (float)(1.0 / xscale[i]);
-  if (!rc) rc = nn_alloc(h, &h->inv_scale, nx);
-  if (!rc) hipMemcpy(h->inv_scale, is.data(), nx * 4, hipMemcpyHostToDevice);
-  if (!rc) rc = nn_alloc(h, &h->ulb, nu);
-  if (!rc) rc = nn_alloc(h, &h->uub, nu);
-  if (!rc && ulb) { hipMemcpy(h->ulb, ulb, nu * 8, hipMemcpyHostToDevice); hipMemcpy(h->uub, uub, nu * 8, hipMemcpyHostToDevice); }
+  if (int rc = res.upload(&h->inv_scale, is.data(), is.size())) return rc;
+  if (int rc = ulb ? res.upload(&h->ulb, ulb, nu) : res.alloc(&h->ulb, nu)) return rc;   // (no clipping: zeros nobody reads)
+  if (int rc = ulb ? res.upload(&h->uub, uub, nu) : res.alloc(&h->uub, nu)) return rc;
   const size_t MB = h->max_batch;
   if (h->split) {                                          // rows of two bf16 planes of up to max(k16, ldc16) columns, in units of float
     int w = 0;
     for (int l = 0; l < nlayers; ++l) w = std::max(w, std::max(h->k16[l], h->ldc16[l]));
     h->maxw = std::max(h->maxw, (2 * w * 2 + 3) / 4);
   }
-  if (!rc) rc = nn_alloc(h, &h->act[0], 2 * MB * h->maxw);
-  if (!rc) rc = nn_alloc(h, &h->act[1], 2 * MB * h->maxw);
-  if (!rc) rc = nn_alloc(h, &h->sx, MB * nx);
-  if (!rc) rc = nn_alloc(h, &h->sxs, MB * nx);
-  if (!rc) rc = nn_alloc(h, &h->suprev, MB * nu);
-  if (!rc) rc = nn_alloc(h, &h->sus, MB * nu);
-  if (!rc) rc = nn_alloc(h, &h->su, MB * nu);
-  if (rc) { nnmpc_nn_destroy(h); return rc; }
-  *out = h;
+  if (int rc = res.alloc(&h->act[0], 2 * MB * h->maxw)) return rc;
+  if (int rc = res.alloc(&h->act[1], 2 * MB * h->maxw)) return rc;
+  if (int rc = res.alloc(&h->sx, MB * nx)) return rc;
+  if (int rc = res.alloc(&h->sxs, MB * nx)) return rc;
+  if (int rc = res.alloc(&h->suprev, MB * nu)) return rc;
+  if (int rc = res.alloc(&h->sus, MB * nu)) return rc;
+  if (int rc = res.alloc(&h->su, MB * nu)) return rc;
+  *out = guard.release();
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_nn_destroy(nnmpc_nn* h) {
   if (!h) return NNMPC_OK;
-  hipDeviceSynchronize();
-  for (void* p : h->allocs) hipFree(p);
-  hipEventDestroy(h->e0); hipEventDestroy(h->e1);
-  for (hipEvent_t e : h->eg) hipEventDestroy(e);
-  if (h->stream) hipStreamDestroy(h->stream);
+  h->res.release();
   delete h;
   return NNMPC_OK;
 }
@@ -403,6 +383,7 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
                      const double* us, double* u, int32_t ptr_kind) {
   if (!h || B < 0 || !x || !xs || !us || !u || (h->with_uprev && !uprev)) { set_error("nnmpc_nn_forward: bad arguments"); return NNMPC_EINVAL; }
   if (B == 0) return NNMPC_OK;
+  GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const int nx = h->nx, nu = h->nu, MB = h->max_batch;
@@ -412,7 +393,9 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
   hipEventRecord(h->e0, s);
   size_t nsub = 0;
   for (int b0 = 0; b0 < B; b0 += MB, ++nsub) {
-    while (h->eg.size() < 3 * (nsub + 1)) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->eg.push_back(e); }
+    hipEvent_t eg_end;
+    if (int rc = h->res.pool_event(3 * nsub + 2, &eg_end)) return rc;
+    const hipEvent_t* eg = h->res.pool.data() + 3 * nsub;  // start, end of the hidden layers, end of this sub-batch's GEMMs
     const int nb = std::min(MB, B - b0);
     const int Bp = ((nb + 127) / 128) * 128;
     const double *dx, *dup, *dxs, *dus; double* du;
@@ -448,14 +431,14 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
     else
       hipLaunchKernelGGL(nn_assemble_k<float>, dim3(8192), dim3(256), 0, s, h->act[0], h->kpad[0], Bp, nb, nx, nu,
                          h->with_uprev, dx, dup, dxs, dus, h->inv_scale);
-    hipEventRecord(h->eg[3 * nsub], s);
+    hipEventRecord(eg[0], s);
     int cur = 0;
     for (int l = 0; l < h->nlayers; ++l) {
       const int K = h->kpad[l], N = h->npad[l];
       float* C = h->act[cur ^ 1];
       const float* A = h->act[cur];
       const bool last = l == h->nlayers - 1;
-      if (last) hipEventRecord(h->eg[3 * nsub + 1], s);    // end of the hidden layers
+      if (last) hipEventRecord(eg[1], s);                  // end of the hidden layers
       if (h->use_bf16) {
         const bf16raw* A16 = reinterpret_cast<const bf16raw*>(A);
         // split: one GEMM of three times the depth (K16), rows of two planes (lda), nk0 chunks per plane
@@ -489,7 +472,7 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
       }
       cur ^= 1;
     }
-    hipEventRecord(h->eg[3 * nsub + 2], s);
+    hipEventRecord(eg_end, s);
     if (un)
       hipLaunchKernelGGL(nn_clip_k, dim3(1024), dim3(256), 0, s, du, h->act[cur], h->npad[h->nlayers - 1], nb, nu, h->ulb,
                          h->uub, h->clip);
@@ -511,8 +494,9 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
   double hid = 0.0;
   for (size_t i = 0; i < nsub; ++i) {
     float ms = 0.f;
-    hipEventElapsedTime(&ms, h->eg[3 * i], h->eg[3 * i + 2]); gemm_ms += ms;
-    hipEventElapsedTime(&ms, h->eg[3 * i], h->eg[3 * i + 1]); hid += ms;
+    const hipEvent_t* eg = h->res.pool.data() + 3 * i;
+    hipEventElapsedTime(&ms, eg[0], eg[2]); gemm_ms += ms;
+    hipEventElapsedTime(&ms, eg[0], eg[1]); hid += ms;
   }
   h->hidden_ms = hid; h->hidden_launches = (int)nsub * (h->nlayers - 1);
   h->gemm_ms = gemm_ms; h->total_ms = tot;
@@ -522,6 +506,7 @@ int nnmpc_nn_forward(nnmpc_nn* h, int32_t B, const double* x, const double* upre
     fprintf(stderr, "nnmpc_nn_forward: enqueue %.3f ms, wait %.3f ms, post %.3f ms, device %.3f ms\n", ms(T0, T1), ms(T1, T2), ms(T2, T3), (double)tot);
   }
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_nn_last_hidden_ms(nnmpc_nn* h, double* hidden_ms, int32_t* launches) {

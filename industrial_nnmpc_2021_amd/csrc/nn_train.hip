@@ -236,8 +236,7 @@ extern "C" {
 
 int nnmpc_train_destroy(nnmpc_train* h) {
   if (!h) return NNMPC_OK;
-  common_release(h->c);
-  if (h->arena) hipFree(h->arena);
+  h->c.res.release();
   delete h;
   return NNMPC_OK;
 }
@@ -252,8 +251,7 @@ static int train_create(const char* who, nnmpc_train** out, int32_t nlayers, con
   if (int rc = check_network(who, "", nlayers, dims, W, b, nx, nu, with_uprev, form)) return rc;
   if (int rc = check_adam(who, lr, beta1, beta2, eps)) return rc;
   if (int rc = check_device(who)) return rc;
-  struct Destroy { void operator()(nnmpc_train* p) const { nnmpc_train_destroy(p); } };
-  std::unique_ptr<nnmpc_train, Destroy> guard(new nnmpc_train());   // released into *out at the end; destroyed on any other way out
+  Building<nnmpc_train, nnmpc_train_destroy> guard(new nnmpc_train());   // released into *out at the end; destroyed on any other way out
   nnmpc_train* h = guard.get();
   TrainCommon& c = h->c;
   if (int rc = common_init(who, c, nlayers, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form)) return rc;
@@ -267,10 +265,7 @@ static int train_create(const char* who, nnmpc_train** out, int32_t nlayers, con
   size_t grad_floats = 0;
   for (int l = 0; l < nlayers; ++l) grad_floats += (size_t)h->m.npad[l] * (h->m.kpad[l] + 1);
   const size_t acc_at = layout_member(c, h->m, nullptr, 0), grad_at = acc_at + 4096, bytes = grad_at + grad_floats * 4;
-  void* q = nullptr;
-  if (hipMalloc(&q, bytes) != hipSuccess) { set_error("%s: hipMalloc(%zu) failed", who, bytes); return NNMPC_ENOMEM; }
-  h->arena = (char*)q;
-  HIPCHK(hipMemset(h->arena, 0, bytes));
+  if (int rc = c.res.alloc(&h->arena, bytes)) return rc;
   layout_member(c, h->m, h->arena, 0);
   h->m.mem.acc = (double*)(h->arena + acc_at);
   h->grad = (float*)(h->arena + grad_at);

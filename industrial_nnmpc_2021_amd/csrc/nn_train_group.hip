@@ -280,9 +280,7 @@ extern "C" {
 
 int nnmpc_train_group_destroy(nnmpc_train_group* h) {
   if (!h) return NNMPC_OK;
-  common_release(h->c);
-  for (void* p : {(void*)h->arena, (void*)h->dlay, (void*)h->dmem, (void*)h->dacc})
-    if (p) hipFree(p);
+  h->c.res.release();
   delete h;
   return NNMPC_OK;
 }
@@ -301,8 +299,7 @@ int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers
   }
   if (int rc = check_adam(__func__, lr, beta1, beta2, eps)) return rc;
   if (int rc = check_device(__func__)) return rc;
-  struct Destroy { void operator()(nnmpc_train_group* p) const { nnmpc_train_group_destroy(p); } };
-  std::unique_ptr<nnmpc_train_group, Destroy> guard(new nnmpc_train_group());
+  Building<nnmpc_train_group, nnmpc_train_group_destroy> guard(new nnmpc_train_group());
   nnmpc_train_group* h = guard.get();
   TrainCommon& c = h->c;
   if (int rc = common_init(__func__, c, L, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, NNMPC_NN_STRUCTURED)) return rc;
@@ -320,13 +317,8 @@ int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers
     for (int S : mb.max_slices)                             // the dW grid carries member x slice in z
       if ((int64_t)G * S > 65535) { set_error("nnmpc_train_group_create: %d members x %d dW slices exceed a grid's z extent", G, S); return NNMPC_EINVAL; }
   }
-  void* q = nullptr;
-  if (hipMalloc(&q, bytes) != hipSuccess) { set_error("nnmpc_train_group_create: hipMalloc(%zu) failed", bytes); return NNMPC_ENOMEM; }
-  h->arena = (char*)q;
-  HIPCHK(hipMemset(h->arena, 0, bytes));
-  if (hipMalloc(&q, (size_t)G * 8) != hipSuccess) { set_error("nnmpc_train_group_create: hipMalloc failed"); return NNMPC_ENOMEM; }
-  h->dacc = (double*)q;
-  HIPCHK(hipMemset(h->dacc, 0, (size_t)G * 8));
+  if (int rc = c.res.alloc(&h->arena, bytes)) return rc;
+  if (int rc = c.res.alloc(&h->dacc, (size_t)G)) return rc;
   std::vector<GLayer> lay;
   std::vector<GMember> mem;
   size_t off = 0;
@@ -338,12 +330,8 @@ int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers
     lay.insert(lay.end(), mb.lay.begin(), mb.lay.end());
     mem.push_back(mb.mem);
   }
-  if (hipMalloc(&q, lay.size() * sizeof(GLayer)) != hipSuccess) { set_error("nnmpc_train_group_create: hipMalloc failed"); return NNMPC_ENOMEM; }
-  h->dlay = (GLayer*)q;
-  if (hipMalloc(&q, mem.size() * sizeof(GMember)) != hipSuccess) { set_error("nnmpc_train_group_create: hipMalloc failed"); return NNMPC_ENOMEM; }
-  h->dmem = (GMember*)q;
-  HIPCHK(hipMemcpy(h->dlay, lay.data(), lay.size() * sizeof(GLayer), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->dmem, mem.data(), mem.size() * sizeof(GMember), hipMemcpyHostToDevice));
+  if (int rc = c.res.upload(&h->dlay, lay.data(), lay.size())) return rc;
+  if (int rc = c.res.upload(&h->dmem, mem.data(), mem.size())) return rc;
   *out = guard.release();
   return NNMPC_OK;
   GUARD_END

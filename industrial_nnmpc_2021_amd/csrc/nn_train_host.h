@@ -15,18 +15,11 @@
 #include <math.h>
 #include <vector>
 #include <algorithm>
-#include <new>
-#include "../../include/nnmpc.h"
 #include "nn_train_dev.h"
-#include "common.h"
+#include "dev_res.h"
 
 namespace nnmpc {
 namespace {
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(e_)); return NNMPC_EHIP; } } while (0)
-#define GUARD_BEGIN try {
-#define GUARD_END } catch (const std::bad_alloc&) { set_error("%s: out of host memory", __func__); return NNMPC_ENOMEM; } \
-                    catch (...) { set_error("%s: unexpected exception", __func__); return NNMPC_EHIP; }
 
 struct GLayer {                                             // operands of layer l of a network
   float *Wt, *Wk, *b, *mW, *vW, *mb, *vb;                   // Wt [N][K], Wk [K][N]
@@ -54,14 +47,15 @@ struct TrainCommon {                                        // what a handle hol
   double lr = 0, beta1 = 0, beta2 = 0, eps = 0;
   int n = 0;                                                // dataset rows
   float *dx = nullptr, *dup = nullptr, *dxs = nullptr, *dus = nullptr, *du = nullptr;
-  char* dcall = nullptr; size_t dcall_cap = 0;              // what the last call uploaded: its row lists (behind its step table, in a group)
-  char* stage[2] = {nullptr, nullptr};                      // pinned images of it, used in turn
-  hipEvent_t stage_done[2] = {nullptr, nullptr};            // the upload out of stage[k] has finished
-  size_t stage_cap[2] = {0, 0}; int stage_turn = 0;
+  char* dcall = nullptr;                                    // what the last call uploaded: its row lists (behind its step table, in a group)
+  hipEvent_t stage_done[2] = {nullptr, nullptr};            // the upload out of the pinned image k (used in turn) has finished
+  int stage_turn = 0;
   hipStream_t stream = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  std::vector<hipEvent_t> ev;                               // 4 per step of the last call: forward GEMMs, backward
   size_t nsets = 0;
+  // Owns all of it and the networks' buffers.  Slot 0: dcall; pinned slots 0, 1: its two images; pool: 4 events per step of
+  // the last call (around the forward GEMMs, around the backward).
+  DevRes res{1, 2};
 };
 
 inline int pad128_host(int B) { return ((B + 127) / 128) * 128; }
@@ -105,15 +99,11 @@ inline int check_rows(const TrainCommon& c, const char* who, size_t count, const
 
 // ---- the handle's common part ----
 
-inline int check_device(const char* who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("%s: no HIP device available (no CPU fallback)", who); return NNMPC_EHIP; }
-  return NNMPC_OK;
-}
 // Device, compute units, the slice override (read once, here), stream and the call's two events.
 inline int common_init(const char* who, TrainCommon& c, int L, int nx, int nu, int with_uprev, int max_batch, double lr,
                        double beta1, double beta2, double eps, int form) {
   HIPCHK(hipGetDevice(&c.device));
+  c.res.device = c.device;
   HIPCHK(hipDeviceGetAttribute(&c.num_cus, hipDeviceAttributeMultiprocessorCount, c.device));
   if (c.num_cus < 1) { set_error("%s: device reports %d compute units", who, c.num_cus); return NNMPC_EHIP; }
   c.L = L; c.nx = nx; c.nu = nu; c.with_uprev = with_uprev != 0; c.form = form;
@@ -121,25 +111,9 @@ inline int common_init(const char* who, TrainCommon& c, int L, int nx, int nu, i
   c.cap_batch = pad128_host(max_batch);
   c.lr = lr; c.beta1 = beta1; c.beta2 = beta2; c.eps = eps;
   if (const char* e = getenv("NNMPC_TRAIN_DW_SLICES")) c.force_slices = std::max(0, atoi(e));   // tests: several slices on a small batch
-  if (hipStreamCreate(&c.stream) != hipSuccess || hipEventCreate(&c.e0) != hipSuccess || hipEventCreate(&c.e1) != hipSuccess) {
-    set_error("%s: stream / event creation failed", who); return NNMPC_EHIP;
-  }
-  return NNMPC_OK;
-}
-// Waits for the device, then frees what common_init, set_data, staged_upload and ev_set made.
-inline void common_release(TrainCommon& c) {
-  hipSetDevice(c.device);
-  hipDeviceSynchronize();
-  for (void* p : {(void*)c.dcall, (void*)c.dx, (void*)c.dup, (void*)c.dxs, (void*)c.dus, (void*)c.du})
-    if (p) hipFree(p);
-  for (int k = 0; k < 2; ++k) {
-    if (c.stage[k]) hipHostFree(c.stage[k]);
-    if (c.stage_done[k]) hipEventDestroy(c.stage_done[k]);
-  }
-  if (c.e0) hipEventDestroy(c.e0);
-  if (c.e1) hipEventDestroy(c.e1);
-  for (hipEvent_t e : c.ev) hipEventDestroy(e);
-  if (c.stream) hipStreamDestroy(c.stream);
+  if (int rc = c.res.stream(&c.stream)) return rc;
+  if (int rc = c.res.event(&c.e0)) return rc;
+  return c.res.event(&c.e1);
 }
 
 // ---- one network ----
@@ -306,7 +280,7 @@ inline int set_data(const char* who, TrainCommon& c, int32_t n, const double* x,
   if (c.with_uprev && !uprev) { set_error("%s: uprev is an input of the network, none given", who); return NNMPC_EINVAL; }
   HIPCHK(hipSetDevice(c.device));
   HIPCHK(stream_sync(c.stream));
-  for (float** p : {&c.dx, &c.dup, &c.dxs, &c.dus, &c.du}) { if (*p) hipFree(*p); *p = nullptr; }
+  for (float** p : {&c.dx, &c.dup, &c.dxs, &c.dus, &c.du}) { c.res.give_back(*p); *p = nullptr; }
   c.n = 0;
   struct { float** d; const double* s; int w; } col[5] = {{&c.dx, x, c.nx}, {&c.dup, c.with_uprev ? uprev : nullptr, c.nu},
                                                           {&c.dxs, xs, c.nx}, {&c.dus, us, c.nu}, {&c.du, u, c.nu}};
@@ -314,9 +288,7 @@ inline int set_data(const char* who, TrainCommon& c, int32_t n, const double* x,
   for (auto& k : col) {
     if (!k.s) continue;
     const size_t cnt = (size_t)n * k.w;
-    void* q = nullptr;
-    if (hipMalloc(&q, cnt * 4) != hipSuccess) { set_error("%s: hipMalloc(%zu) failed", who, cnt * 4); return NNMPC_ENOMEM; }
-    *k.d = (float*)q;
+    if (int rc = c.res.alloc(k.d, cnt)) return rc;
     if (ptr_kind == NNMPC_HOST) {
       tmp.resize(cnt);
       for (size_t i = 0; i < cnt; ++i) tmp[i] = (float)k.s[i];
@@ -337,26 +309,17 @@ inline int set_data(const char* who, TrainCommon& c, int32_t n, const double* x,
 // the kernels of the previous call.
 inline int staged_upload(TrainCommon& c, const void* tab, size_t tb, const int32_t* rows, size_t nrows) {
   const size_t bytes = tb + nrows * 4;
-  if (bytes > c.dcall_cap) {
-    HIPCHK(stream_sync(c.stream));
-    if (c.dcall) { hipFree(c.dcall); c.dcall = nullptr; c.dcall_cap = 0; }
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) { set_error("hipMalloc(%zu) failed", bytes); return NNMPC_ENOMEM; }
-    c.dcall = (char*)q; c.dcall_cap = bytes;
-  }
+  if (bytes > c.res.slots[0].cap) HIPCHK(stream_sync(c.stream));   // the slot is about to grow: nothing may still read the old buffer
+  if (int rc = c.res.slot(0, &c.dcall, bytes)) return rc;
   const int k = c.stage_turn;
   c.stage_turn ^= 1;
-  if (!c.stage_done[k]) HIPCHK(hipEventCreateWithFlags(&c.stage_done[k], hipEventDisableTiming));
+  if (!c.stage_done[k]) { if (int rc = c.res.event(&c.stage_done[k], hipEventDisableTiming)) return rc; }
   else HIPCHK(hipEventSynchronize(c.stage_done[k]));
-  if (bytes > c.stage_cap[k]) {
-    if (c.stage[k]) { hipHostFree(c.stage[k]); c.stage[k] = nullptr; c.stage_cap[k] = 0; }
-    void* q = nullptr;
-    if (hipHostMalloc(&q, bytes, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc(%zu) failed", bytes); return NNMPC_ENOMEM; }
-    c.stage[k] = (char*)q; c.stage_cap[k] = bytes;
-  }
-  if (tb) memcpy(c.stage[k], tab, tb);
-  if (nrows) memcpy(c.stage[k] + tb, rows, nrows * 4);
-  HIPCHK(hipMemcpyAsync(c.dcall, c.stage[k], bytes, hipMemcpyHostToDevice, c.stream));
+  char* img = nullptr;
+  if (int rc = c.res.pinned_slot(k, &img, bytes)) return rc;
+  if (tb) memcpy(img, tab, tb);
+  if (nrows) memcpy(img + tb, rows, nrows * 4);
+  HIPCHK(hipMemcpyAsync(c.dcall, img, bytes, hipMemcpyHostToDevice, c.stream));
   HIPCHK(hipEventRecord(c.stage_done[k], c.stream));
   return NNMPC_OK;
 }
@@ -371,8 +334,9 @@ inline int read_doubles(const TrainCommon& c, const double* src, double* out, si
 
 struct EvSet { hipEvent_t f0, f1, b0, b1; };                // around the forward GEMMs; around the backward up to, not including, Adam
 inline int ev_set(TrainCommon& c, size_t i, EvSet* e) {
-  while (c.ev.size() < 4 * (i + 1)) { hipEvent_t x; HIPCHK(hipEventCreate(&x)); c.ev.push_back(x); }
-  *e = EvSet{c.ev[4 * i], c.ev[4 * i + 1], c.ev[4 * i + 2], c.ev[4 * i + 3]};
+  if (int rc = c.res.pool_event(4 * i + 3, &e->b1)) return rc;
+  const hipEvent_t* ev = c.res.pool.data() + 4 * i;
+  *e = EvSet{ev[0], ev[1], ev[2], ev[3]};
   return NNMPC_OK;
 }
 // hipEvent ms of the last call: the spans of its c.nsets event sets, and e0 .. e1.
@@ -381,9 +345,10 @@ inline int last_ms(TrainCommon& c, double* gemm_ms, double* total_ms) {
   HIPCHK(stream_sync(c.stream));
   double g = 0.0;
   float ms = 0.f;
-  for (size_t i = 0; i < c.nsets && 4 * i + 3 < c.ev.size(); ++i) {
-    if (hipEventElapsedTime(&ms, c.ev[4 * i], c.ev[4 * i + 1]) == hipSuccess) g += ms;
-    if (hipEventElapsedTime(&ms, c.ev[4 * i + 2], c.ev[4 * i + 3]) == hipSuccess) g += ms;
+  const std::vector<hipEvent_t>& ev = c.res.pool;
+  for (size_t i = 0; i < c.nsets && 4 * i + 3 < ev.size(); ++i) {
+    if (hipEventElapsedTime(&ms, ev[4 * i], ev[4 * i + 1]) == hipSuccess) g += ms;
+    if (hipEventElapsedTime(&ms, ev[4 * i + 2], ev[4 * i + 3]) == hipSuccess) g += ms;
   }
   ms = 0.f;
   if (c.nsets) hipEventElapsedTime(&ms, c.e0, c.e1);

@@ -32,7 +32,7 @@
 #include "qp_wide.h"
 #include "qp_small.h"
 #include "qp_predict.h"
-#include "common.h"
+#include "dev_res.h"
 static constexpr int ASM_SMALL9_LDS_MAX = 100 * 1024;   // dynamic LDS the nine-block instance of asm_small_k may ask for (81 KB at n = 1024, nu = 64)
 
 using namespace nnmpc;
@@ -751,73 +751,42 @@ struct nnmpc_qp {
   int* pin_st = nullptr;             // [seg_max]
   bool profiling;
   bool gemm_error = false;      // a GEMM was asked for in a form no kernel implements (gemm64): the call in progress fails
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used;
-  struct EvRec { int kind; size_t e0, e1; double flops; };
+  size_t ev_used;               // profiling events of res.pool taken by the call in progress
+  bool ev_failed = false;       // one of them could not be created: nnmpc_qp_solve_batch_ex fails at its end
+  struct EvRec { int kind; hipEvent_t e0, e1; double flops; };
   std::vector<EvRec> ev_recs;
   nnmpc_qp_stats stats;
-  std::vector<void*> allocs;
-  // grow-only scratch owned by the handle: staging of host-pointer calls, compacted copies for the PDIP fallback
-  struct Scratch { void* p = nullptr; size_t cap = 0; };
+  // grow-only slots of the owner: staging of host-pointer calls, compacted copies for the PDIP fallback
   enum { SC_U = 0, SC_ACT, SC_ST, SC_IT, SC_GUESS, SC_FB_GUESS, SC_FB_LIST, SC_FB_X0, SC_FB_LB, SC_FB_UB, SC_FB_U, SC_FB_ACT, SC_FB_ST, SC_FB_IT, SC_COUNT };
-  Scratch sc[SC_COUNT];
+  DevRes res{SC_COUNT};         // owns every buffer, stream and event below and above
   int ldu, nout;        // layout of the caller's u buffer for the call in progress (nnmpc_qp_solve_batch_ex)
 };
 
 namespace {
 
-template <class T>
-int dev_alloc(nnmpc_qp* h, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, count * sizeof(T));
-  if (e != hipSuccess) { set_error("hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e)); return NNMPC_ENOMEM; }
-  e = hipMemset(q, 0, count * sizeof(T));
-  if (e != hipSuccess) { set_error("hipMemset: %s", hipGetErrorString(e)); return NNMPC_EHIP; }
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  return 0;
-}
-
-// scratch buffer `which` of at least `bytes` (contents undefined); grown buffers replace the old ones
-template <class T>
-int scratch_get(nnmpc_qp* h, int which, T** out, size_t bytes) {
-  nnmpc_qp::Scratch& s = h->sc[which];
-  if (s.cap < bytes) {
-    if (s.p) { hipFree(s.p); s.p = nullptr; s.cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    const hipError_t e = hipMalloc(&s.p, want);
-    if (e != hipSuccess) { s.p = nullptr; set_error("hipMalloc(%zu bytes of scratch): %s", want, hipGetErrorString(e)); return NNMPC_ENOMEM; }
-    s.cap = want;
-  }
-  *out = (T*)s.p;
-  return 0;
-}
-
-size_t ev_get(nnmpc_qp* h) {
-  if (h->ev_used == h->ev_pool.size()) {
-    hipEvent_t e;
-    hipEventCreate(&e);
-    h->ev_pool.push_back(e);
-  }
-  return h->ev_used++;
+// The next profiling event of the call in progress, recorded on st.  nullptr when none could be created: the record that
+// holds it is skipped, and the call fails at its end (ev_failed).
+hipEvent_t ev_mark(nnmpc_qp* h, hipStream_t st) {
+  hipEvent_t e = nullptr;
+  if (h->res.pool_event(h->ev_used, &e)) { h->ev_failed = true; return nullptr; }
+  ++h->ev_used;
+  hipEventRecord(e, st);
+  return e;
 }
 struct EvScope {
-  nnmpc_qp* h; int kind; double flops; size_t e0; hipStream_t st;
-  EvScope(nnmpc_qp* h_, int kind_, double flops_, hipStream_t st_ = nullptr) : h(h_), kind(kind_), flops(flops_), e0(0), st(st_ ? st_ : h_->stream) {
-    if (h->profiling) { e0 = ev_get(h); hipEventRecord(h->ev_pool[e0], st); }
+  nnmpc_qp* h; int kind; double flops; hipEvent_t e0; hipStream_t st;
+  EvScope(nnmpc_qp* h_, int kind_, double flops_, hipStream_t st_ = nullptr) : h(h_), kind(kind_), flops(flops_), e0(nullptr), st(st_ ? st_ : h_->stream) {
+    if (h->profiling) e0 = ev_mark(h, st);
   }
   ~EvScope() {
-    if (h->profiling) {
-      size_t e1 = ev_get(h);
-      hipEventRecord(h->ev_pool[e1], st);
-      h->ev_recs.push_back({kind, e0, e1, flops});
-    }
+    if (h->profiling) h->ev_recs.push_back({kind, e0, ev_mark(h, st), flops});
   }
 };
 void ev_collect(nnmpc_qp* h) {
   for (auto& r : h->ev_recs) {
     float ms = 0.f;
-    hipEventElapsedTime(&ms, h->ev_pool[r.e0], h->ev_pool[r.e1]);
+    if (!r.e0 || !r.e1) continue;
+    hipEventElapsedTime(&ms, r.e0, r.e1);
     if (r.kind == 0) { h->stats.panel_ms += ms; h->stats.panel_launches += 1; h->stats.panel_flops += r.flops; }
     else if (r.kind == 1) h->stats.diag_ms += ms;
     else if (r.kind == 2) h->stats.trsv_ms += ms;
@@ -873,16 +842,11 @@ void gemm64(nnmpc_qp* h, double* C, size_t ldc, const double* A, size_t lda, con
 
 template <int NB>
 int set_lds_attrs() {
-  hipError_t e;
-  e = hipFuncSetAttribute((const void*)chol_diag_k<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, chol_diag_lds_bytes<NB>());
-  if (e != hipSuccess) return -1;
-  e = hipFuncSetAttribute((const void*)chol_panel_k<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, chol_panel_lds_bytes<NB>());
-  if (e != hipSuccess) return -1;
-  e = hipFuncSetAttribute((const void*)trsv_k<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  if (e != hipSuccess) return -1;
-  e = hipFuncSetAttribute((const void*)gemm_nt_f32_k<NB, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<NB>::LDS_FLOATS * 4);
-  if (e != hipSuccess) return -1;
-  return 0;
+  HIPCHK(hipFuncSetAttribute((const void*)chol_diag_k<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, chol_diag_lds_bytes<NB>()));
+  HIPCHK(hipFuncSetAttribute((const void*)chol_panel_k<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, chol_panel_lds_bytes<NB>()));
+  HIPCHK(hipFuncSetAttribute((const void*)trsv_k<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<NB, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<NB>::LDS_FLOATS * 4));
+  return NNMPC_OK;
 }
 
 template <int NB>
@@ -921,8 +885,6 @@ void factor_dispatch(nnmpc_qp* h, int nslots, int nfactor) {
 void solve_dispatch(nnmpc_qp* h, int nslots, const int* flag) {
   if (h->NB == 128) solve_all<128>(h, nslots, flag); else solve_all<64>(h, nslots, flag);
 }
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(e_)); return NNMPC_EHIP; } } while (0)
 
 // One segment (<= h->seg_max problems): q and the warm start for the whole
 // segment by two GEMMs, then lock-step rounds over the resident slots with
@@ -1035,7 +997,7 @@ int build_predictor(nnmpc_qp* h, const std::vector<double>& hh, int np, nnmpc_qp
           hf[pred_frag_index<NT>(jt, ks, lane) * 8 + e] = bf(hh[(size_t)(16 * jt + li) * np + k] / (L * dg[k]));   // H' = H diag(t)
         }
       }
-  if (!pw.Hf) { int rc = dev_alloc(h, (unsigned short**)&pw.Hf, hf.size()); if (rc) return rc; }
+  if (!pw.Hf) { int rc = h->res.alloc((unsigned short**)&pw.Hf, hf.size()); if (rc) return rc; }
   HIPCHK(hipMemcpy(pw.Hf, hf.data(), hf.size() * 2, hipMemcpyHostToDevice));
   pw.L = L;
   return 0;
@@ -1623,17 +1585,17 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   int* list = nullptr; double *x0c = nullptr, *lbc = nullptr, *ubc = nullptr, *uc = nullptr;
   uint32_t* actc = nullptr; int *stc = nullptr, *itc = nullptr;
   unsigned char* guessc = nullptr;
+  DevRes& res = h->res;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_GUESS, &guessc, (size_t)cntf * h->n)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_LIST, &list, cntf * sizeof(int))) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_X0, &x0c, (size_t)cntf * h->n_aug * 8)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_LB, &lbc, (size_t)cntf * h->nu * 8)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_UB, &ubc, (size_t)cntf * h->nu * 8)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_U, &uc, (size_t)cntf * h->n * 8)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_ACT, &actc, (size_t)cntf * h->words * 4)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_ST, &stc, (size_t)cntf * 4)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_FB_IT, &itc, (size_t)cntf * 8)) return rc;
   int rc = 0;
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_GUESS, &guessc, (size_t)cntf * h->n);
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_LIST, &list, cntf * sizeof(int));
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_X0, &x0c, (size_t)cntf * h->n_aug * 8);
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_LB, &lbc, (size_t)cntf * h->nu * 8);
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_UB, &ubc, (size_t)cntf * h->nu * 8);
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_U, &uc, (size_t)cntf * h->n * 8);
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_ACT, &actc, (size_t)cntf * h->words * 4);
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_ST, &stc, (size_t)cntf * 4);
-  if (!rc) rc = scratch_get(h, nnmpc_qp::SC_FB_IT, &itc, (size_t)cntf * 8);
-  if (rc) return rc;
   HIPCHK(hipMemcpy(list, fb.data(), cntf * sizeof(int), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(asm_gather_k, dim3(cntf), dim3(128), 0, s, x0c, lbc, ubc, x0_dev, lb_dev, ub_dev, list, cntf, h->n_aug, h->nu);
   // a problem whose set had settled but failed the check with P (inverse too inaccurate for its x) starts the polish
@@ -1668,12 +1630,11 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
     set_error("nnmpc_qp_create: bad arguments (n=%d nu=%d n_aug=%d)", n, nu, n_aug);
     return NNMPC_EINVAL;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("nnmpc_qp_create: no HIP device available (this library has no CPU fallback)");
-    return NNMPC_EHIP;
-  }
-  nnmpc_qp* h = new nnmpc_qp();
+  GUARD_BEGIN
+  if (int rc = check_device(__func__)) return rc;
+  Building<nnmpc_qp, nnmpc_qp_destroy> guard(new nnmpc_qp());   // released into *out at the end; destroyed on any other way out
+  nnmpc_qp* h = guard.get();
+  DevRes& res = h->res;
   memset(&h->stats, 0, sizeof(h->stats));
   memset(&h->d, 0, sizeof(h->d));
   h->profiling = false; h->ev_used = 0; h->have_inverse = false;
@@ -1682,7 +1643,7 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   nnmpc_qp_opts& o = h->opts;
   if (o.max_batch <= 0) o.max_batch = 1024;
   if (o.nb == 0) o.nb = (n <= 1024) ? 64 : 128;
-  if (o.nb != 64 && o.nb != 128) { set_error("nb must be 64 or 128"); delete h; return NNMPC_EINVAL; }
+  if (o.nb != 64 && o.nb != 128) { set_error("nb must be 64 or 128"); return NNMPC_EINVAL; }
   if (o.max_ipm_iters <= 0) o.max_ipm_iters = 40;
   if (o.max_polish_rounds <= 0) o.max_polish_rounds = 150;
   if (o.max_refine <= 0) o.max_refine = 60;
@@ -1704,7 +1665,8 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   if (o.ipm_tol <= 0.f) o.ipm_tol = 1e-2f;
   if (o.refine_tol <= 0.0) o.refine_tol = 1e-10;
   if (o.bound_tol <= 0.0) o.bound_tol = 1e-9;
-  hipGetDevice(&h->device);
+  HIPCHK(hipGetDevice(&h->device));
+  res.device = h->device;
   h->n = n; h->nu = nu; h->n_aug = n_aug;
   h->NB = o.nb;
   h->np = ((n + h->NB - 1) / h->NB) * h->NB;
@@ -1714,40 +1676,30 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   h->slots = ((o.max_batch + 127) / 128) * 128;
   h->words = (2 * n + 31) / 32;
   h->have_kunc = Kunc != nullptr;
-  if ((size_t)(h->np + 5 * h->NB) * 4 > 96 * 1024) { set_error("n too large for the LDS-resident solve vector"); delete h; return NNMPC_EINVAL; }
-  if (hipStreamCreate(&h->stream) != hipSuccess) { set_error("hipStreamCreate failed"); delete h; return NNMPC_EHIP; }
-  if (hipStreamCreate(&h->stream2) != hipSuccess || hipStreamCreate(&h->stream3) != hipSuccess || hipStreamCreate(&h->stream4) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->ev_join4, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_wfork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->ev_wide, hipEventDisableTiming) != hipSuccess) {
-    set_error("hipStreamCreate / hipEventCreate failed"); nnmpc_qp_destroy(h); return NNMPC_EHIP;
-  }
-  {
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_lambda_reg_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_lambda_reg2_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG2_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_lambda_reg32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_tail_k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_lambda_reg32b_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32B_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_lambda_tile32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_TILE32_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_f64_t128_k, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_wide_gemm_k<WIDE_XUNC>, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_wide_gemm_k<WIDE_LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_wide_gemm_k<WIDE_FAR>, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_wide_t_k, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)asm_small_k<9, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_SMALL9_LDS_MAX);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_f32_kdyn_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); nnmpc_qp_destroy(h); return NNMPC_EHIP; }
-  }
-  if (set_lds_attrs<128>() != 0 || set_lds_attrs<64>() != 0) {
-    set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); nnmpc_qp_destroy(h); return NNMPC_EHIP;
-  }
+  if ((size_t)(h->np + 5 * h->NB) * 4 > 96 * 1024) { set_error("n too large for the LDS-resident solve vector"); return NNMPC_EINVAL; }
+  for (hipStream_t* st : {&h->stream, &h->stream2, &h->stream3, &h->stream4})
+    if (int rc = res.stream(st)) return rc;
+  for (hipEvent_t* ev : {&h->ev_fork, &h->ev_join3, &h->ev_join4, &h->ev_join, &h->ev_wfork, &h->ev_wide})
+    if (int rc = res.event(ev, hipEventDisableTiming)) return rc;
+  HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg2_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG2_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_tail_k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg32b_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32B_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_tile32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_TILE32_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f64_t128_k, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_wide_gemm_k<WIDE_XUNC>, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_wide_gemm_k<WIDE_LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_wide_gemm_k<WIDE_FAR>, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_wide_t_k, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)asm_small_k<9, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_SMALL9_LDS_MAX));
+  HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_kdyn_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+  if (int rc = set_lds_attrs<128>()) return rc;
+  if (int rc = set_lds_attrs<64>()) return rc;
 
   const int np = h->np, NB = h->NB, ka = h->ka, S = h->slots;
   const size_t nb2 = (size_t)NB * NB;
-  int rc = 0;
-#define A_(ptr, cnt) if (!rc) rc = dev_alloc(h, &(ptr), (size_t)(cnt))
+#define A_(ptr, cnt) if (int rc = res.alloc(&(ptr), (size_t)(cnt))) return rc
   A_(h->Pt, h->tiles * nb2); A_(h->P32, (size_t)np * np); A_(h->P64, (size_t)np * np);
   A_(h->tq64, (size_t)np * ka); A_(h->Kunc32, (size_t)np * ka); A_(h->pdiag, np);
   A_(h->L, (size_t)S * h->tiles * nb2); A_(h->Y, (size_t)S * h->T * nb2); A_(h->Dacc, (size_t)S * h->T * nb2); A_(h->trsv_count, 1);
@@ -1776,8 +1728,8 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   A_(h->q64_all, G * np); A_(h->uunc_all, G * np);
   A_(h->lb_d, G * nu); A_(h->ub_d, G * nu);
   A_(h->in_stage, G * n_aug);
-  if (!rc && hipHostMalloc((void**)&h->pin_cnt, (2 * ASM_NCNT + 4) * sizeof(int)) != hipSuccess) { set_error("nnmpc_qp_create: hipHostMalloc failed"); rc = NNMPC_EHIP; }
-  if (!rc && hipHostMalloc((void**)&h->pin_st, G * sizeof(int)) != hipSuccess) { set_error("nnmpc_qp_create: hipHostMalloc failed"); rc = NNMPC_EHIP; }
+  if (int rc = res.pinned_alloc(&h->pin_cnt, 2 * ASM_NCNT + 4)) return rc;
+  if (int rc = res.pinned_alloc(&h->pin_st, G)) return rc;
   A_(d.lb64, (size_t)S * nu); A_(d.ub64, (size_t)S * nu);
   A_(d.slot_prob, S); A_(d.age, S); A_(d.next_prob, 1);
   // workgroups of the large-set kernel in flight (each with its tile slab in HBM / L2): four per CU for bulk batches --
@@ -1809,11 +1761,10 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
       A_(v1.lam, Rr * np); A_(v1.xh, Rr * np); A_(v1.xhw, (Rr + 256) * np); A_(v1.lam32, Rr * np); A_(v1.xh32, Rr * np);
       A_(v1.tnorm, Rr + 128 * (ASM_NKG + 1)); A_(v1.tslack, Rr + 128 * (ASM_NKG + 1)); A_(v1.rowprob, Rr + 256); A_(v1.kblk, 2 * (G / 64 + 2));
       v1.counters = h->asm_counters + ASM_NCNT;
-      if (!rc) v1.rows = (int)R;
+      v1.rows = (int)R;
     }
   }
 #undef A_
-  if (rc) { nnmpc_qp_destroy(h); return rc; }
   d.n = n; d.np = np; d.nu = nu; d.slots = S; d.words = h->words;
   d.max_ipm = o.max_ipm_iters; d.max_polish = o.max_polish_rounds; d.max_refine = o.max_refine;
   d.max_rounds = o.max_rounds; d.stale_max_changes = o.stale_max_changes; d.stale_cg_limit = o.stale_cg_limit;
@@ -1827,7 +1778,7 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
     for (int r = 0; r < n; ++r) dg[r] = P[(size_t)r * n + r];
     std::nth_element(dg.begin(), dg.begin() + n / 2, dg.end());
     h->pscale = dg[n / 2];
-    if (!(h->pscale > 0.0)) { set_error("P has a non-positive diagonal"); nnmpc_qp_destroy(h); return NNMPC_EINVAL; }
+    if (!(h->pscale > 0.0)) { set_error("P has a non-positive diagonal"); return NNMPC_EINVAL; }
   }
   const double ips = 1.0 / h->pscale;
   float pdmax = 0.f;
@@ -1867,43 +1818,27 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
       h->tqmax = std::max(h->tqmax, std::fabs(tq[(size_t)r * n_aug + k]));
       if (Kunc) k32[(size_t)r * ka + k] = (float)Kunc[(size_t)r * n_aug + k];
     }
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess) e = hipMemcpy(h->Pt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->P32, p32.data(), p32.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->P64, p64.data(), p64.size() * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->tq64, t64.data(), t64.size() * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->Kunc32, k32.data(), k32.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->pdiag, pdg.data(), pdg.size() * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { set_error("upload of P/tq failed: %s", hipGetErrorString(e)); nnmpc_qp_destroy(h); return NNMPC_EHIP; }
-  *out = h;
+  HIPCHK(hipMemcpy(h->Pt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->P32, p32.data(), p32.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->P64, p64.data(), p64.size() * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->tq64, t64.data(), t64.size() * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->Kunc32, k32.data(), k32.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->pdiag, pdg.data(), pdg.size() * 4, hipMemcpyHostToDevice));
+  *out = guard.release();
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_qp_destroy(nnmpc_qp* h) {
   if (!h) return NNMPC_OK;
-  hipDeviceSynchronize();
-  for (void* p : h->allocs) hipFree(p);
-  for (auto& g : h->far) { hipFree(g.U); hipFree(g.Vx); hipFree(g.Vl); hipFree(g.cu); hipFree(g.kt); }
-  for (auto& sc : h->sc) if (sc.p) hipFree(sc.p);
-  for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
-  if (h->ev_fork) hipEventDestroy(h->ev_fork);
-  if (h->ev_join) hipEventDestroy(h->ev_join);
-  if (h->ev_join3) hipEventDestroy(h->ev_join3);
-  if (h->ev_join4) hipEventDestroy(h->ev_join4);
-  if (h->ev_wfork) hipEventDestroy(h->ev_wfork);
-  if (h->ev_wide) hipEventDestroy(h->ev_wide);
-  if (h->pin_cnt) hipHostFree(h->pin_cnt);
-  if (h->pin_st) hipHostFree(h->pin_st);
-  if (h->stream2) hipStreamDestroy(h->stream2);
-  if (h->stream3) hipStreamDestroy(h->stream3);
-  if (h->stream4) hipStreamDestroy(h->stream4);
-  if (h->stream) hipStreamDestroy(h->stream);
+  h->res.release();
   delete h;
   return NNMPC_OK;
 }
 
 int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
   if (!h || !Hinv || !Kunc) { set_error("nnmpc_qp_set_inverse: bad arguments"); return NNMPC_EINVAL; }
+  GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
   const int n = h->n, np = h->np, ka = h->ka, n_aug = h->n_aug;
   if ((uint64_t)np * np * 8 >= (1ull << 32)) {            // the multiplier kernels address Pinv with 32-bit byte offsets
@@ -1928,7 +1863,7 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
     if (np >= PRED_W && n >= PRED_W) {
       const int rc = build_predictor<4>(h, hh, np, h->pred[0]);
       if (rc) return rc;
-      if (!h->pred_cnt) { const int rc2 = dev_alloc(h, &h->pred_cnt, 4); if (rc2) return rc2; }
+      if (!h->pred_cnt) { const int rc2 = h->res.alloc(&h->pred_cnt, 4); if (rc2) return rc2; }
       HIPCHK(hipFuncSetAttribute((const void*)asm_predict_k<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, pred_lds_bytes<4, 4>(h->nu)));
       HIPCHK(hipFuncSetAttribute((const void*)asm_predict_k<4, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, pred_lds_bytes<4, 2>(h->nu)));
     }
@@ -1942,15 +1877,16 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
   //      E2 = P Pinv - I,  E1 = P Kunc + tq;  their maxima feed the per-problem certificate
   {
     const int kap = ((n_aug + 63) / 64) * 64;
-    double *tmp = nullptr, *kt = nullptr;
     // tmp holds P Pinv (np x np), then P Kunc (np x kap): kap exceeds np when the horizon is short beside the state (n < n_aug)
     const size_t ntmp = (size_t)np * std::max(np, kap);
-    HIPCHK(hipMalloc((void**)&tmp, ntmp * 8));
-    HIPCHK(hipMalloc((void**)&kt, (size_t)kap * np * 8));
     std::vector<double> ktr((size_t)kap * np, 0.0);
     for (int r = 0; r < n; ++r)
       for (int k = 0; k < n_aug; ++k) ktr[(size_t)k * np + r] = Kunc[(size_t)r * n_aug + k];
-    HIPCHK(hipMemcpy(kt, ktr.data(), ktr.size() * 8, hipMemcpyHostToDevice));
+    DevRes work;                                            // the two temporaries: freed on every way out of this block
+    work.device = h->device;
+    double *tmp = nullptr, *kt = nullptr;
+    if (int rc = work.alloc(&tmp, ntmp)) return rc;
+    if (int rc = work.upload(&kt, ktr.data(), ktr.size())) return rc;
     gemm64(h, tmp, np, h->P64, np, h->H64, np, np, np, np);                 // P Pinv (Pinv symmetric)
     HIPCHK(stream_sync(h->stream));
     std::vector<double> c(ntmp);
@@ -1966,7 +1902,6 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
     double e1 = 0.0;
     for (int r = 0; r < n; ++r)
       for (int k = 0; k < n_aug; ++k) e1 = std::max(e1, std::fabs(c[(size_t)r * kap + k] + tqh[(size_t)r * ka + k]));
-    hipFree(tmp); hipFree(kt);
     h->asm_e1max = e1; h->asm_e2max = e2;
     if (!(e2 < 1e-6) || !(e1 == e1)) {
       set_error("nnmpc_qp_set_inverse: |P Pinv - I|_max = %.3e: the supplied inverse is not usable", e2);
@@ -1975,11 +1910,13 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
   }
   h->have_inverse = true;
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_qp_set_farfield(nnmpc_qp* h, int32_t W, int32_t r, const double* U, const double* Vx, const double* Vl) {
   if (!h || !U || !Vx || !Vl || r <= 0) { set_error("nnmpc_qp_set_farfield: bad arguments"); return NNMPC_EINVAL; }
   if (!h->have_inverse) { set_error("nnmpc_qp_set_farfield: needs nnmpc_qp_set_inverse first"); return NNMPC_EINVAL; }
+  GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
   const int n = h->n, np = h->np, ka = h->ka, n_aug = h->n_aug;
   const int rp = ((r + 127) / 128) * 128;
@@ -2024,44 +1961,40 @@ int nnmpc_qp_set_farfield(nnmpc_qp* h, int32_t W, int32_t r, const double* U, co
   }
   nnmpc_qp::Far f;
   f.W = W; f.r = r; f.rp = rp; f.U = f.Vx = f.Vl = f.cu = nullptr; f.kt = nullptr; f.ksum = ksum; f.efar = 0.0;
-  // the factors' buffers are owned by their Far entry (not by the handle's allocation list): a refused set and a replaced one are
-  // released at once
-  unsigned long long* em = nullptr;
+  // the factors are buffers of the handle's owner, given back at once when a set is refused or replaced
+  DevRes& res = h->res;
   auto release = [&](nnmpc_qp::Far& g) {
-    hipFree(g.U); hipFree(g.Vx); hipFree(g.Vl); hipFree(g.cu); hipFree(g.kt);
+    for (void* p : {(void*)g.U, (void*)g.Vx, (void*)g.Vl, (void*)g.cu, (void*)g.kt}) res.give_back(p);
     g.U = g.Vx = g.Vl = g.cu = nullptr; g.kt = nullptr;
   };
-  auto fail = [&](int code) { release(f); if (em) hipFree(em); return code; };
-#define FFCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(e_)); return fail(e_ == hipErrorOutOfMemory ? NNMPC_ENOMEM : NNMPC_EHIP); } } while (0)
-  FFCHK(hipMalloc((void**)&f.U, u.size() * 8));
-  FFCHK(hipMalloc((void**)&f.Vx, vx.size() * 8));
-  FFCHK(hipMalloc((void**)&f.Vl, vl.size() * 8));
-  FFCHK(hipMalloc((void**)&f.cu, cu.size() * 8));
-  FFCHK(hipMalloc((void**)&f.kt, kt.size() * sizeof(int)));
-  FFCHK(hipMemcpy(f.kt, kt.data(), kt.size() * sizeof(int), hipMemcpyHostToDevice));
-  FFCHK(hipMemcpy(f.U, u.data(), u.size() * 8, hipMemcpyHostToDevice));
-  FFCHK(hipMemcpy(f.Vx, vx.data(), vx.size() * 8, hipMemcpyHostToDevice));
-  FFCHK(hipMemcpy(f.Vl, vl.data(), vl.size() * 8, hipMemcpyHostToDevice));
-  FFCHK(hipMemcpy(f.cu, cu.data(), cu.size() * 8, hipMemcpyHostToDevice));
+  auto hip = [](hipError_t e, const char* what) { if (e != hipSuccess) set_error("%s: %s", what, hipGetErrorString(e)); return e == hipSuccess ? NNMPC_OK : NNMPC_EHIP; };
+#define FFCHK(x) do { if (int rc_ = (x)) { release(f); return rc_; } } while (0)
+  FFCHK(res.upload(&f.U, u.data(), u.size()));
+  FFCHK(res.upload(&f.Vx, vx.data(), vx.size()));
+  FFCHK(res.upload(&f.Vl, vl.data(), vl.size()));
+  FFCHK(res.upload(&f.cu, cu.data(), cu.size()));
+  FFCHK(res.upload(&f.kt, kt.data(), kt.size()));
   // ---- verify on the device copies the passes will use: max |U [Vx | Vl] - [Kunc[W:] | -Pinv[W:, 0:W]]|
   {
-    FFCHK(hipMalloc((void**)&em, 8));
-    FFCHK(hipMemset(em, 0, 8));
+    DevRes work;                                            // the result word (zeroed): freed on every way out of this block
+    work.device = h->device;
+    unsigned long long* em = nullptr;
+    FFCHK(work.alloc(&em, 1));
     hipLaunchKernelGGL(far_verify_k, dim3(nf), dim3(256), rp * sizeof(double), h->stream, f.U, f.Vx, f.Vl, h->Kunc64, h->H64, W, rp, ka, np, em);
     unsigned long long bits = 0;
-    FFCHK(hipMemcpyAsync(&bits, em, 8, hipMemcpyDeviceToHost, h->stream));
-    FFCHK(stream_sync(h->stream));
-    hipFree(em); em = nullptr;
+    FFCHK(hip(hipMemcpyAsync(&bits, em, 8, hipMemcpyDeviceToHost, h->stream), "hipMemcpyAsync"));
+    FFCHK(hip(stream_sync(h->stream), "stream_sync"));
     double e;
     memcpy(&e, &bits, 8);
     f.efar = e;
-    if (!(e < 1e-9)) { set_error("nnmpc_qp_set_farfield: max |U V' - M| = %.3e: the factors are not usable", e); return fail(NNMPC_EINVAL); }
+    if (!(e < 1e-9)) { set_error("nnmpc_qp_set_farfield: max |U V' - M| = %.3e: the factors are not usable", e); release(f); return NNMPC_EINVAL; }
   }
 #undef FFCHK
   h->far_missing.erase(std::remove(h->far_missing.begin(), h->far_missing.end(), W), h->far_missing.end());
   for (auto& g : h->far) if (g.W == W) { HIPCHK(stream_sync(h->stream)); release(g); g = f; return NNMPC_OK; }   // replaces the window's factors
   h->far.push_back(f);
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_qp_farfield_missing(nnmpc_qp* h, int32_t* W) {
@@ -2087,6 +2020,7 @@ int nnmpc_qp_set_profiling(nnmpc_qp* h, int32_t on) {
 
 int nnmpc_qp_get_stats(nnmpc_qp* h, nnmpc_qp_stats* out, int32_t reset) {
   if (!h || !out) return NNMPC_EINVAL;
+  GUARD_BEGIN
   *out = h->stats;
   out->asm_e1max = h->asm_e1max; out->asm_e2max = h->asm_e2max;
   {
@@ -2105,6 +2039,7 @@ int nnmpc_qp_get_stats(nnmpc_qp* h, nnmpc_qp_stats* out, int32_t reset) {
   }
   if (reset) memset(&h->stats, 0, sizeof(h->stats));
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_qp_solve_batch(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub,
@@ -2124,23 +2059,24 @@ int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const doub
   if (!h || B < 0 || !x0 || !lb || !ub || !u) { set_error("nnmpc_qp_solve_batch: bad arguments"); return NNMPC_EINVAL; }
   if (out_kind != NNMPC_OUT_SEQUENCE && out_kind != NNMPC_OUT_FIRST_MOVE) { set_error("nnmpc_qp_solve_batch_ex: bad out_kind %d", out_kind); return NNMPC_EINVAL; }
   if (B == 0) return NNMPC_OK;
+  GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
   const int G = h->seg_max;
   const int ncol = out_kind == NNMPC_OUT_FIRST_MOVE ? h->nu : h->n;   // columns of the caller's u
   h->ldu = ncol; h->nout = ncol;
-  size_t e_tot0 = 0;
-  if (h->profiling) { e_tot0 = ev_get(h); hipEventRecord(h->ev_pool[e_tot0], h->stream); }
+  hipEvent_t e_tot0 = h->profiling ? ev_mark(h, h->stream) : nullptr;
   // device staging for the outputs when the caller hands host pointers (owned by the handle, grown on demand)
   double* u_stage = nullptr; uint32_t* a_stage = nullptr; int32_t* s_stage = nullptr; int32_t* i_stage = nullptr;
   unsigned char* g_stage = nullptr;
   const int gmax = std::min(G, (int)B);
   int rc = 0;
   if (ptr_kind == NNMPC_HOST) {
-    if (!rc) rc = scratch_get(h, nnmpc_qp::SC_U, &u_stage, (size_t)gmax * ncol * sizeof(double));
-    if (!rc && active) rc = scratch_get(h, nnmpc_qp::SC_ACT, &a_stage, (size_t)gmax * h->words * sizeof(uint32_t));
-    if (!rc && status) rc = scratch_get(h, nnmpc_qp::SC_ST, &s_stage, (size_t)gmax * sizeof(int32_t));
-    if (!rc && iters) rc = scratch_get(h, nnmpc_qp::SC_IT, &i_stage, (size_t)gmax * 2 * sizeof(int32_t));
-    if (!rc && guess) rc = scratch_get(h, nnmpc_qp::SC_GUESS, &g_stage, (size_t)gmax * h->n);
+    DevRes& res = h->res;
+    if (!rc) rc = res.slot(nnmpc_qp::SC_U, &u_stage, (size_t)gmax * ncol * sizeof(double));
+    if (!rc && active) rc = res.slot(nnmpc_qp::SC_ACT, &a_stage, (size_t)gmax * h->words * sizeof(uint32_t));
+    if (!rc && status) rc = res.slot(nnmpc_qp::SC_ST, &s_stage, (size_t)gmax * sizeof(int32_t));
+    if (!rc && iters) rc = res.slot(nnmpc_qp::SC_IT, &i_stage, (size_t)gmax * 2 * sizeof(int32_t));
+    if (!rc && guess) rc = res.slot(nnmpc_qp::SC_GUESS, &g_stage, (size_t)gmax * h->n);
   }
   hipError_t he = hipSuccess;
 #define STEP_(x) do { if (!rc && he == hipSuccess) { he = (x); if (he != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(he)); rc = NNMPC_EHIP; } } } while (0)
@@ -2176,18 +2112,19 @@ int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const doub
   }
 #undef STEP_
   if (h->profiling) {
-    size_t e1 = ev_get(h);
-    hipEventRecord(h->ev_pool[e1], h->stream);
+    h->ev_recs.push_back({3, e_tot0, ev_mark(h, h->stream), 0.0});
     stream_sync(h->stream);
-    h->ev_recs.push_back({3, e_tot0, e1, 0.0});
     ev_collect(h);
   }
+  if (h->ev_failed) { h->ev_failed = false; if (!rc) rc = NNMPC_EHIP; }
   return rc;
+  GUARD_END
 }
 
 int nnmpc_qp_debug_factor_solve(nnmpc_qp* h, int32_t B, const float* dvec, const float* mask,
                                 const float* rhs, float* sol) {
   if (!h || B <= 0 || B > h->slots || !dvec || !mask || !rhs || !sol) { set_error("debug_factor_solve: bad arguments"); return NNMPC_EINVAL; }
+  GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
   QpDev& d = h->d;
   const int rows = h->slots;
@@ -2216,6 +2153,7 @@ int nnmpc_qp_debug_factor_solve(nnmpc_qp* h, int32_t B, const float* dvec, const
     for (int r = 0; r < h->n; ++r) sol[(size_t)p * h->n + r] = so[(size_t)p * h->np + r];
   if (h->profiling) { stream_sync(h->stream); ev_collect(h); }
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_qp_debug_factor_fail(nnmpc_qp* h, int32_t B, int32_t* fail) {
@@ -2234,6 +2172,7 @@ int nnmpc_qp_debug_predict(nnmpc_qp* h, int32_t B, const double* x0, const doubl
   if (!h->have_inverse) { set_error("debug_predict: needs nnmpc_qp_set_inverse first"); return NNMPC_EINVAL; }
   if (!(h->pred[0].L > 0.0)) { set_error("debug_predict: the handle has no predictor window (n = %d, nu = %d)", h->n, h->nu); return NNMPC_EINVAL; }
   if (wide == 1 && !(h->pred[1].L > 0.0)) { set_error("debug_predict: the handle has no 1024-column window (n = %d, nu = %d)", h->n, h->nu); return NNMPC_EINVAL; }
+  GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const int nprob = B, segp = ((nprob + 127) / 128) * 128;
@@ -2273,6 +2212,7 @@ int nnmpc_qp_debug_predict(nnmpc_qp* h, int32_t B, const double* x0, const doubl
   *L = h->pred[wide].L;
   if (h->profiling) ev_collect(h);
   return NNMPC_OK;
+  GUARD_END
 }
 
 }  // extern "C"

@@ -18,12 +18,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "../../include/nnmpc.h"
-#include "common.h"
+#include "dev_res.h"
 
 using namespace nnmpc;
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(e_)); return NNMPC_EHIP; } } while (0)
 
 extern "C" {
 
@@ -135,6 +132,7 @@ struct nnmpc_comm {
   int rank = 0, world = 1, device = 0;
   hipStream_t stream = nullptr;
   double* scratch = nullptr;   // 8 doubles on the device (barrier / max-reduce payload)
+  DevRes res;                  // owns the stream and the scratch
 };
 
 extern "C" {
@@ -154,22 +152,22 @@ int nnmpc_comm_init(nnmpc_comm** out, const void* id128, int32_t rank, int32_t w
     set_error("nnmpc_comm_init: bad arguments (rank=%d world=%d)", rank, world);
     return NNMPC_EINVAL;
   }
-  const int rc = rccl_load();
-  if (rc) return rc;
-  nnmpc_comm* c = new nnmpc_comm();
+  GUARD_BEGIN
+  if (int rc = rccl_load()) return rc;
+  Building<nnmpc_comm, nnmpc_comm_destroy> guard(new nnmpc_comm());   // released into *out at the end; destroyed on any other way out
+  nnmpc_comm* c = guard.get();
   c->rank = rank; c->world = world;
-  if (hipGetDevice(&c->device) != hipSuccess) { set_error("nnmpc_comm_init: no HIP device"); delete c; return NNMPC_EHIP; }
+  if (hipGetDevice(&c->device) != hipSuccess) { set_error("nnmpc_comm_init: no HIP device"); return NNMPC_EHIP; }
+  c->res.device = c->device;
   rcclUniqueId id;
   memcpy(id.internal, id128, sizeof(id.internal));
   const int r = g_rccl.CommInitRank(&c->comm, world, id, rank);
-  if (r != RCCL_SUCCESS) { set_error("ncclCommInitRank(rank %d of %d): %s", rank, world, g_rccl.GetErrorString(r)); delete c; return NNMPC_EHIP; }
-  if (hipStreamCreate(&c->stream) != hipSuccess || hipMalloc((void**)&c->scratch, 8 * sizeof(double)) != hipSuccess) {
-    set_error("nnmpc_comm_init: stream / scratch allocation failed");
-    nnmpc_comm_destroy(c);
-    return NNMPC_EHIP;
-  }
-  *out = c;
+  if (r != RCCL_SUCCESS) { set_error("ncclCommInitRank(rank %d of %d): %s", rank, world, g_rccl.GetErrorString(r)); return NNMPC_EHIP; }
+  if (int rc = c->res.stream(&c->stream)) return rc;
+  if (int rc = c->res.alloc(&c->scratch, 8)) return rc;
+  *out = guard.release();
   return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_comm_destroy(nnmpc_comm* c) {
@@ -177,8 +175,7 @@ int nnmpc_comm_destroy(nnmpc_comm* c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->comm) g_rccl.CommDestroy(c->comm);
-  if (c->scratch) hipFree(c->scratch);
-  if (c->stream) hipStreamDestroy(c->stream);
+  c->res.release();
   delete c;
   return NNMPC_OK;
 }
