@@ -234,6 +234,34 @@ int nnmpc_qp_debug_predict(nnmpc_qp* h, int32_t B, const double* x0, const doubl
                            uint8_t* state,  /* out [B][n]: 0 free, 1 upper, 2 lower */
                            int32_t* info,   /* out [4]: W, problems per workgroup, the extent kernel's count (-1 if not run), window chosen (0 / 1) */
                            double* L);      /* out: the step constant of that window, 1.05 lambda_max(D^-1/2 Pinv_WW D^-1/2) */
+/* Kernel-level test hook: the GEMM kernels of the active-set path alone, through the launch code of a solve.
+ *   C[M x N] = A[M x K] B[N x K]'      row-major, K contiguous in A and B; host pointers; any handle will do.
+ * The call uploads A (a_rows rows), B (N rows), C (c_rows rows, ITS CONTENTS included: what a kernel leaves alone comes back as it
+ * went in) and the integer arrays into device memory of its own, launches, waits and copies C back.  Of a row only its first K (A, B)
+ * or N (C) entries belong to the operand; the last row ends there (so B and C may point into wider arrays).
+ * kind 0: what the solves' gemm64() does with these arguments -- the 128 x 128 LDS-DMA kernel when M, N are multiples of 128, K of 16
+ *         and there are 200 tiles or more (or a rowmap), else the 64 x 64 kernel (M, N multiples of 64; K is walked in whole chunks of
+ *         16, a remainder is dropped).  A rowmap off the 128-grid is refused as in a solve: NNMPC_EINVAL with gemm64's message, nothing
+ *         launched, C untouched; the refusal does not stick to the handle (its flag is left as it was found).
+ * kind 1 / 2: gemm_nt_f64_t128_k / gemm_nt_f64_k forced (M, N multiples of 128 / 64, K of 16; kind 2 has no rowmap).
+ * kind 3 / 4: gemm_nt_f32_kdyn_k<128> / <64> as the end of a round launches them: A, B, C are f32, kdyn is required and holds one bound
+ *         per 64 rows (kper 2 / 1); N a multiple of 128 / 64, K of 32; M is the number of rows in use, the grid rounds it up to whole
+ *         tiles and A, C and kdyn reach that far.  No rowphase, mdyn, rowmap.
+ * For tile edge T (128 / 64) and chunk c (16 fp64, 32 f32):
+ *   rowphase [M] : a row tile in which no row has tag `want` is left alone (no entry of C in it is written);
+ *   mdyn [1]     : a row tile whose first row is >= *mdyn is left alone; every other tile is written whole, all T rows;
+ *   kdyn         : bound on the last non-zero column of A.  kblocks = 0: one entry for the launch; else one per 64 rows, and a row tile
+ *                  takes the largest of its T / 64 entries.  The product runs over k < min(K, (bound / c + 1) c); -1: zeros, written;
+ *   rowmap [M]   : (128 x 128 kernel) row i of A and of C is row rowmap[i] of the arrays; an entry < 0 or a row >= *mdyn stores nothing.
+ * NNMPC_EINVAL, with a message that names this function, for a shape off the kind's grid, a leading dimension shorter than its row
+ * or not a multiple of 16 bytes (A, B), kind 3 / 4 without kdyn, null operands, a rowmap entry beyond the arrays. */
+int nnmpc_qp_debug_gemm(nnmpc_qp* h, int32_t kind, int32_t M, int32_t N, int32_t K,
+                        const void* A, int64_t lda, int64_t a_rows,   /* a_rows, c_rows: rows of the arrays A and C (>= M rounded up to T; */
+                        const void* B, int64_t ldb,                   /* with a rowmap: more than its largest entry) */
+                        void* C, int64_t ldc, int64_t c_rows,
+                        const int32_t* rowphase, int32_t want, const int32_t* kdyn, int32_t kblocks,
+                        const int32_t* mdyn, const int32_t* rowmap,   /* each nullable */
+                        int32_t* info);   /* out [4]: kernel (1 t128, 2 64 x 64, 3 f32 <128>, 4 f32 <64>; 0 refused), workgroups, kper, tile edge */
 
 /* Structured NN controller.  dims = [d_in, h1, ..., h_{L-1}, nu]; W[l] is
  * dims[l] x dims[l+1] row-major (Keras kernel layout), b[l] has dims[l+1]

@@ -55,7 +55,7 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_qp_solve_batch_warm", "nnmpc_qp_solve_batch_ex", "nnmpc_qp_set_inverse", "nnmpc_qp_dims",
            "nnmpc_qp_first_moves", "nnmpc_qp_set_farfield", "nnmpc_qp_farfield_missing",
            "nnmpc_qp_set_profiling", "nnmpc_qp_get_stats", "nnmpc_qp_debug_factor_solve", "nnmpc_qp_debug_factor_fail",
-           "nnmpc_qp_debug_predict",
+           "nnmpc_qp_debug_predict", "nnmpc_qp_debug_gemm",
            "nnmpc_nn_create", "nnmpc_nn_create_ex", "nnmpc_nn_destroy", "nnmpc_nn_forward", "nnmpc_nn_last_ms", "nnmpc_nn_last_hidden_ms",
            "nnmpc_train_create", "nnmpc_train_create_ex", "nnmpc_train_destroy", "nnmpc_train_set_data", "nnmpc_train_grad", "nnmpc_train_step",
            "nnmpc_train_epoch", "nnmpc_train_eval", "nnmpc_train_get_weights", "nnmpc_train_set_weights",
@@ -119,6 +119,9 @@ def load():
     lib.nnmpc_qp_debug_factor_fail.argtypes = [vp, i32, dp]
     lib.nnmpc_qp_debug_predict.restype = i32
     lib.nnmpc_qp_debug_predict.argtypes = [vp, i32, dp, dp, dp, i32, i32, dp, dp, C.POINTER(C.c_double)]
+    lib.nnmpc_qp_debug_gemm.restype = i32
+    lib.nnmpc_qp_debug_gemm.argtypes = [vp, i32, i32, i32, i32, dp, C.c_int64, C.c_int64, dp, C.c_int64, dp, C.c_int64, C.c_int64,
+                                        dp, i32, dp, i32, dp, dp, dp]
     lib.nnmpc_nn_create.restype = i32
     lib.nnmpc_nn_create.argtypes = [C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(dp), C.POINTER(dp),
                                     i32, i32, i32, dp, dp, dp, i32, i32]

@@ -815,29 +815,62 @@ void gemm32(nnmpc_qp* h, float* C, size_t ldc, const float* A, size_t lda, const
   if (N % 128 == 0 && M % 128 == 0) launch_gemm32<128>(h->stream, C, ldc, A, lda, B, ldb, M, N, K);
   else launch_gemm32<64>(h->stream, C, ldc, A, lda, B, ldb, M, N, K);
 }
-void gemm64(nnmpc_qp* h, double* C, size_t ldc, const double* A, size_t lda, const double* B,
-            size_t ldb, int M, int N, int K, const int* rowphase = nullptr, int want = 0,
-            const int* kdyn = nullptr, const int* mdyn = nullptr, bool kblocks = false, const int* rowmap = nullptr) {
-  // kblocks: kdyn holds one bound per 64 rows of A (else one for the launch); rowmap: gather / scatter of the rows (gemm64.h)
+// The fp64 NT GEMM of the solves in three parts -- the choice of the kernel and one launch function per kernel -- so that the
+// kernel-level test hook (nnmpc_qp_debug_gemm) runs the launch lines a solve runs.
+// kblocks: kdyn holds one bound per 64 rows of A (else one for the launch); rowmap: gather / scatter of the rows (gemm64.h)
+enum { GEMM64_REFUSED = 0, GEMM64_T128 = 1, GEMM64_K64 = 2 };
+int gemm64_choice(int M, int N, int K, bool rowmap) {
   // (fewer 128 x 128 tiles than CUs -- the x_unc product of a chain step: 149 rows -- leave most of the chip idle behind a few
   // long K loops: four times as many 64 x 64 tiles finish sooner)
   static const bool small64 = getenv("NNMPC_NO_SMALL_GEMM") == nullptr;   // (the variable: A/B)
   const bool few = small64 && !rowmap && (M / 128) * (N / 128) < 200;
-  if (M % 128 == 0 && N % 128 == 0 && K % G64_KC == 0 && !few) {
-    const int ntm = M / 128, ntn = N / 128;
-    hipLaunchKernelGGL(gemm_nt_f64_t128_k, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, h->stream, C, ldc, A, lda, B, ldb, K, ntm, ntn,
-                       rowphase, want, kdyn, kblocks ? 2 : 0, mdyn, rowmap);
-    return;
-  }
-  if (rowmap) {
-    // the 64 x 64 kernel has no gather / scatter of the rows: running it would write the rows of C to the wrong problems.  The one
-    // caller with a rowmap (the device tail's x_unc rows) only exists on the 128-grid (`lazy`); anything else is a bug -- say so.
+  if (M % 128 == 0 && N % 128 == 0 && K % G64_KC == 0 && !few) return GEMM64_T128;
+  // the 64 x 64 kernel has no gather / scatter of the rows: running it would write the rows of C to the wrong problems.  The one
+  // caller with a rowmap (the device tail's x_unc rows) only exists on the 128-grid (`lazy`); anything else is a bug (gemm64 says so).
+  return rowmap ? GEMM64_REFUSED : GEMM64_K64;
+}
+int launch_gemm64_t128(hipStream_t s, double* C, size_t ldc, const double* A, size_t lda, const double* B, size_t ldb, int M, int N, int K,
+                       const int* rowphase, int want, const int* kdyn, const int* mdyn, bool kblocks, const int* rowmap) {
+  const int ntm = M / 128, ntn = N / 128;
+  hipLaunchKernelGGL(gemm_nt_f64_t128_k, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, C, ldc, A, lda, B, ldb, K, ntm, ntn,
+                     rowphase, want, kdyn, kblocks ? 2 : 0, mdyn, rowmap);
+  return g64_grid(ntm, ntn);                               // (workgroups: the hook reports them)
+}
+int launch_gemm64_k64(hipStream_t s, double* C, size_t ldc, const double* A, size_t lda, const double* B, size_t ldb, int M, int N, int K,
+                      const int* rowphase, int want, const int* kdyn, const int* mdyn, bool kblocks) {
+  dim3 grid(N / 64, M / 64);
+  hipLaunchKernelGGL(gemm_nt_f64_k, grid, dim3(256), 0, s, C, ldc, A, lda, B, ldb, K, rowphase, want, kdyn, mdyn, kblocks ? 1 : 0);
+  return (N / 64) * (M / 64);
+}
+// Returns the kernel that was launched (GEMM64_*; the solves do not look at it).  GEMM64_REFUSED: nothing was launched, the last error
+// is set and h->gemm_error makes the call in progress fail at its next check.
+int gemm64(nnmpc_qp* h, double* C, size_t ldc, const double* A, size_t lda, const double* B,
+           size_t ldb, int M, int N, int K, const int* rowphase = nullptr, int want = 0,
+           const int* kdyn = nullptr, const int* mdyn = nullptr, bool kblocks = false, const int* rowmap = nullptr, int* nwg = nullptr) {
+  const int which = gemm64_choice(M, N, K, rowmap != nullptr);
+  int g = 0;
+  if (which == GEMM64_T128) g = launch_gemm64_t128(h->stream, C, ldc, A, lda, B, ldb, M, N, K, rowphase, want, kdyn, mdyn, kblocks, rowmap);
+  else if (which == GEMM64_K64) g = launch_gemm64_k64(h->stream, C, ldc, A, lda, B, ldb, M, N, K, rowphase, want, kdyn, mdyn, kblocks);
+  else {
     set_error("gemm64: rowmap with a shape off the 128 x 128 / K %% 16 grid (M = %d, N = %d, K = %d)", M, N, K);
     h->gemm_error = true;
-    return;
   }
-  dim3 grid(N / 64, M / 64);
-  hipLaunchKernelGGL(gemm_nt_f64_k, grid, dim3(256), 0, h->stream, C, ldc, A, lda, B, ldb, K, rowphase, want, kdyn, mdyn, kblocks ? 1 : 0);
+  if (nwg) *nwg = g;
+  return which;
+}
+// XH32 = LAM32 Pinv32' at the end of a round: `rows` running f32 problems, W window columns, one k-bound per 64 rows (kdyn).
+// The grid rounds `rows` up to whole tiles: A, C and kdyn reach that far.
+// NB x NB tiles, NB / 64 bounds per row tile.  launch_xh32 picks the tile as the round does; the test hook also forces it.
+template <int NB>
+void launch_xh32_nb(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda, const float* B, size_t ldb, int rows, int W, int K,
+                    const int* kdyn) {
+  hipLaunchKernelGGL((gemm_nt_f32_kdyn_k<NB>), dim3(W / NB, (rows + NB - 1) / NB), dim3(256), TileCfg<NB>::LDS_FLOATS * 4, s,
+                     C, ldc, A, lda, B, ldb, K, kdyn, NB / 64);
+}
+void launch_xh32(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda, const float* B, size_t ldb, int rows, int W, int K,
+                 const int* kdyn) {
+  if (W % 128 == 0) launch_xh32_nb<128>(s, C, ldc, A, lda, B, ldb, rows, W, K, kdyn);
+  else launch_xh32_nb<64>(s, C, ldc, A, lda, B, ldb, rows, W, K, kdyn);
 }
 
 template <int NB>
@@ -1522,12 +1555,8 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
         gemm64(h, V.xh, h->np, V.lam, h->np, h->H64, h->np, ((n64 + 127) / 128) * 128, a.W, h->np, nullptr, 0,
                V.kblk, nullptr, true);
       // (rows are ordered by their last active stage: every 64-row block has its own k-range, asm_bins_b_k)
-      if (n32 && a.W % 128 == 0)
-        hipLaunchKernelGGL((gemm_nt_f32_kdyn_k<128>), dim3(a.W / 128, (n32 + 127) / 128), dim3(256), TileCfg<128>::LDS_FLOATS * 4, s,
-                           V.xh32, (size_t)h->np, V.lam32, (size_t)h->np, h->H32, (size_t)h->np, h->np, V.kblk + a.nkblk / 2, 2);
-      else if (n32)
-        hipLaunchKernelGGL((gemm_nt_f32_kdyn_k<64>), dim3(a.W / 64, (n32 + 63) / 64), dim3(256), TileCfg<64>::LDS_FLOATS * 4, s,
-                           V.xh32, (size_t)h->np, V.lam32, (size_t)h->np, h->H32, (size_t)h->np, h->np, V.kblk + a.nkblk / 2, 1);
+      if (n32)
+        launch_xh32(s, V.xh32, (size_t)h->np, V.lam32, (size_t)h->np, h->H32, (size_t)h->np, n32, a.W, h->np, V.kblk + a.nkblk / 2);
     }
     {
       EvScope es(h, 6, 0.0);
@@ -2213,6 +2242,85 @@ int nnmpc_qp_debug_predict(nnmpc_qp* h, int32_t B, const double* x0, const doubl
   if (h->profiling) ev_collect(h);
   return NNMPC_OK;
   GUARD_END
+}
+
+int nnmpc_qp_debug_gemm(nnmpc_qp* h, int32_t kind, int32_t M, int32_t N, int32_t K, const void* A, int64_t lda, int64_t a_rows,
+                        const void* B, int64_t ldb, void* C, int64_t ldc, int64_t c_rows, const int32_t* rowphase, int32_t want,
+                        const int32_t* kdyn, int32_t kblocks, const int32_t* mdyn, const int32_t* rowmap, int32_t* info) {
+#define GEMM_BAD(...) do { set_error("nnmpc_qp_debug_gemm: " __VA_ARGS__); return NNMPC_EINVAL; } while (0)
+  if (!h || !A || !B || !C || !info) GEMM_BAD("null handle, operand or info");
+  if (kind < 0 || kind > 4) GEMM_BAD("kind %d (0 .. 4)", kind);
+  const bool f32 = kind >= 3;
+  const int T = (kind == 1 || kind == 3) ? 128 : 64, kc = f32 ? KC : G64_KC, el = f32 ? 4 : 8;
+  if (M < 1 || N < 1 || K < kc || M > (1 << 20) || N > (1 << 16) || K > (1 << 16)) GEMM_BAD("M = %d, N = %d, K = %d out of range", M, N, K);
+  // what each kernel needs of the shape (kind 0: what either kernel of gemm64 can run without leaving its operands -- the 64 x 64
+  // kernel walks K in whole chunks of 16 and drops a remainder; gemm64's callers pad K)
+  if (kind == 0 ? (M % 64 || N % 64) : f32 ? (N % T || K % kc) : (M % T || N % T || K % kc))
+    GEMM_BAD("M = %d, N = %d, K = %d off the grid of kind %d (tiles of %d, K in chunks of %d)", M, N, K, kind, T, kc);
+  if (f32 && !kdyn) GEMM_BAD("kind %d needs kdyn", kind);
+  if (f32 && (rowphase || mdyn || rowmap)) GEMM_BAD("kind %d has no rowphase, mdyn or rowmap", kind);
+  if (kind == 2 && rowmap) GEMM_BAD("kind 2 (the 64 x 64 kernel) has no rowmap");
+  if (lda < K || ldb < K || ldc < N) GEMM_BAD("a leading dimension shorter than its row (lda = %lld, ldb = %lld, ldc = %lld; K = %d, N = %d)",
+                                              (long long)lda, (long long)ldb, (long long)ldc, K, N);
+  const int vec = 16 / el;                                  // the kernels load 16 bytes at a time
+  if (lda % vec || ldb % vec) GEMM_BAD("lda = %lld, ldb = %lld: rows of A and B must start on 16 bytes", (long long)lda, (long long)ldb);
+  const int64_t mr = ((int64_t)M + T - 1) / T * T;          // rows the grid covers
+  if (a_rows < (rowmap ? 1 : mr) || c_rows < (rowmap ? 1 : mr)) GEMM_BAD("A (%lld rows) or C (%lld rows) shorter than the %lld rows of the grid",
+                                                                         (long long)a_rows, (long long)c_rows, (long long)mr);
+  if (rowmap)
+    for (int i = 0; i < M; ++i)
+      if (rowmap[i] >= a_rows || rowmap[i] >= c_rows) GEMM_BAD("rowmap[%d] = %d beyond the arrays (%lld, %lld rows)", i, rowmap[i], (long long)a_rows, (long long)c_rows);
+  if (mdyn && (*mdyn < 0 || *mdyn > M)) GEMM_BAD("*mdyn = %d outside 0 .. M", *mdyn);
+  const size_t na = (size_t)(a_rows - 1) * lda + K, nb = (size_t)(N - 1) * ldb + K, nc = (size_t)(c_rows - 1) * ldc + N;   // elements in use
+  if (na * el >= ((size_t)1 << 32) || nb * el >= ((size_t)1 << 32) || nc * el >= ((size_t)1 << 32)) GEMM_BAD("an operand of 4 GB or more");
+  GUARD_BEGIN
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  HIPCHK(stream_sync(s));
+  DevRes scratch;                                            // the call's own device memory: freed on every way out
+  scratch.device = h->device;
+  char *dA = nullptr, *dB = nullptr, *dC = nullptr;
+  int *dphase = nullptr, *dk = nullptr, *dm = nullptr, *dmap = nullptr;
+  const size_t nk = kdyn ? ((kblocks || f32) ? (size_t)(mr / 64) : 1) : 0;
+  int rc = scratch.upload(&dA, (const char*)A, na * el);
+  if (!rc) rc = scratch.upload(&dB, (const char*)B, nb * el);
+  if (!rc) rc = scratch.upload(&dC, (const char*)C, nc * el);
+  if (!rc && rowphase) rc = scratch.upload(&dphase, rowphase, (size_t)M);
+  if (!rc && kdyn) rc = scratch.upload(&dk, kdyn, nk);
+  if (!rc && mdyn) rc = scratch.upload(&dm, mdyn, (size_t)1);
+  if (!rc && rowmap) rc = scratch.upload(&dmap, rowmap, (size_t)M);
+  if (rc) return rc;
+  int which = 0, nwg = 0, kper = 0;
+  if (f32) {
+    float* c32 = (float*)dC; const float *a32 = (const float*)dA, *b32 = (const float*)dB;
+    if (kind == 3) launch_xh32_nb<128>(s, c32, (size_t)ldc, a32, (size_t)lda, b32, (size_t)ldb, M, N, K, dk);
+    else launch_xh32_nb<64>(s, c32, (size_t)ldc, a32, (size_t)lda, b32, (size_t)ldb, M, N, K, dk);
+    which = kind; nwg = (N / T) * (int)(mr / T); kper = T / 64;
+  } else {
+    double* c64 = (double*)dC; const double *a64 = (const double*)dA, *b64 = (const double*)dB;
+    if (kind == 0) {
+      // the solves' own entry, flag and all.  A refusal must not outlive this call: the handle's flag is left as it was found
+      // (a solve reads and clears it at its own check).
+      const bool had = h->gemm_error;
+      which = gemm64(h, c64, (size_t)ldc, a64, (size_t)lda, b64, (size_t)ldb, M, N, K, dphase, want, dk, dm, kblocks != 0, dmap, &nwg);
+      h->gemm_error = had;
+      if (which == GEMM64_REFUSED) { info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0; return NNMPC_EINVAL; }   // (gemm64's message)
+    } else if (kind == 1) {
+      which = GEMM64_T128;
+      nwg = launch_gemm64_t128(s, c64, (size_t)ldc, a64, (size_t)lda, b64, (size_t)ldb, M, N, K, dphase, want, dk, dm, kblocks != 0, dmap);
+    } else {
+      which = GEMM64_K64;
+      nwg = launch_gemm64_k64(s, c64, (size_t)ldc, a64, (size_t)lda, b64, (size_t)ldb, M, N, K, dphase, want, dk, dm, kblocks != 0);
+    }
+    kper = (kdyn && kblocks) ? (which == GEMM64_T128 ? 2 : 1) : 0;
+  }
+  HIPCHK(stream_sync(s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(C, dC, nc * el, hipMemcpyDeviceToHost));
+  info[0] = which; info[1] = nwg; info[2] = kper; info[3] = (which == 1 || which == 3) ? 128 : 64;
+  return NNMPC_OK;
+  GUARD_END
+#undef GEMM_BAD
 }
 
 }  // extern "C"

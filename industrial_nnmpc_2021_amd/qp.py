@@ -277,6 +277,40 @@ class BatchedBoxQP:
                                                     C.byref(L)), "nnmpc_qp_debug_predict")
         return dict(state=state, W=int(info[0]), MR=int(info[1]), count=int(info[2]), wide=int(info[3]), L=float(L.value))
 
+    def debug_gemm(self, kind, M, N, K, A, B, C_, rowphase=None, want=0, kdyn=None, kblocks=False, mdyn=None, rowmap=None):
+        """Kernel-level hook: one GEMM kernel of the active-set path alone, C = A B' (include/nnmpc.h: nnmpc_qp_debug_gemm), through the
+        launch code of a solve.  kind: 0 the dispatch of the solves, 1 / 2 the 128 x 128 / 64 x 64 fp64 kernel, 3 / 4 the f32 k-range
+        kernel with 128 / 64 tiles.  A, B, C_: 2-D arrays (float64, kinds 3 / 4 float32) whose rows are contiguous; views into wider
+        arrays give the leading dimensions.  C_ goes up with its contents and is overwritten IN PLACE with what comes back.
+        Returns dict(kernel, grid (workgroups), kper, tile)."""
+        dt = np.float32 if kind in (3, 4) else np.float64
+        for a in (A, B, C_):
+            if a.dtype != dt or a.ndim != 2 or a.strides[1] != a.itemsize or a.strides[0] % a.itemsize:
+                raise ValueError("debug_gemm: operands are 2-D arrays of the kind's type with contiguous rows")
+        if not C_.flags.writeable:
+            raise ValueError("debug_gemm: C is written in place")
+        ld = lambda a: a.strides[0] // a.itemsize
+        ints = lambda v, n=None: None if v is None else np.ascontiguousarray(np.asarray(v, np.int32).reshape(-1 if n is None else n))
+        rowphase, kdyn, mdyn, rowmap = ints(rowphase), ints(kdyn), ints(mdyn, 1), ints(rowmap)
+        T = 128 if kind in (1, 3) else 64
+        nk = -(-M // T) * (T // 64) if (kblocks or kind in (3, 4)) else 1
+        for v, need, what in ((rowphase, M, "rowphase"), (rowmap, M, "rowmap"), (kdyn, nk, "kdyn")):
+            if v is not None and v.size < need:
+                raise ValueError(f"debug_gemm: {what} has {v.size} entries, the kernel reads {need}")
+        # (a leading dimension shorter than the row is the library's to refuse; a VIEW narrower than the row, or B shorter than N rows,
+        # would have it read past the view)
+        for a, cols, what in ((A, K, "A"), (B, K, "B"), (C_, N, "C")):
+            if ld(a) >= cols and a.shape[1] < cols:
+                raise ValueError(f"debug_gemm: {what} has {a.shape[1]} columns, the call names {cols}")
+        if B.shape[0] < N:
+            raise ValueError(f"debug_gemm: B has {B.shape[0]} rows, the call names {N}")
+        info = np.full(4, -9, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_qp_debug_gemm(self._h, int(kind), int(M), int(N), int(K), p(A), ld(A), A.shape[0], p(B), ld(B),
+                                                 p(C_), ld(C_), C_.shape[0], p(rowphase), int(want), p(kdyn), int(bool(kblocks)),
+                                                 p(mdyn), p(rowmap), p(info)), "nnmpc_qp_debug_gemm")
+        return dict(kernel=int(info[0]), grid=int(info[1]), kper=int(info[2]), tile=int(info[3]))
+
     def debug_factor_fail(self, B):
         """(B,) int32: 1 where the last debug_factor_solve met a non-positive pivot in that row's factorisation."""
         fail = np.empty(B, np.int32)

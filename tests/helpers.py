@@ -1487,3 +1487,257 @@ def pred_extent_count(c, x0, lb, ub):
     cols = np.arange(384, 512)
     xu = (x0 @ c["Kunc"].T)[:, cols]
     return int(((xu > ub[:, cols % c["nu"]]) | (xu < lb[:, cols % c["nu"]])).any(axis=1).sum())
+
+
+# ---- the GEMM kernels of the active-set path alone (csrc/gemm64.h, csrc/gemm_kernels.h) through nnmpc_qp_debug_gemm:
+# ---- tests/test_gemm_kernel_gpu.py, tests/test_cpu_gemm_inputs.py ---------------------------------------------------------------
+GEMM_SENTINEL = -777.25                          # no integer: an entry a kernel left alone is told from every exact product
+GEMM_TILE = {1: 128, 2: 64, 3: 128, 4: 64}       # kind of nnmpc_qp_debug_gemm -> tile edge T
+GEMM_CHUNK = {1: 16, 2: 16, 3: 32, 4: 32}        # -> K chunk c
+GEMM_NAMES = {1: "gemm_nt_f64_t128_k", 2: "gemm_nt_f64_k", 3: "gemm_nt_f32_kdyn_k<128>", 4: "gemm_nt_f32_kdyn_k<64>"}
+GEMM_WANT = 3                                    # the tag of the rowphase cases (not 0: rows tagged 0 sit in the tiles that must stay)
+
+
+def gemm_dtype(kind):
+    return np.float32 if kind in (3, 4) else np.float64
+
+
+def gemm_unit(dtype):
+    return 2.0 ** -24 if np.dtype(dtype) == np.float32 else 2.0 ** -53
+
+
+def gemm_gamma(K, dtype):
+    u = gemm_unit(dtype)
+    return K * u / (1.0 - K * u)
+
+
+def gemm_highprec():
+    """The accumulation type of the rounded-data reference: np.longdouble where it has a 64-bit significand, else exact rationals."""
+    if np.finfo(np.longdouble).eps <= 2.0 ** -63:
+        return np.longdouble
+    return object
+
+
+def _gemm_cast(a, acc):
+    if acc is np.int64:
+        return np.nan_to_num(np.asarray(a, np.float64), nan=0.0).astype(np.int64)
+    if acc is object:
+        from fractions import Fraction
+        return np.vectorize(lambda v: Fraction(float(v)), otypes=[object])(np.nan_to_num(np.asarray(a, np.float64), nan=0.0))
+    return np.nan_to_num(np.asarray(a, np.float64), nan=0.0).astype(acc)
+
+
+def gemm_reference(A, B, M, N, K, T, c, c_rows=None, rowphase=None, want=0, kdyn=None, kper=0, mdyn=None, rowmap=None, acc=np.int64):
+    """What nnmpc_qp_debug_gemm's contract (include/nnmpc.h) says of C = A B' for tile edge T and chunk c, from the arguments alone:
+    A (rows x >= K), B (>= N x >= K); row tiles of T rows; a tile is LEFT ALONE when its first row is >= mdyn or (rowphase given) none
+    of its rows has tag `want`, else all its T rows are written; with kdyn the tile's bound is kdyn[0] (kper = 0) or the largest of its
+    kper entries and the product runs over k < min(K, (bound // c + 1) c); with rowmap row i of A and of C is row rowmap[i] of the
+    arrays, an entry < 0 or a row >= mdyn stores nothing.
+    -> dict(val, absval: (c_rows, N) arrays of type acc -- the product and sum |a| |b| where written --, written: bool (c_rows, N),
+    tiles / left: the row tiles written / left alone, kk: tile -> columns of K summed, poison: rows of C whose summed part of A holds a NaN)."""
+    A, B = np.asarray(A), np.asarray(B)
+    ntm = -(-M // T)
+    if c_rows is None:
+        c_rows = ntm * T
+    mlim = 2 ** 31 - 1 if mdyn is None else int(np.asarray(mdyn).reshape(-1)[0])
+    zero = acc(0) if acc is not object else 0
+    val = np.full((c_rows, N), zero, dtype=acc)
+    absval = np.full((c_rows, N), zero, dtype=acc)
+    written = np.zeros((c_rows, N), bool)
+    Bk = _gemm_cast(B[:N, :K], acc)
+    tiles, left, kks, poison = [], [], {}, []
+    for tm in range(ntm):
+        r0 = tm * T
+        if r0 >= mlim or (rowphase is not None and not (np.asarray(rowphase)[r0:r0 + T] == want).any()):
+            left.append(tm)
+            continue
+        kk = K
+        if kdyn is not None:
+            kl = int(kdyn[0]) if kper == 0 else int(max(kdyn[kper * tm:kper * tm + kper]))
+            kk = min(K, (kl // c + 1) * c)
+        tiles.append(tm)
+        kks[tm] = kk
+        if rowmap is None:
+            rows = np.arange(r0, r0 + T)
+        else:
+            idx = np.arange(r0, min(r0 + T, M))
+            idx = idx[idx < mlim]
+            rows = np.asarray(rowmap)[idx]
+            rows = rows[rows >= 0]
+        if rows.size == 0:
+            continue
+        At = A[rows, :kk]
+        poison.extend(rows[np.isnan(np.asarray(At, np.float64)).any(axis=1)].tolist())
+        Ai = _gemm_cast(At, acc)
+        val[rows] = Ai @ Bk[:, :kk].T
+        absval[rows] = np.abs(Ai) @ np.abs(Bk[:, :kk]).T
+        written[rows] = True
+    return dict(val=val, absval=absval, written=written, tiles=tiles, left=left, kk=kks, poison=sorted(poison))
+
+
+def gemm_expected(ref, C0):
+    """C after the call, for exact data: C0 (the view the kernel was given) with the written entries replaced."""
+    out = np.array(C0, copy=True)
+    out[ref["written"]] = ref["val"][ref["written"]].astype(C0.dtype)
+    if ref["poison"]:
+        out[ref["poison"]] = np.nan
+    return out
+
+
+def _gemm_case(cid, group, kind, M, N, K, **kw):
+    T, c = GEMM_TILE[kind], GEMM_CHUNK[kind]
+    d = dict(id=cid, group=group, kind=kind, M=M, N=N, K=K, T=T, c=c, data_id=kw.pop("data_id", cid), rounded=False, pa=0, pb=0, c0=0, cpad=8,
+             spare=2, a_rows=None, rowphase=None, kdyn=None, kblocks=False, mdyn=None, rowmap=None, variant=None, nan=None, twin=None)
+    d.update(kw)
+    return d
+
+
+def gemm_kdyn_orders(c, K):
+    """Bounds per 64-row block, all from {-1, 0, c - 2, c - 1, c, 2 c - 1, K - 1, K + 5}.  o1: every value once; neighbouring blocks and
+    neighbouring pairs of blocks run a different number of chunks; the larger entry of a pair stands first in three pairs and second
+    in one.  o2: the values a pair of o1 hides behind a larger one as the LARGER entry (else a 128-row tile never runs them)."""
+    return dict(o1=[-1, 0, K - 1, c - 2, c, c - 1, K + 5, 2 * c - 1], o2=[-1, -1, c - 2, -1, 0, 2 * c - 1, -1, c - 1])
+
+
+def gemm_rowphase_tags(T):
+    """Six row tiles: none / first row / last row / a middle row / every row / none tagged GEMM_WANT; the others 0, 1, 2 or 4."""
+    rng = np.random.default_rng(4242 + T)
+    tags = rng.choice([0, 1, 2, 4], size=6 * T).astype(np.int32)
+    tags[0] = 0
+    tags[5 * T:] = 0
+    tags[T] = tags[3 * T - 1] = tags[3 * T + T // 2 - 3] = GEMM_WANT
+    tags[4 * T:5 * T] = GEMM_WANT
+    return tags
+
+
+_GEMM_CASES = None
+
+
+def gemm_cases():
+    """The case table of tests/test_gemm_kernel_gpu.py (the dispatch cases of kind 0 apart: gemm_dispatch_inputs)."""
+    global _GEMM_CASES
+    if _GEMM_CASES is not None:
+        return _GEMM_CASES
+    cs = []
+
+    def both(cid, group, M, N, K, **kw):                 # an fp64 case on the 128-grid: the 128 x 128 kernel and, same arguments, the 64 x 64 one
+        cs.append(_gemm_case(cid + "-t128", group, 1, M, N, K, data_id=cid, twin=cid + "-k64", **kw))
+        cs.append(_gemm_case(cid + "-k64", group, 2, M, N, K, data_id=cid, **kw))
+
+    for ntm in (1, 7, 8, 9, 32, 33):                     # tile deal of the 128 x 128 kernel
+        for ntn in (1, 3):
+            both(f"deal-{ntm}x{ntn}", "deal", 128 * ntm, 128 * ntn, 48)
+    for K in (16, 32, 48, 80):                           # the two-stage ring; padded rows, B and C inside wider arrays
+        both(f"ring-K{K}", "ring", 256, 256, K, pa=6, pb=10, c0=128, cpad=64, rounded=True)
+    for M in (64, 192, 320):                             # the same for the 64 x 64 kernel
+        for N in (64, 192, 320):
+            for K in (16, 32, 48):
+                cs.append(_gemm_case(f"k64-{M}x{N}x{K}", "k64", 2, M, N, K, pa=6, pb=10, c0=64, cpad=64, rounded=True))
+    for kind in (1, 2, 3, 4):                            # kdyn
+        T, c = GEMM_TILE[kind], GEMM_CHUNK[kind]
+        K = 4 * c
+        tag = {1: "t128", 2: "k64", 3: "f32x128", 4: "f32x64"}[kind]
+        for oname, order in gemm_kdyn_orders(c, K).items():
+            for v in "ab":
+                cs.append(_gemm_case(f"kdyn-{tag}-{oname}{v}", "kdyn", kind, 512, 128, K, pa=8, pb=12, kdyn=order, kblocks=True, variant=v))
+        if kind in (1, 2):                               # (the f32 kernels are only ever launched with one bound per 64 rows)
+            for kl in sorted(set(gemm_kdyn_orders(c, K)["o1"])):
+                for v in "ab":
+                    cs.append(_gemm_case(f"kdyn-{tag}-one{kl}{v}", "kdyn", kind, 2 * T, 128, K, pa=8, pb=12, kdyn=[kl], variant=v))
+        o1 = gemm_kdyn_orders(c, K)["o1"]                # block 4: bound c, k < 2 c -- a NaN in column 2 c is outside, in column 2 c - 1 inside
+        cs.append(_gemm_case(f"kdyn-{tag}-nan-out", "kdyn", kind, 512, 128, K, pa=8, pb=12, kdyn=o1, kblocks=True, variant="b", nan=(4 * 64 + 5, 2 * c)))
+        cs.append(_gemm_case(f"kdyn-{tag}-nan-in", "kdyn", kind, 512, 128, K, pa=8, pb=12, kdyn=o1, kblocks=True, variant="b", nan=(4 * 64 + 5, 2 * c - 1)))
+    for kind in (3, 4):                                  # tile map of the f32 kernels; <128>: the last tile has its first 64 rows in use
+        T = GEMM_TILE[kind]
+        for ntm in (1, 7, 8, 9, 17):
+            for ntn in (1, 2, 3):
+                M = T * ntm - (64 if kind == 3 else 0)
+                nblk = ntm * (T // 64)
+                kd = [[95, 31, 63][b % 3] if b * 64 < M else -1 for b in range(nblk)]
+                cs.append(_gemm_case(f"f32map-{T}-{ntm}x{ntn}", "f32map", kind, M, T * ntn, 96, pa=4, pb=8, c0=32, cpad=16, kdyn=kd, kblocks=True,
+                                     variant="b", rounded=ntm <= 7))
+    for T, kinds in ((128, (1, 2)), (64, (2,))):         # rowphase
+        for kind in kinds:
+            tag = {1: "t128", 2: "k64"}[kind]
+            cs.append(_gemm_case(f"rowphase-{tag}-T{T}", "rowphase", kind, 6 * T, 128, 32, data_id=f"rowphase-T{T}", rowphase=gemm_rowphase_tags(T),
+                                 twin=f"rowphase-k64-T{T}" if kind == 1 else None))
+    for kind in (1, 2):                                  # mdyn
+        T = GEMM_TILE[kind]
+        tag = {1: "t128", 2: "k64"}[kind]
+        for md in (0, 1, T - 1, T, T + 1, 3 * T):
+            cs.append(_gemm_case(f"mdyn-{tag}-{md}", "mdyn", kind, 3 * T, 128, 32, data_id=f"mdyn-{tag}", mdyn=md))
+    rng = np.random.default_rng(777)                     # rowmap: a partial permutation of 500 rows, twelve entries "no row"
+    rm = rng.permutation(500)[:384].astype(np.int32)
+    rm[[0, 127, 128, 200, 383] + rng.choice(np.arange(1, 383), 7, replace=False).tolist()] = -1
+    cs.append(_gemm_case("rowmap-plain", "rowmap", 1, 384, 256, 48, pa=6, pb=10, a_rows=500, rowmap=rm))
+    cs.append(_gemm_case("rowmap-mdyn185", "rowmap", 1, 384, 256, 48, pa=6, pb=10, a_rows=500, rowmap=rm, mdyn=185))
+    for c in list(cs):                                   # every other case of the 128 x 128 kernel without a rowmap: the same arguments
+        if c["kind"] == 1 and c["rowmap"] is None and c["twin"] is None:      # through the 64 x 64 kernel (tiles of 64, one bound per tile)
+            c["twin"] = c["id"] + "~k64"
+            cs.append(dict(c, id=c["twin"], kind=2, T=64, c=16, twin=None))
+    _GEMM_CASES = cs
+    return cs
+
+
+def gemm_case(cid):
+    return next(c for c in gemm_cases() if c["id"] == cid)
+
+
+def gemm_data(shape, rng, dtype, rounded, nonzero=False):
+    """Exact data: integers in -3 .. 3 (nonzero: without 0).  Rounded data: standard normals scaled per row and per column by
+    10^U(-3, 3) each (+-6 decades together)."""
+    if not rounded:
+        a = rng.integers(-3, 4, size=shape)
+        if nonzero:
+            a = np.where(a == 0, rng.choice([-3, -2, -1, 1, 2, 3], size=shape), a)
+        return a.astype(dtype)
+    a = rng.standard_normal(shape) * 10.0 ** rng.uniform(-3, 3, (shape[0], 1)) * 10.0 ** rng.uniform(-3, 3, (1, shape[1]))
+    return a.astype(dtype)
+
+
+def gemm_inputs(case, rounded=False):
+    """The arrays of one call: full allocations (Af, Bf, Cf: Cf filled with the sentinel), the views the call gets (A, B, C), the
+    keyword arguments of BatchedBoxQP.debug_gemm and of gemm_reference."""
+    import zlib
+    c = case
+    rng = np.random.default_rng(zlib.crc32((c["data_id"] + ("/r" if rounded else "/e")).encode()))
+    dt = gemm_dtype(c["kind"])
+    M, N, K, T = c["M"], c["N"], c["K"], c["T"]
+    mr = -(-M // T) * T
+    a_rows = c["a_rows"] or mr
+    c_rows = (c["a_rows"] or mr) + c["spare"]
+    Af = gemm_data((a_rows, K + c["pa"]), rng, dt, rounded, nonzero=c["variant"] == "b")
+    Bf = gemm_data((c["c0"] + N + 3, K + c["pb"]), rng, dt, rounded)
+    kd = None if c["kdyn"] is None else np.asarray(c["kdyn"], np.int32)
+    if c["variant"] == "a":                              # zeros beyond each 64-row block's own bound (one bound: beyond it)
+        for b in range(mr // 64):
+            Af[64 * b:64 * b + 64, max(int(kd[b] if c["kblocks"] else kd[0]) + 1, 0):] = 0
+    if M < mr:
+        Af[M:] = 0                                       # rows not in use (the f32 round's last tile): zero, as LAM32 keeps them
+    if c["nan"]:
+        Af[c["nan"]] = np.nan
+    Cf = np.full((c_rows, c["c0"] + N + c["cpad"]), GEMM_SENTINEL, dt)
+    kper = (T // 64) if (kd is not None and c["kblocks"]) else 0
+    call = dict(rowphase=c["rowphase"], want=GEMM_WANT if c["rowphase"] is not None else 0, kdyn=kd, kblocks=c["kblocks"], mdyn=c["mdyn"],
+                rowmap=c["rowmap"])
+    ref = dict(c_rows=c_rows, rowphase=c["rowphase"], want=call["want"], kdyn=kd, kper=kper, mdyn=c["mdyn"], rowmap=c["rowmap"])
+    return dict(Af=Af, Bf=Bf, Cf=Cf, A=Af[:, :K], B=Bf[c["c0"]:c["c0"] + N, :K], C=Cf[:, c["c0"]:c["c0"] + N], call=call, ref=ref)
+
+
+def gemm_case_reference(case, inp, rounded=False):
+    return gemm_reference(inp["A"], inp["B"], case["M"], case["N"], case["K"], case["T"], case["c"],
+                          acc=gemm_highprec() if rounded else np.int64, **inp["ref"])
+
+
+def gemm_bar(case, ref):
+    """2 gamma_K |A| |B|' entrywise (any order of summation, one rounding per product and per add; the factor 2: cl_step_reference's)."""
+    return 2.0 * gemm_gamma(case["K"], gemm_dtype(case["kind"])) * ref["absval"].astype(np.float64)
+
+
+GEMM_DISPATCH = dict(t128=(3200, 1024, 16), k64=(3072, 1024, 16), offM=(3264, 1024, 16), offN=(3200, 1088, 16), offK=(3200, 1024, 24))
+
+
+def gemm_dispatch_inputs():
+    """One A (3264 rows), B (1088 rows), 24 columns each, exact data: every shape of GEMM_DISPATCH is a corner of them."""
+    rng = np.random.default_rng(20250)
+    return gemm_data((3264, 24), rng, np.float64, False), gemm_data((1088, 24), rng, np.float64, False)
