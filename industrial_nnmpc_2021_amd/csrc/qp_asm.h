@@ -46,6 +46,11 @@ enum { ASM_RUN = 0, ASM_DONE = 1, ASM_FALLBACK = 2, ASM_CERT = 3, ASM_WIDE = 4, 
 constexpr int ASM_NBIN = 8;        // size classes by the number of 16-blocks: class b holds sets of 16 (b + 4) or fewer
 constexpr int ASM_NREG = 6;        // classes 0..5 (<= 144 bounds): four problems per workgroup (asm_lambda_reg_k); 6, 7: two
 constexpr int ASM_NCNT = 40;       // ints in AsmDev::counters
+constexpr int ASM_CNT_KSUM = 0;    // counters[0]: sum of (last active index + 1) over the running problems: algorithmic k of the window GEMM
+constexpr int ASM_CNT_SLAB = 1;    // counters[1]: length of the list of sets too large for LDS (tiles in an L2 slab: asm_lambda_tile_k)
+constexpr int ASM_CNT_ROWS64 = 2;  // counters[2]: rows of LAM / XH handed out (problems solved in fp64 this round)
+constexpr int ASM_CNT_LAST = 3;    // counters[3]: largest active variable index of the running problems
+constexpr int ASM_CNT_F64 = 4;     // counters[4 + b]: length of the fp64 list of size class b
 constexpr int ASM_CNT_F32 = 16;    // counters[16 + b]: length of the f32 list of size class b
 constexpr int ASM_NLIST = 2 * ASM_NBIN;   // lists in AsmDev::binlist: fp64 classes, then f32 classes, then (list ASM_NLIST) the
                                           // f32 rounds of sets of ASM_MLDS + 1 .. ASM_BIG32 bounds (asm_lambda_tile32_k)

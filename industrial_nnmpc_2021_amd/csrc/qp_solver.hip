@@ -699,14 +699,14 @@ struct nnmpc_qp {
   bool have_inverse;
   double* H64;      // np x np
   double* Kunc64;   // np x ka
-  double *asm_xunc, *asm_x, *asm_lam, *asm_xh, *asm_scratch, *asm_xhw;
-  int *asm_rowprob, *asm_wflag;
+  double *asm_xunc, *asm_x, *asm_scratch;
+  int* asm_wflag;
   unsigned char* asm_wmark;
   unsigned char* asm_st;
-  int *asm_state, *asm_rounds, *asm_counters, *asm_biglist, *asm_status, *asm_binlist, *asm_idxg, *asm_mg, *asm_row, *asm_lrank, *asm_ctot;
+  int *asm_state, *asm_rounds, *asm_biglist, *asm_status, *asm_binlist, *asm_idxg, *asm_mg, *asm_row, *asm_lrank, *asm_ctot;
   unsigned char *asm_prec, *asm_redo, *asm_alpha, *asm_rowk;
-  float *asm_lam32, *asm_xh32, *H32;
-  int *asm_ninf, *asm_hi, *asm_kblk;
+  float* H32;
+  int *asm_ninf, *asm_hi;
   double tqmax;         // max |tq| entry
   int asm_pool;
   double asm_e1max, asm_e2max;
@@ -715,10 +715,10 @@ struct nnmpc_qp {
   std::vector<Far> far;
   std::vector<int> far_missing;   // windows of full-width passes that ran in the dense form for want of factors (handed out once each)
   double p_inf = 0.0;       // max row sum of |P|
-  double *asm_tnorm = nullptr, *asm_tslack = nullptr;
   // Row spaces ("views") of the active-set rounds: the buffers indexed by the ROW a round hands a running problem (and that round's
-  // counters and k-ranges) rather than by the problem.  view[0] is the workspace above (seg_max rows); view[1] a second, small one
-  // for the round that runs beside a full-width pass (solve_segment_asm).  Everything indexed by problem is shared.
+  // counters and k-ranges) rather than by the problem.  view[0] has seg_max rows; view[1] is a second, small one for the round that
+  // runs beside a full-width pass (solve_segment_asm).  Everything indexed by problem is shared.  The counters of both views are one
+  // array of 2 ASM_NCNT ints at view[0].counters (read_counters).
   struct AsmView {
     double *lam = nullptr, *xh = nullptr, *xhw = nullptr, *tnorm = nullptr, *tslack = nullptr;
     float *lam32 = nullptr, *xh32 = nullptr;
@@ -764,6 +764,49 @@ struct nnmpc_qp {
 
 namespace {
 
+// Every environment switch of the QP path ("Environment switches"): diagnostics and A/B runs, results are the same
+// either way.  The table is read once, when the process first uses it; the three functions after it keep the read times tests rely on.
+struct AsmSwitches {
+  bool no_fused_wide;   // NNMPC_NO_FUSED_WIDE: A/B of the fused epilogue (the full-width check as a separate kernel)
+  bool no_lazy_xunc;    // NNMPC_NO_LAZY_XUNC: x_unc for all columns up front (round 2)
+  bool no_farfield;     // NNMPC_NO_FARFIELD: dense form of the full-width pass (A/B)
+  bool no_small_gemm;   // NNMPC_NO_SMALL_GEMM: A/B of the 64 x 64 kernel for GEMMs of few tiles (gemm64_choice)
+  bool trace;           // NNMPC_TRACE_ROUNDS: the populations of every round, iterations and set sizes per problem of the small pass and the tails
+  int tail_gi;          // NNMPC_TAIL_GI: A/B of the tail's exchange rule
+  int use_wg;           // NNMPC_NO_WG (0 when set): A/B against the kernels the workgroup kernels replaced
+  int refine;           // NNMPC_REFINE, 1: A/B against separate f32 and fp64 rounds ...
+  double refine_tol;    // NNMPC_REFINE_TOL, ASM_REFINE_TOL: ... and the residual below which a corrected solve counts as an fp64 solve
+  int early64;          // NNMPC_EARLY64, 4: A/B of the rule
+  int pred_iters;       // NNMPC_PRED_ITERS, -1: A/B; 0 = off, > 0 that many (overrides opts.asm_predict_iters)
+  int pred_wide;        // NNMPC_PRED_WIDE, -1: A/B; 0 / 1 forces the choice of the predictor's window
+  int pred_f64;         // NNMPC_PRED_F64, 0: A/B (the rounds after a prediction start in fp64)
+  int pred_factor;      // NNMPC_PRED_FACTOR, 3: tenths of an iteration per bound x_unc violates (adaptive count)
+  int small_grace;      // NNMPC_SMALL_GRACE, ASM_SM_GRACE: iterations of grace of asm_small_k before single exchanges (small_pass)
+  int tail_max;         // NNMPC_TAIL_MAX, 256: stragglers go to the device tail at this many running problems; > 1024 doubles the slab pool
+};
+bool env_set(const char* name) { return getenv(name) != nullptr; }
+int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+AsmSwitches read_switches() {
+  AsmSwitches w;
+  w.no_fused_wide = env_set("NNMPC_NO_FUSED_WIDE"); w.no_lazy_xunc = env_set("NNMPC_NO_LAZY_XUNC"); w.no_farfield = env_set("NNMPC_NO_FARFIELD");
+  w.no_small_gemm = env_set("NNMPC_NO_SMALL_GEMM"); w.trace = env_set("NNMPC_TRACE_ROUNDS");
+  w.tail_gi = env_set("NNMPC_TAIL_GI") ? 1 : 0; w.use_wg = env_set("NNMPC_NO_WG") ? 0 : 1;
+  w.refine = env_int("NNMPC_REFINE", 1); w.early64 = env_int("NNMPC_EARLY64", 4);
+  { const char* e = getenv("NNMPC_REFINE_TOL"); w.refine_tol = e ? atof(e) : ASM_REFINE_TOL; }
+  w.pred_iters = env_int("NNMPC_PRED_ITERS", -1); w.pred_wide = env_int("NNMPC_PRED_WIDE", -1); w.pred_f64 = env_int("NNMPC_PRED_F64", 0);
+  w.pred_factor = env_int("NNMPC_PRED_FACTOR", 3); w.small_grace = env_int("NNMPC_SMALL_GRACE", ASM_SM_GRACE); w.tail_max = env_int("NNMPC_TAIL_MAX", 256);
+  return w;
+}
+const AsmSwitches& asm_switches() {
+  static const AsmSwitches w = read_switches();
+  return w;
+}
+// Read at every call: tests toggle them inside one process.
+bool env_no_small() { return env_set("NNMPC_NO_SMALL"); }              // A/B, tests of the rounds at small sizes
+bool env_overlap_off() { return env_int("NNMPC_OVERLAP", 1) == 0; }   // A/B runs, 0 = off
+// Read at create (tests only): rows of the second row space, dflt when unset.
+long long env_overlap_rows(long long dflt) { const char* e = getenv("NNMPC_OVERLAP_ROWS"); return e ? std::max(0, atoi(e) / 128 * 128) : dflt; }
+
 // The next profiling event of the call in progress, recorded on st.  nullptr when none could be created: the record that
 // holds it is skipped, and the call fails at its end (ev_failed).
 hipEvent_t ev_mark(nnmpc_qp* h, hipStream_t st) {
@@ -773,9 +816,11 @@ hipEvent_t ev_mark(nnmpc_qp* h, hipStream_t st) {
   hipEventRecord(e, st);
   return e;
 }
+// What a profiling record times (EvRec::kind): where ev_collect adds it up.
+enum EvKind { EV_PANEL = 0, EV_DIAG, EV_TRSV, EV_TOTAL, EV_LAMBDA, EV_GEMM, EV_UPDATE, EV_LAMBDA32, EV_LAMBDA64, EV_SIDE, EV_PREDICT };
 struct EvScope {
   nnmpc_qp* h; int kind; double flops; hipEvent_t e0; hipStream_t st;
-  EvScope(nnmpc_qp* h_, int kind_, double flops_, hipStream_t st_ = nullptr) : h(h_), kind(kind_), flops(flops_), e0(nullptr), st(st_ ? st_ : h_->stream) {
+  EvScope(nnmpc_qp* h_, EvKind kind_, double flops_, hipStream_t st_ = nullptr) : h(h_), kind(kind_), flops(flops_), e0(nullptr), st(st_ ? st_ : h_->stream) {
     if (h->profiling) e0 = ev_mark(h, st);
   }
   ~EvScope() {
@@ -787,17 +832,17 @@ void ev_collect(nnmpc_qp* h) {
     float ms = 0.f;
     if (!r.e0 || !r.e1) continue;
     hipEventElapsedTime(&ms, r.e0, r.e1);
-    if (r.kind == 0) { h->stats.panel_ms += ms; h->stats.panel_launches += 1; h->stats.panel_flops += r.flops; }
-    else if (r.kind == 1) h->stats.diag_ms += ms;
-    else if (r.kind == 2) h->stats.trsv_ms += ms;
-    else if (r.kind == 3) h->stats.total_ms += ms;
-    else if (r.kind == 4) h->stats.asm_lambda_ms += ms;
-    else if (r.kind == 5) { h->stats.asm_gemm_ms += ms; h->stats.asm_gemm_flops += r.flops; h->stats.asm_gemm_launches += 1; }
-    else if (r.kind == 6) h->stats.asm_update_ms += ms;
-    else if (r.kind == 7) { h->stats.asm_lambda32_ms += ms; h->stats.asm_lambda32_launches += 1; }
-    else if (r.kind == 8) { h->stats.asm_lambda64_ms += ms; h->stats.asm_lambda64_launches += 1; }
-    else if (r.kind == 9) h->stats.asm_side_ms += ms;
-    else if (r.kind == 10) { h->stats.asm_predict_ms += ms; h->stats.asm_predict_flops += r.flops; }   // (launches: counted at the launch, profiling or not)
+    if (r.kind == EV_PANEL) { h->stats.panel_ms += ms; h->stats.panel_launches += 1; h->stats.panel_flops += r.flops; }
+    else if (r.kind == EV_DIAG) h->stats.diag_ms += ms;
+    else if (r.kind == EV_TRSV) h->stats.trsv_ms += ms;
+    else if (r.kind == EV_TOTAL) h->stats.total_ms += ms;
+    else if (r.kind == EV_LAMBDA) h->stats.asm_lambda_ms += ms;
+    else if (r.kind == EV_GEMM) { h->stats.asm_gemm_ms += ms; h->stats.asm_gemm_flops += r.flops; h->stats.asm_gemm_launches += 1; }
+    else if (r.kind == EV_UPDATE) h->stats.asm_update_ms += ms;
+    else if (r.kind == EV_LAMBDA32) { h->stats.asm_lambda32_ms += ms; h->stats.asm_lambda32_launches += 1; }
+    else if (r.kind == EV_LAMBDA64) { h->stats.asm_lambda64_ms += ms; h->stats.asm_lambda64_launches += 1; }
+    else if (r.kind == EV_SIDE) h->stats.asm_side_ms += ms;
+    else if (r.kind == EV_PREDICT) { h->stats.asm_predict_ms += ms; h->stats.asm_predict_flops += r.flops; }   // (launches: counted at the launch, profiling or not)
   }
   h->ev_recs.clear();
   h->ev_used = 0;
@@ -822,8 +867,7 @@ enum { GEMM64_REFUSED = 0, GEMM64_T128 = 1, GEMM64_K64 = 2 };
 int gemm64_choice(int M, int N, int K, bool rowmap) {
   // (fewer 128 x 128 tiles than CUs -- the x_unc product of a chain step: 149 rows -- leave most of the chip idle behind a few
   // long K loops: four times as many 64 x 64 tiles finish sooner)
-  static const bool small64 = getenv("NNMPC_NO_SMALL_GEMM") == nullptr;   // (the variable: A/B)
-  const bool few = small64 && !rowmap && (M / 128) * (N / 128) < 200;
+  const bool few = !asm_switches().no_small_gemm && !rowmap && (M / 128) * (N / 128) < 200;
   if (M % 128 == 0 && N % 128 == 0 && K % G64_KC == 0 && !few) return GEMM64_T128;
   // the 64 x 64 kernel has no gather / scatter of the rows: running it would write the rows of C to the wrong problems.  The one
   // caller with a rowmap (the device tail's x_unc rows) only exists on the 128-grid (`lazy`); anything else is a bug (gemm64 says so).
@@ -891,7 +935,7 @@ void factor_all(nnmpc_qp* h, int nslots, int nfactor) {
   const double nb = NB;
   for (int j = 0; j < h->T; ++j) {
     {
-      EvScope es(h, 1, 0.0);
+      EvScope es(h, EV_DIAG, 0.0);
       hipLaunchKernelGGL((chol_diag_k<NB>), dim3(nslots), dim3(256), chol_diag_lds_bytes<NB>(), h->stream, a, j);
     }
     const int below = h->T - 1 - j;
@@ -899,7 +943,7 @@ void factor_all(nnmpc_qp* h, int nslots, int nfactor) {
       // algorithmic flops of this launch: per tile 2 NB^2 (j NB) update + NB^3 triangular solve
       // + NB^3 symmetric rank-NB update of the diagonal tile
       const double fl = (double)nfactor * below * (2.0 * nb * nb * (j * nb) + nb * nb * nb + nb * nb * nb);
-      EvScope es(h, 0, fl);
+      EvScope es(h, EV_PANEL, fl);
       hipLaunchKernelGGL((chol_panel_k<NB>), dim3(below, nslots), dim3(256), chol_panel_lds_bytes<NB>(), h->stream, a, j);
     }
   }
@@ -909,7 +953,7 @@ void solve_all(nnmpc_qp* h, int nslots, const int* flag) {
   TrsvArgs a;
   a.n = h->n; a.np = h->np; a.T = h->T; a.tiles = h->tiles;
   a.L = h->L; a.Y = h->Y; a.rhs = h->d.rhs; a.sol = h->d.sol; a.flag = flag; a.count = h->trsv_count;
-  EvScope es(h, 2, 0.0);
+  EvScope es(h, EV_TRSV, 0.0);
   hipLaunchKernelGGL((trsv_k<NB>), dim3(nslots), dim3(256), (h->np + 5 * NB) * 4, h->stream, a);
 }
 void factor_dispatch(nnmpc_qp* h, int nslots, int nfactor) {
@@ -1048,7 +1092,7 @@ int predictor_extent(nnmpc_qp* h, const AsmDev& a, int nprob, int* count) {
   return 0;
 }
 
-// The one launch of asm_predict_k (solve_segment_asm and nnmpc_qp_debug_predict): its arguments -- the beta schedule, the adaptive
+// The one launch of asm_predict_k (first_sets and nnmpc_qp_debug_predict): its arguments -- the beta schedule, the adaptive
 // rule -- and the instance and grid that go with the window and nu.  iters_req: 0 adaptive (every workgroup between 8 and PRED_MAXIT),
 // 1 .. PRED_MAXIT fixed.  a: n, np, nu, nseg, lb, ub, xunc (the window's columns formed) and st (zeroed) are read.  *W_out, *MR_out:
 // the window, the problems per workgroup; *flops_per_it: the dense count of one iteration of one workgroup.
@@ -1056,7 +1100,7 @@ int launch_predictor(nnmpc_qp* h, const AsmDev& a, int nprob, int iters_req, int
   hipStream_t s = h->stream;
   const int iters = iters_req == 0 ? (int)PRED_MAXIT : iters_req;
   PredArgs pa;
-  { static const int f10 = getenv("NNMPC_PRED_FACTOR") ? atoi(getenv("NNMPC_PRED_FACTOR")) : 3; pa.fac10 = f10; }   // (the variable: diagnostics)
+  pa.fac10 = asm_switches().pred_factor;
   pa.iters = iters; pa.adaptive = iters_req == 0; pa.itsum = h->profiling ? h->pred_cnt + 1 : nullptr;
   if (h->profiling) HIPCHK(hipMemsetAsync(h->pred_cnt + 1, 0, 4, s));
   double t = 1.0;
@@ -1069,79 +1113,100 @@ int launch_predictor(nnmpc_qp* h, const AsmDev& a, int nprob, int iters_req, int
   *flops_per_it = 2.0 * W * (double)W * MR;
   *W_out = W; *MR_out = MR;
   h->stats.asm_predict_launches += 1;
-  EvScope es(h, 10, 0.0);
+  EvScope es(h, EV_PREDICT, 0.0);
   if (wide) hipLaunchKernelGGL((asm_predict_k<8, 2>), dim3((nprob + 31) / 32), dim3(64 * PRED_NW), (pred_lds_bytes<8, 2>(h->nu)), s, a, pa);
   else if (nu4) hipLaunchKernelGGL((asm_predict_k<4, 4>), dim3((nprob + 63) / 64), dim3(64 * PRED_NW), (pred_lds_bytes<4, 4>(h->nu)), s, a, pa);
   else hipLaunchKernelGGL((asm_predict_k<4, 2, false>), dim3((nprob + 31) / 32), dim3(64 * PRED_NW), (pred_lds_bytes<4, 2>(h->nu)), s, a, pa);
   return 0;
 }
 
-// Shared-inverse active-set pass over one segment; problems it cannot finish are marked 3 in
-// h->asm_status and re-solved by the PDIP path (solve_segment) on a compacted copy.
-int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double* lb_dev, const double* ub_dev,
-                      const unsigned char* guess_dev, double* u_dev, uint32_t* act_dev, int32_t* st_dev, int32_t* it_dev) {
-  hipStream_t s = h->stream;
-  const int segp = ((nprob + 127) / 128) * 128;
-  hipLaunchKernelGGL(pad_x0_k, dim3(512), dim3(256), 0, s, h->x0_64, h->x0_32, x0_dev, nprob, h->n_aug, h->ka, segp);
-  static const bool no_fuse = getenv("NNMPC_NO_FUSED_WIDE") != nullptr;   // diagnostics: A/B of the fused epilogue
-  static const bool no_lazy = getenv("NNMPC_NO_LAZY_XUNC") != nullptr;    // diagnostics: x_unc for all columns up front (round 2)
-  const bool tail_only = h->opts.asm_tail_batch >= 0 && nprob <= std::min(std::min(h->asm_pool, 256), h->opts.asm_tail_batch ? h->opts.asm_tail_batch : 256);
-  // x_unc = Kunc x0 -- for the leading columns only (the window the first sets are drawn from; extended should a round's
-  // window outgrow it): beyond them x_unc is one K segment of the full-width pass's GEMM (qp_wide.h).  Calls that go to
-  // the device tail from the start, and shapes the fused kernel's tiles do not fit, form all of it.  q = tq x0 is only
-  // formed for the rows that need the full check with P.
-  // Small problems -- Pinv fits the 4 MB L2 of an XCD (n <= 724: the CSTRs size, 540) -- run the whole iteration in one wave each
-  // (qp_small.h); what that kernel hands back (sets beyond 64 bounds, problems still moving after its budget) carries on below.
-  const bool small = getenv("NNMPC_NO_SMALL") == nullptr && (size_t)h->np * h->np * 8 <= (4u << 20) && h->n <= ASM_SM_NMAX && h->np % 4 == 0;   // (the variable: A/B, tests of the rounds at small sizes)
-  const bool lazy = h->np % 128 == 0 && !no_fuse && !no_lazy && !tail_only && !small && (uint64_t)h->seg_max * h->ka * 8 < (1ull << 32);
-  // (the window the first sets are drawn from: the leading eighth of the horizon, 512 columns at least -- a quarter until round 3;
-  // the CDU batch settles inside 512 columns, a quarter is 1152: 0.4 ms of x_unc GEMM per step.  A bound x_unc violates further
-  // out joins through the full-width pass every problem goes through.  Following the previous call's window instead made the
-  // path of a call depend on the handle's history: other windows, other far-field factors, and for degenerate problems other sets)
-  const int winit = std::min(h->n, std::max(512, ((h->n / 8 + 127) / 128) * 128));
-  int Wx = h->np;
-  if (lazy) Wx = std::min(h->np, guess_dev ? 512 : ((winit + 127) / 128) * 128);
+// ---- The shared-inverse active-set pass over one segment (solve_segment_asm, at the end of this part, holds its loop).
+// The state of one call: what its phases below share.
+struct WideStat { bool open; int view, far_rp, skip, cols; double far_ksum; };
+struct AsmCall {
+  nnmpc_qp* h; hipStream_t s; const AsmSwitches* sw;
+  int nprob, segp;
+  AsmDev a;                     // the rounds' kernel arguments (asm_args; the row-space fields follow the round's view: set_view)
+  int Wx, winit;                // columns x_unc is formed for; the window the first sets are drawn from
+  bool lazy, small, tail_only;  // which form the call takes (solve_segment_asm)
+  bool defer_cnt;               // a tail-only call reads its counters with the status, at the end
+  bool overlap_on;              // a far-field pass may run beside a round
+  int vW[2] = {0, 0}, vrows[2] = {0, 0};   // per view: window and fp64 rows of the last round that ran in it
+  bool tail_ran[2] = {false, false};
+  int pend = -1;                // the view whose settled rows await the full-width pass (-1: none)
+  // the pass whose asm_wide_k ran last: its flops are counted from the scans of the next bins (they count what asm_wide_k marked)
+  // (wnext: the pass just launched -- beside a round its asm_wide_k comes after the bins that count the pass before it)
+  WideStat wst = {false, 0, 0, 0, 0, 0.0}, wnext = wst;
+  int fft_prev[2] = {0, 0};
+  double pred_flops_per_it = 0.0;
+  int kprev = 0;                // largest active index of the round before (AsmDev::kref)
+};
+// A full-width pass as launch_pass left it: what finish_pass needs to decide its problems.
+struct PassLaunch { AsmDev ap; int fused_c0; bool inflight; };   // inflight: on stream4, its asm_wide_k still to come
 
-  {
-    EvScope es(h, 5, 2.0 * Wx * (double)h->ka * nprob);
-    gemm64(h, h->asm_xunc, h->np, h->x0_64, h->ka, h->Kunc64, h->ka, segp, Wx, h->ka);
-  }
-  AsmDev a;
-  a.Kunc = h->Kunc64; a.Wx = Wx; a.winit = winit;
-  a.ffU = a.ffVx = a.ffVl = a.ffcu = nullptr; a.ffk = nullptr; a.ffr = a.ffW = 0; a.T = h->asm_xhw; a.tnorm = h->asm_tnorm; a.tslack = h->asm_tslack;
+void set_view(const nnmpc_qp* h, AsmDev& d, int v) {
+  const nnmpc_qp::AsmView& V = h->view[v];
+  d.lam = V.lam; d.xh = V.xh; d.xhw = V.xhw; d.T = V.xhw; d.tnorm = V.tnorm; d.tslack = V.tslack; d.lam32 = V.lam32; d.xh32 = V.xh32;
+  d.rowprob = V.rowprob; d.kblk = V.kblk; d.counters = V.counters;
+}
+// Both views' round counters -> h->pin_cnt, waited for.
+int read_counters(nnmpc_qp* h) {
+  HIPCHK(hipMemcpyAsync(h->pin_cnt, h->view[0].counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(stream_sync(h->stream));
+  return 0;
+}
+// x_unc = Kunc x0 for the columns c.Wx .. Wto - 1: of the first `rows` problems, or (gather) of the problems on the tail's list
+void extend_xunc(AsmCall& c, int Wto, int rows, bool gather) {
+  nnmpc_qp* h = c.h;
+  gemm64(h, h->asm_xunc + c.Wx, h->np, h->x0_64, h->ka, h->Kunc64 + (size_t)c.Wx * h->ka, h->ka, rows, Wto - c.Wx, h->ka,
+         nullptr, 0, nullptr, gather ? c.a.counters + ASM_CNT_TAIL : nullptr, false, gather ? h->asm_biglist : nullptr);
+  c.a.Wx = Wto;
+  if (!gather) c.Wx = Wto;      // (gather: x_unc beyond Wx exists for the tail's problems only)
+}
+int tail_lds_bytes(const nnmpc_qp* h, const AsmDev& a) {
+  return (a.max_active + ASM_TS + ASM_TAIL_AREA) * 8 + ((h->n + 15) / 16) * 16 + ASM_TAIL_EXTRA;
+}
+
+// The kernel arguments of the call: everything but the row-space fields (set_view) and what the rounds set as they go.
+void asm_args(AsmCall& c, const double* lb_dev, const double* ub_dev, const unsigned char* guess_dev, double* u_dev, uint32_t* act_dev,
+              int32_t* it_dev) {
+  nnmpc_qp* h = c.h;
+  AsmDev& a = c.a;
+  const int nprob = c.nprob;
+  a.Kunc = h->Kunc64; a.Wx = c.Wx; a.winit = c.winit;
+  a.ffU = a.ffVx = a.ffVl = a.ffcu = nullptr; a.ffk = nullptr; a.ffr = a.ffW = 0;
   a.ff_skip = 0; a.ff_err = 0.0; a.ff_efar = 0.0;
-  static const bool no_far = getenv("NNMPC_NO_FARFIELD") != nullptr;      // diagnostics: dense form of the full-width pass (A/B)
+  set_view(h, a, 0);
   a.n = h->n; a.np = h->np; a.nu = h->nu; a.nseg = nprob;
   a.max_active = h->opts.asm_max_active; a.max_rounds = h->opts.asm_max_rounds;
   a.bound_tol = h->opts.bound_tol; a.stat_tol = 1e-8; a.pscale = h->pscale;
   a.e1max = h->asm_e1max; a.e2max = h->asm_e2max; a.x0 = h->x0_64; a.ka = h->ka;
   a.H = h->H64; a.lb = lb_dev; a.ub = ub_dev; a.xunc = h->asm_xunc; a.q64 = h->q64_all;
-  a.x = h->asm_x; a.lam = h->asm_lam; a.xh = h->asm_xh; a.px = h->asm_xh;
-  a.st = h->asm_st; a.guess = guess_dev; a.state = h->asm_state; a.rounds = h->asm_rounds; a.counters = h->asm_counters;
-  a.biglist = h->asm_biglist; a.binlist = h->asm_binlist; a.idxg = h->asm_idxg; a.mg = h->asm_mg; a.row = h->asm_row; a.tqmax = h->tqmax; a.lrank = h->asm_lrank; a.ctot = h->asm_ctot; a.prec = h->asm_prec; a.redo = h->asm_redo; a.rowk = h->asm_rowk; a.lam32 = h->asm_lam32; a.H32 = h->H32; a.xh32 = h->asm_xh32; a.alpha = h->asm_alpha; a.ninf_best = h->asm_ninf; a.hi = h->asm_hi; a.kblk = h->asm_kblk; a.nkblk = 2 * (h->seg_max / 64 + 2); a.kref = 0; a.use_f32 = h->opts.asm_f32_rounds >= 0; a.xhw = h->asm_xhw; a.rowprob = h->asm_rowprob; a.wrows = 0; a.wmark = h->asm_wmark; a.wflag = h->asm_wflag; a.W = h->np; a.scratch = h->asm_scratch; a.work = h->asm_work;
+  a.x = h->asm_x; a.px = h->view[0].xh;
+  a.st = h->asm_st; a.guess = guess_dev; a.state = h->asm_state; a.rounds = h->asm_rounds;
+  a.biglist = h->asm_biglist; a.binlist = h->asm_binlist; a.idxg = h->asm_idxg; a.mg = h->asm_mg; a.row = h->asm_row; a.tqmax = h->tqmax; a.lrank = h->asm_lrank; a.ctot = h->asm_ctot; a.prec = h->asm_prec; a.redo = h->asm_redo; a.rowk = h->asm_rowk; a.H32 = h->H32; a.alpha = h->asm_alpha; a.ninf_best = h->asm_ninf; a.hi = h->asm_hi; a.nkblk = 2 * (h->seg_max / 64 + 2); a.kref = 0; a.use_f32 = h->opts.asm_f32_rounds >= 0; a.wrows = 0; a.wmark = h->asm_wmark; a.wflag = h->asm_wflag; a.W = h->np; a.scratch = h->asm_scratch; a.work = h->asm_work;
   a.u_out = u_dev; a.ldu = h->ldu; a.nout = h->nout; a.act_out = act_dev; a.status_out = h->asm_status; a.iters_out = it_dev; a.words = h->words;
-  a.nseg = nprob;
-  { static const int tgi = getenv("NNMPC_TAIL_GI") ? 1 : 0; a.tail_gi = tgi; }   // (the variable: diagnostics, A/B of the tail's exchange rule)
-  { static const int wg = getenv("NNMPC_NO_WG") ? 0 : 1; a.use_wg = wg; }   // (the variable: diagnostics, A/B against the kernels it replaced)
-  { static const int rfn = getenv("NNMPC_REFINE") ? atoi(getenv("NNMPC_REFINE")) : 1; a.refine = 0; a.refine_later = rfn && a.use_f32;
-    static const double rtol = getenv("NNMPC_REFINE_TOL") ? atof(getenv("NNMPC_REFINE_TOL")) : ASM_REFINE_TOL; a.refine_tol = rtol; }   // (the variable: diagnostics, A/B against separate f32 and fp64 rounds)
-  { static const int e64 = getenv("NNMPC_EARLY64") ? atoi(getenv("NNMPC_EARLY64")) : 4; a.early64 = e64; }   // (the variable: diagnostics, A/B of the rule)
-  // LAM / LAMW are all zero between calls: every entry the multiplier kernels write is cleared again by
-  // asm_update_k / asm_wide_k of the same round
-  if (!guess_dev) HIPCHK(hipMemsetAsync(h->asm_st, 0, (size_t)nprob * h->n, s));   // bound states: asm_init_k writes the leading window only
-  // first sets: named by the dual projected-gradient predictor inside its window (qp_predict.h), by the bounds x_unc violates beyond
-  // it (and everywhere when the predictor is off, the problem small, or the caller brought a guess)
+  a.tail_gi = c.sw->tail_gi; a.use_wg = c.sw->use_wg;
+  a.refine = 0; a.refine_later = c.sw->refine && a.use_f32; a.refine_tol = c.sw->refine_tol;
+  a.early64 = c.sw->early64;
   a.pred_w = 0; a.pred_f64 = 0;
-  double pred_flops_per_it = 0.0;
+}
+
+// First sets: named by the dual projected-gradient predictor inside its window (qp_predict.h), by the bounds x_unc violates beyond
+// it (and everywhere when the predictor is off, the problem small, or the caller brought a guess)
+int first_sets(AsmCall& c) {
+  nnmpc_qp* h = c.h;
+  AsmDev& a = c.a;
+  const int nprob = c.nprob;
   {
-    static const int env_it = getenv("NNMPC_PRED_ITERS") ? atoi(getenv("NNMPC_PRED_ITERS")) : -1;   // (the variable: diagnostics, A/B; 0 = off)
+    const int env_it = c.sw->pred_iters;
     // (opts.asm_predict_iters: 0 adaptive, > 0 that many, < 0 off; the variable: 0 off, > 0 that many)
     const int iters_req = env_it >= 0 ? (env_it == 0 ? -1 : std::min(env_it, (int)PRED_MAXIT)) : h->opts.asm_predict_iters;
     const int iters = iters_req == 0 ? (int)PRED_MAXIT : iters_req;
     // (not for the one-wave-per-problem path of small problems: measured on the CSTRs-size batch of 10 000 -- n = 540, nu = 6, cond 4e7 --
     // the prediction takes the mean iteration count from 5.5 to 2, but a launch of asm_small_k lasts as long as its SLOWEST problem, and
     // that one keeps its ~25 iterations: 1.76 ms per step without, 1.94 with the predictor)
-    if (iters > 0 && h->pred[0].L > 0.0 && !guess_dev && !small && !tail_only && Wx >= PRED_W) {
+    if (iters > 0 && h->pred[0].L > 0.0 && !a.guess && !c.small && !c.tail_only && c.Wx >= PRED_W) {
       // Which window: the optimum's active bounds reach further along the horizon than the bounds x_unc violates.  When more than a
       // quarter of the problems already violate a bound in the last quarter of the 512-column window (CDU plant: 0.05 % at sx = 2,
       // 8 % at sx = 4, 46 % at sx = 6), the 1024-column instance names the sets -- four times the L2 traffic per problem and x_unc
@@ -1149,9 +1214,8 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       // sx = 4 (216 bounds, last column 629) it costs more than it saves (76 -> 88 ms).  (One 4-byte read-back; only handles that
       // have the wide window pay it.)
       int wide = 0;
-      static const int force_w = getenv("NNMPC_PRED_WIDE") ? atoi(getenv("NNMPC_PRED_WIDE")) : -1;   // (the variable: diagnostics, A/B; 0 / 1 forces the choice)
-      if (h->pred[1].L > 0.0 && lazy) {
-        if (force_w >= 0) wide = force_w;
+      if (h->pred[1].L > 0.0 && c.lazy) {
+        if (c.sw->pred_wide >= 0) wide = c.sw->pred_wide;
         else {
           int count = 0;
           const int rc = predictor_extent(h, a, nprob, &count);
@@ -1159,457 +1223,425 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
           wide = count * 4 > nprob;
         }
       }
-      if (wide && Wx < PRED_W2) {
-        EvScope es(h, 5, 2.0 * (PRED_W2 - Wx) * (double)h->ka * nprob);
-        gemm64(h, h->asm_xunc + Wx, h->np, h->x0_64, h->ka, h->Kunc64 + (size_t)Wx * h->ka, h->ka, segp, PRED_W2 - Wx, h->ka);
-        Wx = PRED_W2; a.Wx = Wx;
+      if (wide && c.Wx < PRED_W2) {
+        EvScope es(h, EV_GEMM, 2.0 * (PRED_W2 - c.Wx) * (double)h->ka * nprob);
+        extend_xunc(c, PRED_W2, c.segp, false);
       }
       int W = 0, MR = 0;
-      const int rc = launch_predictor(h, a, nprob, iters_req, wide, &W, &MR, &pred_flops_per_it);
+      const int rc = launch_predictor(h, a, nprob, iters_req, wide, &W, &MR, &c.pred_flops_per_it);
       if (rc) return rc;
       a.pred_w = W;
-      { static const int pf = getenv("NNMPC_PRED_F64") ? atoi(getenv("NNMPC_PRED_F64")) : 0; a.pred_f64 = pf; }   // (the variable: diagnostics, A/B)
+      a.pred_f64 = c.sw->pred_f64;
     }
   }
-  hipLaunchKernelGGL(asm_init_k, dim3((segp + 3) / 4), dim3(256), 0, s, a, segp);
-  const int lds_big = (a.max_active + ASM_TS) * 8;
-  int* cnt = h->pin_cnt;
-  memset(cnt, 0, 2 * ASM_NCNT * sizeof(int));
-  int rounds = 0;
-  int kprev = 0;
-  HIPCHK(hipMemsetAsync(h->asm_counters, 0, 2 * ASM_NCNT * sizeof(int), s));   // (both views' counters)
-  if (small) {
-    EvScope es(h, 4, 0.0);
-    // iterations of grace before single exchanges (the variable: diagnostics).  24, not the rounds' ASM_GRACE = 10: on the cond-4e7
-    // CSTRs-size plant block exchanges that stall for a dozen iterations mostly recover, and a problem sent to single exchanges
-    // early pays for it with hundreds of them -- 131 072 problems at sx = 3: 260 ms per step at 10, 78 at 16, 39 at 24, 40 at 40
-    // (the ones that truly cycle wait longer for the fallback: 146 ms at 100); the 10 000-problem batch: 47 -> 26 iterations at most
-    static const int g0 = getenv("NNMPC_SMALL_GRACE") ? atoi(getenv("NNMPC_SMALL_GRACE")) : ASM_SM_GRACE;
-    hipLaunchKernelGGL((asm_small_k<2, 3, 4>), dim3(nprob), dim3(64), asm_small_lds_bytes(2, h->n, h->nu), s, a, a.max_rounds, g0);
-    hipLaunchKernelGGL((asm_small_k<7, 1, 8>), dim3(nprob), dim3(64), asm_small_lds_bytes(7, h->n, h->nu), s, a, a.max_rounds, g0);
-    // ... and the sets that outgrow its 112 bounds (one problem in two of three 10 000-problem batches of the CSTRs-size plant: handed
-    // to the lock-step machinery it cost a round of bookkeeping launches, a read-back and 30 more iterations in the device tail -- 2.7 -
-    // 3.1 ms per step against 1.4 without such a problem) carry on in a nine-block instance; a wave whose problem is finished exits at once
-    if (asm_small_lds_bytes(9, h->n, h->nu) <= ASM_SMALL9_LDS_MAX)   // (else: handed on as before)
-      hipLaunchKernelGGL((asm_small_k<9, 1, 8>), dim3(nprob), dim3(64), asm_small_lds_bytes(9, h->n, h->nu), s, a, a.max_rounds, g0);
-    h->stats.asm_rounds += 1;
-    h->stats.asm_small_passes += 1;
-    static const bool trace = getenv("NNMPC_TRACE_ROUNDS") != nullptr;   // diagnostics: iterations and set sizes per problem
-    if (trace) {
-      std::vector<int> rd(nprob), mg(nprob), stt(nprob);
-      HIPCHK(stream_sync(s));
-      hipMemcpy(rd.data(), h->asm_rounds, nprob * sizeof(int), hipMemcpyDeviceToHost);
-      hipMemcpy(mg.data(), h->asm_mg, nprob * sizeof(int), hipMemcpyDeviceToHost);
-      hipMemcpy(stt.data(), h->asm_state, nprob * sizeof(int), hipMemcpyDeviceToHost);
-      long sum = 0, sm = 0, big = 0, bigit = 0, left = 0; int mx = 0, mm = 0, mxbig = 0, hist[8] = {0};
-      for (int i = 0; i < nprob; ++i) {
-        sum += rd[i]; mx = std::max(mx, rd[i]); sm += mg[i]; mm = std::max(mm, mg[i]); left += stt[i] == ASM_RUN;
-        if (mg[i] > 32) { ++big; bigit += rd[i]; mxbig = std::max(mxbig, rd[i]); }
-        hist[std::min(7, rd[i] / 8)]++;
-      }
-      fprintf(stderr, "asm small: %d problems, iterations mean %.2f max %d, final sets mean %.1f max %d; sets > 32: %ld (iterations mean %.1f max %d); handed on %ld; iterations/8 histogram",
-              nprob, (double)sum / nprob, mx, (double)sm / nprob, mm, big, big ? (double)bigit / big : 0.0, mxbig, left);
-      for (int b = 0; b < 8; ++b) fprintf(stderr, " %d", hist[b]);
-      fprintf(stderr, "\n");
+  hipLaunchKernelGGL(asm_init_k, dim3((c.segp + 3) / 4), dim3(256), 0, c.s, a, c.segp);
+  return 0;
+}
+
+// ---- NNMPC_TRACE_ROUNDS (diagnostics, AsmSwitches::trace): what the passes print to stderr
+std::vector<int> fetch_ints(const int* dev, int n) {
+  std::vector<int> v(n);
+  hipMemcpy(v.data(), dev, n * sizeof(int), hipMemcpyDeviceToHost);
+  return v;
+}
+// the small pass: iterations and set sizes per problem
+int trace_small(AsmCall& c) {
+  nnmpc_qp* h = c.h;
+  const int nprob = c.nprob;
+  HIPCHK(stream_sync(c.s));
+  const std::vector<int> rd = fetch_ints(h->asm_rounds, nprob), mg = fetch_ints(h->asm_mg, nprob), stt = fetch_ints(h->asm_state, nprob);
+  long sum = 0, sm = 0, big = 0, bigit = 0, left = 0; int mx = 0, mm = 0, mxbig = 0, hist[8] = {0};
+  for (int i = 0; i < nprob; ++i) {
+    sum += rd[i]; mx = std::max(mx, rd[i]); sm += mg[i]; mm = std::max(mm, mg[i]); left += stt[i] == ASM_RUN;
+    if (mg[i] > 32) { ++big; bigit += rd[i]; mxbig = std::max(mxbig, rd[i]); }
+    hist[std::min(7, rd[i] / 8)]++;
+  }
+  fprintf(stderr, "asm small: %d problems, iterations mean %.2f max %d, final sets mean %.1f max %d; sets > 32: %ld (iterations mean %.1f max %d); handed on %ld; iterations/8 histogram",
+          nprob, (double)sum / nprob, mx, (double)sm / nprob, mm, big, big ? (double)bigit / big : 0.0, mxbig, left);
+  for (int b = 0; b < 8; ++b) fprintf(stderr, " %d", hist[b]);
+  fprintf(stderr, "\n");
 #ifdef ASM_SM_PROF
-      unsigned long long tp[2][8];
-      hipMemcpyFromSymbol(tp, HIP_SYMBOL(asm_small_prof), sizeof tp);
-      for (int k = 0; k < 2; ++k)
-        fprintf(stderr, "  small instance %d clock sums: list %llu, rhs + solve %llu, x window %llu, signs %llu, exchange / loop %llu; iterations %llu\n", k, tp[k][0], tp[k][1], tp[k][2], tp[k][3], tp[k][5], tp[k][6]);
-      memset(tp, 0, sizeof tp); hipMemcpyToSymbol(HIP_SYMBOL(asm_small_prof), tp, sizeof tp);
+  unsigned long long tp[2][8];
+  hipMemcpyFromSymbol(tp, HIP_SYMBOL(asm_small_prof), sizeof tp);
+  for (int k = 0; k < 2; ++k)
+    fprintf(stderr, "  small instance %d clock sums: list %llu, rhs + solve %llu, x window %llu, signs %llu, exchange / loop %llu; iterations %llu\n", k, tp[k][0], tp[k][1], tp[k][2], tp[k][3], tp[k][5], tp[k][6]);
+  memset(tp, 0, sizeof tp); hipMemcpyToSymbol(HIP_SYMBOL(asm_small_prof), tp, sizeof tp);
 #endif
-    }
-  }
-  static const bool trace_tail = getenv("NNMPC_TRACE_ROUNDS") != nullptr;   // diagnostics: iterations per problem
-  const bool defer_cnt = tail_only && !trace_tail;
-  if (tail_only) {
-    // A call of at most 256 problems -- the lock-step chains of a task, a controller's single QP -- is finished on the
-    // device from the start (asm_tail_k: count -> fp64 solve -> x over all columns -> exchange rule, one workgroup per
-    // problem): lock-step rounds would be eight launches and a host read-back each for a handful of workgroups.
-    EvScope es(h, 4, 0.0);
-    hipLaunchKernelGGL(asm_taillist_k, dim3((nprob + 255) / 256), dim3(256), 0, s, a);
-    const int lds_tail = (a.max_active + ASM_TS + ASM_TAIL_AREA) * 8 + ((h->n + 15) / 16) * 16 + ASM_TAIL_EXTRA;
-    hipLaunchKernelGGL(asm_tail_k, dim3(nprob), dim3(256), lds_tail, s, a, h->asm_tail_budget);
-    // (the counters are read together with the status at the end of the segment -- one host round trip per call instead of two:
-    // a chain step is such a call, 0.45 ms of which ~0.04 ms was this wait; the check with P is launched unconditionally then)
-    if (!defer_cnt) {
-      HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(stream_sync(s));
-    }
-    h->stats.asm_rounds += 1;
-    if (trace_tail) {
-      std::vector<int> rd(nprob), mg(nprob);
-      hipMemcpy(rd.data(), h->asm_rounds, nprob * sizeof(int), hipMemcpyDeviceToHost);
-      hipMemcpy(mg.data(), h->asm_mg, nprob * sizeof(int), hipMemcpyDeviceToHost);
-      long sum = 0, sm = 0; int mx = 0, mm = 0;
-      for (int i = 0; i < nprob; ++i) { sum += rd[i]; mx = std::max(mx, rd[i]); sm += mg[i]; mm = std::max(mm, mg[i]); }
-      fprintf(stderr, "asm tail only: %d problems, iterations mean %.2f max %d, active bounds mean %.1f max %d\n", nprob, (double)sum / nprob, mx, (double)sm / nprob, mm);
-    }
-  }
-  // ---- The pass beside the round.  A far-field full-width pass does not wait on the main stream: asm_wide_t_k (+ asm_wide_tnorm_k) and
-  // asm_wide_gemm_k run on stream4 over the rows of the view the last round ran in (the "pending" view), while the problems that did
-  // NOT settle in that round -- known since its asm_update_k -- are counted and, if they fit, run their next round (or the device
-  // tail) on the main stream in the other, free view: its own rows of LAM / XH, its own counters and k-ranges.  Then the main stream
-  // waits for the pass and runs asm_wide_k.  Views swap roles from iteration to iteration.  Two rules keep this free of races:
-  //  (1) asm_wide_k is the only kernel of the pass that writes `state` (ASM_WIDE -> RUN / CERT / DONE), and asm_count_k, the bins,
-  //      asm_update_k and asm_taillist_k scan `state` over all problems: it runs on the main stream after everything the round
-  //      enqueued there and on its side streams (their joins come before the round's GEMMs).  Problems it sends back to ASM_RUN are
-  //      found by the next iteration's count, which is why the loop goes on after an overlapped tail.
-  //  (2) asm_wide_t_k / asm_wide_gemm_k write st / wflag / u_out / T only for rows with rowprob >= 0: problems in state ASM_WIDE, which
-  //      no kernel of the round touches (it works on ASM_RUN problems); the far-field form reads no x_unc beyond the window, so an
-  //      x_unc extension or the tail's gathered x_unc rows do not collide with it.  The dense, lazy and plain-GEMM forms of the pass
-  //      keep the serial order.
-  // The size-class lists, ranks and chunk totals (binlist, biglist, lrank, ctot) live from a round's bins to its multiplier kernels,
-  // all ordered on the main stream, and the pass reads none of them: both views share them.
-  auto set_view = [&](AsmDev& d, int v) {
-    const nnmpc_qp::AsmView& V = h->view[v];
-    d.lam = V.lam; d.xh = V.xh; d.xhw = V.xhw; d.T = V.xhw; d.tnorm = V.tnorm; d.tslack = V.tslack; d.lam32 = V.lam32; d.xh32 = V.xh32;
-    d.rowprob = V.rowprob; d.kblk = V.kblk; d.counters = V.counters;
-  };
-  const char* env_ovl = getenv("NNMPC_OVERLAP");         // (the variable: A/B runs, 0 = off; read per call)
-  const bool overlap_on = h->opts.asm_overlap >= 0 && h->view[1].rows > 0 && !(env_ovl && atoi(env_ovl) == 0);
-  int vW[2] = {h->np, h->np}, vrows[2] = {0, 0};         // per view: window and fp64 rows of the last round that ran in it
-  int pend = -1;                                         // the view whose settled rows await the full-width pass (-1: none)
-  bool tail_ran[2] = {false, false};
-  // the pass whose asm_wide_k ran last: its flops are counted from the scans of the next bins (they count what asm_wide_k marked)
-  // (wnext: the pass just launched -- beside a round its asm_wide_k comes after the bins that count the pass before it)
-  struct WideStat { bool open; int view, far_rp, skip, cols; double far_ksum; } wst = {false, 0, 0, 0, 0, 0.0}, wnext = wst;
-  int fft_prev[2] = {0, 0};
-  auto account = [&](const int* c) {                     // c: the counters of the bins pass just read back
-    if (!wst.open) return;
-    wst.open = false;
-    if (!h->profiling) return;
-    // (the problems asm_wide_k handled, the sum of their last active index + 1)
-    const double nw = c[ASM_CNT_WIDE + 1], ksum = c[ASM_CNT_WKSUM];
-    if (wst.far_rp) {
-      // far-field form: T = z V (k = n_aug + own k-range) and x = T U' (k = the column tile's share of the basis) -- over all
-      // columns, or (first-move calls) over the 128 x 128 tiles the certificate did not cover (device count of their k chunks, in
-      // the counters of the view the pass ran in)
-      const int fft = h->pin_cnt[wst.view * ASM_NCNT + ASM_CNT_FFTILES];
-      const double chunks = fft - fft_prev[wst.view];
-      fft_prev[wst.view] = fft;
-      h->stats.asm_gemm_flops += 2.0 * wst.far_rp * (ksum + nw * h->ka) +
-                                 (wst.skip ? 2.0 * G64_KC * 128.0 * 128.0 * chunks : 2.0 * 128.0 * wst.far_ksum * nw);
-    } else {
-      h->stats.asm_gemm_flops += 2.0 * wst.cols * (ksum + (lazy ? nw * h->ka : 0.0));   // (lazy: x_unc beyond the window is part of that pass)
-    }
-  };
-  for (; !tail_only && rounds < 2 * a.max_rounds + 2; ++rounds) {
-    const int pv = pend;
-    bool inflight = false;                               // this iteration's pass runs on stream4: its asm_wide_k is still to come
-    AsmDev ap = a;                                       // the pass's arguments: the pending view, its round's window
-    int fused_c0 = -1;
-    if (pv >= 0) {
-      // problems that settled inside last round's column window: all columns of x, once
-      const int prev_rows = vrows[pv];
-      set_view(ap, pv);
-      ap.W = vW[pv]; ap.wrows = prev_rows;
-      // (ap.W is that round's window: those columns are in that round's XH rows already)
-      const int c0 = (ap.W < h->np && (h->np - ap.W) % 128 == 0) ? ap.W : 0;
-      fused_c0 = ((h->np - c0) % 128 == 0 && !no_fuse) ? c0 : -1;     // the fused kernel's 128-column tiles fit: check in the GEMM's epilogue
-      const int ntm = (prev_rows + 127) / 128, ntn = (h->np - c0) / 128;
-      const nnmpc_qp::Far* ff = nullptr;
-      if (lazy && fused_c0 > 0 && !no_far) {
-        for (const auto& f : h->far) if (f.W == c0) ff = &f;
-        if (!ff && h->far_missing.size() < 16 && std::find(h->far_missing.begin(), h->far_missing.end(), c0) == h->far_missing.end())
-          h->far_missing.push_back(c0);                // (the host wrapper may add the factors for this window: nnmpc_qp_farfield_missing)
-      }
-      const bool ovl = ff && overlap_on && h->view[1 - pv].rows > 0;
-      if (!ovl && wst.open && h->profiling && h->view[1 - pv].rows > 0) {
-        // statistics only: a pass in sequence is about to mark its problems while those of an overlapped pass are still uncounted
-        // -- the two may be priced differently: count the marks now (scans of the bins in the free view; every list and row they
-        // write is written again by the bins that follow this pass)
-        AsmDev af = a;
-        set_view(af, 1 - pv);
-        hipLaunchKernelGGL(asm_bins_a_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, af);
-        hipLaunchKernelGGL(asm_bins_b_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, af);
-        HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(stream_sync(s));
-        account(h->pin_cnt + (1 - pv) * ASM_NCNT);
-      }
-      hipStream_t ps = ovl ? h->stream4 : s;
-      if (ovl) {
-        HIPCHK(hipEventRecord(h->ev_wfork, s));
-        HIPCHK(hipStreamWaitEvent(ps, h->ev_wfork, 0));
-      }
-      ap.ff_err = 0.0; ap.ff_efar = 0.0; ap.ff_skip = 0;
-      int far_rp = 0;
-      double far_ksum = 0.0;
-      {
-        EvScope es(h, 5, 0.0, ps);
-        if (ff) {
-          // far-field form: T = [x0 | lamw] V, x[c0:] = T U'; first-move calls skip the column tiles |U_j| |T_p| certifies
-          ap.ffU = ff->U; ap.ffVx = ff->Vx; ap.ffVl = ff->Vl; ap.ffcu = ff->cu; ap.ffk = ff->kt; ap.ffr = ff->rp; ap.ffW = ff->W;
-          ap.ff_err = h->p_inf * ff->efar; ap.ff_efar = ff->efar;
-          ap.ff_skip = h->nout <= c0 && h->nout < h->n;
-          far_rp = ff->rp; far_ksum = ff->ksum;
-          h->stats.asm_far_passes += 1;
-          hipLaunchKernelGGL(asm_wide_t_k, dim3(g64_grid(ntm, ff->rp / 128)), dim3(256), G64_LDS, ps, ap, ntm, ff->rp / 128);
-          if (ap.ff_skip) hipLaunchKernelGGL(asm_wide_tnorm_k, dim3((ntm * 128 + 3) / 4), dim3(256), 0, ps, ap, ntm);
-          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_FAR>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, ps, ap, c0, ntm, ntn);
-        } else if (fused_c0 >= 0 && lazy) {              // (lazy: c0 = W >= the first window -- never 0 -- and x_unc exists up to Wx >= W)
-          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_LAZY>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, ap, c0, ntm, ntn);
-        } else if (fused_c0 >= 0) {
-          hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_XUNC>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, ap, c0, ntm, ntn);
-        } else {
-          // shapes the fused kernels' tiles do not fit: XHW = LAM Pinv beyond c0 by the plain GEMM, k-range per 64-row block
-          gemm64(h, h->view[pv].xhw + c0, h->np, h->view[pv].lam, h->np, h->H64 + (size_t)c0 * h->np, h->np, ((prev_rows + 127) / 128) * 128,
-                 h->np - c0, h->np, nullptr, 0, h->view[pv].kblk, nullptr, true);
-        }
-      }
-      wnext.view = pv; wnext.far_rp = far_rp; wnext.far_ksum = far_ksum; wnext.skip = ap.ff_skip; wnext.cols = h->np - c0; wnext.open = true;
-      if (ovl) {
-        HIPCHK(hipEventRecord(h->ev_wide, ps));
-        inflight = true;
-      } else {
-        EvScope es(h, 6, 0.0);
-        hipLaunchKernelGGL(asm_wide_k, dim3((prev_rows + 3) / 4), dim3(256), 0, s, ap, fused_c0);
-        wst = wnext;
-      }
-      pend = -1; vrows[pv] = 0;
-    }
-    // the main stream joins the pass on stream4 and decides its problems (rule 1: after everything the round enqueued)
-    auto finish_pass = [&]() -> int {
-      HIPCHK(hipStreamWaitEvent(s, h->ev_wide, 0));
-      EvScope es(h, 6, 0.0);
-      hipLaunchKernelGGL(asm_wide_k, dim3((ap.wrows + 3) / 4), dim3(256), 0, s, ap, fused_c0);
-      wst = wnext;
-      inflight = false;
-      return 0;
-    };
-    if (!a.pred_w) a.refine_later = 0;                   // (only behind predicted first sets: from other starts the f32 rounds are many and their sets still move)
-    a.refine = a.refine_later && rounds >= 1;            // round 0 stays the plain f32 screen
-    a.kref = kprev;
-    // the round's view: beside a pass the one it does not occupy, view 0 otherwise
-    int rv = inflight ? 1 - pv : 0;
-    int n64 = 0, n32 = 0, nrun = 0;
-    for (;;) {
-      set_view(a, rv);
-      cnt = h->pin_cnt + rv * ASM_NCNT;
-      {
-        EvScope es(h, 6, 0.0);                            // set bookkeeping: counted with asm_update_k
-        hipLaunchKernelGGL(asm_count_k, dim3((nprob + 3) / 4), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(asm_bins_a_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, a);
-        hipLaunchKernelGGL(asm_bins_b_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, a);
-      }
-      HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));   // (both views' counters)
-      HIPCHK(stream_sync(s));
-      n64 = cnt[2]; n32 = cnt[ASM_CNT_ROWS32]; nrun = n64 + n32;   // solved in fp64 / f32 this round
-      account(cnt);                                       // flops of the last full-width pass asm_wide_k has decided
-      if (inflight && nrun > h->view[rv].rows) {
-        // more problems still running than the free view has rows (the early rounds of a call without predicted sets): the count was
-        // hidden behind the pass but is of no use -- finish the pass and count again, in view 0, as the serial order would have
-        // (the per-problem flop statistics of asm_count_k are not added a second time)
-        const int rcf = finish_pass();
-        if (rcf) return rcf;
-        rv = 0;
-        a.work = nullptr;
-        continue;
-      }
-      break;
-    }
-    a.work = h->asm_work;
-    kprev = cnt[3];
-    {
-      static const bool trace = getenv("NNMPC_TRACE_ROUNDS") != nullptr;   // diagnostics: the populations of every round
-      if (trace) {
-        fprintf(stderr, "asm round %d%s: fp64 %d f32 %d last-active %d wide-checked %d big %d big32 %d | fp64 classes", rounds, inflight ? " (beside the pass)" : "", n64, n32, cnt[3],
-                cnt[ASM_CNT_WIDE + 1], cnt[1], cnt[ASM_CNT_BIG32] + cnt[ASM_CNT_BIG32B]);
-        for (int b = 0; b < ASM_NBIN; ++b) fprintf(stderr, " %d", cnt[4 + b]);
-        fprintf(stderr, " | f32 classes");
-        for (int b = 0; b < ASM_NBIN; ++b) fprintf(stderr, " %d", cnt[ASM_CNT_F32 + b]);
-        fprintf(stderr, "\n");
-      }
-    }
-    if (nrun == 0) {
-      if (!inflight) break;
-      // nothing left to run beside the pass; asm_wide_k may still send problems back: the next count decides (this was no round)
-      const int rcf = finish_pass();
-      if (rcf) return rcf;
-      --rounds;
-      continue;
-    }
-    const nnmpc_qp::AsmView& V = h->view[rv];
-    static const int tail_max = getenv("NNMPC_TAIL_MAX") ? atoi(getenv("NNMPC_TAIL_MAX")) : 256;   // (the variable: diagnostics)
-    if (nrun <= std::min(h->asm_pool, tail_max) && (rounds >= (a.pred_w ? 2 : 6) || small)) {
-      // the tail: a handful of stragglers (the bulk settles in 5-8 rounds) -- finish them on the device (asm_tail_k)
-      // instead of paying eight launches and a read-back per round for them.  From round 6 on -- from round 2 when the first sets
-      // were predicted (qp_predict.h: the bulk then settles in rounds 1-2, and rounds 3-4 were 0.9 ms for 130 problems) -- (12 before: at 100 000
-      // problems per call the rounds 7..12 were launches for a few dozen problems, 5 % of the step)
-      static const bool trace = getenv("NNMPC_TRACE_ROUNDS") != nullptr;   // diagnostics: iterations of the tail's problems
-      {
-        EvScope es(h, 4, 0.0);
-        if (tail_ran[rv]) HIPCHK(hipMemsetAsync(V.counters + ASM_CNT_TAIL, 0, sizeof(int), s));   // (a second tail of a call, after problems came back from a pass: its own list)
-        hipLaunchKernelGGL(asm_taillist_k, dim3((nprob + 255) / 256), dim3(256), 0, s, a);
-        if (Wx < h->np) {
-          // the tail evaluates all columns of its problems straight from Pinv: their x_unc rows beyond Wx, gathered by problem
-          gemm64(h, h->asm_xunc + Wx, h->np, h->x0_64, h->ka, h->Kunc64 + (size_t)Wx * h->ka, h->ka, ((nrun + 127) / 128) * 128, h->np - Wx, h->ka,
-                 nullptr, 0, nullptr, V.counters + ASM_CNT_TAIL, false, h->asm_biglist);
-          a.Wx = h->np;                                    // (for these problems)
-        }
-        const int lds_tail = (a.max_active + ASM_TS + ASM_TAIL_AREA) * 8 + ((h->n + 15) / 16) * 16 + ASM_TAIL_EXTRA;
-        hipLaunchKernelGGL(asm_tail_k, dim3(nrun), dim3(256), lds_tail, s, a, h->asm_tail_budget);
-        tail_ran[rv] = true;
-      }
-      if (!inflight || trace) {                           // (beside a pass the next iteration's count reads the counters)
-        HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(stream_sync(s));
-      }
-      if (trace) {
-        std::vector<int> rd(nprob), bl(nrun);
-        hipMemcpy(rd.data(), h->asm_rounds, nprob * sizeof(int), hipMemcpyDeviceToHost);
-        hipMemcpy(bl.data(), h->asm_biglist, nrun * sizeof(int), hipMemcpyDeviceToHost);
-        long sum = 0; int mx = 0;
-        for (int i = 0; i < nrun; ++i) { const int r = rd[bl[i]] - rounds; sum += r; mx = std::max(mx, r); }
-        fprintf(stderr, "asm tail after round %d: %d problems, iterations mean %.1f max %d\n", rounds, nrun, (double)sum / nrun, mx);
+  return 0;
+}
+// a tail-only call: iterations per problem
+void trace_tail_only(AsmCall& c) {
+  const int nprob = c.nprob;
+  const std::vector<int> rd = fetch_ints(c.h->asm_rounds, nprob), mg = fetch_ints(c.h->asm_mg, nprob);
+  long sum = 0, sm = 0; int mx = 0, mm = 0;
+  for (int i = 0; i < nprob; ++i) { sum += rd[i]; mx = std::max(mx, rd[i]); sm += mg[i]; mm = std::max(mm, mg[i]); }
+  fprintf(stderr, "asm tail only: %d problems, iterations mean %.2f max %d, active bounds mean %.1f max %d\n", nprob, (double)sum / nprob, mx, (double)sm / nprob, mm);
+}
+// the populations of a round (cnt: its counters)
+void trace_round(int rounds, bool inflight, const int* cnt) {
+  fprintf(stderr, "asm round %d%s: fp64 %d f32 %d last-active %d wide-checked %d big %d big32 %d | fp64 classes", rounds, inflight ? " (beside the pass)" : "",
+          cnt[ASM_CNT_ROWS64], cnt[ASM_CNT_ROWS32], cnt[ASM_CNT_LAST], cnt[ASM_CNT_WIDE + 1], cnt[ASM_CNT_SLAB], cnt[ASM_CNT_BIG32] + cnt[ASM_CNT_BIG32B]);
+  for (int b = 0; b < ASM_NBIN; ++b) fprintf(stderr, " %d", cnt[ASM_CNT_F64 + b]);
+  fprintf(stderr, " | f32 classes");
+  for (int b = 0; b < ASM_NBIN; ++b) fprintf(stderr, " %d", cnt[ASM_CNT_F32 + b]);
+  fprintf(stderr, "\n");
+}
+// the tail after a round: iterations of its nrun problems
+void trace_tail(AsmCall& c, int rounds, int nrun) {
+  const std::vector<int> rd = fetch_ints(c.h->asm_rounds, c.nprob), bl = fetch_ints(c.h->asm_biglist, nrun);
+  long sum = 0; int mx = 0;
+  for (int i = 0; i < nrun; ++i) { const int r = rd[bl[i]] - rounds; sum += r; mx = std::max(mx, r); }
+  fprintf(stderr, "asm tail after round %d: %d problems, iterations mean %.1f max %d\n", rounds, nrun, (double)sum / nrun, mx);
 #ifdef ASM_TAIL_PROF
-        unsigned long long tp[8];
-        hipMemcpyFromSymbol(tp, HIP_SYMBOL(asm_tail_prof), sizeof tp);
-        fprintf(stderr, "  tail clock sums (all workgroups): count/factor/solve %llu, substitutions %llu, x loop %llu, tests %llu, exchange %llu; iterations on the dense factor %llu, on a fresh factorisation %llu\n",
-                tp[0], tp[1], tp[2], tp[3], tp[4], tp[5], tp[6]);
-        memset(tp, 0, sizeof tp); hipMemcpyToSymbol(HIP_SYMBOL(asm_tail_prof), tp, sizeof tp);
+  unsigned long long tp[8];
+  hipMemcpyFromSymbol(tp, HIP_SYMBOL(asm_tail_prof), sizeof tp);
+  fprintf(stderr, "  tail clock sums (all workgroups): count/factor/solve %llu, substitutions %llu, x loop %llu, tests %llu, exchange %llu; iterations on the dense factor %llu, on a fresh factorisation %llu\n",
+          tp[0], tp[1], tp[2], tp[3], tp[4], tp[5], tp[6]);
+  memset(tp, 0, sizeof tp); hipMemcpyToSymbol(HIP_SYMBOL(asm_tail_prof), tp, sizeof tp);
 #endif
-      }
-      h->stats.asm_rounds += 1;
-      if (!inflight) {
-        rounds = 0;                                       // (regular exit: the counters just read are final)
-        break;
-      }
-      a.Wx = Wx;                                          // (x_unc beyond Wx exists for the tail's problems only)
-      const int rcf = finish_pass();
-      if (rcf) return rcf;
-      h->stats.asm_overlapped_passes += 1;
-      continue;                                           // (the next count ends the loop, or finds what asm_wide_k sent back)
-    }
-    h->stats.asm_rounds += 1;
-    // column window of this round: past the last active bound of any running problem plus one stage; a
-    // problem that settles inside it gets one full-width pass (asm_wide_k) at the start of the next round
-    a.W = std::min(h->np, ((cnt[3] + 1 + h->nu + 127) / 128) * 128);
-    if (a.W > Wx) {
-      // a set reaches beyond the columns x_unc was formed for (a bound the full-width pass found violated out there): extend
-      EvScope es(h, 5, 2.0 * (a.W - Wx) * (double)h->ka * nprob);
-      gemm64(h, h->asm_xunc + Wx, h->np, h->x0_64, h->ka, h->Kunc64 + (size_t)Wx * h->ka, h->ka, segp, a.W - Wx, h->ka);
-      Wx = a.W; a.Wx = Wx;
-    }
-    {
-      EvScope es(h, 4, 0.0);
-      // one wave per problem, S in registers: size classes 0..5 (<= 144 bounds) in one launch, four problems per
-      // workgroup; classes 6, 7 (<= 176) two per workgroup and the rare larger sets (tiles in an L2 slab, one
-      // workgroup each: long latency chains on a handful of CUs) beside it on the side stream.
-      const int nreg2_wg = (cnt[4 + 6] + 1) / 2 + (cnt[4 + 7] + 1) / 2;
-      const int nreg32b_wg = (cnt[ASM_CNT_F32 + 6] + 3) / 4 + (cnt[ASM_CNT_F32 + 7] + 3) / 4;
-      // (use_wg, the default: sets of 177 .. 256 bounds, one workgroup of four or eight waves each -- qp_wg.h)
-      const int nwg64 = a.use_wg ? cnt[ASM_CNT_BIG64] : 0;
-      const int nwg32 = a.use_wg ? cnt[ASM_CNT_BIG32] : 0;
-      const int nwg32b = a.use_wg ? cnt[ASM_CNT_BIG32B] : 0;   // f32 rounds of 257 .. 384 bounds: eight waves per problem
-      const int nwg64r = a.use_wg ? cnt[ASM_CNT_BIG64R] : 0;   // ... and their fp64 solves: the same factorisation, refined to fp64 residuals
-      int nbig = cnt[1] + cnt[ASM_CNT_BIG32] + nreg2_wg + nreg32b_wg + nwg64 + nwg32b + nwg64r, nreg_wg = 0, nreg32_wg = 0;
-      for (int b = 0; b < ASM_NREG; ++b) { nreg_wg += (cnt[4 + b] + 3) / 4; nreg32_wg += (cnt[ASM_CNT_F32 + b] + 3) / 4; }
-      // three side streams: [slab kernel: few workgroups, long chains -- it starts first and runs beside everything else],
-      // [four-wave kernels of the 12 .. 16-block sets], [single-wave kernels of the 10- and 11-block classes]
-      // (beside a pass stream4 carries the pass: the slab kernel then goes first on stream2)
-      const bool side4 = cnt[1] > 0, side2 = nwg64 + nwg32 + nwg32b + nwg64r > 0 || (cnt[ASM_CNT_BIG32] && !a.use_wg), side3 = nreg2_wg + nreg32b_wg > 0;
-      hipStream_t st4 = inflight ? h->stream2 : h->stream4;
-      if (nbig) {
-        HIPCHK(hipEventRecord(h->ev_fork, s));
-        if (side4) {
-          HIPCHK(hipStreamWaitEvent(st4, h->ev_fork, 0));
-          { EvScope e9(h, 9, 0.0, st4); hipLaunchKernelGGL((asm_lambda_tile_k<1>), dim3(std::min(cnt[1], h->asm_pool)), dim3(256), lds_big, st4, a, 0); }
-          HIPCHK(hipEventRecord(h->ev_join4, st4));
-        }
-        if (side2) {
-          HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-          EvScope e9(h, 9, 0.0, h->stream2);
-          if (nwg64) hipLaunchKernelGGL(asm_lambda_wg64_k, dim3(nwg64), dim3(256), asm_wg_lds_bytes<double>(), h->stream2, a);
-          if (nwg64r) hipLaunchKernelGGL(asm_lambda_wg64r_k, dim3(nwg64r), dim3(512), (asm_wg_lds_bytes_refine<float, ASM_WG_MB8>()), h->stream2, a);
-          if (nwg32b) hipLaunchKernelGGL(asm_lambda_wg32b_k, dim3(nwg32b), dim3(512), (asm_wg_lds_bytes<float, ASM_WG_MB8>()), h->stream2, a);
-          if (nwg32) hipLaunchKernelGGL(asm_lambda_wg32_k, dim3(nwg32), dim3(256), asm_wg_lds_bytes<float>(), h->stream2, a);
-          if (cnt[ASM_CNT_BIG32] && !a.use_wg) hipLaunchKernelGGL(asm_lambda_tile32_k, dim3(std::min(cnt[ASM_CNT_BIG32], 4096)), dim3(512), ASM_TILE32_LDS, h->stream2, a);
-          HIPCHK(hipEventRecord(h->ev_join, h->stream2));
-        }
-        if (side3) {
-          HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_fork, 0));
-          EvScope e9(h, 9, 0.0, h->stream3);
-          // fp64, 145 .. 176 bounds: two waves per problem (7.3 / 5.2 problems per microsecond at 160 / 176 bounds against the 6.0 / 4.5
-          // of the single-wave kernel; in f32 the single-wave kernel wins, 18.1 against 14.3)
-          if (nreg2_wg && a.use_wg) hipLaunchKernelGGL(asm_lambda_wg64s_k, dim3(cnt[4 + 6] + cnt[4 + 7]), dim3(128), asm_wg_lds_bytes<double>(), h->stream3, a);
-          else if (nreg2_wg) hipLaunchKernelGGL(asm_lambda_reg2_k, dim3(nreg2_wg), dim3(128), ASM_REG2_LDS, h->stream3, a);
-          if (nreg32b_wg) hipLaunchKernelGGL(asm_lambda_reg32b_k, dim3(nreg32b_wg), dim3(256), ASM_REG32B_LDS, h->stream3, a);
-          HIPCHK(hipEventRecord(h->ev_join3, h->stream3));
-        }
-      }
-      // fp64 first (its waves are the long ones), then the f32 rounds of the problems whose set still moves
-      if (nreg_wg) { EvScope e8(h, 8, 0.0); hipLaunchKernelGGL(asm_lambda_reg_k, dim3(nreg_wg), dim3(256), ASM_REG_LDS, s, a); }
-      if (nreg32_wg) { EvScope e7(h, 7, 0.0); hipLaunchKernelGGL(asm_lambda_reg32_k, dim3(nreg32_wg), dim3(256), ASM_REG32_LDS, s, a); }
-      if (side2) HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
-      if (side3) HIPCHK(hipStreamWaitEvent(s, h->ev_join3, 0));
-      if (side4) HIPCHK(hipStreamWaitEvent(s, h->ev_join4, 0));
-    }
-    {
-      // the running problems sit in rows 0..n64-1 of LAM (fp64 solves) and 0..n32-1 of LAM32 (f32 solves), the rest
-      // of the last row block is zero; algorithmic flops of LAM * Pinv: 2 * columns * (k up to the last active bound)
-      // per running problem
-      // algorithmic flops: 2 * window columns * (own last active bound + 1) per running problem (cnt[0] is their sum)
-      EvScope es(h, 5, 2.0 * a.W * (double)cnt[0]);
-      if (n64)
-        gemm64(h, V.xh, h->np, V.lam, h->np, h->H64, h->np, ((n64 + 127) / 128) * 128, a.W, h->np, nullptr, 0,
-               V.kblk, nullptr, true);
-      // (rows are ordered by their last active stage: every 64-row block has its own k-range, asm_bins_b_k)
-      if (n32)
-        launch_xh32(s, V.xh32, (size_t)h->np, V.lam32, (size_t)h->np, h->H32, (size_t)h->np, n32, a.W, h->np, V.kblk + a.nkblk / 2);
-    }
-    {
-      EvScope es(h, 6, 0.0);
-      // (rows of LAM whose problem settles inside the window are marked for the full-width pass that opens the next round)
-      if (n64) HIPCHK(hipMemsetAsync(V.rowprob, 0xFF, (size_t)((n64 + 127) / 128) * 128 * sizeof(int), s));
-      hipLaunchKernelGGL(asm_update_k, dim3((nprob + 3) / 4), dim3(256), 0, s, a);
-    }
-    vW[rv] = a.W;
-    vrows[rv] = a.W < h->n ? n64 : 0;                    // fp64 rows of this round: the problems that settled in them await the full-width check
-    pend = vrows[rv] ? rv : -1;
-    if (inflight) {
-      const int rcf = finish_pass();
-      if (rcf) return rcf;
-      h->stats.asm_overlapped_passes += 1;
+}
+
+// Small problems: the whole iteration in one wave each (qp_small.h), three instances by the size of the set.
+int small_pass(AsmCall& c) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  const AsmDev& a = c.a;
+  const int nprob = c.nprob;
+  EvScope es(h, EV_LAMBDA, 0.0);                       // (to the end of the function)
+  // iterations of grace before single exchanges (the variable: diagnostics).  24, not the rounds' ASM_GRACE = 10: on the cond-4e7
+  // CSTRs-size plant block exchanges that stall for a dozen iterations mostly recover, and a problem sent to single exchanges
+  // early pays for it with hundreds of them -- 131 072 problems at sx = 3: 260 ms per step at 10, 78 at 16, 39 at 24, 40 at 40
+  // (the ones that truly cycle wait longer for the fallback: 146 ms at 100); the 10 000-problem batch: 47 -> 26 iterations at most
+  const int g0 = c.sw->small_grace;
+  hipLaunchKernelGGL((asm_small_k<2, 3, 4>), dim3(nprob), dim3(64), asm_small_lds_bytes(2, h->n, h->nu), s, a, a.max_rounds, g0);
+  hipLaunchKernelGGL((asm_small_k<7, 1, 8>), dim3(nprob), dim3(64), asm_small_lds_bytes(7, h->n, h->nu), s, a, a.max_rounds, g0);
+  // ... and the sets that outgrow its 112 bounds (one problem in two of three 10 000-problem batches of the CSTRs-size plant: handed
+  // to the lock-step machinery it cost a round of bookkeeping launches, a read-back and 30 more iterations in the device tail -- 2.7 -
+  // 3.1 ms per step against 1.4 without such a problem) carry on in a nine-block instance; a wave whose problem is finished exits at once
+  if (asm_small_lds_bytes(9, h->n, h->nu) <= ASM_SMALL9_LDS_MAX)   // (else: handed on as before)
+    hipLaunchKernelGGL((asm_small_k<9, 1, 8>), dim3(nprob), dim3(64), asm_small_lds_bytes(9, h->n, h->nu), s, a, a.max_rounds, g0);
+  h->stats.asm_rounds += 1;
+  h->stats.asm_small_passes += 1;
+  return c.sw->trace ? trace_small(c) : 0;
+}
+
+// A call of at most 256 problems -- the lock-step chains of a task, a controller's single QP -- is finished on the
+// device from the start (asm_tail_k: count -> fp64 solve -> x over all columns -> exchange rule, one workgroup per
+// problem): lock-step rounds would be eight launches and a host read-back each for a handful of workgroups.
+int tail_only_pass(AsmCall& c) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  const AsmDev& a = c.a;
+  const int nprob = c.nprob;
+  EvScope es(h, EV_LAMBDA, 0.0);                       // (to the end of the function)
+  hipLaunchKernelGGL(asm_taillist_k, dim3((nprob + 255) / 256), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(asm_tail_k, dim3(nprob), dim3(256), tail_lds_bytes(h, a), s, a, h->asm_tail_budget);
+  // (the counters are read together with the status at the end of the segment -- one host round trip per call instead of two:
+  // a chain step is such a call, 0.45 ms of which ~0.04 ms was this wait; the check with P is launched unconditionally then)
+  if (!c.defer_cnt)
+    if (int rc = read_counters(h)) return rc;
+  h->stats.asm_rounds += 1;
+  if (c.sw->trace) trace_tail_only(c);
+  return 0;
+}
+
+// Flops of the last full-width pass asm_wide_k has decided (c.wst).  cnt: the counters of the bins pass just read back
+void account(AsmCall& c, const int* cnt) {
+  nnmpc_qp* h = c.h;
+  if (!c.wst.open) return;
+  c.wst.open = false;
+  if (!h->profiling) return;
+  // (the problems asm_wide_k handled, the sum of their last active index + 1)
+  const double nw = cnt[ASM_CNT_WIDE + 1], ksum = cnt[ASM_CNT_WKSUM];
+  if (c.wst.far_rp) {
+    // far-field form: T = z V (k = n_aug + own k-range) and x = T U' (k = the column tile's share of the basis) -- over all
+    // columns, or (first-move calls) over the 128 x 128 tiles the certificate did not cover (device count of their k chunks, in
+    // the counters of the view the pass ran in)
+    const int fft = h->pin_cnt[c.wst.view * ASM_NCNT + ASM_CNT_FFTILES];
+    const double chunks = fft - c.fft_prev[c.wst.view];
+    c.fft_prev[c.wst.view] = fft;
+    h->stats.asm_gemm_flops += 2.0 * c.wst.far_rp * (ksum + nw * h->ka) +
+                               (c.wst.skip ? 2.0 * G64_KC * 128.0 * 128.0 * chunks : 2.0 * 128.0 * c.wst.far_ksum * nw);
+  } else {
+    h->stats.asm_gemm_flops += 2.0 * c.wst.cols * (ksum + (c.lazy ? nw * h->ka : 0.0));   // (lazy: x_unc beyond the window is part of that pass)
+  }
+}
+
+// The full-width pass over the rows of the pending view pv: the problems that settled inside last round's column window get all
+// columns of x, once.  On stream4 beside the coming round (pl.inflight: finish_pass decides its problems), else in sequence here.
+int launch_pass(AsmCall& c, int pv, PassLaunch& pl) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  const AsmDev& a = c.a;
+  const int nprob = c.nprob;
+  AsmDev& ap = pl.ap;                                  // the pass's arguments: the pending view, its round's window
+  const int prev_rows = c.vrows[pv];
+  set_view(h, ap, pv);
+  ap.W = c.vW[pv]; ap.wrows = prev_rows;
+  // (ap.W is that round's window: those columns are in that round's XH rows already)
+  const int c0 = (ap.W < h->np && (h->np - ap.W) % 128 == 0) ? ap.W : 0;
+  pl.fused_c0 = ((h->np - c0) % 128 == 0 && !c.sw->no_fused_wide) ? c0 : -1;     // the fused kernel's 128-column tiles fit: check in the GEMM's epilogue
+  const int ntm = (prev_rows + 127) / 128, ntn = (h->np - c0) / 128;
+  const nnmpc_qp::Far* ff = nullptr;
+  if (c.lazy && pl.fused_c0 > 0 && !c.sw->no_farfield) {
+    for (const auto& f : h->far) if (f.W == c0) ff = &f;
+    if (!ff && h->far_missing.size() < 16 && std::find(h->far_missing.begin(), h->far_missing.end(), c0) == h->far_missing.end())
+      h->far_missing.push_back(c0);                // (the host wrapper may add the factors for this window: nnmpc_qp_farfield_missing)
+  }
+  const bool ovl = ff && c.overlap_on && h->view[1 - pv].rows > 0;
+  if (!ovl && c.wst.open && h->profiling && h->view[1 - pv].rows > 0) {
+    // statistics only: a pass in sequence is about to mark its problems while those of an overlapped pass are still uncounted
+    // -- the two may be priced differently: count the marks now (scans of the bins in the free view; every list and row they
+    // write is written again by the bins that follow this pass)
+    AsmDev af = a;
+    set_view(h, af, 1 - pv);
+    hipLaunchKernelGGL(asm_bins_a_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, af);
+    hipLaunchKernelGGL(asm_bins_b_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, af);
+    if (int rc = read_counters(h)) return rc;
+    account(c, h->pin_cnt + (1 - pv) * ASM_NCNT);
+  }
+  hipStream_t ps = ovl ? h->stream4 : s;
+  if (ovl) {
+    HIPCHK(hipEventRecord(h->ev_wfork, s));
+    HIPCHK(hipStreamWaitEvent(ps, h->ev_wfork, 0));
+  }
+  ap.ff_err = 0.0; ap.ff_efar = 0.0; ap.ff_skip = 0;
+  int far_rp = 0;
+  double far_ksum = 0.0;
+  {
+    EvScope es(h, EV_GEMM, 0.0, ps);
+    if (ff) {
+      // far-field form: T = [x0 | lamw] V, x[c0:] = T U'; first-move calls skip the column tiles |U_j| |T_p| certifies
+      ap.ffU = ff->U; ap.ffVx = ff->Vx; ap.ffVl = ff->Vl; ap.ffcu = ff->cu; ap.ffk = ff->kt; ap.ffr = ff->rp; ap.ffW = ff->W;
+      ap.ff_err = h->p_inf * ff->efar; ap.ff_efar = ff->efar;
+      ap.ff_skip = h->nout <= c0 && h->nout < h->n;
+      far_rp = ff->rp; far_ksum = ff->ksum;
+      h->stats.asm_far_passes += 1;
+      hipLaunchKernelGGL(asm_wide_t_k, dim3(g64_grid(ntm, ff->rp / 128)), dim3(256), G64_LDS, ps, ap, ntm, ff->rp / 128);
+      if (ap.ff_skip) hipLaunchKernelGGL(asm_wide_tnorm_k, dim3((ntm * 128 + 3) / 4), dim3(256), 0, ps, ap, ntm);
+      hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_FAR>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, ps, ap, c0, ntm, ntn);
+    } else if (pl.fused_c0 >= 0 && c.lazy) {              // (lazy: c0 = W >= the first window -- never 0 -- and x_unc exists up to Wx >= W)
+      hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_LAZY>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, ap, c0, ntm, ntn);
+    } else if (pl.fused_c0 >= 0) {
+      hipLaunchKernelGGL(asm_wide_gemm_k<WIDE_XUNC>, dim3(g64_grid(ntm, ntn)), dim3(256), G64_LDS, s, ap, c0, ntm, ntn);
+    } else {
+      // shapes the fused kernels' tiles do not fit: XHW = LAM Pinv beyond c0 by the plain GEMM, k-range per 64-row block
+      gemm64(h, h->view[pv].xhw + c0, h->np, h->view[pv].lam, h->np, h->H64 + (size_t)c0 * h->np, h->np, ((prev_rows + 127) / 128) * 128,
+             h->np - c0, h->np, nullptr, 0, h->view[pv].kblk, nullptr, true);
     }
   }
-  // certification with P itself (rows the inverse-error bound could not certify): q = tq x0 and px = x P
-  if (rounds >= 2 * a.max_rounds + 2) {                  // left by the round cap: the last counters are not final
-    HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(stream_sync(s));
+  c.wnext.view = pv; c.wnext.far_rp = far_rp; c.wnext.far_ksum = far_ksum; c.wnext.skip = ap.ff_skip; c.wnext.cols = h->np - c0; c.wnext.open = true;
+  if (ovl) {
+    HIPCHK(hipEventRecord(h->ev_wide, ps));
+    pl.inflight = true;
+  } else {
+    EvScope es(h, EV_UPDATE, 0.0);
+    hipLaunchKernelGGL(asm_wide_k, dim3((prev_rows + 3) / 4), dim3(256), 0, s, ap, pl.fused_c0);
+    c.wst = c.wnext;
   }
+  c.pend = -1; c.vrows[pv] = 0;
+  return 0;
+}
+// The main stream joins the pass on stream4 and decides its problems (rule 1: after everything the round enqueued)
+int finish_pass(AsmCall& c, PassLaunch& pl) {
+  nnmpc_qp* h = c.h;
+  HIPCHK(hipStreamWaitEvent(c.s, h->ev_wide, 0));
+  EvScope es(h, EV_UPDATE, 0.0);
+  hipLaunchKernelGGL(asm_wide_k, dim3((pl.ap.wrows + 3) / 4), dim3(256), 0, c.s, pl.ap, pl.fused_c0);
+  c.wst = c.wnext;
+  pl.inflight = false;
+  return 0;
+}
+
+// The round's bookkeeping in view rv: the running problems counted and binned, the counters read back (h->pin_cnt + rv * ASM_NCNT).
+// recount: the same problems were counted in the other view already -- the per-problem flop statistics of asm_count_k are not
+// added a second time.
+int count_round(AsmCall& c, int rv, bool recount) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  AsmDev& a = c.a;
+  const int nprob = c.nprob;
+  set_view(h, a, rv);
+  if (recount) a.work = nullptr;
+  {
+    EvScope es(h, EV_UPDATE, 0.0);                            // set bookkeeping: counted with asm_update_k
+    hipLaunchKernelGGL(asm_count_k, dim3((nprob + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(asm_bins_a_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(asm_bins_b_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, a);
+  }
+  a.work = h->asm_work;
+  if (int rc = read_counters(h)) return rc;
+  account(c, h->pin_cnt + rv * ASM_NCNT);
+  return 0;
+}
+
+// The tail: a handful of stragglers (the bulk settles in 5-8 rounds) -- finish them on the device (asm_tail_k)
+// instead of paying eight launches and a read-back per round for them.  From round 6 on -- from round 2 when the first sets
+// were predicted (qp_predict.h: the bulk then settles in rounds 1-2, and rounds 3-4 were 0.9 ms for 130 problems) -- (12 before: at 100 000
+// problems per call the rounds 7..12 were launches for a few dozen problems, 5 % of the step)
+int run_tail(AsmCall& c, int rv, int nrun, int rounds, bool inflight) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  AsmDev& a = c.a;
+  const int nprob = c.nprob;
+  {
+    EvScope es(h, EV_LAMBDA, 0.0);
+    if (c.tail_ran[rv]) HIPCHK(hipMemsetAsync(a.counters + ASM_CNT_TAIL, 0, sizeof(int), s));   // (a second tail of a call, after problems came back from a pass: its own list)
+    hipLaunchKernelGGL(asm_taillist_k, dim3((nprob + 255) / 256), dim3(256), 0, s, a);
+    // the tail evaluates all columns of its problems straight from Pinv: their x_unc rows beyond Wx, gathered by problem
+    if (c.Wx < h->np) extend_xunc(c, h->np, ((nrun + 127) / 128) * 128, true);
+    hipLaunchKernelGGL(asm_tail_k, dim3(nrun), dim3(256), tail_lds_bytes(h, a), s, a, h->asm_tail_budget);
+    c.tail_ran[rv] = true;
+  }
+  if (!inflight || c.sw->trace)                          // (beside a pass the next iteration's count reads the counters)
+    if (int rc = read_counters(h)) return rc;
+  if (c.sw->trace) trace_tail(c, rounds, nrun);
+  h->stats.asm_rounds += 1;
+  return 0;
+}
+
+// The round's multiplier systems, by size class; the large sets on the side streams, joined before the window GEMMs.
+// cnt: the round's counters.
+int launch_multipliers(AsmCall& c, const int* cnt, bool inflight) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  const AsmDev& a = c.a;
+  const int lds_big = (a.max_active + ASM_TS) * 8;
+  EvScope es(h, EV_LAMBDA, 0.0);
+  // one wave per problem, S in registers: size classes 0..5 (<= 144 bounds) in one launch, four problems per
+  // workgroup; classes 6, 7 (<= 176) two per workgroup and the rare larger sets (tiles in an L2 slab, one
+  // workgroup each: long latency chains on a handful of CUs) beside it on the side stream.
+  const int nreg2_wg = (cnt[ASM_CNT_F64 + 6] + 1) / 2 + (cnt[ASM_CNT_F64 + 7] + 1) / 2;
+  const int nreg32b_wg = (cnt[ASM_CNT_F32 + 6] + 3) / 4 + (cnt[ASM_CNT_F32 + 7] + 3) / 4;
+  // (use_wg, the default: sets of 177 .. 256 bounds, one workgroup of four or eight waves each -- qp_wg.h)
+  const int nwg64 = a.use_wg ? cnt[ASM_CNT_BIG64] : 0;
+  const int nwg32 = a.use_wg ? cnt[ASM_CNT_BIG32] : 0;
+  const int nwg32b = a.use_wg ? cnt[ASM_CNT_BIG32B] : 0;   // f32 rounds of 257 .. 384 bounds: eight waves per problem
+  const int nwg64r = a.use_wg ? cnt[ASM_CNT_BIG64R] : 0;   // ... and their fp64 solves: the same factorisation, refined to fp64 residuals
+  int nbig = cnt[ASM_CNT_SLAB] + cnt[ASM_CNT_BIG32] + nreg2_wg + nreg32b_wg + nwg64 + nwg32b + nwg64r, nreg_wg = 0, nreg32_wg = 0;
+  for (int b = 0; b < ASM_NREG; ++b) { nreg_wg += (cnt[ASM_CNT_F64 + b] + 3) / 4; nreg32_wg += (cnt[ASM_CNT_F32 + b] + 3) / 4; }
+  // three side streams: [slab kernel: few workgroups, long chains -- it starts first and runs beside everything else],
+  // [four-wave kernels of the 12 .. 16-block sets], [single-wave kernels of the 10- and 11-block classes]
+  // (beside a pass stream4 carries the pass: the slab kernel then goes first on stream2)
+  const bool side4 = cnt[ASM_CNT_SLAB] > 0, side2 = nwg64 + nwg32 + nwg32b + nwg64r > 0 || (cnt[ASM_CNT_BIG32] && !a.use_wg), side3 = nreg2_wg + nreg32b_wg > 0;
+  hipStream_t st4 = inflight ? h->stream2 : h->stream4;
+  if (nbig) {
+    HIPCHK(hipEventRecord(h->ev_fork, s));
+    if (side4) {
+      HIPCHK(hipStreamWaitEvent(st4, h->ev_fork, 0));
+      { EvScope e9(h, EV_SIDE, 0.0, st4); hipLaunchKernelGGL((asm_lambda_tile_k<1>), dim3(std::min(cnt[ASM_CNT_SLAB], h->asm_pool)), dim3(256), lds_big, st4, a, 0); }
+      HIPCHK(hipEventRecord(h->ev_join4, st4));
+    }
+    if (side2) {
+      HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+      EvScope e9(h, EV_SIDE, 0.0, h->stream2);
+      if (nwg64) hipLaunchKernelGGL(asm_lambda_wg64_k, dim3(nwg64), dim3(256), asm_wg_lds_bytes<double>(), h->stream2, a);
+      if (nwg64r) hipLaunchKernelGGL(asm_lambda_wg64r_k, dim3(nwg64r), dim3(512), (asm_wg_lds_bytes_refine<float, ASM_WG_MB8>()), h->stream2, a);
+      if (nwg32b) hipLaunchKernelGGL(asm_lambda_wg32b_k, dim3(nwg32b), dim3(512), (asm_wg_lds_bytes<float, ASM_WG_MB8>()), h->stream2, a);
+      if (nwg32) hipLaunchKernelGGL(asm_lambda_wg32_k, dim3(nwg32), dim3(256), asm_wg_lds_bytes<float>(), h->stream2, a);
+      if (cnt[ASM_CNT_BIG32] && !a.use_wg) hipLaunchKernelGGL(asm_lambda_tile32_k, dim3(std::min(cnt[ASM_CNT_BIG32], 4096)), dim3(512), ASM_TILE32_LDS, h->stream2, a);
+      HIPCHK(hipEventRecord(h->ev_join, h->stream2));
+    }
+    if (side3) {
+      HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_fork, 0));
+      EvScope e9(h, EV_SIDE, 0.0, h->stream3);
+      // fp64, 145 .. 176 bounds: two waves per problem (7.3 / 5.2 problems per microsecond at 160 / 176 bounds against the 6.0 / 4.5
+      // of the single-wave kernel; in f32 the single-wave kernel wins, 18.1 against 14.3)
+      if (nreg2_wg && a.use_wg) hipLaunchKernelGGL(asm_lambda_wg64s_k, dim3(cnt[ASM_CNT_F64 + 6] + cnt[ASM_CNT_F64 + 7]), dim3(128), asm_wg_lds_bytes<double>(), h->stream3, a);
+      else if (nreg2_wg) hipLaunchKernelGGL(asm_lambda_reg2_k, dim3(nreg2_wg), dim3(128), ASM_REG2_LDS, h->stream3, a);
+      if (nreg32b_wg) hipLaunchKernelGGL(asm_lambda_reg32b_k, dim3(nreg32b_wg), dim3(256), ASM_REG32B_LDS, h->stream3, a);
+      HIPCHK(hipEventRecord(h->ev_join3, h->stream3));
+    }
+  }
+  // fp64 first (its waves are the long ones), then the f32 rounds of the problems whose set still moves
+  if (nreg_wg) { EvScope e8(h, EV_LAMBDA64, 0.0); hipLaunchKernelGGL(asm_lambda_reg_k, dim3(nreg_wg), dim3(256), ASM_REG_LDS, s, a); }
+  if (nreg32_wg) { EvScope e7(h, EV_LAMBDA32, 0.0); hipLaunchKernelGGL(asm_lambda_reg32_k, dim3(nreg32_wg), dim3(256), ASM_REG32_LDS, s, a); }
+  if (side2) HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
+  if (side3) HIPCHK(hipStreamWaitEvent(s, h->ev_join3, 0));
+  if (side4) HIPCHK(hipStreamWaitEvent(s, h->ev_join4, 0));
+  return 0;
+}
+
+// The round's window GEMMs (XH = LAM Pinv' over a.W columns, fp64 and f32 rows) and its set update.  cnt: the round's counters.
+int window_gemms_and_update(AsmCall& c, int rv, int n64, int n32, const int* cnt) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  const AsmDev& a = c.a;
+  const int nprob = c.nprob;
+  const nnmpc_qp::AsmView& V = h->view[rv];
+  {
+    // the running problems sit in rows 0..n64-1 of LAM (fp64 solves) and 0..n32-1 of LAM32 (f32 solves), the rest
+    // of the last row block is zero; algorithmic flops of LAM * Pinv: 2 * columns * (k up to the last active bound)
+    // per running problem
+    // algorithmic flops: 2 * window columns * (own last active bound + 1) per running problem (cnt[ASM_CNT_KSUM] is their sum)
+    EvScope es(h, EV_GEMM, 2.0 * a.W * (double)cnt[ASM_CNT_KSUM]);
+    if (n64)
+      gemm64(h, V.xh, h->np, V.lam, h->np, h->H64, h->np, ((n64 + 127) / 128) * 128, a.W, h->np, nullptr, 0,
+             V.kblk, nullptr, true);
+    // (rows are ordered by their last active stage: every 64-row block has its own k-range, asm_bins_b_k)
+    if (n32)
+      launch_xh32(s, V.xh32, (size_t)h->np, V.lam32, (size_t)h->np, h->H32, (size_t)h->np, n32, a.W, h->np, V.kblk + a.nkblk / 2);
+  }
+  {
+    EvScope es(h, EV_UPDATE, 0.0);
+    // (rows of LAM whose problem settles inside the window are marked for the full-width pass that opens the next round)
+    if (n64) HIPCHK(hipMemsetAsync(V.rowprob, 0xFF, (size_t)((n64 + 127) / 128) * 128 * sizeof(int), s));
+    hipLaunchKernelGGL(asm_update_k, dim3((nprob + 3) / 4), dim3(256), 0, s, a);
+  }
+  return 0;
+}
+
+// Problems finished but not certified by the inverse-error bound, counted in the view a problem finished in (h->pin_cnt)
+int ndone(const nnmpc_qp* h) { return h->pin_cnt[ASM_CNT_DONE] + h->pin_cnt[ASM_NCNT + ASM_CNT_DONE]; }
+// Certification with P itself (rows the inverse-error bound could not certify): q = tq x0 and px = x P; the status of the segment
+// read back (h->pin_st) and handed to the caller.  fb: the problems left for the PDIP path (status 3).
+// capped: the loop was left by the round cap -- the last counters are not final.
+int certify_and_collect(AsmCall& c, bool capped, int32_t* st_dev, std::vector<int>& fb) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  AsmDev& a = c.a;
+  const int nprob = c.nprob, segp = c.segp;
+  if (capped)
+    if (int rc = read_counters(h)) return rc;
   if (h->gemm_error) { h->gemm_error = false; return NNMPC_EINVAL; }
-  set_view(a, 0);
-  cnt = h->pin_cnt;
-  auto ndone = [&]() { return h->pin_cnt[ASM_CNT_DONE] + h->pin_cnt[ASM_NCNT + ASM_CNT_DONE]; };   // (counted in the view a problem finished in)
-  if (!defer_cnt) h->stats.asm_full_checks += ndone();
-  if (defer_cnt || ndone() > 0) {                // (row blocks without an ASM_DONE row leave these GEMMs at once)
+  set_view(h, a, 0);
+  if (!c.defer_cnt) h->stats.asm_full_checks += ndone(h);
+  if (c.defer_cnt || ndone(h) > 0) {             // (row blocks without an ASM_DONE row leave these GEMMs at once)
     gemm64(h, h->q64_all, h->np, h->x0_64, h->ka, h->tq64, h->ka, segp, h->np, h->ka, h->asm_state, ASM_DONE);
-    gemm64(h, h->asm_xh, h->np, h->asm_x, h->np, h->P64, h->np, segp, h->np, h->np, h->asm_state, ASM_DONE);
+    gemm64(h, h->view[0].xh, h->np, h->asm_x, h->np, h->P64, h->np, segp, h->np, h->np, h->asm_state, ASM_DONE);
   }
   hipLaunchKernelGGL(asm_certify_k, dim3(nprob), dim3(256), 0, s, a, h->pscale);
   int* st = h->pin_st;
   HIPCHK(hipMemcpyAsync(st, h->asm_status, (size_t)nprob * sizeof(int), hipMemcpyDeviceToHost, s));
   int* pin_its = h->pin_cnt + 2 * ASM_NCNT;
-  if (h->profiling && pred_flops_per_it > 0.0) HIPCHK(hipMemcpyAsync(pin_its, h->pred_cnt + 1, 4, hipMemcpyDeviceToHost, s));
-  if (defer_cnt) HIPCHK(hipMemcpyAsync(h->pin_cnt, h->asm_counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (h->profiling && c.pred_flops_per_it > 0.0) HIPCHK(hipMemcpyAsync(pin_its, h->pred_cnt + 1, 4, hipMemcpyDeviceToHost, s));
+  if (c.defer_cnt) HIPCHK(hipMemcpyAsync(h->pin_cnt, h->view[0].counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(stream_sync(s));
-  if (defer_cnt) h->stats.asm_full_checks += ndone();
-  if (h->profiling && pred_flops_per_it > 0.0) h->stats.asm_predict_flops += pred_flops_per_it * (double)*pin_its;
+  if (c.defer_cnt) h->stats.asm_full_checks += ndone(h);
+  if (h->profiling && c.pred_flops_per_it > 0.0) h->stats.asm_predict_flops += c.pred_flops_per_it * (double)*pin_its;
   HIPCHK(hipGetLastError());
-  std::vector<int> fb;
   int ninvalid = 0;
   for (int p = 0; p < nprob; ++p) { if (st[p] == 3) fb.push_back(p); else if (st[p] != 0) ++ninvalid; }   // 2: rejected inputs
   h->stats.asm_solved += nprob - (int64_t)fb.size() - ninvalid;
   if (st_dev) HIPCHK(hipMemcpyAsync(st_dev, h->asm_status, (size_t)nprob * sizeof(int), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// What the pass could not finish (fb) is re-solved by the PDIP path (solve_segment) on a compacted copy (scratch owned by the
+// handle: nothing to release on an error path) -- or, with opts.method == 2, reported as not certified.
+int pdip_fallback(AsmCall& c, const std::vector<int>& fb, const double* x0_dev, int32_t* st_dev) {
+  nnmpc_qp* h = c.h;
+  hipStream_t s = c.s;
+  const AsmDev& a = c.a;
+  const int nprob = c.nprob;
   if (fb.empty()) { h->stats.problems += nprob; return 0; }
   if (h->opts.method == 2) {                           // asm only: report the rest as not certified
+    int* st = h->pin_st;
     for (int p = 0; p < nprob; ++p) st[p] = st[p] == 3 ? NNMPC_ST_MAXITER : st[p];
     if (st_dev) HIPCHK(hipMemcpy(st_dev, st, (size_t)nprob * sizeof(int), hipMemcpyHostToDevice));
     h->stats.problems += nprob;
     return 0;
   }
-  // ---- PDIP fallback on the compacted remainder (scratch owned by the handle: nothing to release on an error path)
   const int cntf = (int)fb.size();
   int* list = nullptr; double *x0c = nullptr, *lbc = nullptr, *ubc = nullptr, *uc = nullptr;
   uint32_t* actc = nullptr; int *stc = nullptr, *itc = nullptr;
@@ -1626,7 +1658,7 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   if (int rc = res.slot(nnmpc_qp::SC_FB_IT, &itc, (size_t)cntf * 8)) return rc;
   int rc = 0;
   HIPCHK(hipMemcpy(list, fb.data(), cntf * sizeof(int), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(asm_gather_k, dim3(cntf), dim3(128), 0, s, x0c, lbc, ubc, x0_dev, lb_dev, ub_dev, list, cntf, h->n_aug, h->nu);
+  hipLaunchKernelGGL(asm_gather_k, dim3(cntf), dim3(128), 0, s, x0c, lbc, ubc, x0_dev, a.lb, a.ub, list, cntf, h->n_aug, h->nu);
   // a problem whose set had settled but failed the check with P (inverse too inaccurate for its x) starts the polish
   // on that set; the others (not settled, too large, not positive definite) run the PDIP from scratch
   hipLaunchKernelGGL(asm_gather_guess_k, dim3(cntf), dim3(128), 0, s, guessc, h->asm_st, h->asm_state, list, cntf, h->n);
@@ -1639,12 +1671,141 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   }
   h->ldu = ldu_caller; h->nout = nout_caller;
   if (!rc) {
-    hipLaunchKernelGGL(asm_scatter_k, dim3(cntf), dim3(128), 0, s, u_dev, act_dev, st_dev, it_dev, uc, actc, stc, itc,
+    hipLaunchKernelGGL(asm_scatter_k, dim3(cntf), dim3(128), 0, s, a.u_out, a.act_out, st_dev, a.iters_out, uc, actc, stc, itc,
                        list, cntf, h->n, h->words, h->ldu, h->nout);
     HIPCHK(stream_sync(s));
   }
   h->stats.problems += nprob - cntf;   // solve_segment counted the fallback ones
   return rc;
+}
+
+// Shared-inverse active-set pass over one segment; problems it cannot finish are marked 3 in
+// h->asm_status and re-solved by the PDIP path (solve_segment) on a compacted copy.
+int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double* lb_dev, const double* ub_dev,
+                      const unsigned char* guess_dev, double* u_dev, uint32_t* act_dev, int32_t* st_dev, int32_t* it_dev) {
+  AsmCall c;
+  AsmDev& a = c.a;
+  const AsmSwitches& sw = asm_switches();
+  hipStream_t s = h->stream;
+  c.h = h; c.s = s; c.sw = &sw; c.nprob = nprob; c.segp = ((nprob + 127) / 128) * 128;
+  hipLaunchKernelGGL(pad_x0_k, dim3(512), dim3(256), 0, s, h->x0_64, h->x0_32, x0_dev, nprob, h->n_aug, h->ka, c.segp);
+  c.tail_only = h->opts.asm_tail_batch >= 0 && nprob <= std::min(std::min(h->asm_pool, 256), h->opts.asm_tail_batch ? h->opts.asm_tail_batch : 256);
+  // x_unc = Kunc x0 -- for the leading columns only (the window the first sets are drawn from; extended should a round's
+  // window outgrow it): beyond them x_unc is one K segment of the full-width pass's GEMM (qp_wide.h).  Calls that go to
+  // the device tail from the start, and shapes the fused kernel's tiles do not fit, form all of it.  q = tq x0 is only
+  // formed for the rows that need the full check with P.
+  // Small problems -- Pinv fits the 4 MB L2 of an XCD (n <= 724: the CSTRs size, 540) -- run the whole iteration in one wave each
+  // (qp_small.h); what that kernel hands back (sets beyond 64 bounds, problems still moving after its budget) carries on below.
+  c.small = !env_no_small() && (size_t)h->np * h->np * 8 <= (4u << 20) && h->n <= ASM_SM_NMAX && h->np % 4 == 0;
+  c.lazy = h->np % 128 == 0 && !sw.no_fused_wide && !sw.no_lazy_xunc && !c.tail_only && !c.small && (uint64_t)h->seg_max * h->ka * 8 < (1ull << 32);
+  // (the window the first sets are drawn from: the leading eighth of the horizon, 512 columns at least -- a quarter until round 3;
+  // the CDU batch settles inside 512 columns, a quarter is 1152: 0.4 ms of x_unc GEMM per step.  A bound x_unc violates further
+  // out joins through the full-width pass every problem goes through.  Following the previous call's window instead made the
+  // path of a call depend on the handle's history: other windows, other far-field factors, and for degenerate problems other sets)
+  c.winit = std::min(h->n, std::max(512, ((h->n / 8 + 127) / 128) * 128));
+  c.Wx = h->np;
+  if (c.lazy) c.Wx = std::min(h->np, guess_dev ? 512 : ((c.winit + 127) / 128) * 128);
+  {
+    EvScope es(h, EV_GEMM, 2.0 * c.Wx * (double)h->ka * nprob);
+    gemm64(h, h->asm_xunc, h->np, h->x0_64, h->ka, h->Kunc64, h->ka, c.segp, c.Wx, h->ka);
+  }
+  asm_args(c, lb_dev, ub_dev, guess_dev, u_dev, act_dev, it_dev);
+  // LAM / LAMW are all zero between calls: every entry the multiplier kernels write is cleared again by
+  // asm_update_k / asm_wide_k of the same round
+  if (!guess_dev) HIPCHK(hipMemsetAsync(h->asm_st, 0, (size_t)nprob * h->n, s));   // bound states: asm_init_k writes the leading window only
+  if (int rc = first_sets(c)) return rc;
+  memset(h->pin_cnt, 0, 2 * ASM_NCNT * sizeof(int));
+  HIPCHK(hipMemsetAsync(h->view[0].counters, 0, 2 * ASM_NCNT * sizeof(int), s));   // (both views' counters)
+  if (c.small)
+    if (int rc = small_pass(c)) return rc;
+  c.defer_cnt = c.tail_only && !sw.trace;
+  if (c.tail_only)
+    if (int rc = tail_only_pass(c)) return rc;
+  c.overlap_on = h->opts.asm_overlap >= 0 && h->view[1].rows > 0 && !env_overlap_off();
+  c.vW[0] = c.vW[1] = h->np;
+
+  // ---- The pass beside the round.  A far-field full-width pass does not wait on the main stream: asm_wide_t_k (+ asm_wide_tnorm_k) and
+  // asm_wide_gemm_k run on stream4 over the rows of the view the last round ran in (the pending view, c.pend; its rows and window:
+  // c.vrows, c.vW), while the problems that did NOT settle in that round -- known since its asm_update_k -- are counted and, if they
+  // fit, run their next round (or the device tail) on the main stream in the other, free view (rv): its own rows of LAM / XH, its own
+  // counters and k-ranges.  Then the main stream waits for the pass and runs asm_wide_k (finish_pass).  Views swap roles from
+  // iteration to iteration.  Two rules keep this free of races:
+  //  (1) asm_wide_k is the only kernel of the pass that writes `state` (ASM_WIDE -> RUN / CERT / DONE), and asm_count_k, the bins,
+  //      asm_update_k and asm_taillist_k scan `state` over all problems: finish_pass runs on the main stream after everything the
+  //      round enqueued there and on its side streams (their joins come before the round's GEMMs: launch_multipliers).  Problems it
+  //      sends back to ASM_RUN are found by the next iteration's count, which is why the loop goes on after an overlapped tail.
+  //  (2) asm_wide_t_k / asm_wide_gemm_k write st / wflag / u_out / T only for rows with rowprob >= 0: problems in state ASM_WIDE, which
+  //      no kernel of the round touches (it works on ASM_RUN problems); the far-field form reads no x_unc beyond the window, so an
+  //      x_unc extension or the tail's gathered x_unc rows (extend_xunc: c.Wx, c.a.Wx) do not collide with it.  The dense, lazy and
+  //      plain-GEMM forms of the pass keep the serial order (launch_pass leaves pl.inflight false).
+  // The size-class lists, ranks and chunk totals (binlist, biglist, lrank, ctot) live from a round's bins to its multiplier kernels,
+  // all ordered on the main stream, and the pass reads none of them: both views share them.
+  const int round_cap = 2 * a.max_rounds + 2;
+  int rounds = 0;
+  for (; !c.tail_only && rounds < round_cap; ++rounds) {
+    const int pv = c.pend;
+    PassLaunch pl = {a, -1, false};
+    if (pv >= 0)
+      if (int rc = launch_pass(c, pv, pl)) return rc;
+    if (!a.pred_w) a.refine_later = 0;                   // (only behind predicted first sets: from other starts the f32 rounds are many and their sets still move)
+    a.refine = a.refine_later && rounds >= 1;            // round 0 stays the plain f32 screen
+    a.kref = c.kprev;
+    // the round's view: beside a pass the one it does not occupy, view 0 otherwise
+    int rv = pl.inflight ? 1 - pv : 0;
+    int n64 = 0, n32 = 0, nrun = 0;
+    const int* cnt = nullptr;
+    for (bool recount = false;; recount = true) {
+      if (int rc = count_round(c, rv, recount)) return rc;
+      cnt = h->pin_cnt + rv * ASM_NCNT;
+      n64 = cnt[ASM_CNT_ROWS64]; n32 = cnt[ASM_CNT_ROWS32]; nrun = n64 + n32;   // solved in fp64 / f32 this round
+      if (!pl.inflight || nrun <= h->view[rv].rows) break;
+      // more problems still running than the free view has rows (the early rounds of a call without predicted sets): the count was
+      // hidden behind the pass but is of no use -- finish the pass and count again, in view 0, as the serial order would have
+      if (int rc = finish_pass(c, pl)) return rc;
+      rv = 0;
+    }
+    c.kprev = cnt[ASM_CNT_LAST];
+    if (sw.trace) trace_round(rounds, pl.inflight, cnt);
+    if (nrun == 0) {
+      if (!pl.inflight) break;
+      // nothing left to run beside the pass; asm_wide_k may still send problems back: the next count decides (this was no round)
+      if (int rc = finish_pass(c, pl)) return rc;
+      --rounds;
+      continue;
+    }
+    if (nrun <= std::min(h->asm_pool, sw.tail_max) && (rounds >= (a.pred_w ? 2 : 6) || c.small)) {
+      if (int rc = run_tail(c, rv, nrun, rounds, pl.inflight)) return rc;
+      if (!pl.inflight) {
+        rounds = 0;                                       // (regular exit: the counters just read are final)
+        break;
+      }
+      a.Wx = c.Wx;                                        // (x_unc beyond Wx exists for the tail's problems only)
+      if (int rc = finish_pass(c, pl)) return rc;
+      h->stats.asm_overlapped_passes += 1;
+      continue;                                           // (the next count ends the loop, or finds what asm_wide_k sent back)
+    }
+    h->stats.asm_rounds += 1;
+    // column window of this round: past the last active bound of any running problem plus one stage; a
+    // problem that settles inside it gets one full-width pass (asm_wide_k) at the start of the next round
+    a.W = std::min(h->np, ((cnt[ASM_CNT_LAST] + 1 + h->nu + 127) / 128) * 128);
+    if (a.W > c.Wx) {
+      // a set reaches beyond the columns x_unc was formed for (a bound the full-width pass found violated out there): extend
+      EvScope es(h, EV_GEMM, 2.0 * (a.W - c.Wx) * (double)h->ka * nprob);
+      extend_xunc(c, a.W, c.segp, false);
+    }
+    if (int rc = launch_multipliers(c, cnt, pl.inflight)) return rc;
+    if (int rc = window_gemms_and_update(c, rv, n64, n32, cnt)) return rc;
+    c.vW[rv] = a.W;
+    c.vrows[rv] = a.W < h->n ? n64 : 0;                  // fp64 rows of this round: the problems that settled in them await the full-width check
+    c.pend = c.vrows[rv] ? rv : -1;
+    if (pl.inflight) {
+      if (int rc = finish_pass(c, pl)) return rc;
+      h->stats.asm_overlapped_passes += 1;
+    }
+  }
+  std::vector<int> fb;
+  if (int rc = certify_and_collect(c, rounds >= round_cap, st_dev, fb)) return rc;
+  return pdip_fallback(c, fb, x0_dev, st_dev);
 }
 
 }  // namespace
@@ -1763,33 +1924,30 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   A_(d.slot_prob, S); A_(d.age, S); A_(d.next_prob, 1);
   // workgroups of the large-set kernel in flight (each with its tile slab in HBM / L2): four per CU for bulk batches --
   // the kernel is a latency chain (barriers, tiles in global memory), occupancy is what hides it
-  h->asm_pool = h->seg_max >= 4096 ? (getenv("NNMPC_TAIL_MAX") && atoi(getenv("NNMPC_TAIL_MAX")) > 1024 ? 2048 : 1024) : 256;
+  h->asm_pool = h->seg_max >= 4096 ? (asm_switches().tail_max > 1024 ? 2048 : 1024) : 256;
+  nnmpc_qp::AsmView& v0 = h->view[0];
   A_(h->H64, (size_t)np * np); A_(h->Kunc64, (size_t)np * ka); A_(h->H32, (size_t)np * np);
-  A_(h->asm_xunc, G * np); A_(h->asm_x, G * np); A_(h->asm_lam, G * np); A_(h->asm_xh, G * np);
-  A_(h->asm_xhw, (G + 256) * np); A_(h->asm_rowprob, G + 256); A_(h->asm_wflag, G); A_(h->asm_wmark, G);
-  A_(h->asm_tnorm, G + 128 * (ASM_NKG + 1)); A_(h->asm_tslack, G + 128 * (ASM_NKG + 1));
-  A_(h->asm_st, G * n); A_(h->asm_state, G); A_(h->asm_rounds, G); A_(h->asm_counters, 2 * ASM_NCNT);
+  A_(h->asm_xunc, G * np); A_(h->asm_x, G * np); A_(v0.lam, G * np); A_(v0.xh, G * np);
+  A_(v0.xhw, (G + 256) * np); A_(v0.rowprob, G + 256); A_(h->asm_wflag, G); A_(h->asm_wmark, G);
+  A_(v0.tnorm, G + 128 * (ASM_NKG + 1)); A_(v0.tslack, G + 128 * (ASM_NKG + 1));
+  A_(h->asm_st, G * n); A_(h->asm_state, G); A_(h->asm_rounds, G); A_(v0.counters, 2 * ASM_NCNT);
   A_(h->asm_biglist, G); A_(h->asm_status, G); A_(h->asm_binlist, (size_t)(ASM_NLIST + 4) * G);
-  A_(h->asm_idxg, G * o.asm_max_active); A_(h->asm_mg, G); A_(h->asm_row, G); A_(h->asm_lrank, G); A_(h->asm_ctot, ((G + 1023) / 1024) * ASM_NSCAN); A_(h->asm_prec, G); A_(h->asm_redo, G); A_(h->asm_rowk, G); A_(h->asm_lam32, G * np); A_(h->asm_xh32, G * np); A_(h->asm_alpha, G); A_(h->asm_ninf, G); A_(h->asm_hi, G); A_(h->asm_kblk, 2 * (G / 64 + 2)); A_(h->asm_work, 3 * G);
+  A_(h->asm_idxg, G * o.asm_max_active); A_(h->asm_mg, G); A_(h->asm_row, G); A_(h->asm_lrank, G); A_(h->asm_ctot, ((G + 1023) / 1024) * ASM_NSCAN); A_(h->asm_prec, G); A_(h->asm_redo, G); A_(h->asm_rowk, G); A_(v0.lam32, G * np); A_(v0.xh32, G * np); A_(h->asm_alpha, G); A_(h->asm_ninf, G); A_(h->asm_hi, G); A_(v0.kblk, 2 * (G / 64 + 2)); A_(h->asm_work, 3 * G);
+  v0.rows = (int)G;
   A_(h->asm_scratch, (size_t)h->asm_pool * ((size_t)(o.asm_max_active / 16) * (o.asm_max_active / 16 + 1) / 2 * ASM_TS));
   {
     // the second row space: a thirty-second of the segment, 1024 rows at least (the CDU batch of 100 000 at sx = 2 leaves ~1 300
     // problems running after the round most sets settle in: 3 200 rows, 0.47 GB at np = 4608).  Its k-range array is as long as view
     // 0's: asm_bins_b_k writes the entry of every row it hands out, also in a round that turns out not to fit these rows.
     // (NNMPC_OVERLAP_ROWS: tests only -- a row count that forces the rounds back into view 0)
-    nnmpc_qp::AsmView& v0 = h->view[0];
-    v0.lam = h->asm_lam; v0.xh = h->asm_xh; v0.xhw = h->asm_xhw; v0.tnorm = h->asm_tnorm; v0.tslack = h->asm_tslack;
-    v0.lam32 = h->asm_lam32; v0.xh32 = h->asm_xh32; v0.rowprob = h->asm_rowprob; v0.kblk = h->asm_kblk; v0.counters = h->asm_counters;
-    v0.rows = (int)G;
-    long long R = std::max<long long>(1024, ((long long)G / 32 + 127) / 128 * 128);
-    if (const char* e = getenv("NNMPC_OVERLAP_ROWS")) R = std::max(0, atoi(e) / 128 * 128);
+    long long R = env_overlap_rows(std::max<long long>(1024, ((long long)G / 32 + 127) / 128 * 128));
     R = std::min<long long>(R, (long long)G);
     if (o.asm_overlap >= 0 && R > 0) {
       nnmpc_qp::AsmView& v1 = h->view[1];
       const size_t Rr = (size_t)R;
       A_(v1.lam, Rr * np); A_(v1.xh, Rr * np); A_(v1.xhw, (Rr + 256) * np); A_(v1.lam32, Rr * np); A_(v1.xh32, Rr * np);
       A_(v1.tnorm, Rr + 128 * (ASM_NKG + 1)); A_(v1.tslack, Rr + 128 * (ASM_NKG + 1)); A_(v1.rowprob, Rr + 256); A_(v1.kblk, 2 * (G / 64 + 2));
-      v1.counters = h->asm_counters + ASM_NCNT;
+      v1.counters = v0.counters + ASM_NCNT;
       v1.rows = (int)R;
     }
   }
@@ -2141,7 +2299,7 @@ int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const doub
   }
 #undef STEP_
   if (h->profiling) {
-    h->ev_recs.push_back({3, e_tot0, ev_mark(h, h->stream), 0.0});
+    h->ev_recs.push_back({EV_TOTAL, e_tot0, ev_mark(h, h->stream), 0.0});
     stream_sync(h->stream);
     ev_collect(h);
   }

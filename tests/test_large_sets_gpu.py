@@ -1,6 +1,6 @@
 """Active sets of a CHOSEN size, 16 .. 800 bounds, through every kernel of the shared-inverse active-set pass that factors them.
 
-The pass picks its multiplier-system kernel from the number of active bounds m (thresholds: qp_asm.h, qp_small.h, solve_segment_asm):
+The pass picks its multiplier-system kernel from the number of active bounds m (thresholds: qp_asm.h, qp_small.h, launch_multipliers in qp_solver.hip):
 
     m <= 144        asm_lambda_reg32_k  (f32 rounds)   asm_lambda_reg_k    (fp64 solve)
     145 .. 176      asm_lambda_reg32b_k                asm_lambda_wg64s_k

@@ -1,4 +1,4 @@
-"""The full-width pass beside the round (csrc/qp_solver.hip, solve_segment_asm; opts.asm_overlap).
+"""The full-width pass beside the round (csrc/qp_solver.hip: launch_pass / finish_pass in the loop of solve_segment_asm; opts.asm_overlap).
 
 A far-field full-width pass runs on a side stream while the problems that did not settle run their next round (or the device
 tail) in a second, small row space.  That changes the ORDER of the work and nothing else: status, active sets and u* must equal the
