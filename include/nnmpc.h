@@ -365,14 +365,15 @@ int nnmpc_train_dw_slices(nnmpc_train* h, int32_t* slices);
  * padding has zero gradients by construction and must stay exactly zero through updates; this is the check. */
 int nnmpc_train_padding_max(nnmpc_train* h, double* maxabs);
 
-/* ---- A sweep of structured networks trained in lock step  <-  the loop `for (regulator_dim, num_sample) in
+/* ---- A sweep of networks trained in lock step  <-  the loop `for (regulator_dim, num_sample) in
  * itertools.product(regulator_dims, num_samples)` around train_nn_controller (cstrs_train.py / cdu_train.py main): G networks
  * in ONE handle, every layer of every network in one launch (one per tile class present) instead of G.  All members share nx,
  * nu, with_uprev, the depth, max_batch, the Adam parameters and one dataset; they differ in widths, weights, rows, step count
  * and snapshot.  Arithmetic, padding, validation and error codes are nnmpc_train's, and so are the bytes: a member's weights
  * and losses do not depend on the rest of the group and equal what an nnmpc_train handle computes from the same weights and
  * rows (same tile functions, same summation orders, dW slices from the member's own shape).
- * dims: G x (nlayers + 1), member after member; W, b: G x nlayers pointers (b of a member's last layer is ignored).  Replaces
+ * dims: G x (nlayers + 1), member after member; W, b: G x nlayers pointers (b of a member's last layer is ignored: the
+ * structured head has no bias; nnmpc_train_create_group_ex builds the groups whose head has one).  Replaces
  * G calls of nnmpc_train_create.  G < 1, or a member whose dims[0] / dims[L] disagree with nx, nu: NNMPC_EINVAL. */
 typedef struct nnmpc_train_group nnmpc_train_group;
 int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers, const int32_t* dims,
@@ -380,6 +381,18 @@ int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers
                              int32_t with_uprev, int32_t max_batch, double lr, double beta1,
                              double beta2, double eps);
 int nnmpc_train_group_destroy(nnmpc_train_group* h);
+/* The same with the members' form, the values nnmpc_train_create_ex takes: ONE form per group (a sweep that mixes forms is one
+ * group per form, as it is one group per depth)  <-  the loop of cstrs_train.py run with the comparison network of
+ * cstrs_train_unstd.py.  NNMPC_NN_STRUCTURED: nnmpc_train_group_create.  NNMPC_NN_UNSTD / NNMPC_NN_UNSTD_RELU: every member is
+ * the one-pass network of nnmpc_train_create_ex with a bias on the head (and relu on it): b[g * nlayers + nlayers - 1] (nu entries)
+ * is required for every member and is read and written by nnmpc_train_group_get_weights / _set_weights like every other bias; a
+ * lock-step step is 6 nlayers + 2 launches (the head's bias column sums and bias update) against 6 nlayers.  A member's bytes
+ * equal those of an nnmpc_train_create_ex handle of that form.  Every other nnmpc_train_group_* function serves both.  Any other
+ * form, or a member without a head bias in an unstructured form: NNMPC_EINVAL, the message names the member. */
+int nnmpc_train_create_group_ex(nnmpc_train_group** out, int32_t G, int32_t nlayers, const int32_t* dims,
+                                const double* const* W, const double* const* b, int32_t nx, int32_t nu,
+                                int32_t with_uprev, int32_t max_batch, double lr, double beta1,
+                                double beta2, double eps, int32_t form);
 /* The shared dataset, as nnmpc_train_set_data takes it (what _get_data_for_training(num_samples = the largest) hands the
  * sweep; member g then uses rows [0, n_g)).  Replaces G uploads. */
 int nnmpc_train_group_set_data(nnmpc_train_group* h, int32_t n, const double* x,
@@ -396,7 +409,8 @@ int nnmpc_train_group_epoch(nnmpc_train_group* h, const int32_t* nrows, const in
  * of max_batch rows; count[g] == 0: skipped (mse[g] = NaN). */
 int nnmpc_train_group_eval(nnmpc_train_group* h, const int32_t* first, const int32_t* count,
                            double* mse);
-/* Member g's weights as nnmpc_train_get_weights / nnmpc_train_set_weights exchange them. */
+/* Member g's weights as nnmpc_train_get_weights / nnmpc_train_set_weights exchange them: in a group of an unstructured form
+ * b[nlayers - 1] is the head's bias (required by set_weights), in a structured group it is ignored. */
 int nnmpc_train_group_get_weights(nnmpc_train_group* h, int32_t g, double* const* W,
                                   double* const* b);
 int nnmpc_train_group_set_weights(nnmpc_train_group* h, int32_t g, const double* const* W,

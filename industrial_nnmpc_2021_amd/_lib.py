@@ -65,6 +65,7 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_train_group_epoch", "nnmpc_train_group_eval", "nnmpc_train_group_get_weights",
            "nnmpc_train_group_set_weights", "nnmpc_train_group_snapshot", "nnmpc_train_group_restore",
            "nnmpc_train_group_padding_max", "nnmpc_train_group_last_ms", "nnmpc_train_group_last_launches",
+           "nnmpc_train_create_group_ex",
            "nnmpc_chain_create", "nnmpc_chain_destroy", "nnmpc_chain_run", "nnmpc_chain_reset", "nnmpc_chain_last_ms",
            "nnmpc_ts_create", "nnmpc_ts_destroy", "nnmpc_ts_solve_batch",
            "nnmpc_cl_create", "nnmpc_cl_destroy", "nnmpc_cl_run", "nnmpc_cl_reset", "nnmpc_cl_last_ms",
@@ -169,6 +170,8 @@ def load():
     # the sweep in one handle: each entry replaces G calls of the nnmpc_train_* function named beside it
     lib.nnmpc_train_group_create.restype = i32                    # nnmpc_train_create
     lib.nnmpc_train_group_create.argtypes = [C.POINTER(vp), i32, i32, pi32, pdp, pdp, i32, i32, i32, i32, f64, f64, f64, f64]
+    lib.nnmpc_train_create_group_ex.restype = i32                 # nnmpc_train_create_ex: the same with the group's form
+    lib.nnmpc_train_create_group_ex.argtypes = lib.nnmpc_train_group_create.argtypes + [i32]
     lib.nnmpc_train_group_destroy.restype = i32                   # nnmpc_train_destroy
     lib.nnmpc_train_group_destroy.argtypes = [vp]
     lib.nnmpc_train_group_set_data.restype = i32                  # nnmpc_train_set_data (one shared dataset)

@@ -1,10 +1,10 @@
-// A sweep of structured networks trained in lock step for gfx950: the step of nn_train.hip with the member network as a
+// A sweep of networks of one form trained in lock step for gfx950: the step of nn_train.hip with the member network as a
 // grid coordinate, so a layer of G networks is one launch (one per tile class present) instead of G.  This file holds the
 // grouped kernels, their enqueue order, the per-call step table and the nnmpc_train_group_* entry points; a member's
 // layout, padding, uploads, read-backs, the dataset, events and argument checks are nn_train_host.h's, shared with the
 // single-network handle.
 //
-// Members share nx, nu, with_uprev, the depth, max_batch, the Adam hyper-parameters and ONE f32 dataset; they differ in
+// Members share nx, nu, with_uprev, the depth, the form, max_batch, the Adam hyper-parameters and ONE f32 dataset; they differ in
 // widths, weights, rows, Adam step count and snapshot.  In lock-step step k member g works on its batch k (B rows; B = 0:
 // the member has run out of rows, or sits this call out, and every workgroup of its grid plane returns at once).
 //
@@ -13,6 +13,11 @@
 // with the member's own shapes (padding, tile class, dW slices from its own M and tile count); the scalars of a step (Adam
 // bias corrections from the member's own t, loss scales) are computed on the host in double as nn_train.hip computes them
 // and travel in a table uploaded once per call with the row lists.  No atomics, no hand-off between workgroups.
+//
+// The form (NNMPC_NN_*) is one per group and travels by value in GShape, so it is uniform per launch: the unstructured forms
+// gather one row per sample (train_gather_rows1), stack M = train_rows(form, Bp) = Bp rows wherever the structured form stacks
+// 2 Bp, run the head with its bias (and ReLU) in the GEMM epilogue, take pred from the head as it is (train_output1_block) and
+// add the head's bias column sums and bias Adam: 6 L + 2 launches per lock-step step against 6 L.
 //
 // Device tables:  GLayer [G][L] and GMember [G], written at create (pointers, padded K and N);  GStep [steps][G], per call.
 #include "nn_train_host.h"
@@ -27,7 +32,7 @@ struct GStep {                                              // member g in lock-
   float gscale;
   int B, at, pad_;                                          // rows of the batch (0: inactive); position in the row lists, or first dataset row
 };
-struct GShape { int nx, nu, with_uprev, L, force_slices, num_cus; };
+struct GShape { int nx, nu, with_uprev, L, force_slices, num_cus, form; };
 struct GData { const float *x, *uprev, *xs, *us, *u; };
 
 __device__ __forceinline__ int pad128(int B) { return ((B + 127) / 128) * 128; }
@@ -38,11 +43,15 @@ __global__ __launch_bounds__(128) void grp_gather_k(const GLayer* __restrict__ l
   const int g = blockIdx.y, B = st[g].B;
   if (B == 0) return;
   const GLayer& ld = lay[(size_t)g * sh.L];
-  train_gather_rows(ld.ain, ld.K, pad128(B), B, sh.nx, sh.nu, sh.with_uprev, d.x, d.uprev, d.xs, d.us,
-                    rows ? rows + st[g].at : nullptr, st[g].at, blockIdx.x, gridDim.x);
+  if (sh.form == NNMPC_NN_STRUCTURED)
+    train_gather_rows(ld.ain, ld.K, pad128(B), B, sh.nx, sh.nu, sh.with_uprev, d.x, d.uprev, d.xs, d.us,
+                      rows ? rows + st[g].at : nullptr, st[g].at, blockIdx.x, gridDim.x);
+  else
+    train_gather_rows1(ld.ain, ld.K, pad128(B), B, sh.nx, sh.nu, sh.with_uprev, d.x, d.uprev, d.xs, d.us,
+                       rows ? rows + st[g].at : nullptr, st[g].at, blockIdx.x, gridDim.x);
 }
 
-// Layer l forward for the members whose N is in tile class NB.  Grid (max N / NB, max 2 Bp / NB, G); inside a member's own
+// Layer l forward for the members whose N is in tile class NB.  Grid (max N / NB, max M / NB, G); inside a member's own
 // ntn x ntm extent the workgroup id is remapped as gemm_nt_f32_k remaps it (row panels of 8 back to back: a bijection of
 // the extent; which workgroup computes a tile changes no sum).
 template <int NB, bool RELU, bool BIAS>
@@ -52,7 +61,7 @@ __global__ __launch_bounds__(256) void grp_fwd_k(const GLayer* __restrict__ lay,
   if (B == 0) return;
   const GLayer& ld = lay[(size_t)g * sh.L + l];
   if ((ld.N % 128 == 0) != (NB == 128)) return;
-  const int ntn = ld.N / NB, ntm = 2 * pad128(B) / NB;
+  const int ntn = ld.N / NB, ntm = train_rows(sh.form, pad128(B)) / NB;
   if ((int)blockIdx.x >= ntn || (int)blockIdx.y >= ntm) return;
   int tm, tn;
   {
@@ -72,8 +81,12 @@ __global__ __launch_bounds__(256) void grp_output_k(const GLayer* __restrict__ l
   const int Bp = pad128(B);
   if ((int)blockIdx.x * 64 >= Bp) return;
   const GLayer& ld = lay[(size_t)g * sh.L + sh.L - 1];
-  train_output_block(backward ? mem[g].dz[0] : nullptr, ld.aout, ld.N, Bp, B, sh.nu, d.us, d.u,
-                     rows ? rows + st[g].at : nullptr, st[g].at, st[g].gscale, mem[g].partial, blockIdx.x);
+  if (sh.form == NNMPC_NN_STRUCTURED)
+    train_output_block(backward ? mem[g].dz[0] : nullptr, ld.aout, ld.N, Bp, B, sh.nu, d.us, d.u,
+                       rows ? rows + st[g].at : nullptr, st[g].at, st[g].gscale, mem[g].partial, blockIdx.x);
+  else
+    train_output1_block(backward ? mem[g].dz[0] : nullptr, ld.aout, ld.N, B, sh.nu, sh.form == NNMPC_NN_UNSTD_RELU, d.u,
+                        rows ? rows + st[g].at : nullptr, st[g].at, st[g].gscale, mem[g].partial, blockIdx.x);
 }
 
 // Grid (G): one thread per member.
@@ -99,24 +112,24 @@ __global__ __launch_bounds__(256) void grp_dw_k(const GLayer* __restrict__ lay, 
   const GLayer& ld = lay[(size_t)g * sh.L + l];
   if ((ld.N % 128 == 0 && ld.K % 128 == 0) != (NB == 128)) return;
   if ((int)blockIdx.x >= ld.K / NB || (int)blockIdx.y >= ld.N / NB) return;
-  const int M = 2 * pad128(B);
+  const int M = train_rows(sh.form, pad128(B));
   int slice_rows = 0;
   if (s >= layer_slices(ld, sh, M, &slice_rows)) return;
   train_tn_tile<NB>(ld.planes, (size_t)ld.N * ld.K, (size_t)ld.K, mem[g].dz[cur], (size_t)ld.N, ld.ain, (size_t)ld.K, M,
                     slice_rows, blockIdx.x, blockIdx.y, s, lds);
 }
 
-// Grid (max N / 64, max 2 Bp / 128, G).
+// Grid (max N / 64, max M / 128, G).
 __global__ __launch_bounds__(256) void grp_colsum_k(const GLayer* __restrict__ lay, const GMember* __restrict__ mem,
                                                     const GStep* __restrict__ st, GShape sh, int l, int cur) {
   const int g = blockIdx.z, B = st[g].B;
   if (B == 0) return;
   const GLayer& ld = lay[(size_t)g * sh.L + l];
-  if ((int)blockIdx.x >= ld.N / 64 || (int)blockIdx.y >= 2 * pad128(B) / 128) return;
+  if ((int)blockIdx.x >= ld.N / 64 || (int)blockIdx.y >= train_rows(sh.form, pad128(B)) / 128) return;
   train_colsum_block(ld.bplanes, mem[g].dz[cur], ld.N, blockIdx.x, blockIdx.y);
 }
 
-// dZ_{l-1} of layer l for the members whose K is in tile class NB.  Grid (max K / NB, max 2 Bp / NB, G).
+// dZ_{l-1} of layer l for the members whose K is in tile class NB.  Grid (max K / NB, max M / NB, G).
 template <int NB>
 __global__ __launch_bounds__(256) void grp_da_k(const GLayer* __restrict__ lay, const GMember* __restrict__ mem,
                                                 const GStep* __restrict__ st, GShape sh, int l, int cur) {
@@ -125,7 +138,7 @@ __global__ __launch_bounds__(256) void grp_da_k(const GLayer* __restrict__ lay, 
   if (B == 0) return;
   const GLayer& ld = lay[(size_t)g * sh.L + l];
   if ((ld.K % 128 == 0) != (NB == 128)) return;
-  if ((int)blockIdx.x >= ld.K / NB || (int)blockIdx.y >= 2 * pad128(B) / NB) return;
+  if ((int)blockIdx.x >= ld.K / NB || (int)blockIdx.y >= train_rows(sh.form, pad128(B)) / NB) return;
   train_nt_mask_tile<NB>(mem[g].dz[cur ^ 1], (size_t)ld.K, mem[g].dz[cur], (size_t)ld.N, ld.Wk, (size_t)ld.N, ld.N, ld.ain,
                          blockIdx.x, blockIdx.y, lds);
 }
@@ -137,7 +150,7 @@ __global__ __launch_bounds__(256) void grp_adam_w_k(const GLayer* __restrict__ l
   const GLayer& ld = lay[(size_t)g * sh.L + l];
   if ((int)blockIdx.x >= ld.K / 64 || (int)blockIdx.y >= ld.N / 64) return;
   int slice_rows = 0;
-  const int S = layer_slices(ld, sh, 2 * pad128(B), &slice_rows);
+  const int S = layer_slices(ld, sh, train_rows(sh.form, pad128(B)), &slice_rows);
   const AdamCoef k = st[g].k;
   train_adam_w_tile(ld.Wt, ld.Wk, ld.mW, ld.vW, ld.planes, (size_t)ld.N * ld.K, S, ld.K, ld.N, k, blockIdx.x, blockIdx.y);
 }
@@ -149,7 +162,7 @@ __global__ void grp_adam_b_k(const GLayer* __restrict__ lay, const GStep* __rest
   const GLayer& ld = lay[(size_t)g * sh.L + l];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const AdamCoef k = st[g].k;
-  if (i < ld.N) ld.b[i] = adam_entry(plane_sum(ld.bplanes, (size_t)ld.N, 2 * pad128(B) / 128, (size_t)i), ld.mb + i, ld.vb + i, ld.b[i], k);
+  if (i < ld.N) ld.b[i] = adam_entry(plane_sum(ld.bplanes, (size_t)ld.N, train_rows(sh.form, pad128(B)) / 128, (size_t)i), ld.mb + i, ld.vb + i, ld.b[i], k);
 }
 
 }  // namespace
@@ -173,17 +186,27 @@ void launch(nnmpc_train_group* h, void (*k)(P...), dim3 grid, dim3 block, size_t
   hipLaunchKernelGGL(k, grid, block, lds, h->c.stream, args...);
 }
 
+// The forward instance of a layer, as nn_train.hip picks it: relu and bias on the hidden layers; on the head neither
+// (structured), the bias (NNMPC_NN_UNSTD) or both (NNMPC_NN_UNSTD_RELU: the hidden layers' instance).
+template <int NB>
+void launch_fwd(nnmpc_train_group* h, dim3 grid, bool relu, bool bias, const GStep* st, const GShape& sh, int l) {
+  const size_t lds = TileCfg<NB>::LDS_FLOATS * 4;
+  if (relu) launch(h, grp_fwd_k<NB, true, true>, grid, dim3(256), lds, h->dlay, st, sh, l);
+  else if (bias) launch(h, grp_fwd_k<NB, false, true>, grid, dim3(256), lds, h->dlay, st, sh, l);
+  else launch(h, grp_fwd_k<NB, false, false>, grid, dim3(256), lds, h->dlay, st, sh, l);
+}
+
 // One lock-step step on the handle's stream: gather, forward, output, and (backward) the gradient planes and Adam, for
 // the members with host[g].B > 0.  st: this step's row of the device table; rows: the device row lists, or nullptr (eval).
 int enqueue_step(nnmpc_train_group* h, const GStep* host, const GStep* st, const int* rows, bool backward, size_t set) {
   TrainCommon& c = h->c;
   const int G = h->G, L = c.L;
-  const GShape sh{c.nx, c.nu, c.with_uprev, L, c.force_slices, c.num_cus};
+  const GShape sh{c.nx, c.nu, c.with_uprev, L, c.force_slices, c.num_cus, c.form};
   const GData d{c.dx, c.dup, c.dxs, c.dus, c.du};
   int Bpmax = 0;
   for (int g = 0; g < G; ++g) Bpmax = std::max(Bpmax, pad128_host(host[g].B));
   if (Bpmax == 0) return NNMPC_OK;
-  const int Mmax = 2 * Bpmax;
+  const int Mmax = train_rows(c.form, Bpmax);
   EvSet e;
   if (int rc = ev_set(c, set, &e)) return rc;
   struct Ext { int n = 0, k = 0, s = 0; };                  // largest extents of a tile class (0: 64, 1: 128) among the active members; 0: class absent
@@ -193,17 +216,9 @@ int enqueue_step(nnmpc_train_group* h, const GStep* host, const GStep* st, const
     int nmax[2] = {0, 0};
     for (int g = 0; g < G; ++g)
       if (host[g].B) { const int N = h->m[g].npad[l]; int& x = nmax[N % 128 == 0]; x = std::max(x, N); }
-    const bool last = l == L - 1;
-    if (nmax[1]) {
-      const dim3 grid(nmax[1] / 128, Mmax / 128, G);
-      if (last) launch(h, grp_fwd_k<128, false, false>, grid, dim3(256), TileCfg<128>::LDS_FLOATS * 4, h->dlay, st, sh, l);
-      else launch(h, grp_fwd_k<128, true, true>, grid, dim3(256), TileCfg<128>::LDS_FLOATS * 4, h->dlay, st, sh, l);
-    }
-    if (nmax[0]) {
-      const dim3 grid(nmax[0] / 64, Mmax / 64, G);
-      if (last) launch(h, grp_fwd_k<64, false, false>, grid, dim3(256), TileCfg<64>::LDS_FLOATS * 4, h->dlay, st, sh, l);
-      else launch(h, grp_fwd_k<64, true, true>, grid, dim3(256), TileCfg<64>::LDS_FLOATS * 4, h->dlay, st, sh, l);
-    }
+    const bool last = l == L - 1, relu = !last || c.form == NNMPC_NN_UNSTD_RELU;
+    if (nmax[1]) launch_fwd<128>(h, dim3(nmax[1] / 128, Mmax / 128, G), relu, has_bias(c.form, L, l), st, sh, l);
+    if (nmax[0]) launch_fwd<64>(h, dim3(nmax[0] / 64, Mmax / 64, G), relu, has_bias(c.form, L, l), st, sh, l);
   }
   hipEventRecord(e.f1, c.stream);
   launch(h, grp_output_k, dim3(Bpmax / 64, G), dim3(256), 0, h->dlay, h->dmem, st, sh, d, rows, backward ? 1 : 0);
@@ -220,7 +235,7 @@ int enqueue_step(nnmpc_train_group* h, const GStep* host, const GStep* st, const
         const int K = mb.kpad[l], N = mb.npad[l];
         const int big = N % 128 == 0 && K % 128 == 0;
         int slice_rows = 0;
-        const int S = member_slices(c, mb, l, 2 * pad128_host(host[g].B), &slice_rows);
+        const int S = member_slices(c, mb, l, train_rows(c.form, pad128_host(host[g].B)), &slice_rows);
         if (S > mb.max_slices[l]) { set_error("nnmpc_train_group: %d dW slices for layer %d of member %d, planes for %d", S, l, g, mb.max_slices[l]); return NNMPC_EINVAL; }
         dw[big].n = std::max(dw[big].n, N); dw[big].k = std::max(dw[big].k, K); dw[big].s = std::max(dw[big].s, S);
         Ext& a = da[K % 128 == 0];
@@ -231,7 +246,7 @@ int enqueue_step(nnmpc_train_group* h, const GStep* host, const GStep* st, const
                           h->dlay, h->dmem, st, sh, l, cur, dw[1].s);
       if (dw[0].s) launch(h, grp_dw_k<64>, dim3(dw[0].k / 64, dw[0].n / 64, G * dw[0].s), dim3(256), TileCfgTN<64>::LDS_FLOATS * 4,
                           h->dlay, h->dmem, st, sh, l, cur, dw[0].s);
-      if (l < L - 1) launch(h, grp_colsum_k, dim3(nall / 64, Mmax / 128, G), dim3(256), 0, h->dlay, h->dmem, st, sh, l, cur);
+      if (has_bias(c.form, L, l)) launch(h, grp_colsum_k, dim3(nall / 64, Mmax / 128, G), dim3(256), 0, h->dlay, h->dmem, st, sh, l, cur);
       if (l > 0) {
         if (da[1].k) launch(h, grp_da_k<128>, dim3(da[1].k / 128, Mmax / 128, G), dim3(256), TileCfg<128>::LDS_FLOATS * 4,
                             h->dlay, h->dmem, st, sh, l, cur);
@@ -248,7 +263,7 @@ int enqueue_step(nnmpc_train_group* h, const GStep* host, const GStep* st, const
       for (int g = 0; g < G; ++g)
         if (host[g].B) { nall = std::max(nall, h->m[g].npad[l]); kall = std::max(kall, h->m[g].kpad[l]); }
       launch(h, grp_adam_w_k, dim3(kall / 64, nall / 64, G), dim3(256), 0, h->dlay, st, sh, l);
-      if (l < L - 1) launch(h, grp_adam_b_k, dim3((nall + 255) / 256, G), dim3(256), 0, h->dlay, st, sh, l);
+      if (has_bias(c.form, L, l)) launch(h, grp_adam_b_k, dim3((nall + 255) / 256, G), dim3(256), 0, h->dlay, st, sh, l);
     }
   return NNMPC_OK;
 }
@@ -285,27 +300,30 @@ int nnmpc_train_group_destroy(nnmpc_train_group* h) {
   return NNMPC_OK;
 }
 
-int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers, const int32_t* dims, const double* const* W,
-                             const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev, int32_t max_batch,
-                             double lr, double beta1, double beta2, double eps) {
+// Both create entry points; `who` is the one that was called.
+static int group_create(const char* who, nnmpc_train_group** out, int32_t G, int32_t nlayers, const int32_t* dims,
+                        const double* const* W, const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev,
+                        int32_t max_batch, double lr, double beta1, double beta2, double eps, int32_t form) {
   GUARD_BEGIN
-  if (!out || nlayers < 1 || !dims || !W || !b || nx <= 0 || nu <= 0 || max_batch < 1) { set_error("nnmpc_train_group_create: bad arguments"); return NNMPC_EINVAL; }
-  if (G < 1) { set_error("nnmpc_train_group_create: a group of %d networks", G); return NNMPC_EINVAL; }
+  if (!out || nlayers < 1 || !dims || !W || !b || nx <= 0 || nu <= 0 || max_batch < 1) { set_error("%s: bad arguments", who); return NNMPC_EINVAL; }
+  if (G < 1) { set_error("%s: a group of %d networks", who, G); return NNMPC_EINVAL; }
+  if (int rc = check_form(who, form)) return rc;
   const int L = nlayers;
   for (int g = 0; g < G; ++g) {
     char mem[32];
     snprintf(mem, sizeof mem, "member %d: ", g);
-    if (int rc = check_network(__func__, mem, L, dims + (size_t)g * (L + 1), W + (size_t)g * L, b + (size_t)g * L, nx, nu, with_uprev, NNMPC_NN_STRUCTURED)) return rc;
+    if (int rc = check_network(who, mem, L, dims + (size_t)g * (L + 1), W + (size_t)g * L, b + (size_t)g * L, nx, nu, with_uprev, form)) return rc;
   }
-  if (int rc = check_adam(__func__, lr, beta1, beta2, eps)) return rc;
-  if (int rc = check_device(__func__)) return rc;
+  if (int rc = check_adam(who, lr, beta1, beta2, eps)) return rc;
+  if (int rc = check_device(who)) return rc;
   Building<nnmpc_train_group, nnmpc_train_group_destroy> guard(new nnmpc_train_group());
   nnmpc_train_group* h = guard.get();
   TrainCommon& c = h->c;
-  if (int rc = common_init(__func__, c, L, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, NNMPC_NN_STRUCTURED)) return rc;
+  if (int rc = common_init(who, c, L, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form)) return rc;
   h->G = G;
   HIPCHK(hipFuncSetAttribute((const void*)grp_fwd_k<128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)grp_fwd_k<128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+  HIPCHK(hipFuncSetAttribute((const void*)grp_fwd_k<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));   // the unstructured linear head
   HIPCHK(hipFuncSetAttribute((const void*)grp_da_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)grp_dw_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfgTN<128>::LDS_FLOATS * 4));
   h->m.resize(G);
@@ -315,7 +333,7 @@ int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers
     member_shapes(c, mb, dims + (size_t)g * (L + 1));
     bytes = layout_member(c, mb, nullptr, bytes);
     for (int S : mb.max_slices)                             // the dW grid carries member x slice in z
-      if ((int64_t)G * S > 65535) { set_error("nnmpc_train_group_create: %d members x %d dW slices exceed a grid's z extent", G, S); return NNMPC_EINVAL; }
+      if ((int64_t)G * S > 65535) { set_error("%s: %d members x %d dW slices exceed a grid's z extent", who, G, S); return NNMPC_EINVAL; }
   }
   if (int rc = c.res.alloc(&h->arena, bytes)) return rc;
   if (int rc = c.res.alloc(&h->dacc, (size_t)G)) return rc;
@@ -335,6 +353,18 @@ int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers
   *out = guard.release();
   return NNMPC_OK;
   GUARD_END
+}
+
+int nnmpc_train_group_create(nnmpc_train_group** out, int32_t G, int32_t nlayers, const int32_t* dims, const double* const* W,
+                             const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev, int32_t max_batch,
+                             double lr, double beta1, double beta2, double eps) {
+  return group_create(__func__, out, G, nlayers, dims, W, b, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, NNMPC_NN_STRUCTURED);
+}
+
+int nnmpc_train_create_group_ex(nnmpc_train_group** out, int32_t G, int32_t nlayers, const int32_t* dims, const double* const* W,
+                                const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev, int32_t max_batch,
+                                double lr, double beta1, double beta2, double eps, int32_t form) {
+  return group_create(__func__, out, G, nlayers, dims, W, b, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form);
 }
 
 int nnmpc_train_group_set_data(nnmpc_train_group* h, int32_t n, const double* x, const double* uprev, const double* xs,

@@ -15,7 +15,8 @@ backward, Adam, the epoch loop -- in f32 on hand-written gfx950 kernels
 trained weights.  ``train_nn_controllers`` trains a whole sweep of networks in
 one lock-step launch group (csrc/nn_train_group.hip, ``HipGroupTrainer``).
 ``train_unstd_nn_controller`` trains the reference's unstructured comparison
-network (``cstrs_train_unstd.py``) on the one-pass form of the single-network step.
+network (``cstrs_train_unstd.py``) on the one-pass form of the single-network step,
+``train_unstd_nn_controllers`` a sweep of them in one launch group of that form.
 """
 import copy
 import ctypes as C
@@ -86,7 +87,8 @@ class UnstdRegulatorModel(torch.nn.Module):
     ``head_relu``: the Keras layer builds every Dense with activation='relu', the output one included (:147-148), while the
     numpy controller that runs the trained weights ends in a linear head (lib/controller_evaluation.py:907-908).  True
     (the default) is the Keras code as written, False the controller's form.  Trains natively through
-    ``train_unstd_nn_controller`` (the one-pass form of the HIP step, one network per handle) or in stock PyTorch
+    ``train_unstd_nn_controller`` (the one-pass form of the HIP step, one network per handle),
+    ``train_unstd_nn_controllers`` (a sweep in one launch group) or in stock PyTorch
     through ``train_nn_controller(backend="torch")``; ``backend="hip"`` of the structured entry points refuses it."""
 
     unstructured = True
@@ -131,8 +133,8 @@ def _refuse_unstructured(model, who):
     the unstructured weight list."""
     if getattr(model, "unstructured", False):
         raise ValueError(f"{who}: this entry point runs the structured form of the native HIP training step; train an "
-                         "UnstdRegulatorModel natively with train_unstd_nn_controller, or "
-                         "through stock PyTorch with train_nn_controller(..., backend=\"torch\")")
+                         "UnstdRegulatorModel natively with train_unstd_nn_controller (a sweep of them with "
+                         "train_unstd_nn_controllers), or through stock PyTorch with train_nn_controller(..., backend=\"torch\")")
 
 
 def _unstd_form(model, who):
@@ -320,18 +322,21 @@ class HipGroupTrainer:
     members share nx, nu, nnwithuprev, the depth, max_batch, Adam's parameters and one dataset, of which each uses the rows
     it is given.  A member's weights and losses are, byte for byte, those of a ``HipTrainer`` fed the same rows.
 
+    ``form``: one per group, the values ``HipTrainer`` takes.  ``_lib.NN_STRUCTURED`` (the default): every list ends in
+    Wout.  ``_lib.NN_UNSTD`` / ``_lib.NN_UNSTD_RELU``: every member is the one-pass network with a bias (and relu) on the
+    head, the lists are [W1, b1, ..., WL, bL] and ``get_weights`` / ``set_weights`` exchange that list.
+
     No device: ``_lib.NnmpcError`` (no CPU fallback)."""
 
-    def __init__(self, weights, nx, nu, *, nnwithuprev=True, max_batch=2048, lr=1e-3, betas=(0.9, 0.999), eps=1e-7):
+    def __init__(self, weights, nx, nu, *, nnwithuprev=True, max_batch=2048, lr=1e-3, betas=(0.9, 0.999), eps=1e-7,
+                 form=_lib.NN_STRUCTURED):
+        self.form = _check_form(form)
         lib = _lib.load()
         self.G = len(weights)
         Ws, bs, self.dims = [], [], []
         for w in weights:
-            Wg = [np.ascontiguousarray(a, np.float64) for a in w[0:-1:2]] + [np.ascontiguousarray(w[-1], np.float64)]
-            bg = [np.ascontiguousarray(a, np.float64).ravel() for a in w[1::2]]
-            if len(bg) != len(Wg) - 1:
-                raise ValueError("weights must be [W1, b1, ..., W_{L-1}, b_{L-1}, Wout]")
-            Ws.append(Wg); bs.append(bg + [None])
+            Wg, bg = _split_keras(w, self.form)
+            Ws.append(Wg); bs.append(bg)
             self.dims.append([Wg[0].shape[0]] + [a.shape[1] for a in Wg])
         L = len(Ws[0]) if Ws else 1
         if any(len(Wg) != L for Wg in Ws):
@@ -340,11 +345,11 @@ class HipGroupTrainer:
         self.max_batch = int(max_batch)
         self._lib, self._h = lib, C.c_void_p()
         flat = lambda ll: [a for l in ll for a in l]
-        _lib.check(lib.nnmpc_train_group_create(C.byref(self._h), self.G, L,
-                                                (C.c_int32 * max(1, self.G * (L + 1)))(*flat(self.dims)),
-                                                HipTrainer._plist(flat(Ws)), HipTrainer._plist(flat(bs)), nx, nu,
-                                                int(self.nnwithuprev), self.max_batch, lr, betas[0], betas[1], eps),
-                   "nnmpc_train_group_create")
+        _lib.check(lib.nnmpc_train_create_group_ex(C.byref(self._h), self.G, L,
+                                                   (C.c_int32 * max(1, self.G * (L + 1)))(*flat(self.dims)),
+                                                   HipTrainer._plist(flat(Ws)), HipTrainer._plist(flat(bs)), nx, nu,
+                                                   int(self.nnwithuprev), self.max_batch, lr, betas[0], betas[1], eps,
+                                                   self.form), "nnmpc_train_create_group_ex")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -404,22 +409,21 @@ class HipGroupTrainer:
         return [float(v) for v in mse[:self.G]]
 
     def _empty(self, g):
-        d = self.dims[g]
-        return [np.empty((d[l], d[l + 1])) for l in range(self.L)], [np.empty(d[l + 1]) for l in range(self.L - 1)]
+        return HipTrainer._empty_for(self.dims[g], self.form)
 
     def get_weights(self, g):
+        """Member g's Keras list of the group's form."""
         Ws, bs = self._empty(g)
         _lib.check(self._lib.nnmpc_train_group_get_weights(self._h, int(g), HipTrainer._plist(Ws),
-                                                           HipTrainer._plist(bs + [None])), "nnmpc_train_group_get_weights")
+                                                           HipTrainer._plist(bs)), "nnmpc_train_group_get_weights")
         return HipTrainer._keras(Ws, bs)
 
     def set_weights(self, g, weights):
-        Ws = [np.ascontiguousarray(w, np.float64) for w in weights[0:-1:2]] + [np.ascontiguousarray(weights[-1], np.float64)]
-        bs = [np.ascontiguousarray(b, np.float64).ravel() for b in weights[1::2]]
-        if [Ws[0].shape[0]] + [w.shape[1] for w in Ws] != self.dims[g] or len(bs) != self.L - 1:
+        Ws, bs = _split_keras(weights, self.form)
+        if [Ws[0].shape[0]] + [w.shape[1] for w in Ws] != self.dims[g]:
             raise ValueError("set_weights: shapes differ from the member's")
         _lib.check(self._lib.nnmpc_train_group_set_weights(self._h, int(g), HipTrainer._plist(Ws),
-                                                           HipTrainer._plist(bs + [None])), "nnmpc_train_group_set_weights")
+                                                           HipTrainer._plist(bs)), "nnmpc_train_group_set_weights")
 
     def snapshot(self, mask):
         m = self._i32([1 if v else 0 for v in mask], "snapshot")
@@ -447,44 +451,30 @@ class HipGroupTrainer:
         return m.value
 
 
-def train_nn_controllers(models, data, *, num_samples=None, epochs=1500, batch_size=2048, validation_split=0.05,
-                         lr=1e-3, seed=1, log=None, backend="hip"):
-    """``train_nn_controller`` for a sweep: member i is ``models[i]`` trained on the first ``num_samples[i]`` rows of
-    ``data`` (default: all), which is what the reference's loop over ``itertools.product(regulator_dims, num_samples)``
-    hands each of its calls.  Keras semantics per member: the last ``int(n_i * validation_split)`` of its rows are its
-    validation set, the rest is reshuffled every epoch by the member's own ``np.random.default_rng(seed)`` -- the row
-    order a separate ``train_nn_controller(..., backend="hip", seed=seed)`` would give it -- and the weights of its best
-    validation epoch are restored at the end.  Returns (models, training_time, hists), hists[i] as that call's history.
-
-    ``backend="hip"``: one ``HipGroupTrainer``, all members in lock step; the models must agree in Nx, Nu, nnwithuprev
-    and depth (``ValueError`` otherwise; build one group per depth).  ``backend="torch"``: a loop over
-    ``train_nn_controller``."""
+def _sweep_args(who, models, data, num_samples, backend):
+    """The checks train_nn_controllers and train_unstd_nn_controllers share (host only): (models, rows per member)."""
     models = list(models)
     if backend not in ("hip", "torch"):
         raise ValueError(f"unknown backend {backend!r}: 'torch' or 'hip'")
     if not models:
-        raise ValueError("train_nn_controllers: no models")
+        raise ValueError(f"{who}: no models")
     n = int(np.asarray(data["x"]).shape[0])
     ns = [n] * len(models) if num_samples is None else [int(v) for v in num_samples]
     if len(ns) != len(models) or any(v < 1 or v > n for v in ns):
         raise ValueError(f"num_samples: one entry per model, each in [1, {n}]")
-    if backend == "torch":
-        t0, hists = time.time(), []
-        for i, m in enumerate(models):
-            part = {k: (None if data.get(k) is None else np.asarray(data[k])[:ns[i]]) for k in ("x", "uprev", "xs", "us", "u")}
-            models[i], _, h = train_nn_controller(m, part, epochs=epochs, batch_size=batch_size,
-                                                  validation_split=validation_split, lr=lr, seed=seed, log=log)
-            hists.append(h)
-        return models, time.time() - t0, hists
-    for m in models:
-        _refuse_unstructured(m, "train_nn_controllers(backend=\"hip\")")
-    m0 = models[0]
-    for m in models[1:]:
-        if (m.Nx, m.Nu, bool(m.nnwithuprev), len(m.layers)) != (m0.Nx, m0.Nu, bool(m0.nnwithuprev), len(m0.layers)):
-            raise ValueError("train_nn_controllers: the models of a group agree in Nx, Nu, nnwithuprev and depth")
-    G = len(models)
+    return models, ns
+
+
+def _first_rows(data, n):
+    return {k: (None if data.get(k) is None else np.asarray(data[k])[:n]) for k in ("x", "uprev", "xs", "us", "u")}
+
+
+def _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr, seed, log, form=_lib.NN_STRUCTURED):
+    """The "hip" backend of train_nn_controllers / train_unstd_nn_controllers: one ``HipGroupTrainer`` of ``form``, the
+    epoch loop of ``_train_hip`` for every member at once (own rows, own generator, own best epoch)."""
+    m0, G = models[0], len(models)
     tr = HipGroupTrainer([m.get_weights() for m in models], m0.Nx, m0.Nu, nnwithuprev=m0.nnwithuprev,
-                         max_batch=batch_size, lr=lr, eps=1e-7)
+                         max_batch=batch_size, lr=lr, eps=1e-7, form=form)
     try:
         tr.set_data(data)
         nval = [int(v * validation_split) for v in ns]
@@ -514,6 +504,64 @@ def train_nn_controllers(models, data, *, num_samples=None, epochs=1500, batch_s
     finally:
         tr.close()
     return models, ttime, hists
+
+
+def train_nn_controllers(models, data, *, num_samples=None, epochs=1500, batch_size=2048, validation_split=0.05,
+                         lr=1e-3, seed=1, log=None, backend="hip"):
+    """``train_nn_controller`` for a sweep: member i is ``models[i]`` trained on the first ``num_samples[i]`` rows of
+    ``data`` (default: all), which is what the reference's loop over ``itertools.product(regulator_dims, num_samples)``
+    hands each of its calls.  Keras semantics per member: the last ``int(n_i * validation_split)`` of its rows are its
+    validation set, the rest is reshuffled every epoch by the member's own ``np.random.default_rng(seed)`` -- the row
+    order a separate ``train_nn_controller(..., backend="hip", seed=seed)`` would give it -- and the weights of its best
+    validation epoch are restored at the end.  Returns (models, training_time, hists), hists[i] as that call's history.
+
+    ``backend="hip"``: one ``HipGroupTrainer``, all members in lock step; the models must agree in Nx, Nu, nnwithuprev
+    and depth (``ValueError`` otherwise; build one group per depth), and an ``UnstdRegulatorModel`` is refused: its sweep
+    is ``train_unstd_nn_controllers``.  ``backend="torch"``: a loop over ``train_nn_controller``."""
+    models, ns = _sweep_args("train_nn_controllers", models, data, num_samples, backend)
+    if backend == "torch":
+        t0, hists = time.time(), []
+        for i, m in enumerate(models):
+            models[i], _, h = train_nn_controller(m, _first_rows(data, ns[i]), epochs=epochs, batch_size=batch_size,
+                                                  validation_split=validation_split, lr=lr, seed=seed, log=log)
+            hists.append(h)
+        return models, time.time() - t0, hists
+    for m in models:
+        _refuse_unstructured(m, "train_nn_controllers(backend=\"hip\")")
+    m0 = models[0]
+    for m in models[1:]:
+        if (m.Nx, m.Nu, bool(m.nnwithuprev), len(m.layers)) != (m0.Nx, m0.Nu, bool(m0.nnwithuprev), len(m0.layers)):
+            raise ValueError("train_nn_controllers: the models of a group agree in Nx, Nu, nnwithuprev and depth")
+    return _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr, seed, log)
+
+
+def train_unstd_nn_controllers(models, data, *, num_samples=None, epochs=2000, batch_size=1024, validation_split=0.1,
+                               lr=1e-3, seed=1, log=None, backend="hip"):
+    """``train_unstd_nn_controller`` for a sweep, with the semantics of ``train_nn_controllers`` and the defaults of
+    ``cstrs_train_unstd.py``: member i is the ``UnstdRegulatorModel`` ``models[i]`` trained on the first
+    ``num_samples[i]`` rows of ``data`` (default: all), validated on the last ``int(n_i * validation_split)`` of them,
+    shuffled by its own ``np.random.default_rng(seed)``, and comes back with the weights of its own best validation epoch.
+    Weights and histories are, byte for byte, those of a separate ``train_unstd_nn_controller(..., backend="hip",
+    seed=seed)`` on those rows.  Returns (models, training_time, hists).
+
+    ``backend="hip"``: one ``HipGroupTrainer`` of the models' form; they must agree in Nx, Nu, nnwithuprev, depth and
+    ``head_relu`` (a group has one form; ``ValueError`` otherwise, as for a structured model, before the library is
+    loaded).  ``backend="torch"``: a loop over ``train_unstd_nn_controller(backend="torch")``."""
+    models, ns = _sweep_args("train_unstd_nn_controllers", models, data, num_samples, backend)
+    forms = [_unstd_form(m, "train_unstd_nn_controllers") for m in models]
+    m0 = models[0]
+    for m in models[1:]:
+        if (m.Nx, m.Nu, bool(m.nnwithuprev), len(m.layers), m.head_relu) != (m0.Nx, m0.Nu, bool(m0.nnwithuprev), len(m0.layers), m0.head_relu):
+            raise ValueError("train_unstd_nn_controllers: the models of a group agree in Nx, Nu, nnwithuprev, depth and head_relu")
+    if backend == "torch":
+        t0, hists = time.time(), []
+        for i, m in enumerate(models):
+            models[i], _, h = train_unstd_nn_controller(m, _first_rows(data, ns[i]), epochs=epochs, batch_size=batch_size,
+                                                        validation_split=validation_split, lr=lr, seed=seed, log=log,
+                                                        backend="torch")
+            hists.append(h)
+        return models, time.time() - t0, hists
+    return _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr, seed, log, forms[0])
 
 
 def _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log, form=_lib.NN_STRUCTURED):

@@ -33,6 +33,10 @@ and prints one JSON line per way: ms per sweep epoch (min / median / max over th
 time, the launches per lock-step step and the fraction of the f32 MFMA peak on the sweep's own flop count.
 
     python scripts/train_bench.py --sweep cstrs [--epochs 5] [--repeats 5] [--ways loop,group]
+
+--sweep cstrs --unstd [--head linear|relu] times the same 48-member grid with the unstructured comparison network
+(UnstdRegulatorModel [36, w, w, w, 6], one pass, a bias on the head): "loop" is 48 HipTrainer(form=...), "group" one
+HipGroupTrainer(form=...); the flop count is the one-pass one.
 """
 import argparse
 import json
@@ -136,26 +140,33 @@ SWEEPS = {
 }
 
 
-def run_sweep(name, epochs, repeats, ways):
+def run_sweep(name, epochs, repeats, ways, unstd=None):
+    """unstd = "linear" | "relu": the sweep's grid with the unstructured network of that head, through form=."""
     import itertools
     import time
-    from industrial_nnmpc_2021_amd.train import HipGroupTrainer, HipTrainer, RegulatorModel, group_schedule
+    from industrial_nnmpc_2021_amd import _lib
+    from industrial_nnmpc_2021_amd.train import HipGroupTrainer, HipTrainer, RegulatorModel, UnstdRegulatorModel, group_schedule
     sw = SWEEPS[name]
     uprev, batch, vs = sw["uprev"], sw["batch"], sw["validation_split"]
     members = list(itertools.product(sw["dims"], sw["rows"]))                 # the reference's loop order
     nx, nu = geometry(members[0][0], uprev)
     data = synthetic(max(sw["rows"]), nx, nu)
-    weights = [RegulatorModel(nx, nu, d, nnwithuprev=uprev).get_weights() for d, _ in members]
+    if unstd:
+        form, passes = (_lib.NN_UNSTD_RELU if unstd == "relu" else _lib.NN_UNSTD), 1
+        weights = [UnstdRegulatorModel(nx, nu, d, nnwithuprev=uprev, head_relu=unstd == "relu").get_weights() for d, _ in members]
+    else:
+        form, passes = _lib.NN_STRUCTURED, 2
+        weights = [RegulatorModel(nx, nu, d, nnwithuprev=uprev).get_weights() for d, _ in members]
     nval = [int(n * vs) for _, n in members]
     ntr = [n - v for (_, n), v in zip(members, nval)]
     sched = group_schedule(ntr, batch)
-    flop = sum(step_flop(d, B) for (d, _), s in zip(members, sched) for B in s)
-    common = dict(sweep=name, members=len(members), batch=batch, epochs=epochs, repeats=repeats,
+    flop = sum(step_flop(d, B, passes) for (d, _), s in zip(members, sched) for B in s)
+    common = dict(sweep=name, form=("unstd_" + unstd) if unstd else "structured", members=len(members), batch=batch, epochs=epochs, repeats=repeats,
                   member_steps_per_epoch=sum(len(s) for s in sched), lockstep_steps_per_epoch=max(len(s) for s in sched))
     if "loop" in ways:
         runs = [0.0] * repeats
         for (d, n), w, a, v in zip(members, weights, ntr, nval):
-            tr = HipTrainer(w, nx, nu, nnwithuprev=uprev, max_batch=batch)
+            tr = HipTrainer(w, nx, nu, nnwithuprev=uprev, max_batch=batch, form=form)
             tr.set_data({k: x[:n] for k, x in data.items()})
             rng = np.random.default_rng(1)
             tr.epoch(rng.permutation(a), batch)                               # warm-up
@@ -169,7 +180,7 @@ def run_sweep(name, epochs, repeats, ways):
             tr.close()
         print(json.dumps(dict(common, way="loop", epoch_ms=spread([1e3 * t / epochs for t in runs]))), flush=True)
     if "group" in ways:
-        tr = HipGroupTrainer(weights, nx, nu, nnwithuprev=uprev, max_batch=batch)
+        tr = HipGroupTrainer(weights, nx, nu, nnwithuprev=uprev, max_batch=batch, form=form)
         tr.set_data(data)
         rngs = [np.random.default_rng(1) for _ in members]
         tr.epoch([g.permutation(a) for g, a in zip(rngs, ntr)], batch)        # warm-up
@@ -203,14 +214,14 @@ def main():
     ap.add_argument("--paths", default="torch64,torch32,hip")
     ap.add_argument("--shapes", default="cdu,small")
     ap.add_argument("--validation-split", type=float, default=0.05)
-    ap.add_argument("--unstd", action="store_true", help="the unstructured network through the same three paths")
+    ap.add_argument("--unstd", action="store_true", help="the unstructured network through the same three paths (with --sweep: both ways)")
     ap.add_argument("--head", default="relu", choices=("linear", "relu"), help="with --unstd: the head's form")
     ap.add_argument("--sweep", default="", help="cstrs or cdu: time the whole sweep, looped and grouped, instead of the shapes")
     ap.add_argument("--ways", default="loop,group")
     a = ap.parse_args()
     if a.sweep:
         for name in a.sweep.split(","):
-            run_sweep(name, a.epochs, a.repeats, a.ways.split(","))
+            run_sweep(name, a.epochs, a.repeats, a.ways.split(","), a.head if a.unstd else None)
         return
     for sname in a.shapes.split(","):
         dims, uprev = SHAPES[sname]
