@@ -181,7 +181,12 @@ int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const doub
  * iteration needs no n^3 factorisation.  The inverse is verified once on the device (|P Pinv - I|,
  * |P Kunc + tq|); those bounds certify each result's KKT residual and multiplier signs, results too
  * close to call are re-checked against P itself in fp64, and problems the pass cannot finish go
- * through the PDIP path. */
+ * through the PDIP path.  A pair with |P Pinv - I|_max >= 1e-6 (or a NaN in P Kunc + tq) is refused.
+ * The call may be repeated on a live handle.  Whatever was derived from the previous pair goes when it starts: an ACCEPTED
+ * call releases every far-field factorisation (nnmpc_qp_set_farfield: they were verified against the previous inverse) and
+ * queues their windows in nnmpc_qp_farfield_missing again; a REFUSED call leaves the handle without an inverse, without
+ * far-field factors and without predictor images -- it solves by the PDIP path alone until a later call is accepted (the
+ * statistics keep the refused pair's asm_e1max / asm_e2max). */
 int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc);
 
 /* Far-field form of the full-width pass.  A problem whose active set lies inside the leading W variables (the column
@@ -192,7 +197,8 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc);
  * function of the state at the window's end.  With M = U [Vx | Vl] (r columns; e.g. a truncated SVD, U = U_r S_r) the pass
  * costs 2 r (n_aug + W + n - W) instead of 2 (n_aug + W)(n - W) flops per problem.  U: (n - W) x r, Vx: r x n_aug,
  * Vl: r x W, host, row-major.  The library verifies the factors on the device (max |U [Vx | Vl] - M|, refused above 1e-9,
- * and that bound enters every certificate that rests on them).  W must be a multiple of 128 below n; several windows
+ * and that bound enters every certificate that rests on them; a problem that bound cannot certify gets its far variables
+ * again from Hinv itself, and those -- the ones the check with P then sees -- are the ones delivered).  W must be a multiple of 128 below n; several windows
  * may be set.  Trailing exact zeros in the rows of U shorten the work: a 128-column tile of the pass only multiplies the
  * leading columns of U that any of its rows uses (a basis ordered so that far tiles need few coordinates -- a staircase --
  * pays: the closed loop forgets its fast modes first).  First-move calls (NNMPC_OUT_FIRST_MOVE) additionally skip the

@@ -1709,6 +1709,9 @@ __global__ __launch_bounds__(256) void asm_wide_k(AsmDev d, int fused_c0) {
         x = xu - a0;
       }
       d.x[o + r] = x;
+      // ... and it is what the caller gets: beyond the window a far-field pass wrote the FACTORED product to u_out, off by up to
+      // max|U V' - M| (|x0|_1 + |lam|_1) per entry, which the check with P of d.x would not cover
+      if (r < d.nout) d.u_out[(size_t)p * d.ldu + r] = x;
     }
   }
   for (int i = lane; i < m; i += 64) d.lam[orow + idx[i]] = 0.0;   // the row of LAM goes back to zero

@@ -2032,6 +2032,18 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
     set_error("nnmpc_qp_set_inverse: n = %d is too large for the active-set pass (n < 23168)", n);
     return NNMPC_EINVAL;
   }
+  // From here on the device copies of the previous pair are overwritten: the handle has no inverse until this pair has passed the
+  // check below (a refused call leaves it to the PDIP path), and what was derived from the previous pair goes with it -- the
+  // far-field factors and their verified error (their windows are asked for again once the new pair is in), the predictor images.
+  HIPCHK(stream_sync(h->stream));
+  h->have_inverse = false;
+  h->pred[0].L = h->pred[1].L = 0.0;
+  std::vector<int> refactor;
+  for (auto& g : h->far) {
+    for (void* p : {(void*)g.U, (void*)g.Vx, (void*)g.Vl, (void*)g.cu, (void*)g.kt}) h->res.give_back(p);
+    refactor.push_back(g.W);
+  }
+  h->far.clear();
   std::vector<double> hh((size_t)np * np, 0.0), kk((size_t)np * ka, 0.0);
   for (int r = 0; r < n; ++r) {
     for (int c = 0; c < n; ++c) hh[(size_t)r * np + c] = 0.5 * (Hinv[(size_t)r * n + c] + Hinv[(size_t)c * n + r]);
@@ -2092,9 +2104,12 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
     h->asm_e1max = e1; h->asm_e2max = e2;
     if (!(e2 < 1e-6) || !(e1 == e1)) {
       set_error("nnmpc_qp_set_inverse: |P Pinv - I|_max = %.3e: the supplied inverse is not usable", e2);
+      h->pred[0].L = h->pred[1].L = 0.0;                    // (images of the refused pair)
       return NNMPC_EINVAL;
     }
   }
+  for (int W : refactor)
+    if (h->far_missing.size() < 16 && std::find(h->far_missing.begin(), h->far_missing.end(), W) == h->far_missing.end()) h->far_missing.push_back(W);
   h->have_inverse = true;
   return NNMPC_OK;
   GUARD_END

@@ -143,6 +143,25 @@ class BatchedBoxQP:
 
     __del__ = close
 
+    def set_inverse(self, Hinv, Kunc):
+        """Replace the inverse (nnmpc_qp_set_inverse on a live handle).  The library drops every far-field factorisation -- they were
+        verified against the previous inverse -- and queues their windows as missing again; the wrapper forgets which windows it
+        factored and factors from the new pair.  Returns the library's code: 0, or EINVAL when the pair was refused, after which the
+        handle has NO inverse and solves by the PDIP path until a later call is accepted."""
+        Hinv = np.ascontiguousarray(Hinv, dtype=np.float64)
+        Kunc = np.ascontiguousarray(Kunc, dtype=np.float64)
+        if Hinv.shape != (self.n, self.n) or Kunc.shape != (self.n, self.n_aug):
+            raise ValueError("Hinv must be (n, n), Kunc (n, n_aug)")
+        rc = self._lib.nnmpc_qp_set_inverse(self._h, Hinv.ctypes.data_as(C.c_void_p), Kunc.ctypes.data_as(C.c_void_p))
+        factoring = self._ff_src is not None
+        self.have_inverse = rc == 0
+        self._ff_done, self.farfield_info, self._ff_src = set(), {}, None
+        if rc != _lib.EINVAL:
+            _lib.check(rc, "nnmpc_qp_set_inverse")
+            if factoring:
+                self._ff_src = (np.ascontiguousarray(Hinv[:, :self._ff_wmax]), Kunc)
+        return rc
+
     def prepare_farfield(self, W, rtol=1e-13):
         """Factor M = [Kunc[W:] | -Hinv[W:, 0:W]] = U [Vx | Vl] (truncated SVD: singular values above rtol times the
         largest; M has numerical rank ~Nx; basis rotated so that U is a staircase, see _staircase) and hand the factors to the

@@ -1741,3 +1741,380 @@ def gemm_dispatch_inputs():
     """One A (3264 rows), B (1088 rows), 24 columns each, exact data: every shape of GEMM_DISPATCH is a corner of them."""
     rng = np.random.default_rng(20250)
     return gemm_data((3264, 24), rng, np.float64, False), gemm_data((1088, 24), rng, np.float64, False)
+
+
+# ---- certificates under inexact inverses and far-field factors: tests/test_certificate_gpu.py, tests/test_cpu_certificate_inputs.py
+
+CERT_STAT_TOL = 1e-8       # csrc/qp_solver.hip, asm_args (the AsmDev setup of a segment): a.stat_tol = 1e-8; nnmpc_qp_create: d.stat_tol = 1e-8
+CERT_BOUND_TOL = 1e-9      # csrc/qp_solver.hip, nnmpc_qp_create: opts.bound_tol <= 0 -> 1e-9 (BatchedBoxQP passes 0)
+CERT_ROUND = 1e-14         # the rounding term of the bound (asm_update_k, asm_wide_k, asm_tail_k, asm_small_k)
+CERT_GATE_E2 = 1e-6        # nnmpc_qp_set_inverse refuses |P Pinv - I|_max >= 1e-6
+CERT_GATE_FAR = 1e-9       # nnmpc_qp_set_farfield refuses max |U V' - M| >= 1e-9
+CERT_GATE_BAND = 1e-3      # numpy's figure and the device's differ by the rounding of an n-term product, n eps |P|_inf max |Pinv| ~ 2e-10 on
+                           # entries the gate compares with 1e-6: inputs are held this far, relatively, from either gate
+CERT_ST_REJECTED = 1       # NNMPC_ST_MAXITER: what a method-"asm" handle reports for a row its pass marked 3, "not solved here" (pdip_fallback)
+CERT_PDIP_TOL = 1e-8       # |u - u*| <= 1e-8 max(1, |u*|inf): "certified exact" of tests/test_pdip_paths_gpu.py
+CERT_MARGIN_FLOOR = 10.0 * CERT_STAT_TOL   # a kept row's margins are ten stationarity bars at least: a multiplier below the bar cannot be told from zero at that bar
+CERT_MARGIN_SIGMA = 6.0    # ... and twice as far as entrywise relative errors of 6 sigma of the plant's REFUSED rung can move it, to first
+                           # order (cert_shift): no accepted handle of the ladders is further from the exact inverse than that
+CERT_MIN_CLASS = 8
+CERT_MAX_LOST = 0.20
+
+CERT_PLANTS = dict(mini_cdu=dict(seed=5, B=96, sample_seed=6, sx=2.5),
+                   cstrs=dict(seed=0, B=128, sample_seed=1, sx=2.0),
+                   mid_cdu=dict(seed=3, B=320, sample_seed=11, sx=2.0))
+# relative-noise ladder: accepted rungs, then the rung just above the e2 < 1e-6 gate (tests/test_cpu_certificate_inputs.py holds every
+# accepted rung below 0.9e-6 and the refused one above 1.1e-6 with e2 computed in numpy: the device's figure differs by rounding only)
+CERT_LADDER = dict(mini_cdu=((0.0, 1e-13, 1e-12, 1e-11, 1e-10, 2e-10, 3e-8), 5e-8),
+                   cstrs=((0.0, 1e-13), 5e-12),
+                   mid_cdu=((0.0, 1e-13, 1e-12, 5e-11, 1e-10, 2e-10, 8e-9), 2e-8))
+CERT_SITES = dict(small=dict(plant="mini_cdu", env={}, opts={}),
+                  small_ill=dict(plant="cstrs", env={}, opts=dict(nb=64)),
+                  update=dict(plant="mini_cdu", env={"NNMPC_NO_SMALL": "1"}, opts=dict(asm_tail_batch=-1)),
+                  tail=dict(plant="mini_cdu", env={"NNMPC_NO_SMALL": "1"}, opts={}),
+                  wide=dict(plant="mid_cdu", env={}, opts={}))
+CERT_FAR_W = 256           # the column window of the mid_cdu batch's rounds: past its last active bound (index 191) plus one stage, on the 128 grid
+CERT_FAR_SETTINGS = dict(exact=0.0, small=1e-11, aligned=8e-10, refused=2e-9)    # max |U V' - M| asked for
+_CERT_CASES = {}
+
+
+def cert_ld_eps():
+    return float(np.finfo(np.longdouble).eps)
+
+
+def cert_oracle_row(H, xunc, lbn, ubn):
+    """Optimal bound states of one problem by a primal-dual active-set iteration on the exact inverse (all infeasible indices change
+    sides while their number keeps falling, then the smallest one only): x = x_unc - H[:, A] lam, lam = H_AA^-1 (x_unc_A - b_A).
+    What comes back is a candidate; cert_case certifies every row with P itself in np.longdouble (cert_property_a)."""
+    n = xunc.size
+    state = np.where(xunc > ubn, 1, np.where(xunc < lbn, 2, 0)).astype(np.uint8)
+    best, grace = n + 1, 3
+    for _ in range(2000):
+        x, A, lam = cert_solve_on_set_inv(H, xunc, lbn, ubn, state)
+        new = np.full(n, 255, np.uint8)
+        fr = state == 0
+        new[fr & (x > ubn)] = 1
+        new[fr & (x < lbn)] = 2
+        new[A[np.where(state[A] == 1, lam <= 0.0, lam >= 0.0)]] = 0
+        inf = np.flatnonzero(new != 255)
+        if inf.size == 0:
+            return state, x, lam
+        if inf.size < best:
+            best, grace = inf.size, 3
+        elif grace > 0:
+            grace -= 1
+        else:
+            inf = inf[:1]
+        state[inf] = new[inf]
+    raise RuntimeError("cert_oracle_row: no settled set")
+
+
+def cert_solve_on_set_inv(H, xunc, lbn, ubn, state):
+    """(x, A, lam) on the set `state` through an inverse H, as the solver forms them: lam = H_AA^-1 (x_unc_A - b_A) (positive on
+    upper bounds, negative on lower ones at an optimum), x = x_unc - H[:, A] lam with x_A = b_A exactly."""
+    A = np.flatnonzero(state)
+    if A.size == 0:
+        return xunc.copy(), A, np.zeros(0)
+    b = np.where(state[A] == 1, ubn[A], lbn[A])
+    lam = np.linalg.solve(H[np.ix_(A, A)], xunc[A] - b)
+    x = xunc - H[:, A] @ lam
+    x[A] = b
+    return x, A, lam
+
+
+def cert_shift(H, K, x0, state, lam, eps):
+    """First-order bound on how far entrywise relative errors of at most e = eps in H and K move the solution on a fixed set:
+    with S = H_AA,  |d lam| <= |S^-1| e (|K_A| |x0| + |S| |lam|)  and  |d x_F| <= e (|K| |x0| + |H_:A| |lam|) + |H_:A| |d lam|.
+    -> (max |d lam|, max |d x| over the free variables)."""
+    e = eps
+    A = np.flatnonzero(state)
+    kx = np.abs(K) @ np.abs(x0)
+    if A.size == 0:
+        return 0.0, float(e * kx.max())
+    S = H[np.ix_(A, A)]
+    dl = np.abs(np.linalg.inv(S)) @ (e * (kx[A] + np.abs(S) @ np.abs(lam)))
+    HA = np.abs(H[:, A])
+    dx = e * (kx + HA @ np.abs(lam)) + HA @ dl
+    fr = state == 0
+    return float(dl.max()), float(dx[fr].max(initial=0.0))
+
+
+def cert_case(plant):
+    """Everything of one plant that is computed once: P (symmetric), tq, the exact inverse, the batch, the oracle's sets and optima
+    (certified with P in np.longdouble), margins and the kept rows."""
+    if plant in _CERT_CASES:
+        return _CERT_CASES[plant]
+    import scipy.linalg as sla
+    from industrial_nnmpc_2021_amd.linearMPC_build import build_regulator_matrices
+    spec = CERT_PLANTS[plant]
+    pl = synthetic.plant(plant, spec["seed"])
+    P, tq, nu = build_regulator_matrices(pl)
+    Ps = np.tril(P) + np.tril(P, -1).T
+    n = Ps.shape[0]
+    N = n // nu
+    cf = sla.cho_factor(Ps, lower=True)
+    H = sla.cho_solve(cf, np.eye(n))
+    H = np.ascontiguousarray(0.5 * (H + H.T))
+    K = np.ascontiguousarray(-sla.cho_solve(cf, tq))
+    _, x0, lb, ub = batch_inputs(pl, spec["B"], spec["sample_seed"], spec["sx"])
+    x0, lb, ub = np.ascontiguousarray(x0), np.ascontiguousarray(lb), np.ascontiguousarray(ub)
+    B = spec["B"]
+    c = dict(plant=plant, pl=pl, P=P, Ps=Ps, tq=tq, nu=nu, N=N, n=n, B=B, H=H, K=K, x0=x0, lb=lb, ub=ub,
+             pscale=float(np.sort(np.diag(Ps))[n // 2]), tqmax=float(np.abs(tq).max()), p_inf=float(np.abs(Ps).sum(axis=1).max()),
+             LB=np.tile(lb, (1, N)), UB=np.tile(ub, (1, N)), q=x0 @ tq.T)
+    c["scale"] = np.maximum(c["pscale"], np.abs(c["q"]).max(axis=1))
+    c["bar"] = CERT_STAT_TOL * c["scale"]
+    c["x1"] = np.abs(x0).sum(axis=1)
+    state = np.zeros((B, n), np.uint8)
+    xs = np.empty((B, n))
+    lam = np.zeros((B, n))                                         # signed multipliers on the active bounds, 0 elsewhere
+    lam_margin, slack_margin = np.empty(B), np.empty(B)
+    dlam, dx = np.empty(B), np.empty(B)
+    xunc = x0 @ K.T
+    for b in range(B):
+        state[b], xs[b], lm = cert_oracle_row(H, xunc[b], c["LB"][b], c["UB"][b])
+        A = np.flatnonzero(state[b])
+        lam[b, A] = lm
+        fr = state[b] == 0
+        lam_margin[b] = np.abs(lm).min(initial=np.inf) / c["scale"][b]
+        slack_margin[b] = (np.minimum(c["UB"][b] - xs[b], xs[b] - c["LB"][b]) / (c["UB"][b] - c["LB"][b]))[fr].min(initial=np.inf)
+        dl, dxf = cert_shift(H, K, x0[b], state[b], lm, CERT_MARGIN_SIGMA * CERT_LADDER[plant][1])
+        dlam[b], dx[b] = dl / c["scale"][b], dxf / (c["UB"][b] - c["LB"][b]).min()
+    c.update(state=state, xs=xs, lam=lam, active=state_to_active(state, nu), lam_margin=lam_margin, slack_margin=slack_margin,
+             shift_lam=dlam, shift_x=dx)
+    # kept: both margins above the floor and above twice what the largest inverse error of the plant's ladder can move (cert_shift)
+    c["kept"] = (lam_margin > np.maximum(CERT_MARGIN_FLOOR, 2.0 * dlam)) & (slack_margin > np.maximum(CERT_MARGIN_FLOOR, 2.0 * dx))
+    ref = cert_property_a(c, dict(u=xs, active=c["active"], status=np.zeros(B, np.int32)), precise=True)
+    if not ref["ok"].all() or ref["ratio"].max() > 1e-3:
+        raise RuntimeError(f"cert_case({plant}): the oracle's optimum is not certified: {ref['why'][:3]}, ratio {ref['ratio'].max():.2e}")
+    c["oracle_ratio"] = ref["ratio"]
+    _CERT_CASES[plant] = c
+    return c
+
+
+def cert_property_a(c, out, rows=None, precise=False):
+    """The solver's own claim about every row with status 0, evaluated with the original P, q = tq x0 and the bounds: active entries
+    equal their bounds bit for bit, no variable active on both sides, lb - bound_tol <= u <= ub + bound_tol, g = P u + q < 0 on
+    upper-active and > 0 on lower-active entries, |g|inf over the free entries <= 1e-8 max(pscale, |q|inf).  g is evaluated in
+    np.longdouble, and the only slack is the rounding of that evaluation, gamma(n + n_aug + 2) (|P| |u| + |tq| |x0|), on the
+    stationarity bar.  (A longdouble product of the mid_cdu batch takes seconds: a row whose every comparison an fp64 evaluation
+    with ITS rounding bound already decides, either way, keeps that verdict -- the longdouble one cannot differ; `precise` turns the
+    short cut off.)  rows: the rows of the case the result holds (default: all, in order).
+    -> dict(ok (B,) bool -- True for rows with status != 0, which may hold anything --, ratio (B,) free-set gradient / bar (0 for
+    rows not checked), slack (largest longdouble rounding slack / bar), ld_rows (rows evaluated in longdouble), why [(row, reason)])."""
+    u, act, status = np.asarray(out["u"]), np.asarray(out["active"]), np.asarray(out["status"])
+    B, n = u.shape
+    nu, na = c["nu"], c["tq"].shape[1]
+    rows = np.arange(c["B"]) if rows is None else np.asarray(rows)
+    k, cc = np.arange(n) // nu, np.arange(n) % nu
+    ok = np.ones(B, bool)
+    ratio = np.zeros(B)
+    why = []
+    chk = np.flatnonzero(status == 0)
+    if chk.size == 0:
+        return dict(ok=ok, ratio=ratio, slack=0.0, ld_rows=0, why=why)
+    LB, UB = c["LB"][rows][chk], c["UB"][rows][chk]
+    a_u, a_l = act[chk][:, k * 2 * nu + cc], act[chk][:, k * 2 * nu + nu + cc]
+    fr = ~(a_u | a_l)
+    finite = np.isfinite(u[chk]).all(axis=1)
+    U = np.where(np.isfinite(u[chk]), u[chk], 0.0)
+    x0 = c["x0"][rows][chk]
+    Pa, ta = np.abs(c["Ps"]), np.abs(c["tq"])
+    q = x0 @ c["tq"].T
+    G = U @ c["Ps"] + q
+    mag = np.abs(U) @ Pa + np.abs(x0) @ ta.T
+    slack = cl_gamma(n + na + 2) * mag * (1.0 + 1e-12)
+    bar = CERT_STAT_TOL * np.maximum(c["pscale"], np.abs(q).max(axis=1))
+    ld = np.longdouble
+    gam_ld = float((n + na + 2) * np.finfo(ld).eps)
+    open_ = (fr & (np.abs(np.abs(G) - bar[:, None]) <= slack + 1e-12 * bar[:, None])).any(axis=1) | (~fr & (np.abs(G) <= slack)).any(axis=1)
+    need = np.flatnonzero(open_ | precise)
+    if need.size:
+        if "_ld" not in c:
+            c["_ld"] = (c["Ps"].astype(ld), c["tq"].astype(ld))
+        Pl, tl = c["_ld"]
+        ql = x0[need].astype(ld) @ tl.T
+        Gl = U[need].astype(ld) @ Pl + ql
+        # these rows' gradients, from longdouble (rounding them to fp64 moves them by 1e-16 |g|, far inside the slack below; a sign
+        # is never lost: no gradient here is near the underflow threshold)
+        G[need] = Gl.astype(np.float64)
+        slack[need] = gam_ld * mag[need] + 2.0 * TS_EPS * np.abs(G[need])
+    tol = CERT_BOUND_TOL
+    # (u - ub and lb - u are exact or correctly rounded differences of fp64 numbers; 1e-9 is compared as the library compares it)
+    tests = (("not finite", ~finite),
+             ("active on both sides", (a_u & a_l).any(axis=1)),
+             ("active entry off its bound", (a_u & (u[chk] != UB)).any(axis=1) | (a_l & (u[chk] != LB)).any(axis=1)),
+             ("beyond a bound", ((U > UB + tol) | (U < LB - tol)).any(axis=1)),
+             ("multiplier sign", (a_u & ~(G < 0)).any(axis=1) | (a_l & ~(G > 0)).any(axis=1)),
+             ("free-set gradient", (fr & (np.abs(G) > bar[:, None] + slack)).any(axis=1)))
+    for name, bad in tests:
+        for i in np.flatnonzero(bad):
+            why.append((int(chk[i]), name))
+        ok[chk[bad]] = False
+    ratio[chk] = np.where(fr, np.abs(G), 0).max(axis=1) / bar
+    return dict(ok=ok, ratio=ratio, slack=float((gam_ld * mag.max(axis=1) / bar).max()), ld_rows=int(need.size), why=why)
+
+
+def cert_perturb(c, eps, seed=1):
+    """Relative noise: (Hinv (1 + eps N) symmetrised, Kunc (1 + eps N')); eps = 0: the exact pair."""
+    rng = np.random.default_rng(seed)
+    Nh, Nk = rng.standard_normal(c["H"].shape), rng.standard_normal(c["K"].shape)
+    Hp = c["H"] * (1.0 + eps * Nh)
+    return np.ascontiguousarray(0.5 * (Hp + Hp.T)), np.ascontiguousarray(c["K"] * (1.0 + eps * Nk))
+
+
+def cert_perturb_rowcol(c, j, rel=1e-7):
+    """Row and column j of Hinv scaled by 1 + rel (the diagonal entry twice), Kunc exact."""
+    Hp = c["H"].copy()
+    Hp[j, :] *= 1.0 + rel
+    Hp[:, j] *= 1.0 + rel
+    return np.ascontiguousarray(Hp), c["K"]
+
+
+def cert_rowcol_index(c):
+    """The first-stage variable whose scaled row and column leave the smallest |P Pinv - I|_max (~ rel (1 + P_jj Hinv_jj): most of them
+    miss the gate at rel = 1e-7)."""
+    if "rowcol" not in c:
+        c["rowcol"] = int(np.argmin([cert_errors(c, *cert_perturb_rowcol(c, j))[1] for j in range(c["nu"])]))
+    return c["rowcol"]
+
+
+def cert_perturb_kunc(c, rel=1e-3, seed=2):
+    """Kunc alone off by rel N', Hinv exact."""
+    rng = np.random.default_rng(seed)
+    return c["H"], np.ascontiguousarray(c["K"] * (1.0 + rel * rng.standard_normal(c["K"].shape)))
+
+
+def cert_errors(c, Hp, Kp):
+    """(e1max, e2max) as nnmpc_qp_set_inverse measures them, in numpy."""
+    return float(np.abs(c["Ps"] @ Kp + c["tq"]).max()), float(np.abs(c["Ps"] @ Hp - np.eye(c["n"])).max())
+
+
+def cert_errors_rounding(c, Hp, Kp):
+    """How far two fp64 evaluations of (e1max, e2max) can differ: 2 gamma(n) max(|P| |Kunc| + |tq|), 2 gamma(n) max(|P| |Pinv| + I)."""
+    g = 2.0 * cl_gamma(c["n"] + 2)
+    Pa = np.abs(c["Ps"])
+    return float(g * (Pa @ np.abs(Kp) + np.abs(c["tq"])).max()), float(g * ((Pa @ np.abs(Hp)).max() + 1.0))
+
+
+def cert_emulate(c, Hp, Kp, e1max, e2max, ff_err=0.0, precise=False):
+    """What the solver computes from the pair (Hp, Kp) on the oracle's sets, and the certificate it then forms:
+    bnd = 2 (e1max |x0|_1 + e2max |lam|_1) + 1e-14 (tqmax |x0|_1 + |lam|_1) + ff_err (|x0|_1 + |lam|_1),
+    sure = bnd <= stat_tol pscale and min |lam_a| > bnd.  -> dict of (B,) arrays: bnd, sure, undetermined (bnd within a factor 2 of
+    either comparison), gfree (max |P x + q| over the free set; precise: every row in np.longdouble), ratio = gfree / bar, setok (the emulated
+    solution keeps the oracle's set: feasible within bound_tol, multiplier signs right), and x (B, n), l1, lmin."""
+    B, n = c["B"], c["n"]
+    xunc = c["x0"] @ Kp.T
+    x = np.empty((B, n))
+    l1, lmin, setok = np.zeros(B), np.full(B, 1e300), np.ones(B, bool)
+    for b in range(B):
+        x[b], A, lm = cert_solve_on_set_inv(Hp, xunc[b], c["LB"][b], c["UB"][b], c["state"][b])
+        if A.size:
+            l1[b], lmin[b] = np.abs(lm).sum(), np.abs(lm).min()
+            setok[b] = not np.where(c["state"][b][A] == 1, lm <= 0.0, lm >= 0.0).any()
+        setok[b] &= bool(((x[b] <= c["UB"][b] + CERT_BOUND_TOL) & (x[b] >= c["LB"][b] - CERT_BOUND_TOL)).all())
+    ev = cert_property_a(c, dict(u=x, active=c["active"], status=np.zeros(B, np.int32)), precise=precise)
+    x1 = c["x1"]
+    bnd = 2.0 * (e1max * x1 + e2max * l1) + CERT_ROUND * (c["tqmax"] * x1 + l1) + ff_err * (x1 + l1)
+    lim = CERT_STAT_TOL * c["pscale"]
+    sure = (bnd <= lim) & (lmin > bnd)
+    und = ((bnd > 0.5 * lim) & (bnd < 2.0 * lim)) | ((bnd <= lim) & (lmin > 0.5 * bnd) & (lmin < 2.0 * bnd))
+    return dict(x=x, l1=l1, lmin=lmin, bnd=bnd, sure=sure, undetermined=und, ratio=ev["ratio"], gfree=ev["ratio"] * c["bar"], setok=setok)
+
+
+def cert_classes(c, em):
+    """Kept, determined rows by class: 'sure'; 'accepted' (not sure, free-set gradient below a quarter of the bar: the check with P
+    passes); 'rejected' (above four times the bar: it fails).  Rows in between, undetermined rows and rows that are not kept are in
+    'lost'."""
+    det = c["kept"] & ~em["undetermined"] & em["setok"]
+    sure = det & em["sure"]
+    acc = det & ~em["sure"] & (em["ratio"] < 0.25)
+    rej = det & ~em["sure"] & (em["ratio"] > 4.0)
+    return dict(sure=sure, accepted=acc, rejected=rej, lost=~(sure | acc | rej))
+
+
+def cert_full_check_range(c, em):
+    """[lo, hi] of asm_full_checks under method 'asm': the kept, determined rows that are not sure, plus at most the rest."""
+    det = c["kept"] & ~em["undetermined"] & em["setok"]
+    lo = int((det & ~em["sure"]).sum())
+    return lo, lo + int((~det).sum())
+
+
+def cert_u_tol(c, b):
+    """1e-8 max(1, |u*|inf) + |P_FF^-1|inf bar: an accepted row's distance from the oracle's optimum (P_FF (u - u*)_F = g_F)."""
+    tol = c.setdefault("_utol", {})
+    if b not in tol:
+        fr, A = c["state"][b] == 0, np.flatnonzero(c["state"][b])
+        # the inverse of a principal block from the inverse of the whole: P_FF^-1 = H_FF - H_FA H_AA^-1 H_AF (n^2 |A| flops, not n^3)
+        inv = c["H"][np.ix_(fr, fr)]
+        if A.size:
+            HFA = c["H"][np.ix_(fr, A)]
+            inv = inv - HFA @ np.linalg.solve(c["H"][np.ix_(A, A)], HFA.T)
+        norm = np.abs(inv).sum(axis=1).max() if fr.any() else 0.0
+        tol[b] = 1e-8 * max(1.0, np.abs(c["xs"][b]).max()) + norm * c["bar"][b]
+    return tol[b]
+
+
+def cert_farfield_factors(c, W=CERT_FAR_W, rtol=1e-13):
+    """U, Vx, Vl of M = [Kunc[W:] | -Hinv[W:, 0:W]] as BatchedBoxQP.prepare_farfield builds them (truncated SVD, staircase basis)."""
+    import scipy.linalg as sla
+    from industrial_nnmpc_2021_amd.qp import _staircase
+    key = ("far", W)
+    if key not in c:
+        M = np.hstack((c["K"][W:], -c["H"][W:, :W]))
+        U, s, Vt = sla.svd(M, full_matrices=False, lapack_driver="gesdd")
+        r = max(1, int((s > rtol * s[0]).sum()))
+        Uf, G = _staircase(U[:, :r] * s[:r], rtol * s[0])
+        V = G @ Vt[:G.shape[1]]
+        c[key] = (Uf, np.ascontiguousarray(V), M)
+    return c[key]
+
+
+CERT_FAR_ALIGNED = 8       # rows the 'aligned' factors are built for, one after the other: which rows of a batch settle in the rounds -- and go
+                           # through the full-width pass -- and which are finished by the device tail, from Pinv itself, is the solver's to say
+
+
+def cert_far_aligned_rows(c, W=CERT_FAR_W, k=CERT_FAR_ALIGNED):
+    """[(row, ratio)]: the k kept rows whose z = [x0; lam[0:W]] has the largest |V z|^2 / max |V' V z| -- the rows 'aligned' factors
+    move furthest --, each with the free-set gradient / bar of its optimum with the far columns moved by its factors (what a pass
+    that delivered the factored product uncertified would hand out)."""
+    Uf, V, _ = cert_farfield_factors(c, W)
+    cand = []
+    for b in np.flatnonzero(c["kept"]):
+        if np.flatnonzero(c["state"][b]).max(initial=-1) >= W:
+            continue
+        Vz = V @ np.concatenate((c["x0"][b], c["lam"][b][:W]))
+        cand.append((float(Vz @ Vz / np.abs(Vz @ V).max()), int(b)))
+    out = []
+    for _, row in sorted(cand, reverse=True)[:k]:
+        Up = cert_farfield_perturbed(c, "aligned", row=row, W=W)[0]
+        x = c["xs"][row].copy()
+        x[W:] += (Up - Uf) @ (V @ np.concatenate((c["x0"][row], c["lam"][row][:W])))
+        ev = cert_property_a(c, dict(u=x[None], active=c["active"][row][None], status=np.zeros(1, np.int32)), rows=[row])
+        out.append((row, float(ev["ratio"][0])))
+    return out
+
+
+def cert_farfield_perturbed(c, setting, row=None, W=CERT_FAR_W, seed=3):
+    """(U', Vx, Vl, efar): U perturbed so that max |U' V - M| is about CERT_FAR_SETTINGS[setting] (on top of the factors' own ~1e-13).
+    'small', 'refused': dU = a N.  'aligned': rank one, dU = a w (V z)', z = [x0; lam[0:W]] of `row`: the row's far columns move by
+    a |V z|^2 w, as far as max |dU V| = a max |V' V z| allows, with the signs w of the far row of P whose absolute sum is largest."""
+    Uf, V, M = cert_farfield_factors(c, W)
+    na = c["tq"].shape[1]
+    target = CERT_FAR_SETTINGS[setting]
+    rng = np.random.default_rng(seed)
+    if setting == "exact":
+        dU = np.zeros_like(Uf)
+    elif setting == "aligned":
+        z = np.concatenate((c["x0"][row], c["lam"][row][:W]))
+        far = np.abs(c["Ps"][W:, W:]).sum(axis=1)
+        w = np.sign(c["Ps"][W + int(np.argmax(far)), W:])           # ... and the moves add up in one far entry of P du
+        w[w == 0] = 1.0
+        dU = np.outer(w, V @ z)
+    else:
+        dU = rng.standard_normal(Uf.shape)
+    if target > 0.0:
+        dU *= target / np.abs(dU @ V).max()
+    Up = np.ascontiguousarray(Uf + dU)
+    efar = float(np.abs(Up @ V - M).max())
+    return Up, np.ascontiguousarray(V[:, :na]), np.ascontiguousarray(V[:, na:]), efar
