@@ -134,6 +134,8 @@ typedef struct {
   double asm_predict_ms;     /* their hipEvent time (profiling on) */
   double asm_predict_flops;  /* bf16 MFMA flops they executed: 2 * 64 * 512 * (columns of Y in use) per workgroup and iteration */
   int64_t asm_overlapped_passes; /* full-width passes that ran beside the round of the problems still running (asm_overlap) */
+  double mult_ms;            /* hipEvent time of the bound-multiplier kernel (asm_mult_k: nnmpc_qp_solve_batch_dual, nnmpc_qp_multipliers; profiling on) */
+  int64_t mult_launches;     /* ... and its launches (one per segment) */
 } nnmpc_qp_stats;
 
 const char* nnmpc_last_error(void);
@@ -174,6 +176,33 @@ int nnmpc_qp_solve_batch_warm(nnmpc_qp* h, int32_t B, const double* x0, const do
 int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const double* lb,
                             const double* ub, const uint8_t* guess, double* u, uint32_t* active,
                             int32_t* status, int32_t* iters, int32_t ptr_kind, int32_t out_kind);
+
+/* Bound multipliers of delivered results.  With q = tq x0 and g = P u + q (P as the handle holds it: the lower triangle, mirrored),
+ * for problem b and variable i = k nu + c (stage k, input c):
+ *     mult[b, i] = -g_i   upper bound of i active (bit k 2nu + c of `active`)        = z of that row of the reference's G
+ *     mult[b, i] = +g_i   lower bound active      (bit k 2nu + nu + c)               = z of that row
+ *     mult[b, i] = +0.0   variable free
+ * i.e. P u + q + z_up - z_lo = 0 on the active rows, and z >= 0 at an optimum.  The side is taken from `active`, never from the sign
+ * of the value: a weakly active bound may come back as a tiny negative number (rounding of an fp64 dot product of n + n_aug terms:
+ * |error| <= (n + n_aug + 2) 2^-53 (|P_i| |u| + |tq_i| |x0|)).  The values are formed from what was delivered and from P itself --
+ * one gathered fp64 row product per active bound (csrc/qp_mult.h) -- not taken from a solver path's own multipliers, so they are the
+ * same whichever path solved a problem and need neither an inverse nor far-field factors.
+ * x0: B x n_aug, u: B x n, active: B x ceil(2n/32) words, status: B or NULL  ->  mult: B x n, every entry written.
+ * A row with status NNMPC_ST_NUMERIC, a non-finite u or both bits of one variable set is no answer: its mult row is quiet NaN
+ * throughout.  A row with status NNMPC_ST_MAXITER is computed from what was delivered like any other and is as little certified as
+ * its u.  A pure function of the handle's P and tq and the arguments; B = 0: NNMPC_OK, nothing is written. */
+int nnmpc_qp_multipliers(nnmpc_qp* h, int32_t B, const double* x0, const double* u, const uint32_t* active,
+                         const int32_t* status /* may be NULL */, double* mult, int32_t ptr_kind);
+/* nnmpc_qp_solve_batch_ex that also hands back those multipliers (mult: B x n): it solves exactly as nnmpc_qp_solve_batch_ex does --
+ * same kernels, same launches, same u / active / status / iters -- and then forms mult from each segment's device-resident u and
+ * active words before anything is copied out (a host caller never uploads u again).  active and status may be NULL: the library
+ * keeps them in its own workspace (allocated when first asked for, like mult's staging).  mult = NULL: nnmpc_qp_solve_batch_ex.
+ * out_kind = NNMPC_OUT_FIRST_MOVE with a non-NULL mult: NNMPC_EINVAL (the whole sequence is not delivered on that path).
+ * With a non-NULL mult and NNMPC_DEVICE pointers the call is synchronous: it waits for the handle's stream before it returns, so
+ * mult is there (nnmpc_qp_solve_batch_ex only enqueues).  With profiling on, total_ms of such a call includes mult_ms. */
+int nnmpc_qp_solve_batch_dual(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub,
+                              const uint8_t* guess, double* u, uint32_t* active, int32_t* status,
+                              int32_t* iters, double* mult, int32_t ptr_kind, int32_t out_kind);
 
 /* Enables the shared-inverse active-set pass: Hinv = P^-1 (n x n, fp64), Kunc = -Hinv tq (n x n_aug).
  * All samples share P (reference lib/linearMPC.py:472), so on an active set A the equality-constrained

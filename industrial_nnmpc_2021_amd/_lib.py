@@ -32,7 +32,8 @@ class QpStats(C.Structure):
                 ("asm_lambda64_ms", C.c_double), ("asm_lambda32_flops", C.c_double),
                 ("asm_lambda32_launches", C.c_int64), ("asm_lambda64_launches", C.c_int64), ("asm_far_passes", C.c_int64), ("asm_side_ms", C.c_double),
                 ("asm_small_passes", C.c_int64), ("asm_predict_launches", C.c_int64), ("asm_predict_ms", C.c_double),
-                ("asm_predict_flops", C.c_double), ("asm_overlapped_passes", C.c_int64)]
+                ("asm_predict_flops", C.c_double), ("asm_overlapped_passes", C.c_int64),
+                ("mult_ms", C.c_double), ("mult_launches", C.c_int64)]
 
 
 CL_MPC, CL_NN, CL_SATDLQR, CL_US, CL_NN_UNSTD = 0, 1, 2, 3, 4
@@ -52,7 +53,8 @@ class ClSlot(C.Structure):
 
 
 EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_solve_batch",
-           "nnmpc_qp_solve_batch_warm", "nnmpc_qp_solve_batch_ex", "nnmpc_qp_set_inverse", "nnmpc_qp_dims",
+           "nnmpc_qp_solve_batch_warm", "nnmpc_qp_solve_batch_ex", "nnmpc_qp_solve_batch_dual", "nnmpc_qp_multipliers",
+           "nnmpc_qp_set_inverse", "nnmpc_qp_dims",
            "nnmpc_qp_first_moves", "nnmpc_qp_set_farfield", "nnmpc_qp_farfield_missing",
            "nnmpc_qp_set_profiling", "nnmpc_qp_get_stats", "nnmpc_qp_debug_factor_solve", "nnmpc_qp_debug_factor_fail",
            "nnmpc_qp_debug_predict", "nnmpc_qp_debug_gemm",
@@ -197,6 +199,10 @@ def load():
     u64 = C.c_uint64
     lib.nnmpc_qp_solve_batch_ex.restype = i32
     lib.nnmpc_qp_solve_batch_ex.argtypes = [vp, i32, dp, dp, dp, dp, dp, dp, dp, dp, i32, i32]
+    lib.nnmpc_qp_solve_batch_dual.restype = i32                   # _ex plus the bound multipliers (mult before ptr_kind)
+    lib.nnmpc_qp_solve_batch_dual.argtypes = [vp, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, i32, i32]
+    lib.nnmpc_qp_multipliers.restype = i32
+    lib.nnmpc_qp_multipliers.argtypes = [vp, i32, dp, dp, dp, dp, dp, i32]
     lib.nnmpc_qp_first_moves.restype = i32
     lib.nnmpc_qp_first_moves.argtypes = [dp, C.c_int64, dp, i32, i32, dp]
     lib.nnmpc_qp_dims.restype = i32

@@ -32,6 +32,7 @@
 #include "qp_wide.h"
 #include "qp_small.h"
 #include "qp_predict.h"
+#include "qp_mult.h"
 #include "dev_res.h"
 static constexpr int ASM_SMALL9_LDS_MAX = 100 * 1024;   // dynamic LDS the nine-block instance of asm_small_k may ask for (81 KB at n = 1024, nu = 64)
 
@@ -757,7 +758,9 @@ struct nnmpc_qp {
   std::vector<EvRec> ev_recs;
   nnmpc_qp_stats stats;
   // grow-only slots of the owner: staging of host-pointer calls, compacted copies for the PDIP fallback
-  enum { SC_U = 0, SC_ACT, SC_ST, SC_IT, SC_GUESS, SC_FB_GUESS, SC_FB_LIST, SC_FB_X0, SC_FB_LB, SC_FB_UB, SC_FB_U, SC_FB_ACT, SC_FB_ST, SC_FB_IT, SC_COUNT };
+  enum { SC_U = 0, SC_ACT, SC_ST, SC_IT, SC_GUESS, SC_FB_GUESS, SC_FB_LIST, SC_FB_X0, SC_FB_LB, SC_FB_UB, SC_FB_U, SC_FB_ACT, SC_FB_ST, SC_FB_IT,
+         SC_MULT, SC_M_X0, SC_M_U, SC_M_ACT, SC_M_ST,   // bound multipliers: the staged result; the staged inputs of nnmpc_qp_multipliers
+         SC_COUNT };
   DevRes res{SC_COUNT};         // owns every buffer, stream and event below and above
   int ldu, nout;        // layout of the caller's u buffer for the call in progress (nnmpc_qp_solve_batch_ex)
 };
@@ -817,7 +820,7 @@ hipEvent_t ev_mark(nnmpc_qp* h, hipStream_t st) {
   return e;
 }
 // What a profiling record times (EvRec::kind): where ev_collect adds it up.
-enum EvKind { EV_PANEL = 0, EV_DIAG, EV_TRSV, EV_TOTAL, EV_LAMBDA, EV_GEMM, EV_UPDATE, EV_LAMBDA32, EV_LAMBDA64, EV_SIDE, EV_PREDICT };
+enum EvKind { EV_PANEL = 0, EV_DIAG, EV_TRSV, EV_TOTAL, EV_LAMBDA, EV_GEMM, EV_UPDATE, EV_LAMBDA32, EV_LAMBDA64, EV_SIDE, EV_PREDICT, EV_MULT };
 struct EvScope {
   nnmpc_qp* h; int kind; double flops; hipEvent_t e0; hipStream_t st;
   EvScope(nnmpc_qp* h_, EvKind kind_, double flops_, hipStream_t st_ = nullptr) : h(h_), kind(kind_), flops(flops_), e0(nullptr), st(st_ ? st_ : h_->stream) {
@@ -842,6 +845,7 @@ void ev_collect(nnmpc_qp* h) {
     else if (r.kind == EV_LAMBDA32) { h->stats.asm_lambda32_ms += ms; h->stats.asm_lambda32_launches += 1; }
     else if (r.kind == EV_LAMBDA64) { h->stats.asm_lambda64_ms += ms; h->stats.asm_lambda64_launches += 1; }
     else if (r.kind == EV_SIDE) h->stats.asm_side_ms += ms;
+    else if (r.kind == EV_MULT) { h->stats.mult_ms += ms; h->stats.mult_launches += 1; }
     else if (r.kind == EV_PREDICT) { h->stats.asm_predict_ms += ms; h->stats.asm_predict_flops += r.flops; }   // (launches: counted at the launch, profiling or not)
   }
   h->ev_recs.clear();
@@ -1808,6 +1812,18 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   return pdip_fallback(c, fb, x0_dev, st_dev);
 }
 
+// Bound multipliers of nprob delivered rows (qp_mult.h), enqueued on the handle's stream; device pointers.
+int launch_mult(nnmpc_qp* h, int nprob, const double* x0_dev, const double* u_dev, const uint32_t* act_dev, const int32_t* st_dev,
+                double* mult_dev) {
+  MultArgs m;
+  m.P64 = h->P64; m.tq64 = h->tq64; m.x0 = x0_dev; m.u = u_dev; m.active = act_dev; m.status = st_dev; m.mult = mult_dev;
+  m.n = h->n; m.np = h->np; m.nu = h->nu; m.n_aug = h->n_aug; m.ka = h->ka; m.words = h->words;
+  EvScope es(h, EV_MULT, 0.0);
+  hipLaunchKernelGGL(asm_mult_k, dim3(nprob), dim3(MULT_THREADS), 0, h->stream, m);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 hipStream_t nnmpc_qp_stream_internal(nnmpc_qp* h) { return h->stream; }
@@ -2255,9 +2271,10 @@ int nnmpc_qp_solve_batch_warm(nnmpc_qp* h, int32_t B, const double* x0, const do
   return nnmpc_qp_solve_batch_ex(h, B, x0, lb, ub, guess, u, active, status, iters, ptr_kind, NNMPC_OUT_SEQUENCE);
 }
 
-int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub,
-                            const uint8_t* guess, double* u, uint32_t* active, int32_t* status,
-                            int32_t* iters, int32_t ptr_kind, int32_t out_kind) {
+// nnmpc_qp_solve_batch_ex, and with mult != nullptr nnmpc_qp_solve_batch_dual: the same segments, the same launches, then asm_mult_k on
+// each segment's device-resident u and active words before anything is copied out.
+static int solve_batch_impl(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub, const uint8_t* guess, double* u,
+                            uint32_t* active, int32_t* status, int32_t* iters, int32_t ptr_kind, int32_t out_kind, double* mult) {
   if (!h || B < 0 || !x0 || !lb || !ub || !u) { set_error("nnmpc_qp_solve_batch: bad arguments"); return NNMPC_EINVAL; }
   if (out_kind != NNMPC_OUT_SEQUENCE && out_kind != NNMPC_OUT_FIRST_MOVE) { set_error("nnmpc_qp_solve_batch_ex: bad out_kind %d", out_kind); return NNMPC_EINVAL; }
   if (B == 0) return NNMPC_OK;
@@ -2270,13 +2287,18 @@ int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const doub
   // device staging for the outputs when the caller hands host pointers (owned by the handle, grown on demand)
   double* u_stage = nullptr; uint32_t* a_stage = nullptr; int32_t* s_stage = nullptr; int32_t* i_stage = nullptr;
   unsigned char* g_stage = nullptr;
+  double* m_stage = nullptr;
   const int gmax = std::min(G, (int)B);
   int rc = 0;
+  DevRes& res = h->res;
+  // the multiplier kernel reads the segment's active words and status on the device: kept in the handle's staging when the caller
+  // does not ask for them (or hands host pointers)
+  const bool own_act = mult && (ptr_kind == NNMPC_HOST || !active), own_st = mult && (ptr_kind == NNMPC_HOST || !status);
+  if (!rc && (own_act || (ptr_kind == NNMPC_HOST && active))) rc = res.slot(nnmpc_qp::SC_ACT, &a_stage, (size_t)gmax * h->words * sizeof(uint32_t));
+  if (!rc && (own_st || (ptr_kind == NNMPC_HOST && status))) rc = res.slot(nnmpc_qp::SC_ST, &s_stage, (size_t)gmax * sizeof(int32_t));
+  if (!rc && mult && ptr_kind == NNMPC_HOST) rc = res.slot(nnmpc_qp::SC_MULT, &m_stage, (size_t)gmax * h->n * sizeof(double));
   if (ptr_kind == NNMPC_HOST) {
-    DevRes& res = h->res;
     if (!rc) rc = res.slot(nnmpc_qp::SC_U, &u_stage, (size_t)gmax * ncol * sizeof(double));
-    if (!rc && active) rc = res.slot(nnmpc_qp::SC_ACT, &a_stage, (size_t)gmax * h->words * sizeof(uint32_t));
-    if (!rc && status) rc = res.slot(nnmpc_qp::SC_ST, &s_stage, (size_t)gmax * sizeof(int32_t));
     if (!rc && iters) rc = res.slot(nnmpc_qp::SC_IT, &i_stage, (size_t)gmax * 2 * sizeof(int32_t));
     if (!rc && guess) rc = res.slot(nnmpc_qp::SC_GUESS, &g_stage, (size_t)gmax * h->n);
   }
@@ -2293,26 +2315,33 @@ int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const doub
       STEP_(hipMemcpyAsync(h->lb_d, lb + (size_t)b0 * h->nu, (size_t)nb * h->nu * 8, hipMemcpyHostToDevice, h->stream));
       STEP_(hipMemcpyAsync(h->ub_d, ub + (size_t)b0 * h->nu, (size_t)nb * h->nu * 8, hipMemcpyHostToDevice, h->stream));
       x0d = h->in_stage; lbd = h->lb_d; ubd = h->ub_d;
-      ud = u_stage; ad = active ? a_stage : nullptr; sd = status ? s_stage : nullptr; idv = iters ? i_stage : nullptr;
+      ud = u_stage; ad = a_stage; sd = s_stage; idv = iters ? i_stage : nullptr;
     } else {
       x0d = x0 + (size_t)b0 * h->n_aug; lbd = lb + (size_t)b0 * h->nu; ubd = ub + (size_t)b0 * h->nu;
       if (guess) gd = guess + (size_t)b0 * h->n;
       ud = u + (size_t)b0 * ncol;
-      ad = active ? active + (size_t)b0 * h->words : nullptr;
-      sd = status ? status + b0 : nullptr;
+      ad = active ? active + (size_t)b0 * h->words : a_stage;
+      sd = status ? status + b0 : s_stage;
       idv = iters ? iters + 2 * (size_t)b0 : nullptr;
     }
     if (rc) break;
     if (h->have_inverse && h->opts.method != 1) rc = solve_segment_asm(h, nb, x0d, lbd, ubd, gd, ud, ad, sd, idv);
     else rc = solve_segment(h, nb, x0d, lbd, ubd, gd, ud, ad, sd, idv);
+    double* md = mult ? (ptr_kind == NNMPC_HOST ? m_stage : mult + (size_t)b0 * h->n) : nullptr;
+    if (!rc && mult) rc = launch_mult(h, nb, x0d, ud, ad, sd, md);
     if (!rc && ptr_kind == NNMPC_HOST) {
       STEP_(hipMemcpy(u + (size_t)b0 * ncol, u_stage, (size_t)nb * ncol * 8, hipMemcpyDeviceToHost));
       if (active) STEP_(hipMemcpy(active + (size_t)b0 * h->words, a_stage, (size_t)nb * h->words * 4, hipMemcpyDeviceToHost));
       if (status) STEP_(hipMemcpy(status + b0, s_stage, (size_t)nb * 4, hipMemcpyDeviceToHost));
       if (iters) STEP_(hipMemcpy(iters + 2 * (size_t)b0, i_stage, (size_t)nb * 8, hipMemcpyDeviceToHost));
+      if (mult) STEP_(hipMemcpy(mult + (size_t)b0 * h->n, m_stage, (size_t)nb * h->n * 8, hipMemcpyDeviceToHost));
     }
   }
 #undef STEP_
+  if (mult && ptr_kind == NNMPC_DEVICE && !rc && stream_sync(h->stream) != hipSuccess) {   // the multipliers are there when the call returns
+    set_error("nnmpc_qp_solve_batch_dual: the multiplier kernel failed");
+    rc = NNMPC_EHIP;
+  }
   if (h->profiling) {
     h->ev_recs.push_back({EV_TOTAL, e_tot0, ev_mark(h, h->stream), 0.0});
     stream_sync(h->stream);
@@ -2320,6 +2349,62 @@ int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const doub
   }
   if (h->ev_failed) { h->ev_failed = false; if (!rc) rc = NNMPC_EHIP; }
   return rc;
+  GUARD_END
+}
+
+int nnmpc_qp_solve_batch_ex(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub,
+                            const uint8_t* guess, double* u, uint32_t* active, int32_t* status,
+                            int32_t* iters, int32_t ptr_kind, int32_t out_kind) {
+  return solve_batch_impl(h, B, x0, lb, ub, guess, u, active, status, iters, ptr_kind, out_kind, nullptr);
+}
+
+int nnmpc_qp_solve_batch_dual(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub,
+                              const uint8_t* guess, double* u, uint32_t* active, int32_t* status,
+                              int32_t* iters, double* mult, int32_t ptr_kind, int32_t out_kind) {
+  if (mult && out_kind == NNMPC_OUT_FIRST_MOVE) {
+    set_error("nnmpc_qp_solve_batch_dual: multipliers need the whole sequence, which NNMPC_OUT_FIRST_MOVE does not form in the caller's u");
+    return NNMPC_EINVAL;
+  }
+  return solve_batch_impl(h, B, x0, lb, ub, guess, u, active, status, iters, ptr_kind, out_kind, mult);
+}
+
+int nnmpc_qp_multipliers(nnmpc_qp* h, int32_t B, const double* x0, const double* u, const uint32_t* active,
+                         const int32_t* status, double* mult, int32_t ptr_kind) {
+  if (!h || B < 0 || !x0 || !u || !active || !mult || (ptr_kind != NNMPC_HOST && ptr_kind != NNMPC_DEVICE)) {
+    set_error("nnmpc_qp_multipliers: bad arguments");
+    return NNMPC_EINVAL;
+  }
+  if (B == 0) return NNMPC_OK;
+  GUARD_BEGIN
+  HIPCHK(hipSetDevice(h->device));
+  if (ptr_kind == NNMPC_DEVICE) {
+    if (int rc = launch_mult(h, B, x0, u, active, status, mult)) return rc;
+    HIPCHK(stream_sync(h->stream));
+    if (h->profiling) ev_collect(h);
+    if (h->ev_failed) { h->ev_failed = false; return NNMPC_EHIP; }
+    return NNMPC_OK;
+  }
+  const int G = std::min(h->seg_max, (int)B);
+  DevRes& res = h->res;
+  double *x0d = nullptr, *ud = nullptr, *md = nullptr; uint32_t* ad = nullptr; int32_t* sd = nullptr;
+  if (int rc = res.slot(nnmpc_qp::SC_M_X0, &x0d, (size_t)G * h->n_aug * 8)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_M_U, &ud, (size_t)G * h->n * 8)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_M_ACT, &ad, (size_t)G * h->words * 4)) return rc;
+  if (status) if (int rc = res.slot(nnmpc_qp::SC_M_ST, &sd, (size_t)G * 4)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_MULT, &md, (size_t)G * h->n * 8)) return rc;
+  for (int b0 = 0; b0 < B; b0 += G) {
+    const int nb = std::min(G, B - b0);
+    HIPCHK(hipMemcpyAsync(x0d, x0 + (size_t)b0 * h->n_aug, (size_t)nb * h->n_aug * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(ud, u + (size_t)b0 * h->n, (size_t)nb * h->n * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(ad, active + (size_t)b0 * h->words, (size_t)nb * h->words * 4, hipMemcpyHostToDevice, h->stream));
+    if (status) HIPCHK(hipMemcpyAsync(sd, status + b0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+    if (int rc = launch_mult(h, nb, x0d, ud, ad, sd, md)) return rc;
+    HIPCHK(hipMemcpyAsync(mult + (size_t)b0 * h->n, md, (size_t)nb * h->n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h->stream));
+  }
+  if (h->profiling) ev_collect(h);
+  if (h->ev_failed) { h->ev_failed = false; return NNMPC_EHIP; }
+  return NNMPC_OK;
   GUARD_END
 }
 

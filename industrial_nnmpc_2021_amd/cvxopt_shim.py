@@ -1,7 +1,8 @@
 """cvxopt-shaped entry point: ``qp(P, q, G, h[, A, b]) -> {'x': (n,1), 'status': ...}``.
 
 The reference reaches its solver only through ``cvx.solvers.qp(*array_to_matrix(...))``
-and reads only ``solution['x']`` (lib/linearMPC.py:304-306, :503-506).  Installing
+and reads only ``solution['x']`` (lib/linearMPC.py:304-306, :503-506).  The regulator forms also
+return cvxopt's ``'z'`` (2n, 1), the multipliers of G x <= h, and ``'s'`` = h - G x.  Installing
 this module as ``sys.modules['cvxopt']`` therefore runs the
 reference's own classes on the HIP path without touching them:
 
@@ -103,7 +104,7 @@ def qp(P, q, G, h, A=None, b=None, **kw):
         if not np.allclose(hb, hb[0]):
             raise NotImplementedError("qp shim: bounds must be the same for every stage (tile of [uub; -ulb])")
         solver, _ = _solver_for("box", P, nu, lambda: (P, None))
-        out = solver.solve_batch(q.reshape(1, -1), -hb[0, nu:].reshape(1, -1), hb[0, :nu].reshape(1, -1))
+        out = solver.solve_batch(q.reshape(1, -1), -hb[0, nu:].reshape(1, -1), hb[0, :nu].reshape(1, -1), multipliers=True)
         x = out["u"].reshape(-1)
     else:
         rp = _reparam_map(G, n)
@@ -132,12 +133,15 @@ def qp(P, q, G, h, A=None, b=None, **kw):
         # objective in wt: 1/2 (wt - c)' Pw (wt - c) + q' Y (wt - c)  ->  linear term Y'q - Pw c
         Ps = np.tril(P) + np.tril(P, -1).T
         qw = Y.T @ q - Y.T @ (Ps @ (Y @ c))
-        out = solver.solve_batch(qw.reshape(1, -1), lo[0].reshape(1, -1), up[0].reshape(1, -1))
+        # (the box problem's rows are the rows of G x <= h and its stationarity is this problem's multiplied by Mg^-T: same z)
+        out = solver.solve_batch(qw.reshape(1, -1), lo[0].reshape(1, -1), up[0].reshape(1, -1), multipliers=True)
         x = Y @ (out["u"].reshape(-1) - c)
     st = {0: "optimal", 1: "unknown", 2: "unknown"}[int(out["status"][0])]
     if out["status"][0] == 2:
         raise ArithmeticError("KKT factorisation failed")
-    return {"x": x.reshape(-1, 1), "status": st, "iterations": int(out["ipm_iters"][0])}
+    z = solver.mult_to_z(out["mult"], out["active"]).reshape(-1, 1)
+    return {"x": x.reshape(-1, 1), "s": (h - G @ x).reshape(-1, 1), "z": z, "status": st,
+            "iterations": int(out["ipm_iters"][0])}
 
 
 solvers = types.SimpleNamespace(qp=qp, options={})

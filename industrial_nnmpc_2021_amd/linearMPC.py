@@ -289,19 +289,29 @@ class DenseQPRegulator:
             self._qp = BatchedBoxQP(Pb, tqb, self.Nu, max_batch=self._max_batch, **self._opts)
         return self._qp
 
-    def solve_batch(self, X0, ulb=None, uub=None, first_move_only=False, guess=None):
+    def solve_batch(self, X0, ulb=None, uub=None, first_move_only=False, guess=None, multipliers=False):
         """B problems at once.  X0 (B, n_aug); ulb/uub (B, Nu) or (Nu,[1]) (default: self.ulb/uub).
 
         Returns (U (B, N*Nu) or (B, Nu), info) with info = dict(active (B, 2 N Nu) bool in the
         row order of G, status (B,), ipm_iters, factorizations).  ``guess`` (B, N*Nu) uint8
         (0 free / 1 upper / 2 lower) warm-starts the solver on an estimated active set.
+
+        ``multipliers=True`` (not with first_move_only) adds info["z"] (B, 2 N Nu): the multipliers of the rows of
+        G v <= h in the row order of G, like info["active"] -- P v + q + G'z = 0 with z >= 0 at an optimum, zero on
+        the rows that are not active, NaN rows for problems that were not solved (info["mult"] keeps them per
+        variable).  For a re-parameterised (unstable) plant the solver works on the box problem in
+        w = Mg v + tK tA x0 (_box_form), whose inequality rows are the rows of G v <= h themselves; its stationarity
+        Pw w + qw + tE'z = 0 is the reference's P v + q + G'z = 0 multiplied by Mg^-T (Pw = Mg^-T P Mg^-1,
+        G = tE Mg), so the same z serves both problems and nothing is transformed.
         """
         lb = self.ulb if ulb is None else ulb
         ub = self.uub if uub is None else uub
         out = self._solver().solve_batch(np.asarray(X0, float).reshape(-1, self.Nx),
                                          np.asarray(lb, float).reshape(-1, self.Nu),
                                          np.asarray(ub, float).reshape(-1, self.Nu), guess=guess,
-                                         first_move_only=first_move_only)
+                                         first_move_only=first_move_only, multipliers=multipliers)
+        if multipliers:
+            out["z"] = self._solver().mult_to_z(out["mult"], out["active"])
         U = out.pop("u")
         self.last_info = out
         return U, out

@@ -215,14 +215,18 @@ class BatchedBoxQP:
                 break
             self.prepare_farfield(W.value)
 
-    def solve_batch(self, x0, lb, ub, guess=None, first_move_only=False):
+    def solve_batch(self, x0, lb, ub, guess=None, first_move_only=False, multipliers=False):
         """numpy in / numpy out.  x0 (B, n_aug), lb/ub (B, nu) or (nu,); guess: optional (B, n) uint8
         active-set estimate (0 free, 1 upper, 2 lower) that replaces the PDIP phase (warm start).
 
         Returns dict(u (B, n) -- or (B, nu) with first_move_only, all the reference keeps of a solve in its
         simulation loops (lib/linearMPC.py:856) --, active (B, 2n) bool in the row order of the reference's G,
-        status (B,), ipm_iters (B,), factorizations (B,)).
+        status (B,), ipm_iters (B,), factorizations (B,)).  multipliers=True adds mult (B, n): the bound multipliers
+        of the delivered u (include/nnmpc.h: nnmpc_qp_multipliers -- -(P u + q) at an upper bound, +(P u + q) at a lower
+        one, +0.0 on free variables, NaN rows for problems that were not solved); not available with first_move_only.
         """
+        if multipliers and first_move_only:
+            raise ValueError("multipliers=True needs the whole sequence: not available with first_move_only=True")
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, self.n_aug)
         B = x0.shape[0]
         lb = np.ascontiguousarray(np.broadcast_to(np.asarray(lb, np.float64).reshape(-1, self.nu), (B, self.nu)))
@@ -236,12 +240,54 @@ class BatchedBoxQP:
             guess = np.ascontiguousarray(guess, dtype=np.uint8).reshape(B, self.n)
             gp = guess.ctypes.data_as(C.c_void_p)
         p = lambda a: a.ctypes.data_as(C.c_void_p)
-        _lib.check(self._lib.nnmpc_qp_solve_batch_ex(
-            self._h, B, p(x0), p(lb), p(ub), gp, p(u), p(act), p(status), p(iters), _lib.HOST,
-            _lib.OUT_FIRST_MOVE if first_move_only else _lib.OUT_SEQUENCE), "nnmpc_qp_solve_batch_ex")
+        mult = np.empty((B, self.n)) if multipliers else None
+        if multipliers:
+            _lib.check(self._lib.nnmpc_qp_solve_batch_dual(
+                self._h, B, p(x0), p(lb), p(ub), gp, p(u), p(act), p(status), p(iters), p(mult), _lib.HOST,
+                _lib.OUT_SEQUENCE), "nnmpc_qp_solve_batch_dual")
+        else:
+            _lib.check(self._lib.nnmpc_qp_solve_batch_ex(
+                self._h, B, p(x0), p(lb), p(ub), gp, p(u), p(act), p(status), p(iters), _lib.HOST,
+                _lib.OUT_FIRST_MOVE if first_move_only else _lib.OUT_SEQUENCE), "nnmpc_qp_solve_batch_ex")
         self._farfield_auto()
         bits = np.unpackbits(act.view(np.uint8), axis=1, bitorder="little")[:, :2 * self.n].astype(bool)
-        return dict(u=u, active=bits, status=status, ipm_iters=iters[:, 0], factorizations=iters[:, 1])
+        out = dict(u=u, active=bits, status=status, ipm_iters=iters[:, 0], factorizations=iters[:, 1])
+        if multipliers:
+            out["mult"] = mult
+        return out
+
+    def multipliers(self, x0, u, active_words, status=None):
+        """The bound multipliers of ANY (x0, u, active) alone (nnmpc_qp_multipliers): a pure function of the handle's P and
+        tq.  x0 (B, n_aug), u (B, n), active_words (B, ceil(2n/32)) uint32 as the C ABI packs them (active_to_words), status
+        (B,) or None; numpy in, numpy out.  Returns mult (B, n).  (With a solve, on device buffers: solve_batch_device(mult=...).)"""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, self.n_aug)
+        B = x0.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(B, self.n)
+        act = np.ascontiguousarray(active_words, dtype=np.uint32).reshape(B, self.words)
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(B)
+        mult = np.empty((B, self.n))
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_qp_multipliers(self._h, B, p(x0), p(u), p(act), p(st), p(mult), _lib.HOST),
+                   "nnmpc_qp_multipliers")
+        return mult
+
+    def mult_to_z(self, mult, active):
+        """mult (B, n) per variable + active (B, 2n) bool -> z (B, 2n) in the row order of the reference's G: the
+        variable's multiplier on its active row, zero on the others; a NaN row of mult stays a NaN row."""
+        n, nu = self.n, self.nu
+        k, c = np.arange(n) // nu, np.arange(n) % nu
+        up, lo = k * 2 * nu + c, k * 2 * nu + nu + c
+        z = np.zeros((mult.shape[0], 2 * n))
+        z[:, up] = np.where(active[:, up], mult, 0.0)
+        z[:, lo] = np.where(active[:, lo], mult, 0.0)
+        z[np.isnan(mult).all(axis=1)] = np.nan
+        return z
+
+    def active_to_words(self, active):
+        """(B, 2n) bool rows of G -> (B, ceil(2n/32)) uint32 words as the C ABI packs them (bit i = row i)."""
+        a = np.zeros((active.shape[0], self.words * 32), np.uint8)
+        a[:, :2 * self.n] = active
+        return np.ascontiguousarray(np.packbits(a, axis=1, bitorder="little")).view(np.uint32)
 
     def active_to_state(self, active):
         """(B, 2n) bool rows of G -> (B, n) uint8 per-variable state (the `guess` format)."""
@@ -250,10 +296,19 @@ class BatchedBoxQP:
         return (active[:, k * 2 * nu + c].astype(np.uint8) + 2 * active[:, k * 2 * nu + nu + c].astype(np.uint8))
 
     def solve_batch_device(self, B, x0, lb, ub, u, active=None, status=None, iters=None, guess=None,
-                           first_move_only=False):
+                           first_move_only=False, mult=None):
         """HBM-resident buffers (objects with data_ptr(): _lib.DeviceArray, torch CUDA tensors; f64/u32/i32/u8).
-        u is (B, n), or (B, nu) with first_move_only."""
+        u is (B, n), or (B, nu) with first_move_only.  mult: optional (B, n) f64 buffer for the bound multipliers
+        (nnmpc_qp_solve_batch_dual; not with first_move_only)."""
         q = lambda a: (_ptr(a)[0] if a is not None else None)
+        if mult is not None:
+            if first_move_only:
+                raise ValueError("mult needs the whole sequence: not available with first_move_only=True")
+            _lib.check(self._lib.nnmpc_qp_solve_batch_dual(
+                self._h, B, q(x0), q(lb), q(ub), q(guess), q(u), q(active), q(status), q(iters), q(mult), _lib.DEVICE,
+                _lib.OUT_SEQUENCE), "nnmpc_qp_solve_batch_dual")
+            self._farfield_auto()
+            return
         _lib.check(self._lib.nnmpc_qp_solve_batch_ex(
             self._h, B, q(x0), q(lb), q(ub), q(guess), q(u), q(active), q(status), q(iters), _lib.DEVICE,
             _lib.OUT_FIRST_MOVE if first_move_only else _lib.OUT_SEQUENCE), "nnmpc_qp_solve_batch_ex")
