@@ -136,6 +136,11 @@ typedef struct {
   int64_t asm_overlapped_passes; /* full-width passes that ran beside the round of the problems still running (asm_overlap) */
   double mult_ms;            /* hipEvent time of the bound-multiplier kernel (asm_mult_k: nnmpc_qp_solve_batch_dual, nnmpc_qp_multipliers; profiling on) */
   int64_t mult_launches;     /* ... and its launches (one per segment) */
+  double sens_ms;            /* hipEvent time of the sensitivity kernels (sens_k, both instances: nnmpc_qp_sensitivity; profiling on) */
+  int64_t sens_launches;     /* ... and their launches (at most one per instance and segment) */
+  int64_t sens_lds_problems; /* problems nnmpc_qp_sensitivity ran in the LDS instance (sets of at most 160 bounds, and the flagged ones); counted always */
+  int64_t sens_slab_problems; /* ... and in the slab instance (161 to 768 bounds) */
+  double sens_total_ms;      /* hipEvent time of whole nnmpc_qp_sensitivity calls on the handle's stream, the host's sorting between the launches included (profiling on) */
 } nnmpc_qp_stats;
 
 const char* nnmpc_last_error(void);
@@ -203,6 +208,31 @@ int nnmpc_qp_multipliers(nnmpc_qp* h, int32_t B, const double* x0, const double*
 int nnmpc_qp_solve_batch_dual(nnmpc_qp* h, int32_t B, const double* x0, const double* lb, const double* ub,
                               const uint8_t* guess, double* u, uint32_t* active, int32_t* status,
                               int32_t* iters, double* mult, int32_t ptr_kind, int32_t out_kind);
+
+/* Directional derivatives of the solution map (x0, lb, ub) -> u* restricted to a delivered active set.  For problem b, variable
+ * i = k nu + c and direction d with perturbations dx0 (n_aug), dlb (nu), dub (nu); A = the variables with a bit set, F = the rest:
+ *     du_i = dub_c (upper bit of i set) | dlb_c (lower bit set)            -- copied, bit for bit (a NULL dlb / dub: +0.0)
+ *     du_F = -P_FF^-1 (tq_F dx0 + P_FA du_A)
+ * evaluated through the inverse on the handle:  t = Kunc dx0,  lam = (Hinv_AA)^-1 (t_A - du_A),  du = t - Hinv[:, A] lam,  so that
+ * P du + tq dx0 = 0 on the free rows and = -lam on the active ones.  It equals the directional derivative of u* wherever the set is
+ * locally constant (strict complementarity); for a finite step u + du is the exact optimum at the perturbed data as long as it is
+ * feasible and mult + dmult >= 0.  One factorisation of Hinv_AA per problem serves all D directions (csrc/qp_sens.h); sets of up
+ * to 160 bounds are factored in LDS, up to 768 in a slab of device memory.
+ * active: B x ceil(2n/32) words as delivered; status: B or NULL; dx0: B x D x n_aug; dlb, dub: B x D x nu each or NULL (zeros)
+ *   ->  du: B x D x n (NNMPC_OUT_SEQUENCE) or B x D x nu (NNMPC_OUT_FIRST_MOVE: the first stage alone, without the two products of
+ *       the sequence);  dmult: B x D x n or NULL, the definition of nnmpc_qp_multipliers applied to (dx0, du, active) -- it is linear,
+ *       so this is the change of mult, and (du, dmult) satisfies stationarity on the active rows by construction
+ *       (NNMPC_OUT_SEQUENCE only: NNMPC_EINVAL with NNMPC_OUT_FIRST_MOVE, as the solves);  flag: B or NULL:
+ *       0 computed | 1 more than 768 bounds | 2 no answer: status NNMPC_ST_NUMERIC, both bits of one variable, or a non-finite
+ *       perturbation in any of the problem's directions | 3 non-positive pivot of Hinv_AA.  Every row of a problem whose flag is not 0
+ *       is quiet NaN throughout (du and dmult); the other problems are not affected.
+ * A row with status NNMPC_ST_MAXITER is computed from its delivered set like any other and is as little certified as its u.
+ * Needs an accepted inverse (nnmpc_qp_set_inverse; NNMPC_EINVAL without) and no far-field factors.  D < 1, a NULL active, dx0 or du,
+ * a bad ptr_kind or out_kind: NNMPC_EINVAL.  B = 0: NNMPC_OK, nothing is written.  Synchronous, and a pure function of the handle's
+ * P, tq, Hinv, Kunc and the arguments. */
+int nnmpc_qp_sensitivity(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* active, const int32_t* status, const double* dx0,
+                         const double* dlb, const double* dub, double* du, double* dmult, int32_t* flag,
+                         int32_t ptr_kind, int32_t out_kind);
 
 /* Enables the shared-inverse active-set pass: Hinv = P^-1 (n x n, fp64), Kunc = -Hinv tq (n x n_aug).
  * All samples share P (reference lib/linearMPC.py:472), so on an active set A the equality-constrained

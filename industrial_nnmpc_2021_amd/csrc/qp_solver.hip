@@ -33,6 +33,7 @@
 #include "qp_small.h"
 #include "qp_predict.h"
 #include "qp_mult.h"
+#include "qp_sens.h"
 #include "dev_res.h"
 static constexpr int ASM_SMALL9_LDS_MAX = 100 * 1024;   // dynamic LDS the nine-block instance of asm_small_k may ask for (81 KB at n = 1024, nu = 64)
 
@@ -760,6 +761,10 @@ struct nnmpc_qp {
   // grow-only slots of the owner: staging of host-pointer calls, compacted copies for the PDIP fallback
   enum { SC_U = 0, SC_ACT, SC_ST, SC_IT, SC_GUESS, SC_FB_GUESS, SC_FB_LIST, SC_FB_X0, SC_FB_LB, SC_FB_UB, SC_FB_U, SC_FB_ACT, SC_FB_ST, SC_FB_IT,
          SC_MULT, SC_M_X0, SC_M_U, SC_M_ACT, SC_M_ST,   // bound multipliers: the staged result; the staged inputs of nnmpc_qp_multipliers
+         // nnmpc_qp_sensitivity: staged inputs and outputs of host-pointer calls; the segment's counts, launch list and flags; the
+         // padded dX0, T = dX0 Kunc', LAM, X = LAM Hinv', the active words once per row (for asm_mult_k); the slab instance's factors
+         SC_S_ACT, SC_S_ST, SC_S_DX0, SC_S_DLB, SC_S_DUB, SC_S_DU, SC_S_DM, SC_S_FLAG, SC_S_CNT, SC_S_LIST,
+         SC_S_XP, SC_S_T, SC_S_LAM, SC_S_X, SC_S_AREP, SC_S_SLAB,
          SC_COUNT };
   DevRes res{SC_COUNT};         // owns every buffer, stream and event below and above
   int ldu, nout;        // layout of the caller's u buffer for the call in progress (nnmpc_qp_solve_batch_ex)
@@ -820,7 +825,7 @@ hipEvent_t ev_mark(nnmpc_qp* h, hipStream_t st) {
   return e;
 }
 // What a profiling record times (EvRec::kind): where ev_collect adds it up.
-enum EvKind { EV_PANEL = 0, EV_DIAG, EV_TRSV, EV_TOTAL, EV_LAMBDA, EV_GEMM, EV_UPDATE, EV_LAMBDA32, EV_LAMBDA64, EV_SIDE, EV_PREDICT, EV_MULT };
+enum EvKind { EV_PANEL = 0, EV_DIAG, EV_TRSV, EV_TOTAL, EV_LAMBDA, EV_GEMM, EV_UPDATE, EV_LAMBDA32, EV_LAMBDA64, EV_SIDE, EV_PREDICT, EV_MULT, EV_SENS, EV_SENS_TOTAL };
 struct EvScope {
   nnmpc_qp* h; int kind; double flops; hipEvent_t e0; hipStream_t st;
   EvScope(nnmpc_qp* h_, EvKind kind_, double flops_, hipStream_t st_ = nullptr) : h(h_), kind(kind_), flops(flops_), e0(nullptr), st(st_ ? st_ : h_->stream) {
@@ -846,6 +851,8 @@ void ev_collect(nnmpc_qp* h) {
     else if (r.kind == EV_LAMBDA64) { h->stats.asm_lambda64_ms += ms; h->stats.asm_lambda64_launches += 1; }
     else if (r.kind == EV_SIDE) h->stats.asm_side_ms += ms;
     else if (r.kind == EV_MULT) { h->stats.mult_ms += ms; h->stats.mult_launches += 1; }
+    else if (r.kind == EV_SENS) { h->stats.sens_ms += ms; h->stats.sens_launches += 1; }
+    else if (r.kind == EV_SENS_TOTAL) h->stats.sens_total_ms += ms;
     else if (r.kind == EV_PREDICT) { h->stats.asm_predict_ms += ms; h->stats.asm_predict_flops += r.flops; }   // (launches: counted at the launch, profiling or not)
   }
   h->ev_recs.clear();
@@ -1900,6 +1907,8 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   HIPCHK(hipFuncSetAttribute((const void*)asm_wide_t_k, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));
   HIPCHK(hipFuncSetAttribute((const void*)asm_small_k<9, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_SMALL9_LDS_MAX));
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_kdyn_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+  HIPCHK(hipFuncSetAttribute((const void*)sens_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sens_lds_bytes<false>()));
+  HIPCHK(hipFuncSetAttribute((const void*)sens_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sens_lds_bytes<true>()));
   if (int rc = set_lds_attrs<128>()) return rc;
   if (int rc = set_lds_attrs<64>()) return rc;
 
@@ -2403,6 +2412,157 @@ int nnmpc_qp_multipliers(nnmpc_qp* h, int32_t B, const double* x0, const double*
     HIPCHK(stream_sync(h->stream));
   }
   if (h->profiling) ev_collect(h);
+  if (h->ev_failed) { h->ev_failed = false; return NNMPC_EHIP; }
+  return NNMPC_OK;
+  GUARD_END
+}
+
+// One segment of nnmpc_qp_sensitivity on device pointers: nb problems, D directions each (qp_sens.h).  du: nb D x n (seq) or x nu.
+struct SensWork {
+  bool seq; int D;
+  int* cnt; int* list; double* xp; double* T; double* lam; double* X; uint32_t* arep;
+  std::vector<int> hcnt, hlist;
+};
+static int sens_segment(nnmpc_qp* h, SensWork& w, int nb, const uint32_t* act, const int32_t* st, const double* dx0, const double* dlb,
+                        const double* dub, double* du, double* dmult, int32_t* flag) {
+  const int n = h->n, np = h->np, nu = h->nu, n_aug = h->n_aug, ka = h->ka, D = w.D;
+  const size_t rows = (size_t)nb * D, mpad = (rows + 127) / 128 * 128;
+  // the host sorts the segment into the two instances from one read-back of the counts (and takes the window of the second product)
+  hipLaunchKernelGGL(sens_count_k, dim3((nb + 3) / 4), dim3(256), 0, h->stream, act, h->words, n, nu, nb, w.cnt);
+  HIPCHK(hipGetLastError());
+  w.hcnt.resize(2 * (size_t)nb); w.hlist.resize(nb);
+  HIPCHK(hipMemcpyAsync(w.hcnt.data(), w.cnt, 2 * (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(stream_sync(h->stream));
+  int nl = 0, ns = 0, hi = -1;
+  for (int b = 0; b < nb; ++b) {
+    const int m = w.hcnt[2 * b];
+    if (m > SENS_M_LDS && m <= SENS_M_MAX) ++ns;
+    if (m <= SENS_M_MAX) hi = std::max(hi, w.hcnt[2 * b + 1]);
+  }
+  nl = nb - ns;
+  for (int b = 0, il = 0, is = nl; b < nb; ++b) {
+    const int m = w.hcnt[2 * b];
+    if (m > SENS_M_LDS && m <= SENS_M_MAX) w.hlist[is++] = b; else w.hlist[il++] = b;
+  }
+  HIPCHK(hipMemcpyAsync(w.list, w.hlist.data(), (size_t)nb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const int W = std::min(np, (hi + 16) / 16 * 16);           // columns of LAM in use (0: no active bound in the segment)
+  if (w.seq) {
+    hipLaunchKernelGGL(sens_pad_k, dim3((unsigned)std::min<size_t>((mpad * ka + 255) / 256, 65535)), dim3(256), 0, h->stream,
+                       w.xp, dx0, rows, n_aug, ka, mpad);
+    HIPCHK(hipGetLastError());
+    gemm64(h, w.T, np, w.xp, ka, h->Kunc64, ka, (int)mpad, np, ka);                      // T = dX0 Kunc'
+    if (W > 0) HIPCHK(hipMemset2DAsync(w.lam, (size_t)np * 8, 0, (size_t)W * 8, mpad, h->stream));
+  }
+  SensArgs a;
+  a.H64 = h->H64; a.Kunc64 = h->Kunc64; a.active = act; a.status = st; a.dx0 = dx0; a.dlb = dlb; a.dub = dub;
+  a.slab = nullptr; a.lam = w.seq ? w.lam : nullptr; a.ldl = np; a.du0 = w.seq ? nullptr : du; a.flag = flag;
+  a.n = n; a.np = np; a.nu = nu; a.n_aug = n_aug; a.ka = ka; a.words = h->words; a.D = D;
+  if (nl > 0) {
+    a.list = w.list; a.count = nl;
+    EvScope es(h, EV_SENS, 0.0);
+    hipLaunchKernelGGL(sens_k<false>, dim3(nl), dim3(SENS_THREADS), sens_lds_bytes<false>(), h->stream, a);
+    HIPCHK(hipGetLastError());
+  }
+  if (ns > 0) {
+    const int pool = std::min(ns, 64);                       // workgroups, each with a slab of 2.4 MB, that walk the list together
+    if (int rc = h->res.slot(nnmpc_qp::SC_S_SLAB, &a.slab, (size_t)pool * SENS_SLAB * 8)) return rc;
+    a.list = w.list + nl; a.count = ns;
+    EvScope es(h, EV_SENS, 0.0);
+    hipLaunchKernelGGL(sens_k<true>, dim3(pool), dim3(SENS_THREADS), sens_lds_bytes<true>(), h->stream, a);
+    HIPCHK(hipGetLastError());
+  }
+  h->stats.sens_lds_problems += nl; h->stats.sens_slab_problems += ns;
+  if (w.seq) {
+    if (W > 0) gemm64(h, w.X, np, w.lam, np, h->H64, np, (int)mpad, np, W);             // X = LAM Hinv[:, 0:W]'
+    hipLaunchKernelGGL(sens_epilogue_k, dim3((unsigned)rows), dim3(256), 0, h->stream, du, w.T, W > 0 ? w.X : nullptr, (size_t)np, act,
+                       flag, dlb, dub, dmult ? w.arep : nullptr, n, nu, h->words, D);
+    HIPCHK(hipGetLastError());
+    if (dmult)
+      if (int rc = launch_mult(h, (int)rows, dx0, du, w.arep, nullptr, dmult)) return rc;
+  }
+  return NNMPC_OK;
+}
+
+int nnmpc_qp_sensitivity(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* active, const int32_t* status, const double* dx0,
+                         const double* dlb, const double* dub, double* du, double* dmult, int32_t* flag,
+                         int32_t ptr_kind, int32_t out_kind) {
+  if (!h || B < 0 || D < 1 || !active || !dx0 || !du || (ptr_kind != NNMPC_HOST && ptr_kind != NNMPC_DEVICE) ||
+      (out_kind != NNMPC_OUT_SEQUENCE && out_kind != NNMPC_OUT_FIRST_MOVE)) {
+    set_error("nnmpc_qp_sensitivity: bad arguments");
+    return NNMPC_EINVAL;
+  }
+  if (dmult && out_kind == NNMPC_OUT_FIRST_MOVE) {
+    set_error("nnmpc_qp_sensitivity: dmult needs the whole sequence, which NNMPC_OUT_FIRST_MOVE does not form");
+    return NNMPC_EINVAL;
+  }
+  if (!h->have_inverse) {
+    set_error("nnmpc_qp_sensitivity: needs an accepted inverse (nnmpc_qp_set_inverse)");
+    return NNMPC_EINVAL;
+  }
+  if (B == 0) return NNMPC_OK;
+  GUARD_BEGIN
+  HIPCHK(hipSetDevice(h->device));
+  const int n = h->n, np = h->np, nu = h->nu, n_aug = h->n_aug, ka = h->ka, words = h->words;
+  const bool seq = out_kind == NNMPC_OUT_SEQUENCE, host = ptr_kind == NNMPC_HOST;
+  const int ncol = seq ? n : nu;
+  // rows (problem, direction) of a segment: the three np-wide row buffers of the sequence output stay within 1 GiB
+  const long long rowcap = seq ? std::max<long long>(128, (1ll << 30) / (3ll * np * 8)) : std::max<long long>(h->seg_max, 1024);
+  const int G = (int)std::min<long long>(std::min<long long>(B, h->seg_max), std::max<long long>(1, rowcap / D));
+  if ((long long)G * D > 0x7fffff00ll) { set_error("nnmpc_qp_sensitivity: D = %d is too large", D); return NNMPC_EINVAL; }
+  const size_t rmax = (size_t)G * D, mpad = (rmax + 127) / 128 * 128;
+  DevRes& res = h->res;
+  SensWork w;
+  w.seq = seq; w.D = D; w.cnt = nullptr; w.list = nullptr; w.xp = w.T = w.lam = w.X = nullptr; w.arep = nullptr;
+  uint32_t* a_st = nullptr; int32_t *s_st = nullptr, *f_st = nullptr;
+  double *x_st = nullptr, *lb_st = nullptr, *ub_st = nullptr, *du_st = nullptr, *dm_st = nullptr;
+#define SLOT_(id, ptr, bytes) if (int rc = res.slot(nnmpc_qp::id, &(ptr), (size_t)(bytes))) return rc
+  SLOT_(SC_S_CNT, w.cnt, 2 * (size_t)G * 4); SLOT_(SC_S_LIST, w.list, (size_t)G * 4);
+  if (host || !flag) SLOT_(SC_S_FLAG, f_st, (size_t)G * 4);
+  if (seq) {
+    SLOT_(SC_S_XP, w.xp, mpad * ka * 8); SLOT_(SC_S_T, w.T, mpad * np * 8); SLOT_(SC_S_LAM, w.lam, mpad * np * 8); SLOT_(SC_S_X, w.X, mpad * np * 8);
+    if (dmult) SLOT_(SC_S_AREP, w.arep, rmax * words * 4);
+  }
+  if (host) {
+    SLOT_(SC_S_ACT, a_st, (size_t)G * words * 4);
+    if (status) SLOT_(SC_S_ST, s_st, (size_t)G * 4);
+    SLOT_(SC_S_DX0, x_st, rmax * n_aug * 8);
+    if (dlb) SLOT_(SC_S_DLB, lb_st, rmax * nu * 8);
+    if (dub) SLOT_(SC_S_DUB, ub_st, rmax * nu * 8);
+    SLOT_(SC_S_DU, du_st, rmax * ncol * 8);
+    if (dmult) SLOT_(SC_S_DM, dm_st, rmax * n * 8);
+  }
+#undef SLOT_
+  hipEvent_t e_tot0 = h->profiling ? ev_mark(h, h->stream) : nullptr;
+  for (int b0 = 0; b0 < B; b0 += G) {
+    const int nb = std::min(G, B - b0);
+    const size_t r0 = (size_t)b0 * D, nr = (size_t)nb * D;
+    const uint32_t* ad = active + (size_t)b0 * words;
+    const int32_t* sd = status ? status + b0 : nullptr;
+    const double *xd = dx0 + r0 * n_aug, *lbd = dlb ? dlb + r0 * nu : nullptr, *ubd = dub ? dub + r0 * nu : nullptr;
+    double *dud = du + r0 * ncol, *dmd = dmult ? dmult + r0 * n : nullptr;
+    int32_t* fd = flag ? flag + b0 : f_st;
+    if (host) {
+      HIPCHK(hipMemcpyAsync(a_st, ad, (size_t)nb * words * 4, hipMemcpyHostToDevice, h->stream));
+      if (status) HIPCHK(hipMemcpyAsync(s_st, sd, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(x_st, xd, nr * n_aug * 8, hipMemcpyHostToDevice, h->stream));
+      if (dlb) HIPCHK(hipMemcpyAsync(lb_st, lbd, nr * nu * 8, hipMemcpyHostToDevice, h->stream));
+      if (dub) HIPCHK(hipMemcpyAsync(ub_st, ubd, nr * nu * 8, hipMemcpyHostToDevice, h->stream));
+      ad = a_st; sd = status ? s_st : nullptr; xd = x_st; lbd = dlb ? lb_st : nullptr; ubd = dub ? ub_st : nullptr;
+      dud = du_st; dmd = dmult ? dm_st : nullptr; fd = f_st;
+    }
+    if (int rc = sens_segment(h, w, nb, ad, sd, xd, lbd, ubd, dud, dmd, fd)) return rc;
+    if (host) {
+      HIPCHK(hipMemcpyAsync(du + r0 * ncol, du_st, nr * ncol * 8, hipMemcpyDeviceToHost, h->stream));
+      if (dmult) HIPCHK(hipMemcpyAsync(dmult + r0 * n, dm_st, nr * n * 8, hipMemcpyDeviceToHost, h->stream));
+      if (flag) HIPCHK(hipMemcpyAsync(flag + b0, f_st, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(stream_sync(h->stream));                          // (the staging and the row buffers are the next segment's)
+  }
+  if (h->profiling) {
+    h->ev_recs.push_back({EV_SENS_TOTAL, e_tot0, ev_mark(h, h->stream), 0.0});
+    HIPCHK(stream_sync(h->stream));
+    ev_collect(h);
+  }
   if (h->ev_failed) { h->ev_failed = false; return NNMPC_EHIP; }
   return NNMPC_OK;
   GUARD_END

@@ -316,6 +316,31 @@ class DenseQPRegulator:
         self.last_info = out
         return U, out
 
+    def sensitivity_batch(self, info, dX0, dulb=None, duub=None, first_move_only=False, multipliers=False):
+        """Directional derivatives of the sequences of a solve_batch call, restricted to its delivered active sets
+        (BatchedBoxQP.sensitivity; include/nnmpc.h: nnmpc_qp_sensitivity).  ``info``: that call's info (its active rows and status are
+        used); dX0 (B, D, n_aug) -- or (B, n_aug) for one direction, the outputs then drop that axis too --, dulb / duub (B, D, Nu)
+        perturbations of the bounds or None (zeros).
+
+        Returns dict(du (B, D, N*Nu) -- (B, D, Nu) with first_move_only --, flag (B,)); ``multipliers=True`` adds dmult (B, D, N*Nu) and
+        dz (B, D, 2 N Nu), the change of info["z"] in the row order of G.  Where the set is locally constant du is the derivative of U
+        along the direction, and inside the critical region U + du is the optimum at X0 + dX0.  For a re-parameterised (unstable) plant
+        nothing changes: the box problem of _box_form is in the input sequence w that solve_batch returns, its linear term is linear
+        in x0, and its rows are the rows of G v <= h, so du is the change of that sequence and dz serves both problems.
+        """
+        qp = self._solver()
+        out = qp.sensitivity(qp.active_to_words(np.asarray(info["active"], bool)), dX0, dlb=dulb, dub=duub, status=info.get("status"),
+                             first_move_only=first_move_only, multipliers=multipliers)
+        if multipliers:
+            dm = out["dmult"]
+            act = np.asarray(info["active"], bool)
+            if dm.ndim == 3:
+                dz = qp.mult_to_z(dm.reshape(-1, qp.n), np.repeat(act, dm.shape[1], axis=0)).reshape(dm.shape[0], dm.shape[1], 2 * qp.n)
+            else:
+                dz = qp.mult_to_z(dm, act)
+            out["dz"] = dz
+        return out
+
     def solve(self, x0):
         """One problem, reference signature: x0 (n_aug, 1) -> useq (N*Nu, 1)  (reference :495-512)."""
         U, info = self.solve_batch(x0.reshape(1, -1), self.ulb.reshape(1, -1), self.uub.reshape(1, -1))

@@ -271,6 +271,35 @@ class BatchedBoxQP:
                    "nnmpc_qp_multipliers")
         return mult
 
+    def sensitivity(self, active_words, dx0, dlb=None, dub=None, status=None, first_move_only=False, multipliers=False):
+        """Directional derivatives of u*(x0, lb, ub) restricted to the delivered active sets (nnmpc_qp_sensitivity, include/nnmpc.h).
+        active_words (B, ceil(2n/32)) uint32 (active_to_words), dx0 (B, D, n_aug), dlb / dub (B, D, nu) or None (zeros), status (B,) or
+        None; numpy in, numpy out.  dx0 (B, n_aug) is one direction (D = 1), and the outputs then drop that axis too.
+        Returns dict(du (B, D, n) -- (B, D, nu) with first_move_only --, flag (B,) int32: 0 computed, 1 more than 768 bounds, 2 no
+        answer, 3 non-positive pivot; NaN rows where flag != 0); multipliers=True adds dmult (B, D, n), the change of mult (not with
+        first_move_only).  Needs the inverse (Kunc="auto" or set_inverse)."""
+        if multipliers and first_move_only:
+            raise ValueError("multipliers=True needs the whole sequence: not available with first_move_only=True")
+        act = np.ascontiguousarray(active_words, dtype=np.uint32).reshape(-1, self.words)
+        B = act.shape[0]
+        dx0 = np.asarray(dx0, dtype=np.float64)
+        one = dx0.ndim == 2
+        dx0 = np.ascontiguousarray(dx0.reshape(B, -1, self.n_aug))
+        D = dx0.shape[1]
+        pert = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, np.float64).reshape(B, D, self.nu))
+        dlb, dub = pert(dlb), pert(dub)
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(B)
+        du = np.empty((B, D, self.nu if first_move_only else self.n))
+        dmult = np.empty((B, D, self.n)) if multipliers else None
+        flag = np.empty(B, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_qp_sensitivity(self._h, B, D, p(act), p(st), p(dx0), p(dlb), p(dub), p(du), p(dmult), p(flag), _lib.HOST,
+                                                  _lib.OUT_FIRST_MOVE if first_move_only else _lib.OUT_SEQUENCE), "nnmpc_qp_sensitivity")
+        out = dict(du=du[:, 0] if one else du, flag=flag)
+        if multipliers:
+            out["dmult"] = dmult[:, 0] if one else dmult
+        return out
+
     def mult_to_z(self, mult, active):
         """mult (B, n) per variable + active (B, 2n) bool -> z (B, 2n) in the row order of the reference's G: the
         variable's multiplier on its active row, zero on the others; a NaN row of mult stays a NaN row."""
