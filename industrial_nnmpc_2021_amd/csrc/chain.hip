@@ -499,7 +499,8 @@ struct nnmpc_ts {
   double *Pr = nullptr, *E = nullptr, *esc = nullptr, *lb = nullptr, *ub = nullptr;   // E: rows scaled by esc
   double dsc = 1.0;
   hipStream_t stream = nullptr;
-  DevRes res{6};                                            // owns all of it; its slots: staging for host-pointer calls
+  enum { SC_Q = 0, SC_E, SC_US, SC_LAM, SC_ACT, SC_ST, SC_COUNT };   // slots: staging of nnmpc_ts_solve_batch's arguments
+  DevRes res{SC_COUNT};                                     // owns all of it
 };
 
 extern "C" {
@@ -582,31 +583,18 @@ int nnmpc_ts_solve_batch(nnmpc_ts* h, int32_t B, const double* q, const double* 
   if (B == 0) return NNMPC_OK;
   HIPCHK(hipSetDevice(h->device));
   const int nu = h->nu, nz = h->nz, N = nu + nz;
-  const double *qd = q, *ed = e;
-  double *ud = us, *ld = lam_eq;
-  unsigned char* ad = active;
-  int* sd = status;
-  if (ptr_kind == NNMPC_HOST) {
-    double *a = nullptr, *b = nullptr;
-    DevRes& res = h->res;
-    if (int rc = res.slot(0, &a, (size_t)B * nu * 8)) return rc;
-    if (int rc = res.slot(1, &b, std::max<size_t>((size_t)B * nz, 1) * 8)) return rc;
-    if (int rc = res.slot(2, &ud, (size_t)B * nu * 8)) return rc;
-    if (lam_eq) if (int rc = res.slot(3, &ld, std::max<size_t>((size_t)B * nz, 1) * 8)) return rc;
-    if (active) if (int rc = res.slot(4, &ad, (size_t)B * nu)) return rc;
-    if (int rc = res.slot(5, &sd, (size_t)B * 4)) return rc;
-    HIPCHK(hipMemcpyAsync(a, q, (size_t)B * nu * 8, hipMemcpyHostToDevice, h->stream));
-    if (nz) HIPCHK(hipMemcpyAsync(b, e, (size_t)B * nz * 8, hipMemcpyHostToDevice, h->stream));
-    qd = a; ed = b;
-  }
+  const double *qd, *ed;
+  double *ud, *ld; unsigned char* ad; int* sd;
+  Staging stg{h->res, h->stream, ptr_kind == NNMPC_HOST};   // lax: any ptr_kind but NNMPC_HOST counts as NNMPC_DEVICE (callers may rely on it)
+  if (int rc = stg.in(&qd, q, 0, B, nu, nnmpc_ts::SC_Q)) return rc;
+  if (int rc = stg.in(&ed, e, 0, B, nz, nnmpc_ts::SC_E)) return rc;
+  if (int rc = stg.out(&ud, us, 0, B, nu, nnmpc_ts::SC_US)) return rc;
+  if (int rc = stg.out(&ld, lam_eq, 0, B, nz, nnmpc_ts::SC_LAM)) return rc;
+  if (int rc = stg.out(&ad, active, 0, B, nu, nnmpc_ts::SC_ACT)) return rc;
+  if (int rc = stg.out(&sd, status, 0, B, 1, nnmpc_ts::SC_ST)) return rc;
   const size_t lds = ((size_t)N * (N + 2) + N) * sizeof(double);
   hipLaunchKernelGGL(ts_solve_k, dim3(B), dim3(64), lds, h->stream, B, nu, nz, h->Pr, h->E, h->esc, h->dsc, h->lb, h->ub, qd, ed, ud, ld, ad, sd, 1e-9);
-  if (ptr_kind == NNMPC_HOST) {
-    HIPCHK(hipMemcpyAsync(us, ud, (size_t)B * nu * 8, hipMemcpyDeviceToHost, h->stream));
-    if (lam_eq && nz) HIPCHK(hipMemcpyAsync(lam_eq, ld, (size_t)B * nz * 8, hipMemcpyDeviceToHost, h->stream));
-    if (active) HIPCHK(hipMemcpyAsync(active, ad, (size_t)B * nu, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(status, sd, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-  }
+  if (int rc = stg.copy_out()) return rc;
   HIPCHK(stream_sync(h->stream));
   HIPCHK(hipGetLastError());
   return NNMPC_OK;

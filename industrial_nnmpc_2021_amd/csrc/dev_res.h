@@ -1,6 +1,7 @@
 // What every handle of libnnmpc_hip.so owns on the device, in one place: the error macros, and DevRes -- the owner of a
 // handle's device memory, pinned host memory, streams and events.  A handle holds one DevRes; its named pointers, streams
-// and events are plain non-owning copies of what the owner made.  No kernels here: a host compiler builds this header.
+// and events are plain non-owning copies of what the owner made.  Staging forms the device pointers of a batched call's
+// arguments on top of the owner's slots.  No kernels here: a host compiler builds this header.
 #pragma once
 #include <stddef.h>
 #include <algorithm>
@@ -142,6 +143,50 @@ struct DevRes {
     for (Slot& s : pinned_slots) { if (s.p) (void)hipHostFree(s.p); s = Slot{}; }
     for (hipStream_t s : streams) (void)hipStreamDestroy(s);
     events.clear(); pool.clear(); mem.clear(); pinned.clear(); streams.clear();
+  }
+};
+
+// The arguments of a batched call whose caller hands host or device pointers (nnmpc.h, ptr_kind), one segment at a time:
+// in() and out() give the device pointer of rows [r0, r0 + nr) of one argument with `per` elements a row.  A null argument
+// gives a null pointer and no copy; a device pointer is offset; a host pointer gets slot `slot` of the owner (or `fixed`, a
+// buffer the handle made at create), inputs copied in on the stream at once, outputs by copy_out() after the segment's
+// kernels.  keep: the kernels need the output on the device whether or not the caller asked for it; it is not copied out
+// unless asked for.  Slots grow only and a call's first segment is its largest, so no later segment moves a buffer.
+struct Staging {
+  DevRes& res; hipStream_t stream; bool host;
+  struct Copy { void* dst; const void* src; size_t bytes; };
+  Copy pending[8] = {};
+  int npending = 0;
+
+  template <class T>
+  int in(const T** d, const T* p, size_t r0, size_t nr, size_t per, size_t slot, T* fixed = nullptr) {
+    *d = nullptr;
+    if (!p) return NNMPC_OK;
+    if (!host) { *d = p + r0 * per; return NNMPC_OK; }
+    const size_t bytes = nr * per * sizeof(T);
+    T* q = fixed;
+    if (!q) if (int rc = res.slot(slot, &q, std::max<size_t>(bytes, 1))) return rc;
+    if (bytes) HIPCHK(hipMemcpyAsync(q, p + r0 * per, bytes, hipMemcpyHostToDevice, stream));
+    *d = q;
+    return NNMPC_OK;
+  }
+  template <class T>
+  int out(T** d, T* p, size_t r0, size_t nr, size_t per, size_t slot, bool keep = false) {
+    *d = nullptr;
+    if (!p && !keep) return NNMPC_OK;
+    if (!host && p) { *d = p + r0 * per; return NNMPC_OK; }
+    const size_t bytes = nr * per * sizeof(T);
+    if (p && npending == (int)(sizeof pending / sizeof pending[0])) { set_error("Staging: more than %d outputs", npending); return NNMPC_EINVAL; }
+    if (int rc = res.slot(slot, d, std::max<size_t>(bytes, 1))) return rc;
+    if (p && bytes) pending[npending++] = Copy{p + r0 * per, *d, bytes};
+    return NNMPC_OK;
+  }
+  // Enqueues the segment's outputs for the caller; they are there once the stream has been waited for.
+  int copy_out() {
+    const int np = npending;
+    npending = 0;
+    for (int i = 0; i < np; ++i) HIPCHK(hipMemcpyAsync(pending[i].dst, pending[i].src, pending[i].bytes, hipMemcpyDeviceToHost, stream));
+    return NNMPC_OK;
   }
 };
 

@@ -754,17 +754,19 @@ struct nnmpc_qp {
   bool profiling;
   bool gemm_error = false;      // a GEMM was asked for in a form no kernel implements (gemm64): the call in progress fails
   size_t ev_used;               // profiling events of res.pool taken by the call in progress
-  bool ev_failed = false;       // one of them could not be created: nnmpc_qp_solve_batch_ex fails at its end
+  bool ev_failed = false;       // one of them could not be created: the call in progress fails at its end (CallScope)
   struct EvRec { int kind; hipEvent_t e0, e1; double flops; };
   std::vector<EvRec> ev_recs;
   nnmpc_qp_stats stats;
-  // grow-only slots of the owner: staging of host-pointer calls, compacted copies for the PDIP fallback
-  enum { SC_U = 0, SC_ACT, SC_ST, SC_IT, SC_GUESS, SC_FB_GUESS, SC_FB_LIST, SC_FB_X0, SC_FB_LB, SC_FB_UB, SC_FB_U, SC_FB_ACT, SC_FB_ST, SC_FB_IT,
-         SC_MULT, SC_M_X0, SC_M_U, SC_M_ACT, SC_M_ST,   // bound multipliers: the staged result; the staged inputs of nnmpc_qp_multipliers
-         // nnmpc_qp_sensitivity: staged inputs and outputs of host-pointer calls; the segment's counts, launch list and flags; the
-         // padded dX0, T = dX0 Kunc', LAM, X = LAM Hinv', the active words once per row (for asm_mult_k); the slab instance's factors
-         SC_S_ACT, SC_S_ST, SC_S_DX0, SC_S_DLB, SC_S_DUB, SC_S_DU, SC_S_DM, SC_S_FLAG, SC_S_CNT, SC_S_LIST,
-         SC_S_XP, SC_S_T, SC_S_LAM, SC_S_X, SC_S_AREP, SC_S_SLAB,
+  // grow-only slots of the owner
+  enum { // staging of a call's arguments (Staging), one per role whichever entry point runs: a handle runs one call at a time.
+         // u / du, active words, status, iters, guess, mult / dmult, an x0-shaped input (nnmpc_qp_multipliers, dx0), dlb, dub, flag
+         SC_U = 0, SC_ACT, SC_ST, SC_IT, SC_GUESS, SC_MULT, SC_X0, SC_LB, SC_UB, SC_FLAG,
+         // compacted copies for the PDIP fallback: live inside a solve, beside the caller's staging
+         SC_FB_GUESS, SC_FB_LIST, SC_FB_X0, SC_FB_LB, SC_FB_UB, SC_FB_U, SC_FB_ACT, SC_FB_ST, SC_FB_IT,
+         // nnmpc_qp_sensitivity's work: the segment's counts and launch list; the padded dX0, T = dX0 Kunc', LAM, X = LAM Hinv',
+         // the active words once per row (for asm_mult_k); the slab instance's factors
+         SC_S_CNT, SC_S_LIST, SC_S_XP, SC_S_T, SC_S_LAM, SC_S_X, SC_S_AREP, SC_S_SLAB,
          SC_COUNT };
   DevRes res{SC_COUNT};         // owns every buffer, stream and event below and above
   int ldu, nout;        // layout of the caller's u buffer for the call in progress (nnmpc_qp_solve_batch_ex)
@@ -858,6 +860,36 @@ void ev_collect(nnmpc_qp* h) {
   h->ev_recs.clear();
   h->ev_used = 0;
 }
+// One call of an entry point that launches on the handle.  When profiling, and with a `total` kind, the whole call is timed
+// from here to finish().  finish(rc) is the end of a call that got there: the profiling records are added up once the stream
+// has drained, and an event that could not be created fails the call.  Every other way out drops the call's records and
+// its pending ev_failed, so that the next call on the handle starts clean.
+struct CallScope {
+  nnmpc_qp* h; int total; hipEvent_t e0 = nullptr;
+  explicit CallScope(nnmpc_qp* h_, int total_ = -1) : h(h_), total(total_) {
+    if (h->profiling && total >= 0) e0 = ev_mark(h, h->stream);
+  }
+  int finish(int rc) {
+    if (h->profiling) {
+      if (total >= 0) h->ev_recs.push_back({total, e0, ev_mark(h, h->stream), 0.0});
+      const hipError_t e = stream_sync(h->stream);
+      if (e == hipSuccess) ev_collect(h);
+      else if (!rc) { set_error("stream_sync at the end of the call: %s", hipGetErrorString(e)); rc = NNMPC_EHIP; }
+    }
+    return h->ev_failed && !rc ? NNMPC_EHIP : rc;           // (ev_mark left the error text)
+  }
+  ~CallScope() {
+    h->ev_recs.clear();
+    h->ev_used = 0;
+    h->ev_failed = false;
+  }
+};
+// The layout of u for a nested solve (pdip_fallback's compacted copies), the caller's again on the way out.
+struct LayoutScope {
+  nnmpc_qp* h; int ldu, nout;
+  LayoutScope(nnmpc_qp* h_, int ldu_, int nout_) : h(h_), ldu(h_->ldu), nout(h_->nout) { h->ldu = ldu_; h->nout = nout_; }
+  ~LayoutScope() { h->ldu = ldu; h->nout = nout; }
+};
 
 template <int NB>
 void launch_gemm32(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda, const float* B,
@@ -1673,14 +1705,12 @@ int pdip_fallback(AsmCall& c, const std::vector<int>& fb, const double* x0_dev, 
   // a problem whose set had settled but failed the check with P (inverse too inaccurate for its x) starts the polish
   // on that set; the others (not settled, too large, not positive definite) run the PDIP from scratch
   hipLaunchKernelGGL(asm_gather_guess_k, dim3(cntf), dim3(128), 0, s, guessc, h->asm_st, h->asm_state, list, cntf, h->n);
-  const int ldu_caller = h->ldu, nout_caller = h->nout;
-  h->ldu = h->n; h->nout = h->n;                       // the compacted copies hold whole sequences
   for (int b0 = 0; b0 < cntf && !rc; b0 += h->seg_max) {
+    const LayoutScope whole(h, h->n, h->n);            // the compacted copies hold whole sequences
     const int nb = std::min(h->seg_max, cntf - b0);
     rc = solve_segment(h, nb, x0c + (size_t)b0 * h->n_aug, lbc + (size_t)b0 * h->nu, ubc + (size_t)b0 * h->nu, guessc + (size_t)b0 * h->n,
                        uc + (size_t)b0 * h->n, actc + (size_t)b0 * h->words, stc + b0, itc + 2 * (size_t)b0);
   }
-  h->ldu = ldu_caller; h->nout = nout_caller;
   if (!rc) {
     hipLaunchKernelGGL(asm_scatter_k, dim3(cntf), dim3(128), 0, s, a.u_out, a.act_out, st_dev, a.iters_out, uc, actc, stc, itc,
                        list, cntf, h->n, h->words, h->ldu, h->nout);
@@ -2291,73 +2321,36 @@ static int solve_batch_impl(nnmpc_qp* h, int32_t B, const double* x0, const doub
   HIPCHK(hipSetDevice(h->device));
   const int G = h->seg_max;
   const int ncol = out_kind == NNMPC_OUT_FIRST_MOVE ? h->nu : h->n;   // columns of the caller's u
+  const size_t n = h->n, nu = h->nu, n_aug = h->n_aug, words = h->words;
   h->ldu = ncol; h->nout = ncol;
-  hipEvent_t e_tot0 = h->profiling ? ev_mark(h, h->stream) : nullptr;
-  // device staging for the outputs when the caller hands host pointers (owned by the handle, grown on demand)
-  double* u_stage = nullptr; uint32_t* a_stage = nullptr; int32_t* s_stage = nullptr; int32_t* i_stage = nullptr;
-  unsigned char* g_stage = nullptr;
-  double* m_stage = nullptr;
-  const int gmax = std::min(G, (int)B);
-  int rc = 0;
-  DevRes& res = h->res;
-  // the multiplier kernel reads the segment's active words and status on the device: kept in the handle's staging when the caller
-  // does not ask for them (or hands host pointers)
-  const bool own_act = mult && (ptr_kind == NNMPC_HOST || !active), own_st = mult && (ptr_kind == NNMPC_HOST || !status);
-  if (!rc && (own_act || (ptr_kind == NNMPC_HOST && active))) rc = res.slot(nnmpc_qp::SC_ACT, &a_stage, (size_t)gmax * h->words * sizeof(uint32_t));
-  if (!rc && (own_st || (ptr_kind == NNMPC_HOST && status))) rc = res.slot(nnmpc_qp::SC_ST, &s_stage, (size_t)gmax * sizeof(int32_t));
-  if (!rc && mult && ptr_kind == NNMPC_HOST) rc = res.slot(nnmpc_qp::SC_MULT, &m_stage, (size_t)gmax * h->n * sizeof(double));
-  if (ptr_kind == NNMPC_HOST) {
-    if (!rc) rc = res.slot(nnmpc_qp::SC_U, &u_stage, (size_t)gmax * ncol * sizeof(double));
-    if (!rc && iters) rc = res.slot(nnmpc_qp::SC_IT, &i_stage, (size_t)gmax * 2 * sizeof(int32_t));
-    if (!rc && guess) rc = res.slot(nnmpc_qp::SC_GUESS, &g_stage, (size_t)gmax * h->n);
-  }
-  hipError_t he = hipSuccess;
-#define STEP_(x) do { if (!rc && he == hipSuccess) { he = (x); if (he != hipSuccess) { set_error("%s: %s", #x, hipGetErrorString(he)); rc = NNMPC_EHIP; } } } while (0)
-  for (int b0 = 0; b0 < B && !rc; b0 += G) {
+  CallScope call(h, EV_TOTAL);
+  Staging stg{h->res, h->stream, ptr_kind == NNMPC_HOST};   // lax: any ptr_kind but NNMPC_HOST counts as NNMPC_DEVICE (callers may rely on it)
+  for (int b0 = 0; b0 < B; b0 += G) {
     const int nb = std::min(G, B - b0);
     const double *x0d, *lbd, *ubd;
-    double* ud; uint32_t* ad; int32_t* sd; int32_t* idv;
-    const unsigned char* gd = nullptr;
-    if (ptr_kind == NNMPC_HOST) {
-      if (guess) { STEP_(hipMemcpyAsync(g_stage, guess + (size_t)b0 * h->n, (size_t)nb * h->n, hipMemcpyHostToDevice, h->stream)); gd = g_stage; }
-      STEP_(hipMemcpyAsync(h->in_stage, x0 + (size_t)b0 * h->n_aug, (size_t)nb * h->n_aug * 8, hipMemcpyHostToDevice, h->stream));
-      STEP_(hipMemcpyAsync(h->lb_d, lb + (size_t)b0 * h->nu, (size_t)nb * h->nu * 8, hipMemcpyHostToDevice, h->stream));
-      STEP_(hipMemcpyAsync(h->ub_d, ub + (size_t)b0 * h->nu, (size_t)nb * h->nu * 8, hipMemcpyHostToDevice, h->stream));
-      x0d = h->in_stage; lbd = h->lb_d; ubd = h->ub_d;
-      ud = u_stage; ad = a_stage; sd = s_stage; idv = iters ? i_stage : nullptr;
-    } else {
-      x0d = x0 + (size_t)b0 * h->n_aug; lbd = lb + (size_t)b0 * h->nu; ubd = ub + (size_t)b0 * h->nu;
-      if (guess) gd = guess + (size_t)b0 * h->n;
-      ud = u + (size_t)b0 * ncol;
-      ad = active ? active + (size_t)b0 * h->words : a_stage;
-      sd = status ? status + b0 : s_stage;
-      idv = iters ? iters + 2 * (size_t)b0 : nullptr;
-    }
-    if (rc) break;
-    if (h->have_inverse && h->opts.method != 1) rc = solve_segment_asm(h, nb, x0d, lbd, ubd, gd, ud, ad, sd, idv);
-    else rc = solve_segment(h, nb, x0d, lbd, ubd, gd, ud, ad, sd, idv);
-    double* md = mult ? (ptr_kind == NNMPC_HOST ? m_stage : mult + (size_t)b0 * h->n) : nullptr;
-    if (!rc && mult) rc = launch_mult(h, nb, x0d, ud, ad, sd, md);
-    if (!rc && ptr_kind == NNMPC_HOST) {
-      STEP_(hipMemcpy(u + (size_t)b0 * ncol, u_stage, (size_t)nb * ncol * 8, hipMemcpyDeviceToHost));
-      if (active) STEP_(hipMemcpy(active + (size_t)b0 * h->words, a_stage, (size_t)nb * h->words * 4, hipMemcpyDeviceToHost));
-      if (status) STEP_(hipMemcpy(status + b0, s_stage, (size_t)nb * 4, hipMemcpyDeviceToHost));
-      if (iters) STEP_(hipMemcpy(iters + 2 * (size_t)b0, i_stage, (size_t)nb * 8, hipMemcpyDeviceToHost));
-      if (mult) STEP_(hipMemcpy(mult + (size_t)b0 * h->n, m_stage, (size_t)nb * h->n * 8, hipMemcpyDeviceToHost));
-    }
+    const unsigned char* gd;
+    double *ud, *md; uint32_t* ad; int32_t *sd, *idv;
+    if (int rc = stg.in(&gd, guess, b0, nb, n, nnmpc_qp::SC_GUESS)) return rc;
+    if (int rc = stg.in(&x0d, x0, b0, nb, n_aug, 0, h->in_stage)) return rc;
+    if (int rc = stg.in(&lbd, lb, b0, nb, nu, 0, h->lb_d)) return rc;
+    if (int rc = stg.in(&ubd, ub, b0, nb, nu, 0, h->ub_d)) return rc;
+    if (int rc = stg.out(&ud, u, b0, nb, ncol, nnmpc_qp::SC_U)) return rc;
+    // the multiplier kernel reads the segment's active words and status on the device, asked for or not
+    if (int rc = stg.out(&ad, active, b0, nb, words, nnmpc_qp::SC_ACT, mult != nullptr)) return rc;
+    if (int rc = stg.out(&sd, status, b0, nb, 1, nnmpc_qp::SC_ST, mult != nullptr)) return rc;
+    if (int rc = stg.out(&idv, iters, b0, nb, 2, nnmpc_qp::SC_IT)) return rc;
+    if (int rc = stg.out(&md, mult, b0, nb, n, nnmpc_qp::SC_MULT)) return rc;
+    if (int rc = h->have_inverse && h->opts.method != 1 ? solve_segment_asm(h, nb, x0d, lbd, ubd, gd, ud, ad, sd, idv)
+                                                        : solve_segment(h, nb, x0d, lbd, ubd, gd, ud, ad, sd, idv)) return rc;
+    if (mult) if (int rc = launch_mult(h, nb, x0d, ud, ad, sd, md)) return rc;
+    if (int rc = stg.copy_out()) return rc;
+    if (stg.host) HIPCHK(stream_sync(h->stream));            // (the staging is the next segment's)
   }
-#undef STEP_
-  if (mult && ptr_kind == NNMPC_DEVICE && !rc && stream_sync(h->stream) != hipSuccess) {   // the multipliers are there when the call returns
+  if (mult && !stg.host && stream_sync(h->stream) != hipSuccess) {   // the multipliers are there when the call returns
     set_error("nnmpc_qp_solve_batch_dual: the multiplier kernel failed");
-    rc = NNMPC_EHIP;
+    return NNMPC_EHIP;
   }
-  if (h->profiling) {
-    h->ev_recs.push_back({EV_TOTAL, e_tot0, ev_mark(h, h->stream), 0.0});
-    stream_sync(h->stream);
-    ev_collect(h);
-  }
-  if (h->ev_failed) { h->ev_failed = false; if (!rc) rc = NNMPC_EHIP; }
-  return rc;
+  return call.finish(NNMPC_OK);
   GUARD_END
 }
 
@@ -2386,34 +2379,22 @@ int nnmpc_qp_multipliers(nnmpc_qp* h, int32_t B, const double* x0, const double*
   if (B == 0) return NNMPC_OK;
   GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
-  if (ptr_kind == NNMPC_DEVICE) {
-    if (int rc = launch_mult(h, B, x0, u, active, status, mult)) return rc;
-    HIPCHK(stream_sync(h->stream));
-    if (h->profiling) ev_collect(h);
-    if (h->ev_failed) { h->ev_failed = false; return NNMPC_EHIP; }
-    return NNMPC_OK;
-  }
-  const int G = std::min(h->seg_max, (int)B);
-  DevRes& res = h->res;
-  double *x0d = nullptr, *ud = nullptr, *md = nullptr; uint32_t* ad = nullptr; int32_t* sd = nullptr;
-  if (int rc = res.slot(nnmpc_qp::SC_M_X0, &x0d, (size_t)G * h->n_aug * 8)) return rc;
-  if (int rc = res.slot(nnmpc_qp::SC_M_U, &ud, (size_t)G * h->n * 8)) return rc;
-  if (int rc = res.slot(nnmpc_qp::SC_M_ACT, &ad, (size_t)G * h->words * 4)) return rc;
-  if (status) if (int rc = res.slot(nnmpc_qp::SC_M_ST, &sd, (size_t)G * 4)) return rc;
-  if (int rc = res.slot(nnmpc_qp::SC_MULT, &md, (size_t)G * h->n * 8)) return rc;
+  CallScope call(h);
+  Staging stg{h->res, h->stream, ptr_kind == NNMPC_HOST};
+  const int G = stg.host ? std::min(h->seg_max, (int)B) : B;   // device pointers: one launch over the batch
   for (int b0 = 0; b0 < B; b0 += G) {
     const int nb = std::min(G, B - b0);
-    HIPCHK(hipMemcpyAsync(x0d, x0 + (size_t)b0 * h->n_aug, (size_t)nb * h->n_aug * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(ud, u + (size_t)b0 * h->n, (size_t)nb * h->n * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(ad, active + (size_t)b0 * h->words, (size_t)nb * h->words * 4, hipMemcpyHostToDevice, h->stream));
-    if (status) HIPCHK(hipMemcpyAsync(sd, status + b0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+    const double *x0d, *ud; const uint32_t* ad; const int32_t* sd; double* md;
+    if (int rc = stg.in(&x0d, x0, b0, nb, h->n_aug, nnmpc_qp::SC_X0)) return rc;
+    if (int rc = stg.in(&ud, u, b0, nb, h->n, nnmpc_qp::SC_U)) return rc;
+    if (int rc = stg.in(&ad, active, b0, nb, h->words, nnmpc_qp::SC_ACT)) return rc;
+    if (int rc = stg.in(&sd, status, b0, nb, 1, nnmpc_qp::SC_ST)) return rc;
+    if (int rc = stg.out(&md, mult, b0, nb, h->n, nnmpc_qp::SC_MULT)) return rc;
     if (int rc = launch_mult(h, nb, x0d, ud, ad, sd, md)) return rc;
-    HIPCHK(hipMemcpyAsync(mult + (size_t)b0 * h->n, md, (size_t)nb * h->n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = stg.copy_out()) return rc;
     HIPCHK(stream_sync(h->stream));
   }
-  if (h->profiling) ev_collect(h);
-  if (h->ev_failed) { h->ev_failed = false; return NNMPC_EHIP; }
-  return NNMPC_OK;
+  return call.finish(NNMPC_OK);
   GUARD_END
 }
 
@@ -2503,7 +2484,7 @@ int nnmpc_qp_sensitivity(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* acti
   GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
   const int n = h->n, np = h->np, nu = h->nu, n_aug = h->n_aug, ka = h->ka, words = h->words;
-  const bool seq = out_kind == NNMPC_OUT_SEQUENCE, host = ptr_kind == NNMPC_HOST;
+  const bool seq = out_kind == NNMPC_OUT_SEQUENCE;
   const int ncol = seq ? n : nu;
   // rows (problem, direction) of a segment: the three np-wide row buffers of the sequence output stay within 1 GiB
   const long long rowcap = seq ? std::max<long long>(128, (1ll << 30) / (3ll * np * 8)) : std::max<long long>(h->seg_max, 1024);
@@ -2513,58 +2494,35 @@ int nnmpc_qp_sensitivity(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* acti
   DevRes& res = h->res;
   SensWork w;
   w.seq = seq; w.D = D; w.cnt = nullptr; w.list = nullptr; w.xp = w.T = w.lam = w.X = nullptr; w.arep = nullptr;
-  uint32_t* a_st = nullptr; int32_t *s_st = nullptr, *f_st = nullptr;
-  double *x_st = nullptr, *lb_st = nullptr, *ub_st = nullptr, *du_st = nullptr, *dm_st = nullptr;
-#define SLOT_(id, ptr, bytes) if (int rc = res.slot(nnmpc_qp::id, &(ptr), (size_t)(bytes))) return rc
-  SLOT_(SC_S_CNT, w.cnt, 2 * (size_t)G * 4); SLOT_(SC_S_LIST, w.list, (size_t)G * 4);
-  if (host || !flag) SLOT_(SC_S_FLAG, f_st, (size_t)G * 4);
+  if (int rc = res.slot(nnmpc_qp::SC_S_CNT, &w.cnt, 2 * (size_t)G * 4)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_S_LIST, &w.list, (size_t)G * 4)) return rc;
   if (seq) {
-    SLOT_(SC_S_XP, w.xp, mpad * ka * 8); SLOT_(SC_S_T, w.T, mpad * np * 8); SLOT_(SC_S_LAM, w.lam, mpad * np * 8); SLOT_(SC_S_X, w.X, mpad * np * 8);
-    if (dmult) SLOT_(SC_S_AREP, w.arep, rmax * words * 4);
+    if (int rc = res.slot(nnmpc_qp::SC_S_XP, &w.xp, mpad * ka * 8)) return rc;
+    if (int rc = res.slot(nnmpc_qp::SC_S_T, &w.T, mpad * np * 8)) return rc;
+    if (int rc = res.slot(nnmpc_qp::SC_S_LAM, &w.lam, mpad * np * 8)) return rc;
+    if (int rc = res.slot(nnmpc_qp::SC_S_X, &w.X, mpad * np * 8)) return rc;
+    if (dmult) if (int rc = res.slot(nnmpc_qp::SC_S_AREP, &w.arep, rmax * words * 4)) return rc;
   }
-  if (host) {
-    SLOT_(SC_S_ACT, a_st, (size_t)G * words * 4);
-    if (status) SLOT_(SC_S_ST, s_st, (size_t)G * 4);
-    SLOT_(SC_S_DX0, x_st, rmax * n_aug * 8);
-    if (dlb) SLOT_(SC_S_DLB, lb_st, rmax * nu * 8);
-    if (dub) SLOT_(SC_S_DUB, ub_st, rmax * nu * 8);
-    SLOT_(SC_S_DU, du_st, rmax * ncol * 8);
-    if (dmult) SLOT_(SC_S_DM, dm_st, rmax * n * 8);
-  }
-#undef SLOT_
-  hipEvent_t e_tot0 = h->profiling ? ev_mark(h, h->stream) : nullptr;
+  CallScope call(h, EV_SENS_TOTAL);
+  Staging stg{res, h->stream, ptr_kind == NNMPC_HOST};
   for (int b0 = 0; b0 < B; b0 += G) {
     const int nb = std::min(G, B - b0);
     const size_t r0 = (size_t)b0 * D, nr = (size_t)nb * D;
-    const uint32_t* ad = active + (size_t)b0 * words;
-    const int32_t* sd = status ? status + b0 : nullptr;
-    const double *xd = dx0 + r0 * n_aug, *lbd = dlb ? dlb + r0 * nu : nullptr, *ubd = dub ? dub + r0 * nu : nullptr;
-    double *dud = du + r0 * ncol, *dmd = dmult ? dmult + r0 * n : nullptr;
-    int32_t* fd = flag ? flag + b0 : f_st;
-    if (host) {
-      HIPCHK(hipMemcpyAsync(a_st, ad, (size_t)nb * words * 4, hipMemcpyHostToDevice, h->stream));
-      if (status) HIPCHK(hipMemcpyAsync(s_st, sd, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(x_st, xd, nr * n_aug * 8, hipMemcpyHostToDevice, h->stream));
-      if (dlb) HIPCHK(hipMemcpyAsync(lb_st, lbd, nr * nu * 8, hipMemcpyHostToDevice, h->stream));
-      if (dub) HIPCHK(hipMemcpyAsync(ub_st, ubd, nr * nu * 8, hipMemcpyHostToDevice, h->stream));
-      ad = a_st; sd = status ? s_st : nullptr; xd = x_st; lbd = dlb ? lb_st : nullptr; ubd = dub ? ub_st : nullptr;
-      dud = du_st; dmd = dmult ? dm_st : nullptr; fd = f_st;
-    }
+    const uint32_t* ad; const int32_t* sd; const double *xd, *lbd, *ubd;
+    double *dud, *dmd; int32_t* fd;
+    if (int rc = stg.in(&ad, active, b0, nb, words, nnmpc_qp::SC_ACT)) return rc;
+    if (int rc = stg.in(&sd, status, b0, nb, 1, nnmpc_qp::SC_ST)) return rc;
+    if (int rc = stg.in(&xd, dx0, r0, nr, n_aug, nnmpc_qp::SC_X0)) return rc;
+    if (int rc = stg.in(&lbd, dlb, r0, nr, nu, nnmpc_qp::SC_LB)) return rc;
+    if (int rc = stg.in(&ubd, dub, r0, nr, nu, nnmpc_qp::SC_UB)) return rc;
+    if (int rc = stg.out(&dud, du, r0, nr, ncol, nnmpc_qp::SC_U)) return rc;
+    if (int rc = stg.out(&dmd, dmult, r0, nr, n, nnmpc_qp::SC_MULT)) return rc;
+    if (int rc = stg.out(&fd, flag, b0, nb, 1, nnmpc_qp::SC_FLAG, true)) return rc;   // the kernels write it, asked for or not
     if (int rc = sens_segment(h, w, nb, ad, sd, xd, lbd, ubd, dud, dmd, fd)) return rc;
-    if (host) {
-      HIPCHK(hipMemcpyAsync(du + r0 * ncol, du_st, nr * ncol * 8, hipMemcpyDeviceToHost, h->stream));
-      if (dmult) HIPCHK(hipMemcpyAsync(dmult + r0 * n, dm_st, nr * n * 8, hipMemcpyDeviceToHost, h->stream));
-      if (flag) HIPCHK(hipMemcpyAsync(flag + b0, f_st, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
-    }
+    if (int rc = stg.copy_out()) return rc;
     HIPCHK(stream_sync(h->stream));                          // (the staging and the row buffers are the next segment's)
   }
-  if (h->profiling) {
-    h->ev_recs.push_back({EV_SENS_TOTAL, e_tot0, ev_mark(h, h->stream), 0.0});
-    HIPCHK(stream_sync(h->stream));
-    ev_collect(h);
-  }
-  if (h->ev_failed) { h->ev_failed = false; return NNMPC_EHIP; }
-  return NNMPC_OK;
+  return call.finish(NNMPC_OK);
   GUARD_END
 }
 
@@ -2573,6 +2531,7 @@ int nnmpc_qp_debug_factor_solve(nnmpc_qp* h, int32_t B, const float* dvec, const
   if (!h || B <= 0 || B > h->slots || !dvec || !mask || !rhs || !sol) { set_error("debug_factor_solve: bad arguments"); return NNMPC_EINVAL; }
   GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
+  CallScope call(h);
   QpDev& d = h->d;
   const int rows = h->slots;
   std::vector<float> dv((size_t)rows * h->np, 0.f), mk((size_t)rows * h->np, 1.f), rh((size_t)rows * h->np, 0.f);
@@ -2598,8 +2557,7 @@ int nnmpc_qp_debug_factor_solve(nnmpc_qp* h, int32_t B, const float* dvec, const
   HIPCHK(hipMemcpy(so.data(), d.sol, so.size() * 4, hipMemcpyDeviceToHost));
   for (int p = 0; p < B; ++p)
     for (int r = 0; r < h->n; ++r) sol[(size_t)p * h->n + r] = so[(size_t)p * h->np + r];
-  if (h->profiling) { stream_sync(h->stream); ev_collect(h); }
-  return NNMPC_OK;
+  return call.finish(NNMPC_OK);
   GUARD_END
 }
 
@@ -2621,6 +2579,7 @@ int nnmpc_qp_debug_predict(nnmpc_qp* h, int32_t B, const double* x0, const doubl
   if (wide == 1 && !(h->pred[1].L > 0.0)) { set_error("debug_predict: the handle has no 1024-column window (n = %d, nu = %d)", h->n, h->nu); return NNMPC_EINVAL; }
   GUARD_BEGIN
   HIPCHK(hipSetDevice(h->device));
+  CallScope call(h);
   hipStream_t s = h->stream;
   const int nprob = B, segp = ((nprob + 127) / 128) * 128;
   HIPCHK(hipMemcpyAsync(h->in_stage, x0, (size_t)nprob * h->n_aug * 8, hipMemcpyHostToDevice, s));
@@ -2657,8 +2616,7 @@ int nnmpc_qp_debug_predict(nnmpc_qp* h, int32_t B, const double* x0, const doubl
   HIPCHK(hipMemcpy(state, h->asm_st, (size_t)nprob * h->n, hipMemcpyDeviceToHost));
   info[0] = W; info[1] = MR; info[2] = count; info[3] = wide;
   *L = h->pred[wide].L;
-  if (h->profiling) ev_collect(h);
-  return NNMPC_OK;
+  return call.finish(NNMPC_OK);
   GUARD_END
 }
 

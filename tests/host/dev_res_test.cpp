@@ -1,5 +1,5 @@
-// DevRes (csrc/dev_res.h) against a fake HIP runtime: one scripted life of an owner, run clean and then once for every k
-// with the k-th fake call failing.  Links nothing from ROCm: the HIP entry points the header calls are defined here over
+// DevRes and Staging (csrc/dev_res.h) against a fake HIP runtime: one scripted life of an owner, and one host-pointer call
+// of three segments through the staging helper, each run clean and then once for every k with the k-th fake call failing.  Links nothing from ROCm: the HIP entry points the header calls are defined here over
 // malloc, with a set of live objects per kind.  Built and run by tests/test_cpu_dev_res.py:
 //   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I<rocm>/include -I<csrc> -I<include> dev_res_test.cpp
 #include "dev_res.h"
@@ -16,7 +16,7 @@ namespace {
 std::set<void*> g_dev, g_host, g_events, g_streams;         // live objects per kind
 int g_calls = 0, g_fail_at = 0;                             // calls that can fail so far; the one that does (0: none)
 const char* g_failed = nullptr;                             // the call that did
-int g_bad_frees = 0, g_mallocs = 0, g_syncs = 0;
+int g_bad_frees = 0, g_mallocs = 0, g_syncs = 0, g_copies = 0;
 size_t g_last_bytes = 0;
 unsigned g_last_flags = 0;
 char g_err[512];
@@ -55,6 +55,12 @@ hipError_t hipMemset(void* p, int v, size_t n) {
 }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
   if (fails("hipMemcpy")) return hipErrorInvalidValue;
+  memcpy(d, s, n);
+  return hipSuccess;
+}
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) {
+  if (fails("hipMemcpyAsync")) return hipErrorInvalidValue;
+  ++g_copies;
   memcpy(d, s, n);
   return hipSuccess;
 }
@@ -188,6 +194,91 @@ int life(int fail_at) {
   return g_calls;
 }
 
+// One host-pointer call through Staging with the fail_at-th fake call failing (0: none): B = 5 rows in segments of 2, 2 and 1.
+// x (3 doubles a row) is an input in a slot, w (1 double a row) an input in a buffer the handle owns, y (2 ints a row) an
+// output, k (1 int a row) an output the "kernel" needs though the caller passes none, and one input and one output are null.
+// Returns the number of fake calls that can fail.
+int staged_call(int fail_at) {
+  g_calls = 0; g_fail_at = fail_at; g_failed = nullptr; g_bad_frees = 0;
+  const char* before = nullptr;
+  enum { S_X = 0, S_Y, S_K, S_NULL_IN, S_NULL_OUT, S_COUNT };
+  const int B = 5, G = 2;
+  double x[B * 3], w[B];
+  int y[(B + 1) * 2];
+  for (int i = 0; i < B * 3; ++i) x[i] = 10.0 * (i / 3) + i % 3;
+  for (int i = 0; i < B; ++i) w[i] = 100.0 * i;
+  for (int& v : y) v = -7;
+  {
+    DevRes r(S_COUNT);
+    double* fixed = nullptr;
+    bool ok = STEP(r.alloc(&fixed, G));
+    Staging st{r, nullptr, true};
+    int done = 0;                                           // rows delivered
+    for (int b0 = 0; b0 < B && ok; b0 += G) {
+      const int nb = std::min(G, B - b0);
+      const double *xd = nullptr, *wd = nullptr, *none_in = (const double*)0x10;
+      int *yd = nullptr, *kd = nullptr, *none_out = (int*)0x10;
+      const int mallocs = g_mallocs;
+      ok = STEP(st.in(&xd, x, b0, nb, 3, S_X)) && STEP(st.in(&wd, w, b0, nb, 1, S_NULL_IN, fixed)) &&
+           STEP(st.in(&none_in, (const double*)nullptr, b0, nb, 3, S_NULL_IN)) && STEP(st.out(&yd, y, b0, nb, 2, S_Y)) &&
+           STEP(st.out(&kd, (int*)nullptr, b0, nb, 1, S_K, true)) && STEP(st.out(&none_out, (int*)nullptr, b0, nb, 2, S_NULL_OUT));
+      if (!ok) break;
+      CHECK(xd == r.slots[S_X].p && wd == fixed && yd == r.slots[S_Y].p && kd == r.slots[S_K].p && kd);
+      CHECK(!none_in && !none_out && !r.slots[S_NULL_IN].p && !r.slots[S_NULL_OUT].p);   // null optionals: no pointer, no slot
+      if (b0) CHECK(g_mallocs == mallocs);                  // the first segment is the largest: no slot grows after it
+      CHECK(!memcmp(xd, x + b0 * 3, nb * 3 * sizeof(double)) && !memcmp(wd, w + b0, nb * sizeof(double)));   // inputs are in already
+      CHECK(st.npending == 1);                              // y alone goes back
+      for (int i = 0; i < nb; ++i) {                        // the "kernel"
+        kd[i] = (int)wd[i] + 1;
+        for (int j = 0; j < 2; ++j) yd[i * 2 + j] = (int)xd[i * 3 + j] + kd[i];
+      }
+      CHECK(y[b0 * 2] == -7);                               // nothing before copy_out
+      const int copies = g_copies;
+      ok = STEP(st.copy_out());
+      if (ok) { CHECK(g_copies == copies + 1 && st.npending == 0); done = b0 + nb; }
+    }
+    if (ok) CHECK(done == B);
+    for (int i = 0; i < done; ++i)
+      for (int j = 0; j < 2; ++j) CHECK(y[i * 2 + j] == 10 * i + j + 100 * i + 1);
+    for (int i = done * 2; i < (B + 1) * 2; ++i) CHECK(y[i] == -7);   // rows not delivered, and the row past B, untouched
+
+    // device pointers: offsets of the caller's own, no slot, no copy; a kept output the caller did not pass still gets its slot
+    if (ok) {
+      DevRes r2(S_COUNT);
+      Staging dv{r2, nullptr, false};
+      const int copies = g_copies, calls = g_calls;
+      const double *xd = nullptr, *none_in = (const double*)0x10;
+      int *yd = nullptr, *none_out = (int*)0x10, *kd = nullptr;
+      CHECK(dv.in(&xd, x, 2, 2, 3, S_X) == NNMPC_OK && xd == x + 6);
+      CHECK(dv.in(&xd, x, 2, 2, 3, S_X, fixed) == NNMPC_OK && xd == x + 6);
+      CHECK(dv.in(&none_in, (const double*)nullptr, 2, 2, 3, S_NULL_IN) == NNMPC_OK && !none_in);
+      CHECK(dv.out(&yd, y, 4, 1, 2, S_Y) == NNMPC_OK && yd == y + 8);
+      CHECK(dv.out(&yd, y, 4, 1, 2, S_Y, true) == NNMPC_OK && yd == y + 8);
+      CHECK(dv.out(&none_out, (int*)nullptr, 4, 1, 2, S_NULL_OUT) == NNMPC_OK && !none_out);
+      CHECK(dv.copy_out() == NNMPC_OK && g_copies == copies && g_calls == calls && dv.npending == 0);
+      for (const DevRes::Slot& s : r2.slots) CHECK(!s.p);
+      if (STEP(dv.out(&kd, (int*)nullptr, 4, 1, 1, S_K, true))) CHECK(kd && kd == r2.slots[S_K].p);
+      else CHECK(!kd && !r2.slots[S_K].p);
+      CHECK(dv.copy_out() == NNMPC_OK && g_copies == copies);
+    }
+  }
+  CHECK(live() == 0 && g_bad_frees == 0);                   // the owner released everything, whichever step failed
+  if (fail_at) CHECK(g_failed != nullptr);
+  return g_calls;
+}
+
+// More outputs than a call can hold pending is an error return, not a write past the array.
+void staging_bounds() {
+  g_fail_at = 0;
+  DevRes r(1);
+  Staging st{r, nullptr, true};
+  int y[4] = {0, 0, 0, 0}, *d = nullptr;
+  const int cap = (int)(sizeof st.pending / sizeof st.pending[0]);
+  for (int i = 0; i < cap; ++i) CHECK(st.out(&d, y, 0, 1, 4, 0) == NNMPC_OK);
+  g_err[0] = 0;
+  CHECK(st.out(&d, y, 0, 1, 4, 0) == NNMPC_EINVAL && g_err[0] && st.npending == cap);
+}
+
 // An owner that is only destroyed releases too.
 void destructor_releases() {
   g_fail_at = 0;
@@ -206,6 +297,10 @@ int main() {
   CHECK(n >= 25);                                           // every step of the script reached the fake runtime
   for (int k = 1; k <= n; ++k) life(k);
   destructor_releases();
-  printf("dev_res_test: ok (%d fake calls failed in turn, %d checks)\n", n, g_checks);
+  const int m = staged_call(0);
+  CHECK(m >= 1 + 3 + 3 * 2 + 3);                            // the buffer, three slots, two copies in a segment, three out
+  for (int k = 1; k <= m; ++k) staged_call(k);
+  staging_bounds();
+  printf("dev_res_test: ok (%d + %d fake calls failed in turn, %d checks)\n", n, m, g_checks);
   return 0;
 }

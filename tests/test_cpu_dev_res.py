@@ -3,8 +3,11 @@
 tests/host/dev_res_test.cpp is a stand-alone program: it defines the HIP entry points the header calls over malloc, runs
 one scripted life of an owner clean and then once for every k with the k-th fake call failing, and checks after each run
 that nothing is left alive or freed twice, that every failing step returned its documented code with an error text and left
-its output untouched, and that the slots follow the one growth rule.  It needs a host C++ compiler and the HIP headers,
-no GPU and no ROCm library."""
+its output untouched, and that the slots follow the one growth rule.  It then walks one host-pointer call of three segments
+(the last one ragged) through the staging helper of the same header, again clean and with every fake call failing in turn:
+inputs and outputs arrive at their rows, null arguments take no slot and no copy, an output kept on the device gets a slot
+and is not copied out, device pointers are only offset, and the owner still releases everything.  It needs a host C++
+compiler and the HIP headers, no GPU and no ROCm library."""
 import os
 import shutil
 import subprocess
