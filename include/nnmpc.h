@@ -141,6 +141,11 @@ typedef struct {
   int64_t sens_lds_problems; /* problems nnmpc_qp_sensitivity ran in the LDS instance (sets of at most 160 bounds, and the flagged ones); counted always */
   int64_t sens_slab_problems; /* ... and in the slab instance (161 to 768 bounds) */
   double sens_total_ms;      /* hipEvent time of whole nnmpc_qp_sensitivity calls on the handle's stream, the host's sorting between the launches included (profiling on) */
+  double adj_ms;             /* hipEvent time of the adjoint kernels (adj_k, both instances: nnmpc_qp_adjoint; profiling on) */
+  int64_t adj_launches;      /* ... and their launches (at most one per instance and segment) */
+  int64_t adj_lds_problems;  /* problems nnmpc_qp_adjoint ran in the LDS instance (sets of at most 160 bounds, and the flagged ones); counted always */
+  int64_t adj_slab_problems; /* ... and in the slab instance (161 to 768 bounds) */
+  double adj_total_ms;       /* hipEvent time of whole nnmpc_qp_adjoint calls on the handle's stream, the host's sorting between the launches included (profiling on) */
 } nnmpc_qp_stats;
 
 const char* nnmpc_last_error(void);
@@ -233,6 +238,33 @@ int nnmpc_qp_solve_batch_dual(nnmpc_qp* h, int32_t B, const double* x0, const do
 int nnmpc_qp_sensitivity(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* active, const int32_t* status, const double* dx0,
                          const double* dlb, const double* dub, double* du, double* dmult, int32_t* flag,
                          int32_t ptr_kind, int32_t out_kind);
+
+/* The adjoint (vector-Jacobian) product of the same map: the transpose of what nnmpc_qp_sensitivity evaluates, on the same delivered
+ * active set.  For problem b and cotangent d, v a cotangent of the sequence (n entries; in_kind = NNMPC_OUT_FIRST_MOVE: of the first
+ * stage alone, nu entries, the rest zero); A = the variables with a bit set:
+ *     w = (Hinv_AA)^-1 (Hinv[A, :] v),      z = v - E_A w  (w subtracted on the active entries),      gx0 = Kunc' z
+ *     gbound_i = w_i on A, +0.0 on the free variables         -- the cotangent of each variable's own bound
+ *     gub_c = sum { w_i : upper bit of i set, i mod nu = c },   glb_c = sum { w_i : lower bit of i set, i mod nu = c }
+ * so that for every direction (dx0, dlb, dub) of nnmpc_qp_sensitivity and its du
+ *     <v, du> = <gx0, dx0> + <glb, dlb> + <gub, dub>
+ * (with NNMPC_OUT_FIRST_MOVE on both sides: v against the first moves).  One cotangent gives the gradient of a scalar loss of u*
+ * with respect to x0 and the bounds; the nu unit cotangents of the first stage give the local feedback gain du0/dx0 (nu x n_aug)
+ * of the critical region.  One factorisation of Hinv_AA per problem serves all D cotangents (csrc/qp_adj.h, the factorisation of
+ * csrc/qp_sens.h); sets of up to 160 bounds are factored in LDS, up to 768 in a slab of device memory.  Every sum has one order that
+ * depends on the problem alone (no atomics): a problem's rows do not depend on its place in the batch.
+ * active: B x ceil(2n/32) words as delivered; status: B or NULL; v: B x D x n (NNMPC_OUT_SEQUENCE) or B x D x nu (NNMPC_OUT_FIRST_MOVE:
+ * without the two products of the sequence)
+ *   ->  gx0: B x D x n_aug;  glb, gub: B x D x nu each or NULL;  gbound: B x D x n or NULL, every entry written;  flag: B or NULL:
+ *       0 computed | 1 more than 768 bounds | 2 no answer: status NNMPC_ST_NUMERIC, both bits of one variable, or a non-finite
+ *       cotangent in any of the problem's D rows | 3 non-positive pivot of Hinv_AA.  Every row of a problem whose flag is not 0 is quiet
+ *       NaN throughout (every output); the other problems are not affected.
+ * A row with status NNMPC_ST_MAXITER is computed from its delivered set like any other.  Needs an accepted inverse
+ * (nnmpc_qp_set_inverse; NNMPC_EINVAL without) and no far-field factors.  D < 1, a NULL active, v or gx0, a bad ptr_kind or in_kind:
+ * NNMPC_EINVAL, nothing is written.  B = 0: NNMPC_OK, nothing is written.  Synchronous, and a pure function of the handle's Hinv,
+ * Kunc and the arguments. */
+int nnmpc_qp_adjoint(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* active, const int32_t* status /* may be NULL */,
+                     const double* v, double* gx0, double* glb, double* gub, double* gbound, int32_t* flag,
+                     int32_t ptr_kind, int32_t in_kind);
 
 /* Enables the shared-inverse active-set pass: Hinv = P^-1 (n x n, fp64), Kunc = -Hinv tq (n x n_aug).
  * All samples share P (reference lib/linearMPC.py:472), so on an active set A the equality-constrained

@@ -35,7 +35,9 @@ class QpStats(C.Structure):
                 ("asm_predict_flops", C.c_double), ("asm_overlapped_passes", C.c_int64),
                 ("mult_ms", C.c_double), ("mult_launches", C.c_int64),
                 ("sens_ms", C.c_double), ("sens_launches", C.c_int64), ("sens_lds_problems", C.c_int64),
-                ("sens_slab_problems", C.c_int64), ("sens_total_ms", C.c_double)]
+                ("sens_slab_problems", C.c_int64), ("sens_total_ms", C.c_double),
+                ("adj_ms", C.c_double), ("adj_launches", C.c_int64), ("adj_lds_problems", C.c_int64),
+                ("adj_slab_problems", C.c_int64), ("adj_total_ms", C.c_double)]
 
 
 CL_MPC, CL_NN, CL_SATDLQR, CL_US, CL_NN_UNSTD = 0, 1, 2, 3, 4
@@ -56,7 +58,7 @@ class ClSlot(C.Structure):
 
 EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_solve_batch",
            "nnmpc_qp_solve_batch_warm", "nnmpc_qp_solve_batch_ex", "nnmpc_qp_solve_batch_dual", "nnmpc_qp_multipliers",
-           "nnmpc_qp_sensitivity",
+           "nnmpc_qp_sensitivity", "nnmpc_qp_adjoint",
            "nnmpc_qp_set_inverse", "nnmpc_qp_dims",
            "nnmpc_qp_first_moves", "nnmpc_qp_set_farfield", "nnmpc_qp_farfield_missing",
            "nnmpc_qp_set_profiling", "nnmpc_qp_get_stats", "nnmpc_qp_debug_factor_solve", "nnmpc_qp_debug_factor_fail",
@@ -208,6 +210,8 @@ def load():
     lib.nnmpc_qp_multipliers.argtypes = [vp, i32, dp, dp, dp, dp, dp, i32]
     lib.nnmpc_qp_sensitivity.restype = i32                        # (h, B, D, active, status, dx0, dlb, dub, du, dmult, flag, ptr_kind, out_kind)
     lib.nnmpc_qp_sensitivity.argtypes = [vp, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, i32, i32]
+    lib.nnmpc_qp_adjoint.restype = i32                            # (h, B, D, active, status, v, gx0, glb, gub, gbound, flag, ptr_kind, in_kind)
+    lib.nnmpc_qp_adjoint.argtypes = [vp, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, i32, i32]
     lib.nnmpc_qp_first_moves.restype = i32
     lib.nnmpc_qp_first_moves.argtypes = [dp, C.c_int64, dp, i32, i32, dp]
     lib.nnmpc_qp_dims.restype = i32

@@ -93,6 +93,11 @@ struct DevRes {
     return NNMPC_OK;
   }
 
+  // Frees slot i before the handle dies (its next use allocates again).  The caller has waited for whatever used it.
+  void drop_slot(size_t i) {
+    if (i < slots.size() && slots[i].p) { (void)hipFree(slots[i].p); slots[i] = Slot{}; }
+  }
+
   // `count` elements of pinned host memory (default flags; not zeroed).
   template <class T>
   int pinned_alloc(T** p, size_t count) {

@@ -95,19 +95,15 @@ __device__ __forceinline__ void sens_subst(const double* L, double* y1, double* 
   }
 }
 
-// One problem.  L: room for the packed factor of sens_maxm<SLAB>() rows; R: SENS_CHUNK x MAXM, col: MAXM, idx: MAXM (LDS).
+// Steps 1 to 4, shared with adj_k (qp_adj.h).
+// 1. The list of problem b's active variables from its words aw: entry = 2 i + (lower ? 1 : 0), the first sens_maxm<SLAB>() of them in
+//    idx.  Returns m, counted beyond what the list holds; `bad` gains "both bits of one variable".  All threads of the workgroup.
 template <bool SLAB>
-__device__ void sens_problem(const SensArgs& a, int b, double* L, double* R, double* col, int* idx) {
+__device__ int sens_list(const uint32_t* aw, int n, int nu, int* idx, int& bad) {
   constexpr int MAXM = sens_maxm<SLAB>();
   __shared__ int scnt[SENS_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = a.n, np = a.np, nu = a.nu, n_aug = a.n_aug, ka = a.ka, D = a.D;
-  const uint32_t* aw = a.active + (size_t)b * a.words;
-  const size_t r0 = (size_t)b * D;
-  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-
-  // 1. the list: entry = 2 i + (lower ? 1 : 0)
-  int m = 0, bad = a.status && a.status[b] == NNMPC_ST_NUMERIC;
+  int m = 0;
   for (int i0 = 0; i0 < n; i0 += SENS_THREADS) {
     const int i = i0 + tid;
     const int side = i < n ? mult_side(aw, i, nu) : 0;
@@ -123,20 +119,18 @@ __device__ void sens_problem(const SensArgs& a, int b, double* L, double* R, dou
     m += total;
     __syncthreads();
   }
-  // 2. the flag
-  {
-    const double* x = a.dx0 + r0 * n_aug;
-    for (size_t i = tid; i < (size_t)D * n_aug; i += SENS_THREADS) bad |= !sens_finite(x[i]);
-    for (size_t i = tid; i < (size_t)D * nu; i += SENS_THREADS) {
-      if (a.dlb) bad |= !sens_finite(a.dlb[r0 * nu + i]);
-      if (a.dub) bad |= !sens_finite(a.dub[r0 * nu + i]);
-    }
-  }
+  return m;
+}
+// 2. to 4. The flag from the threads' `bad` and m, then S = H64[A, A] and its factor in L.  Returns the flag, the same in every thread.
+template <bool SLAB>
+__device__ int sens_factor(const double* H64, int np, int m, int bad, double* L, double* col, const int* idx) {
+  constexpr int MAXM = sens_maxm<SLAB>();
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int fl = __syncthreads_or(bad) ? 2 : (m > MAXM ? 1 : 0);
   if (fl == 0) {
     // 3. S = H64[A, A], lower triangle
     for (int i = wave; i < m; i += SENS_THREADS / 64) {
-      const double* hr = a.H64 + (size_t)(idx[i] >> 1) * np;
+      const double* hr = H64 + (size_t)(idx[i] >> 1) * np;
       double* Li = L + sens_tri(i);
       for (int j = lane; j <= i; j += 64) Li[j] = hr[idx[j] >> 1];
     }
@@ -161,6 +155,43 @@ __device__ void sens_problem(const SensArgs& a, int b, double* L, double* R, dou
     }
     __syncthreads();
   }
+  return fl;
+}
+// Both substitutions of a chunk of nd right-hand sides (the rows of R), between two workgroup barriers: wave w takes (w, w + 4).
+template <bool SLAB>
+__device__ __forceinline__ void sens_subst_chunk(const double* L, double* R, int m, int nd) {
+  constexpr int MAXM = sens_maxm<SLAB>();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (wave < nd) {
+    if (wave + 4 < nd) sens_subst<true>(L, R + wave * MAXM, R + (wave + 4) * MAXM, m, lane);
+    else sens_subst<false>(L, R + wave * MAXM, nullptr, m, lane);
+  }
+  __syncthreads();
+}
+
+// One problem.  L: room for the packed factor of sens_maxm<SLAB>() rows; R: SENS_CHUNK x MAXM, col: MAXM, idx: MAXM (LDS).
+template <bool SLAB>
+__device__ void sens_problem(const SensArgs& a, int b, double* L, double* R, double* col, int* idx) {
+  constexpr int MAXM = sens_maxm<SLAB>();
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = a.n, np = a.np, nu = a.nu, n_aug = a.n_aug, ka = a.ka, D = a.D;
+  const uint32_t* aw = a.active + (size_t)b * a.words;
+  const size_t r0 = (size_t)b * D;
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+
+  int bad = a.status && a.status[b] == NNMPC_ST_NUMERIC;
+  const int m = sens_list<SLAB>(aw, n, nu, idx, bad);
+  // 2. the flag
+  {
+    const double* x = a.dx0 + r0 * n_aug;
+    for (size_t i = tid; i < (size_t)D * n_aug; i += SENS_THREADS) bad |= !sens_finite(x[i]);
+    for (size_t i = tid; i < (size_t)D * nu; i += SENS_THREADS) {
+      if (a.dlb) bad |= !sens_finite(a.dlb[r0 * nu + i]);
+      if (a.dub) bad |= !sens_finite(a.dub[r0 * nu + i]);
+    }
+  }
+  const int fl = sens_factor<SLAB>(a.H64, np, m, bad, L, col, idx);
   if (tid == 0) a.flag[b] = fl;
   if (fl != 0) {
     if (a.du0)
@@ -195,13 +226,8 @@ __device__ void sens_problem(const SensArgs& a, int b, double* L, double* R, dou
         if (lane == 0) R[c * MAXM + i] = t - (pb ? pb[(size_t)c * nu + cc] : 0.0);
       }
     }
-    __syncthreads();
     // 7. both substitutions, right-hand sides (wave, wave + 4)
-    if (wave < nd) {
-      if (wave + 4 < nd) sens_subst<true>(L, R + wave * MAXM, R + (wave + 4) * MAXM, m, lane);
-      else sens_subst<false>(L, R + wave * MAXM, nullptr, m, lane);
-    }
-    __syncthreads();
+    sens_subst_chunk<SLAB>(L, R, m, nd);
     // 8. lam
     if (a.lam)
       for (int t = tid; t < nd * m; t += SENS_THREADS) {

@@ -34,6 +34,7 @@
 #include "qp_predict.h"
 #include "qp_mult.h"
 #include "qp_sens.h"
+#include "qp_adj.h"
 #include "dev_res.h"
 static constexpr int ASM_SMALL9_LDS_MAX = 100 * 1024;   // dynamic LDS the nine-block instance of asm_small_k may ask for (81 KB at n = 1024, nu = 64)
 
@@ -767,7 +768,11 @@ struct nnmpc_qp {
          // nnmpc_qp_sensitivity's work: the segment's counts and launch list; the padded dX0, T = dX0 Kunc', LAM, X = LAM Hinv',
          // the active words once per row (for asm_mult_k); the slab instance's factors
          SC_S_CNT, SC_S_LIST, SC_S_XP, SC_S_T, SC_S_LAM, SC_S_X, SC_S_AREP, SC_S_SLAB,
+         // nnmpc_qp_adjoint works in the same ones (SC_S_T: the padded V, then Z; SC_S_LAM: Y = V Hinv'; SC_S_X: GX = Z KuncT') and
+         // keeps the transposed image of Kunc64 in a slot of its own (kunct_ok: it holds the accepted pair's)
+         SC_A_KT,
          SC_COUNT };
+  bool kunct_ok = false;
   DevRes res{SC_COUNT};         // owns every buffer, stream and event below and above
   int ldu, nout;        // layout of the caller's u buffer for the call in progress (nnmpc_qp_solve_batch_ex)
 };
@@ -827,7 +832,7 @@ hipEvent_t ev_mark(nnmpc_qp* h, hipStream_t st) {
   return e;
 }
 // What a profiling record times (EvRec::kind): where ev_collect adds it up.
-enum EvKind { EV_PANEL = 0, EV_DIAG, EV_TRSV, EV_TOTAL, EV_LAMBDA, EV_GEMM, EV_UPDATE, EV_LAMBDA32, EV_LAMBDA64, EV_SIDE, EV_PREDICT, EV_MULT, EV_SENS, EV_SENS_TOTAL };
+enum EvKind { EV_PANEL = 0, EV_DIAG, EV_TRSV, EV_TOTAL, EV_LAMBDA, EV_GEMM, EV_UPDATE, EV_LAMBDA32, EV_LAMBDA64, EV_SIDE, EV_PREDICT, EV_MULT, EV_SENS, EV_SENS_TOTAL, EV_ADJ, EV_ADJ_TOTAL };
 struct EvScope {
   nnmpc_qp* h; int kind; double flops; hipEvent_t e0; hipStream_t st;
   EvScope(nnmpc_qp* h_, EvKind kind_, double flops_, hipStream_t st_ = nullptr) : h(h_), kind(kind_), flops(flops_), e0(nullptr), st(st_ ? st_ : h_->stream) {
@@ -855,6 +860,8 @@ void ev_collect(nnmpc_qp* h) {
     else if (r.kind == EV_MULT) { h->stats.mult_ms += ms; h->stats.mult_launches += 1; }
     else if (r.kind == EV_SENS) { h->stats.sens_ms += ms; h->stats.sens_launches += 1; }
     else if (r.kind == EV_SENS_TOTAL) h->stats.sens_total_ms += ms;
+    else if (r.kind == EV_ADJ) { h->stats.adj_ms += ms; h->stats.adj_launches += 1; }
+    else if (r.kind == EV_ADJ_TOTAL) h->stats.adj_total_ms += ms;
     else if (r.kind == EV_PREDICT) { h->stats.asm_predict_ms += ms; h->stats.asm_predict_flops += r.flops; }   // (launches: counted at the launch, profiling or not)
   }
   h->ev_recs.clear();
@@ -1939,6 +1946,8 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_kdyn_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)sens_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sens_lds_bytes<false>()));
   HIPCHK(hipFuncSetAttribute((const void*)sens_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sens_lds_bytes<true>()));
+  HIPCHK(hipFuncSetAttribute((const void*)adj_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sens_lds_bytes<false>()));
+  HIPCHK(hipFuncSetAttribute((const void*)adj_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sens_lds_bytes<true>()));
   if (int rc = set_lds_attrs<128>()) return rc;
   if (int rc = set_lds_attrs<64>()) return rc;
 
@@ -2092,6 +2101,8 @@ int nnmpc_qp_set_inverse(nnmpc_qp* h, const double* Hinv, const double* Kunc) {
   // far-field factors and their verified error (their windows are asked for again once the new pair is in), the predictor images.
   HIPCHK(stream_sync(h->stream));
   h->have_inverse = false;
+  h->kunct_ok = false;                                      // (nnmpc_qp_adjoint builds the accepted pair's image when it first needs it)
+  h->res.drop_slot(nnmpc_qp::SC_A_KT);
   h->pred[0].L = h->pred[1].L = 0.0;
   std::vector<int> refactor;
   for (auto& g : h->far) {
@@ -2398,18 +2409,12 @@ int nnmpc_qp_multipliers(nnmpc_qp* h, int32_t B, const double* x0, const double*
   GUARD_END
 }
 
-// One segment of nnmpc_qp_sensitivity on device pointers: nb problems, D directions each (qp_sens.h).  du: nb D x n (seq) or x nu.
-struct SensWork {
-  bool seq; int D;
-  int* cnt; int* list; double* xp; double* T; double* lam; double* X; uint32_t* arep;
-  std::vector<int> hcnt, hlist;
-};
-static int sens_segment(nnmpc_qp* h, SensWork& w, int nb, const uint32_t* act, const int32_t* st, const double* dx0, const double* dlb,
-                        const double* dub, double* du, double* dmult, int32_t* flag) {
-  const int n = h->n, np = h->np, nu = h->nu, n_aug = h->n_aug, ka = h->ka, D = w.D;
-  const size_t rows = (size_t)nb * D, mpad = (rows + 127) / 128 * 128;
-  // the host sorts the segment into the two instances from one read-back of the counts (and takes the window of the second product)
-  hipLaunchKernelGGL(sens_count_k, dim3((nb + 3) / 4), dim3(256), 0, h->stream, act, h->words, n, nu, nb, w.cnt);
+// The problems of a segment sorted into the two instances of sens_k / adj_k from one read-back of the counts: list (device) holds
+// the nl problems of the LDS instance (sets of at most SENS_M_LDS bounds, and those beyond SENS_M_MAX, which it flags), then the ns
+// of the slab instance; hi = the largest active variable of any problem that is computed (-1: none).
+struct SensSort { int* cnt; int* list; std::vector<int> hcnt, hlist; int nl, ns, hi; };
+static int sens_sort(nnmpc_qp* h, SensSort& w, int nb, const uint32_t* act) {
+  hipLaunchKernelGGL(sens_count_k, dim3((nb + 3) / 4), dim3(256), 0, h->stream, act, h->words, h->n, h->nu, nb, w.cnt);
   HIPCHK(hipGetLastError());
   w.hcnt.resize(2 * (size_t)nb); w.hlist.resize(nb);
   HIPCHK(hipMemcpyAsync(w.hcnt.data(), w.cnt, 2 * (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -2426,6 +2431,22 @@ static int sens_segment(nnmpc_qp* h, SensWork& w, int nb, const uint32_t* act, c
     if (m > SENS_M_LDS && m <= SENS_M_MAX) w.hlist[is++] = b; else w.hlist[il++] = b;
   }
   HIPCHK(hipMemcpyAsync(w.list, w.hlist.data(), (size_t)nb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  w.nl = nl; w.ns = ns; w.hi = hi;
+  return NNMPC_OK;
+}
+
+// One segment of nnmpc_qp_sensitivity on device pointers: nb problems, D directions each (qp_sens.h).  du: nb D x n (seq) or x nu.
+struct SensWork {
+  bool seq; int D;
+  SensSort s; double* xp; double* T; double* lam; double* X; uint32_t* arep;
+};
+static int sens_segment(nnmpc_qp* h, SensWork& w, int nb, const uint32_t* act, const int32_t* st, const double* dx0, const double* dlb,
+                        const double* dub, double* du, double* dmult, int32_t* flag) {
+  const int n = h->n, np = h->np, nu = h->nu, n_aug = h->n_aug, ka = h->ka, D = w.D;
+  const size_t rows = (size_t)nb * D, mpad = (rows + 127) / 128 * 128;
+  // the host sorts the segment into the two instances from one read-back of the counts (and takes the window of the second product)
+  if (int rc = sens_sort(h, w.s, nb, act)) return rc;
+  const int nl = w.s.nl, ns = w.s.ns, hi = w.s.hi;
   const int W = std::min(np, (hi + 16) / 16 * 16);           // columns of LAM in use (0: no active bound in the segment)
   if (w.seq) {
     hipLaunchKernelGGL(sens_pad_k, dim3((unsigned)std::min<size_t>((mpad * ka + 255) / 256, 65535)), dim3(256), 0, h->stream,
@@ -2439,7 +2460,7 @@ static int sens_segment(nnmpc_qp* h, SensWork& w, int nb, const uint32_t* act, c
   a.slab = nullptr; a.lam = w.seq ? w.lam : nullptr; a.ldl = np; a.du0 = w.seq ? nullptr : du; a.flag = flag;
   a.n = n; a.np = np; a.nu = nu; a.n_aug = n_aug; a.ka = ka; a.words = h->words; a.D = D;
   if (nl > 0) {
-    a.list = w.list; a.count = nl;
+    a.list = w.s.list; a.count = nl;
     EvScope es(h, EV_SENS, 0.0);
     hipLaunchKernelGGL(sens_k<false>, dim3(nl), dim3(SENS_THREADS), sens_lds_bytes<false>(), h->stream, a);
     HIPCHK(hipGetLastError());
@@ -2447,7 +2468,7 @@ static int sens_segment(nnmpc_qp* h, SensWork& w, int nb, const uint32_t* act, c
   if (ns > 0) {
     const int pool = std::min(ns, 64);                       // workgroups, each with a slab of 2.4 MB, that walk the list together
     if (int rc = h->res.slot(nnmpc_qp::SC_S_SLAB, &a.slab, (size_t)pool * SENS_SLAB * 8)) return rc;
-    a.list = w.list + nl; a.count = ns;
+    a.list = w.s.list + nl; a.count = ns;
     EvScope es(h, EV_SENS, 0.0);
     hipLaunchKernelGGL(sens_k<true>, dim3(pool), dim3(SENS_THREADS), sens_lds_bytes<true>(), h->stream, a);
     HIPCHK(hipGetLastError());
@@ -2493,9 +2514,9 @@ int nnmpc_qp_sensitivity(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* acti
   const size_t rmax = (size_t)G * D, mpad = (rmax + 127) / 128 * 128;
   DevRes& res = h->res;
   SensWork w;
-  w.seq = seq; w.D = D; w.cnt = nullptr; w.list = nullptr; w.xp = w.T = w.lam = w.X = nullptr; w.arep = nullptr;
-  if (int rc = res.slot(nnmpc_qp::SC_S_CNT, &w.cnt, 2 * (size_t)G * 4)) return rc;
-  if (int rc = res.slot(nnmpc_qp::SC_S_LIST, &w.list, (size_t)G * 4)) return rc;
+  w.seq = seq; w.D = D; w.s.cnt = nullptr; w.s.list = nullptr; w.xp = w.T = w.lam = w.X = nullptr; w.arep = nullptr;
+  if (int rc = res.slot(nnmpc_qp::SC_S_CNT, &w.s.cnt, 2 * (size_t)G * 4)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_S_LIST, &w.s.list, (size_t)G * 4)) return rc;
   if (seq) {
     if (int rc = res.slot(nnmpc_qp::SC_S_XP, &w.xp, mpad * ka * 8)) return rc;
     if (int rc = res.slot(nnmpc_qp::SC_S_T, &w.T, mpad * np * 8)) return rc;
@@ -2519,6 +2540,116 @@ int nnmpc_qp_sensitivity(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* acti
     if (int rc = stg.out(&dmd, dmult, r0, nr, n, nnmpc_qp::SC_MULT)) return rc;
     if (int rc = stg.out(&fd, flag, b0, nb, 1, nnmpc_qp::SC_FLAG, true)) return rc;   // the kernels write it, asked for or not
     if (int rc = sens_segment(h, w, nb, ad, sd, xd, lbd, ubd, dud, dmd, fd)) return rc;
+    if (int rc = stg.copy_out()) return rc;
+    HIPCHK(stream_sync(h->stream));                          // (the staging and the row buffers are the next segment's)
+  }
+  return call.finish(NNMPC_OK);
+  GUARD_END
+}
+
+// One segment of nnmpc_qp_adjoint on device pointers: nb problems, D cotangents each (qp_adj.h).  v: nb D x n (seq) or x nu.
+struct AdjWork {
+  bool seq; int D, kap;
+  SensSort s; double* Vp; double* Y; double* GX; const double* KT;
+};
+static int adj_segment(nnmpc_qp* h, AdjWork& w, int nb, const uint32_t* act, const int32_t* st, const double* v, double* gx0, double* glb,
+                       double* gub, double* gbound, int32_t* flag) {
+  const int n = h->n, np = h->np, nu = h->nu, n_aug = h->n_aug, ka = h->ka, D = w.D;
+  const size_t rows = (size_t)nb * D, mpad = (rows + 127) / 128 * 128;
+  if (int rc = sens_sort(h, w.s, nb, act)) return rc;
+  const int nl = w.s.nl, ns = w.s.ns;
+  const int W = std::min(np, (w.s.hi + 64) / 64 * 64);       // columns of Y in use (0: no active bound in the segment)
+  if (w.seq) {
+    hipLaunchKernelGGL(sens_pad_k, dim3((unsigned)std::min<size_t>((mpad * np + 255) / 256, 65535)), dim3(256), 0, h->stream,
+                       w.Vp, v, rows, n, np, mpad);
+    HIPCHK(hipGetLastError());
+    if (W > 0) gemm64(h, w.Y, np, w.Vp, np, h->H64, np, (int)mpad, W, np);               // Y = V Hinv[0:W, :]'
+  }
+  AdjArgs a;
+  a.H64 = h->H64; a.Kunc64 = h->Kunc64; a.active = act; a.status = st; a.v = v; a.slab = nullptr;
+  a.vp = w.seq ? w.Vp : nullptr; a.y = w.seq ? w.Y : nullptr; a.ld = np; a.gx0 = w.seq ? nullptr : gx0;
+  a.glb = glb; a.gub = gub; a.gbound = gbound; a.flag = flag;
+  a.n = n; a.np = np; a.nu = nu; a.n_aug = n_aug; a.ka = ka; a.words = h->words; a.D = D;
+  if (nl > 0) {
+    a.list = w.s.list; a.count = nl;
+    EvScope es(h, EV_ADJ, 0.0);
+    hipLaunchKernelGGL(adj_k<false>, dim3(nl), dim3(SENS_THREADS), sens_lds_bytes<false>(), h->stream, a);
+    HIPCHK(hipGetLastError());
+  }
+  if (ns > 0) {
+    const int pool = std::min(ns, 64);                       // as sens_segment's
+    if (int rc = h->res.slot(nnmpc_qp::SC_S_SLAB, &a.slab, (size_t)pool * SENS_SLAB * 8)) return rc;
+    a.list = w.s.list + nl; a.count = ns;
+    EvScope es(h, EV_ADJ, 0.0);
+    hipLaunchKernelGGL(adj_k<true>, dim3(pool), dim3(SENS_THREADS), sens_lds_bytes<true>(), h->stream, a);
+    HIPCHK(hipGetLastError());
+  }
+  h->stats.adj_lds_problems += nl; h->stats.adj_slab_problems += ns;
+  if (w.seq) {
+    gemm64(h, w.GX, w.kap, w.Vp, np, w.KT, np, (int)mpad, w.kap, np);                    // GX = Z KuncT'
+    hipLaunchKernelGGL(adj_epilogue_k, dim3((unsigned)rows), dim3(256), 0, h->stream, gx0, w.GX, (size_t)w.kap, flag, n_aug, D);
+    HIPCHK(hipGetLastError());
+  }
+  return NNMPC_OK;
+}
+
+int nnmpc_qp_adjoint(nnmpc_qp* h, int32_t B, int32_t D, const uint32_t* active, const int32_t* status, const double* v,
+                     double* gx0, double* glb, double* gub, double* gbound, int32_t* flag, int32_t ptr_kind, int32_t in_kind) {
+  if (!h || B < 0 || D < 1 || !active || !v || !gx0 || (ptr_kind != NNMPC_HOST && ptr_kind != NNMPC_DEVICE) ||
+      (in_kind != NNMPC_OUT_SEQUENCE && in_kind != NNMPC_OUT_FIRST_MOVE)) {
+    set_error("nnmpc_qp_adjoint: bad arguments");
+    return NNMPC_EINVAL;
+  }
+  if (!h->have_inverse) {
+    set_error("nnmpc_qp_adjoint: needs an accepted inverse (nnmpc_qp_set_inverse)");
+    return NNMPC_EINVAL;
+  }
+  if (B == 0) return NNMPC_OK;
+  GUARD_BEGIN
+  HIPCHK(hipSetDevice(h->device));
+  const int n = h->n, np = h->np, nu = h->nu, n_aug = h->n_aug, ka = h->ka, words = h->words;
+  const bool seq = in_kind == NNMPC_OUT_SEQUENCE;
+  const int ncol = seq ? n : nu, kap = (n_aug + 63) / 64 * 64;
+  // rows (problem, cotangent) of a segment: the row buffers of the sequence input (V / Z, Y, GX) stay within 1 GiB
+  const long long rowcap = seq ? std::max<long long>(128, (1ll << 30) / ((2ll * np + kap) * 8)) : std::max<long long>(h->seg_max, 1024);
+  const int G = (int)std::min<long long>(std::min<long long>(B, h->seg_max), std::max<long long>(1, rowcap / D));
+  if ((long long)G * D > 0x7fffff00ll) { set_error("nnmpc_qp_adjoint: D = %d is too large", D); return NNMPC_EINVAL; }
+  const size_t rmax = (size_t)G * D, mpad = (rmax + 127) / 128 * 128;
+  DevRes& res = h->res;
+  AdjWork w;
+  w.seq = seq; w.D = D; w.kap = kap; w.s.cnt = nullptr; w.s.list = nullptr; w.Vp = w.Y = w.GX = nullptr; w.KT = nullptr;
+  if (int rc = res.slot(nnmpc_qp::SC_S_CNT, &w.s.cnt, 2 * (size_t)G * 4)) return rc;
+  if (int rc = res.slot(nnmpc_qp::SC_S_LIST, &w.s.list, (size_t)G * 4)) return rc;
+  if (seq) {
+    if (int rc = res.slot(nnmpc_qp::SC_S_T, &w.Vp, mpad * np * 8)) return rc;
+    if (int rc = res.slot(nnmpc_qp::SC_S_LAM, &w.Y, mpad * np * 8)) return rc;
+    if (int rc = res.slot(nnmpc_qp::SC_S_X, &w.GX, mpad * kap * 8)) return rc;
+    double* kt = nullptr;
+    if (int rc = res.slot(nnmpc_qp::SC_A_KT, &kt, (size_t)kap * np * 8)) return rc;
+    if (!h->kunct_ok) {
+      hipLaunchKernelGGL(adj_transpose_k, dim3((unsigned)std::min<size_t>(((size_t)kap * np + 255) / 256, 65535)), dim3(256), 0, h->stream,
+                         kt, h->Kunc64, np, ka, n_aug, kap);
+      HIPCHK(hipGetLastError());
+      h->kunct_ok = true;
+    }
+    w.KT = kt;
+  }
+  CallScope call(h, EV_ADJ_TOTAL);
+  Staging stg{res, h->stream, ptr_kind == NNMPC_HOST};
+  for (int b0 = 0; b0 < B; b0 += G) {
+    const int nb = std::min(G, B - b0);
+    const size_t r0 = (size_t)b0 * D, nr = (size_t)nb * D;
+    const uint32_t* ad; const int32_t* sd; const double* vd;
+    double *gxd, *gld, *gud, *gbd; int32_t* fd;
+    if (int rc = stg.in(&ad, active, b0, nb, words, nnmpc_qp::SC_ACT)) return rc;
+    if (int rc = stg.in(&sd, status, b0, nb, 1, nnmpc_qp::SC_ST)) return rc;
+    if (int rc = stg.in(&vd, v, r0, nr, ncol, nnmpc_qp::SC_X0)) return rc;
+    if (int rc = stg.out(&gxd, gx0, r0, nr, n_aug, nnmpc_qp::SC_U)) return rc;
+    if (int rc = stg.out(&gld, glb, r0, nr, nu, nnmpc_qp::SC_LB)) return rc;
+    if (int rc = stg.out(&gud, gub, r0, nr, nu, nnmpc_qp::SC_UB)) return rc;
+    if (int rc = stg.out(&gbd, gbound, r0, nr, n, nnmpc_qp::SC_MULT)) return rc;
+    if (int rc = stg.out(&fd, flag, b0, nb, 1, nnmpc_qp::SC_FLAG, true)) return rc;   // the kernels write it, asked for or not
+    if (int rc = adj_segment(h, w, nb, ad, sd, vd, gxd, gld, gud, gbd, fd)) return rc;
     if (int rc = stg.copy_out()) return rc;
     HIPCHK(stream_sync(h->stream));                          // (the staging and the row buffers are the next segment's)
   }

@@ -341,6 +341,29 @@ class DenseQPRegulator:
             out["dz"] = dz
         return out
 
+    def adjoint_batch(self, info, V, first_move_only=False, bounds=False, per_variable=False):
+        """Vector-Jacobian products of the sequences of a solve_batch call, restricted to its delivered active sets: the transpose of
+        sensitivity_batch (BatchedBoxQP.adjoint; include/nnmpc.h: nnmpc_qp_adjoint).  ``info``: that call's info (its active rows and
+        status are used); V (B, D, N*Nu) cotangents of the sequence -- (B, D, Nu) of the first moves with first_move_only; (B, ...) for
+        one cotangent, the outputs then drop that axis too.
+
+        Returns dict(gx0 (B, D, n_aug), flag (B,)); ``bounds=True`` adds glb, gub (B, D, Nu), the cotangents of ulb / uub;
+        ``per_variable=True`` adds gbound (B, D, N*Nu).  With du of sensitivity_batch: <V, du> = <gx0, dX0> + <glb, dulb> + <gub, duub>.
+        For a re-parameterised (unstable) plant nothing is transformed, for the reason sensitivity_batch gives: the box problem of
+        _box_form is in the input sequence w that solve_batch returns, its linear term is linear in x0 and its rows are the rows of
+        G v <= h, so V is a cotangent of that sequence and gx0, glb, gub are cotangents of X0 and the plant's bounds themselves.
+        """
+        qp = self._solver()
+        return qp.adjoint(qp.active_to_words(np.asarray(info["active"], bool)), V, status=info.get("status"),
+                          first_move_only=first_move_only, bounds=bounds, per_variable=per_variable)
+
+    def first_move_gain_batch(self, info, bounds=False):
+        """The local affine law u0 = K x0 + k of every problem's critical region: K (B, Nu, n_aug) from one adjoint call
+        (BatchedBoxQP.first_move_gain); ``bounds=True``: (K, Klb, Kub, flag) with the gains on ulb / uub (B, Nu, Nu).  Unchanged for a
+        re-parameterised plant, as adjoint_batch."""
+        qp = self._solver()
+        return qp.first_move_gain(qp.active_to_words(np.asarray(info["active"], bool)), status=info.get("status"), bounds=bounds)
+
     def solve(self, x0):
         """One problem, reference signature: x0 (n_aug, 1) -> useq (N*Nu, 1)  (reference :495-512)."""
         U, info = self.solve_batch(x0.reshape(1, -1), self.ulb.reshape(1, -1), self.uub.reshape(1, -1))

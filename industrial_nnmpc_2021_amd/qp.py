@@ -300,6 +300,48 @@ class BatchedBoxQP:
             out["dmult"] = dmult[:, 0] if one else dmult
         return out
 
+    def adjoint(self, active_words, v, status=None, first_move_only=False, bounds=False, per_variable=False):
+        """The adjoint (vector-Jacobian) product of the same map: J'v where sensitivity gives J d (nnmpc_qp_adjoint, include/nnmpc.h).
+        active_words (B, ceil(2n/32)) uint32 (active_to_words), v (B, D, n) cotangents of the sequence -- (B, D, nu) of the first moves
+        with first_move_only --, status (B,) or None; numpy in, numpy out.  v (B, n) is one cotangent (D = 1), and the outputs then drop
+        that axis too.
+        Returns dict(gx0 (B, D, n_aug), flag (B,) int32: 0 computed, 1 more than 768 bounds, 2 no answer, 3 non-positive pivot; NaN rows
+        where flag != 0); bounds=True adds glb, gub (B, D, nu), the cotangents of the stage bounds; per_variable=True adds gbound
+        (B, D, n), the cotangent of each variable's own bound (+0.0 on free variables).  For every direction of sensitivity:
+        <v, du> = <gx0, dx0> + <glb, dlb> + <gub, dub>.  Needs the inverse (Kunc="auto" or set_inverse)."""
+        act = np.ascontiguousarray(active_words, dtype=np.uint32).reshape(-1, self.words)
+        B = act.shape[0]
+        ncol = self.nu if first_move_only else self.n
+        v = np.asarray(v, dtype=np.float64)
+        one = v.ndim == 2
+        v = np.ascontiguousarray(v.reshape(B, -1, ncol))
+        D = v.shape[1]
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(B)
+        gx0 = np.empty((B, D, self.n_aug))
+        glb = np.empty((B, D, self.nu)) if bounds else None
+        gub = np.empty((B, D, self.nu)) if bounds else None
+        gbound = np.empty((B, D, self.n)) if per_variable else None
+        flag = np.empty(B, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_qp_adjoint(self._h, B, D, p(act), p(st), p(v), p(gx0), p(glb), p(gub), p(gbound), p(flag), _lib.HOST,
+                                              _lib.OUT_FIRST_MOVE if first_move_only else _lib.OUT_SEQUENCE), "nnmpc_qp_adjoint")
+        drop = (lambda a: a[:, 0]) if one else (lambda a: a)
+        out = dict(gx0=drop(gx0), flag=flag)
+        if bounds:
+            out.update(glb=drop(glb), gub=drop(gub))
+        if per_variable:
+            out["gbound"] = drop(gbound)
+        return out
+
+    def first_move_gain(self, active_words, status=None, bounds=False):
+        """The local feedback law of every problem's critical region: K (B, nu, n_aug) = du0/dx0 on the delivered active set, from ONE
+        adjoint call with the nu unit cotangents of the first stage (forward mode needs n_aug directions).  bounds=True: returns
+        (K, Klb, Kub, flag) with Klb, Kub (B, nu, nu) = du0/dlb, du0/dub and flag (B,) as adjoint's; NaN where flag != 0."""
+        act = np.ascontiguousarray(active_words, dtype=np.uint32).reshape(-1, self.words)
+        v = np.ascontiguousarray(np.broadcast_to(np.eye(self.nu), (act.shape[0], self.nu, self.nu)))
+        out = self.adjoint(act, v, status=status, first_move_only=True, bounds=bounds)
+        return (out["gx0"], out["glb"], out["gub"], out["flag"]) if bounds else out["gx0"]
+
     def mult_to_z(self, mult, active):
         """mult (B, n) per variable + active (B, 2n) bool -> z (B, 2n) in the row order of the reference's G: the
         variable's multiplier on its active row, zero on the others; a NaN row of mult stays a NaN row."""
