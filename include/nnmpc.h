@@ -461,6 +461,34 @@ int nnmpc_train_dw_slices(nnmpc_train* h, int32_t* slices);
 /* Largest |entry| over the padding rows and columns of every weight, bias and moment image (a NaN there: NaN).  The
  * padding has zero gradients by construction and must stay exactly zero through updates; this is the check. */
 int nnmpc_train_padding_max(nnmpc_train* h, double* maxabs);
+/* The tangent loss (Sobolev training)  <-  train_nn_controller's targets are MPC solves (cdu_train.py:40-62), and inside a
+ * critical region the MPC law is affine: a sample carries a slope as well as a value, and nnmpc_qp_sensitivity delivers it
+ * (du0 along a direction).  A handle built here trains the structured network on both:
+ *     L = mean over B nu of (pred - u)^2  +  w mean over B nu of (J d - t)^2,
+ * d = [dx, (duprev)] one direction per dataset row in the units of the dataset's x, t (nu entries) the target, J d the tangent of
+ * pred along d, propagated forward through the same weights: a'_0 = [dx, (duprev), 0, 0], a'_l = (a'_{l-1} W_l) * [a_l(pass 1) > 0],
+ * J d = a'_{L-1} W_L -- no bias, ReLU derivative 0 at 0; pass 2 does not depend on x or uprev.  The masks are constants of the
+ * backward pass (ReLU has no second derivative), so the gradient is the one autograd gives.  Arguments as nnmpc_train_create_ex;
+ * form must be NNMPC_NN_STRUCTURED (anything else: NNMPC_EINVAL before a device is looked for).  Workspaces for 3 stacked row
+ * blocks of max_batch rows.  The weight w is 0 after create, and with w == 0 every call runs the plain step: the bytes of an
+ * nnmpc_train_create handle.  With w > 0 a step keeps the plain step's number of launches and its fixed summation orders. */
+int nnmpc_train_create_tan(nnmpc_train** out, int32_t nlayers, const int32_t* dims,
+                           const double* const* W, const double* const* b, int32_t nx, int32_t nu,
+                           int32_t with_uprev, int32_t max_batch, double lr, double beta1,
+                           double beta2, double eps, int32_t form);
+/* The directions and targets of the dataset nnmpc_train_set_data gave, one per row (train.tangent_data makes them from a solved
+ * batch): dx n x nx, duprev n x nu (NULL unless with_uprev), t n x nu, f64 on the host or in HBM, converted to f32 and kept.
+ * A plain handle, no dataset yet, n != the dataset's rows, or a with-uprev network without duprev: NNMPC_EINVAL.  A later
+ * nnmpc_train_set_data drops them.  Non-finite entries are not rejected and not hidden: a NaN gives a NaN tan_mse and L. */
+int nnmpc_train_set_tangents(nnmpc_train* h, int32_t n, const double* dx, const double* duprev,
+                             const double* t, int32_t ptr_kind);
+/* The weight w of the tangent term: finite and >= 0, on a tangent handle (NNMPC_EINVAL otherwise).  With w > 0 and no
+ * tangents, grad, step, epoch and eval return NNMPC_EINVAL before any launch. */
+int nnmpc_train_set_tan_weight(nnmpc_train* h, double w);
+/* The two parts of what the last grad / step (that batch), epoch (row-weighted means) or eval (over its rows) returned
+ * (waits for it): grad, step and epoch return L = mse + w tan_mse, and so does eval.  With w == 0, and on a plain handle,
+ * mse is that loss and tan_mse 0.  Before the first such call: NNMPC_EINVAL. */
+int nnmpc_train_last_losses(nnmpc_train* h, double* mse, double* tan_mse);
 
 /* ---- A sweep of networks trained in lock step  <-  the loop `for (regulator_dim, num_sample) in
  * itertools.product(regulator_dims, num_samples)` around train_nn_controller (cstrs_train.py / cdu_train.py main): G networks

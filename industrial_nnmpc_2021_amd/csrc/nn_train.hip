@@ -22,6 +22,18 @@
 // ONE pass, so a batch is M = Bp stacked rows (train_gather1_k); the head has a bias (and a ReLU) in its GEMM epilogue, a
 // bias gradient (train_colsum_k over the head's dZ) and a bias Adam; the output kernel (train_output1_k) takes pred from the
 // head as it is and, under the ReLU, zeroes dZ where pred <= 0.  Every other launch is the structured one at M rows.
+//
+// The tangent loss (nnmpc_train_create_tan, structured form; nn_train_dev.h has the arithmetic):
+//   L = mean (pred - u)^2 + w mean (J d - t)^2,  J d the tangent of pred along the row's direction d = [dx, (duprev)].
+// With w > 0 a batch is M = 3Bp stacked rows, the tangent rows in [2Bp, 3Bp), and the step keeps its 6 nlayers launches:
+// every one below is a variant of the plain launch in the same place.
+//   gather      all three blocks                                                                 (train_gather_tan_k)
+//   forward     hidden layers: a pass-1 row tile and its tangent tile in one workgroup, pass 2    (gemm_nt_f32_pair_k)
+//               as before; the head is bias-free and linear: the plain launch over 3Bp rows      (gemm_nt_f32_k)
+//   output      the plain output and dZ'_L = 2 w (J d - t) / (B nu), a second set of partials     (train_output_tan_k)
+//   backward    dW over 3Bp rows; db over the first 2Bp (tangent rows carry no bias gradient);    (gemm_tn_f32_k, train_colsum_k)
+//               dA over 3Bp rows, the mask row of a tangent row being its pass-1 row              (gemm_nt_mask_wrap_k)
+// With w == 0 the handle runs the plain step, launch for launch.
 #include "gemm_kernels.h"
 #include "tile_gemm_tn.h"
 #include "nn_train_host.h"
@@ -60,6 +72,42 @@ __global__ __launch_bounds__(256) void train_output1_k(float* __restrict__ dz, c
   train_output1_block(dz, o, ldo, B, nu, head_relu, u, idx, first, gscale, partial, blockIdx.x);
 }
 
+// The tangent loss: all three row blocks; the plain output plus the tangent rows; both sums.
+__global__ __launch_bounds__(128) void train_gather_tan_k(float* __restrict__ in, int ldk, int Bp, int B, int nx, int nu,
+                                                          int with_uprev, const float* __restrict__ x,
+                                                          const float* __restrict__ uprev, const float* __restrict__ xs,
+                                                          const float* __restrict__ us, const float* __restrict__ tdx,
+                                                          const float* __restrict__ tdup, const int* __restrict__ idx, int first) {
+  train_gather_rows(in, ldk, Bp, B, nx, nu, with_uprev, x, uprev, xs, us, idx, first, blockIdx.x, gridDim.x);
+  train_gather_tan_rows(in, ldk, Bp, B, nx, nu, with_uprev, tdx, tdup, idx, first, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(256) void train_output_tan_k(float* __restrict__ dz, const float* __restrict__ o, int ldo, int Bp,
+                                                          int B, int nu, const float* __restrict__ us,
+                                                          const float* __restrict__ u, const float* __restrict__ t,
+                                                          const int* __restrict__ idx, int first, float gscale, float gw,
+                                                          double* __restrict__ partial, double* __restrict__ partial_tan) {
+  train_output_tan_block(dz, o, ldo, Bp, B, nu, us, u, t, idx, first, gscale, gw, partial, partial_tan, blockIdx.x);
+}
+
+__global__ void train_loss_finish_tan_k(const double* __restrict__ partial, const double* __restrict__ partial_tan, int np,
+                                        double scale, double weight, double w, double* __restrict__ loss,
+                                        double* __restrict__ acc) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  train_loss_finish_tan(partial, partial_tan, np, scale, weight, w, loss, acc);
+}
+
+// Hidden-layer forward under the tangent loss.  Grid (N/NB, 2Bp/NB): the low blockIdx.y are the pass-1 row tiles, each with
+// its tangent tile (twice the work: they start first); the others are pass 2, the plain tile.
+template <int NB>
+__global__ __launch_bounds__(256) void gemm_nt_f32_pair_k(float* __restrict__ C, size_t ldc, const float* __restrict__ A,
+                                                          size_t lda, const float* __restrict__ B, size_t ldb, int K,
+                                                          const float* __restrict__ bias, int Bp) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  if ((int)blockIdx.y < Bp / NB) train_fwd_pair_tile<NB>(C, ldc, A, lda, B, ldb, K, bias, Bp, blockIdx.y, blockIdx.x, lds);
+  else train_fwd_tile<NB, true, true>(C, ldc, A, lda, B, ldb, K, bias, blockIdx.y, blockIdx.x, lds);
+}
+
 __global__ void train_loss_finish_k(const double* __restrict__ partial, int np, double scale, double w,
                                     double* __restrict__ loss, double* __restrict__ acc) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -81,6 +129,17 @@ __global__ __launch_bounds__(256) void gemm_nt_mask_k(float* __restrict__ C, siz
                                                       const float* __restrict__ act) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   train_nt_mask_tile<NB>(C, ldc, A, lda, B, ldb, K, act, blockIdx.x, blockIdx.y, lds);
+}
+
+// gemm_nt_mask_k over the 3Bp rows of the tangent loss: a row tile at or above `wrap` = 2Bp takes its mask from the
+// activation tile `wrap` rows up, the pass-1 rows its tangents belong to (tiles never straddle: wrap is a multiple of 128).
+template <int NB>
+__global__ __launch_bounds__(256) void gemm_nt_mask_wrap_k(float* __restrict__ C, size_t ldc, const float* __restrict__ A,
+                                                           size_t lda, const float* __restrict__ B, size_t ldb, int K,
+                                                           const float* __restrict__ act, int wrap) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const float* mask = (int)blockIdx.y * NB >= wrap ? act - (size_t)wrap * ldc : act;
+  train_nt_mask_tile<NB>(C, ldc, A, lda, B, ldb, K, mask, blockIdx.x, blockIdx.y, lds);
 }
 
 // Grid (N/64, rows/128).
@@ -114,9 +173,21 @@ struct nnmpc_train {
   std::vector<int> slices;                                  // of the last backward pass, per layer
   char* arena = nullptr;                                    // the network's buffers, its acc word, then grad
   float* grad = nullptr;                                    // summed gradient (nnmpc_train_grad only): per layer gW [N][K] then gb [N]
+  // What nnmpc_train_last_losses reads: the loss words of a batch (LAST_BATCH) or the running sums over last_den (LAST_SUMS);
+  // last_tan: that call ran the tangent step, so the words hold L, mse, tan_mse (otherwise L alone, which is the mse).
+  enum { LAST_NONE, LAST_BATCH, LAST_SUMS } last = LAST_NONE;
+  bool last_tan = false;
+  double last_den = 1.0;
 };
 
 namespace {
+
+template <int NB>
+void launch_fwd_pair(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda, const float* Wt, size_t ldb, int Bp, int N,
+                     int K, const float* bias) {
+  hipLaunchKernelGGL((gemm_nt_f32_pair_k<NB>), dim3(N / NB, 2 * Bp / NB), dim3(256), TileCfg<NB>::LDS_FLOATS * 4, s,
+                     C, ldc, A, lda, Wt, ldb, K, bias, Bp);
+}
 
 template <int NB, bool RELU, bool BIAS>
 void launch_fwd(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda, const float* Wt, size_t ldb, int M, int N,
@@ -127,16 +198,21 @@ void launch_fwd(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda,
 
 // Gather, forward, output kernel and (backward) the gradient planes of one batch on the handle's stream; no host wait.
 // idx: device row list (nullptr: rows first .. first + B - 1).  The loss goes to the network's loss word = loss_scale * sum
-// of squares, and acc += acc_w * that.
+// of squares, and acc += acc_w * that.  With the tangent term in the loss (tan_active) every launch is its tangent variant
+// over M = 3Bp rows, the loss words are L, mse, tan_mse and acc[0..2] take all three.
 int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backward, double loss_scale, double acc_w, size_t set) {
   TrainCommon& c = h->c;
   const GMember& mem = h->m.mem;
   hipStream_t s = c.stream;
-  const int L = c.L, Bp = pad128_host(B), M = train_rows(c.form, Bp);
+  const bool tan = tan_active(c);
+  const int L = c.L, Bp = pad128_host(B), M = train_rows_tan(c.form, Bp, tan);
   const bool un = c.form != NNMPC_NN_STRUCTURED, hrelu = c.form == NNMPC_NN_UNSTD_RELU;
   EvSet e;
   if (int rc = ev_set(c, set, &e)) return rc;
-  if (un)
+  if (tan)
+    hipLaunchKernelGGL(train_gather_tan_k, dim3(std::min(Bp, 2048)), dim3(128), 0, s, h->m.lay[0].ain, h->m.lay[0].K, Bp, B, c.nx, c.nu,
+                       c.with_uprev, c.dx, c.dup, c.dxs, c.dus, c.tdx, c.tdup, idx, first);
+  else if (un)
     hipLaunchKernelGGL(train_gather1_k, dim3(std::min(Bp, 2048)), dim3(128), 0, s, h->m.lay[0].ain, h->m.lay[0].K, Bp, B, c.nx, c.nu,
                        c.with_uprev, c.dx, c.dup, c.dxs, c.dus, idx, first);
   else
@@ -147,7 +223,10 @@ int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backwar
     const GLayer& d = h->m.lay[l];
     const int K = d.K, N = d.N;
     const bool last = l == L - 1;
-    if (N % 128 == 0) {
+    if (tan && !last) {
+      if (N % 128 == 0) launch_fwd_pair<128>(s, d.aout, N, d.ain, K, d.Wt, K, Bp, N, K, d.b);
+      else launch_fwd_pair<64>(s, d.aout, N, d.ain, K, d.Wt, K, Bp, N, K, d.b);
+    } else if (N % 128 == 0) {
       if (last && hrelu) launch_fwd<128, true, true>(s, d.aout, N, d.ain, K, d.Wt, K, M, N, K, d.b);
       else if (last && un) launch_fwd<128, false, true>(s, d.aout, N, d.ain, K, d.Wt, K, M, N, K, d.b);
       else if (last) launch_fwd<128, false, false>(s, d.aout, N, d.ain, K, d.Wt, K, M, N, K, nullptr);
@@ -161,13 +240,22 @@ int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backwar
   }
   hipEventRecord(e.f1, s);
   const GLayer& head = h->m.lay[L - 1];
-  if (un)
+  const double gs = 2.0 / ((double)B * c.nu);
+  double* partial_tan = mem.partial + c.cap_batch / 64;
+  if (tan)
+    hipLaunchKernelGGL(train_output_tan_k, dim3(Bp / 64), dim3(256), 0, s, backward ? mem.dz[0] : nullptr, head.aout, head.N, Bp, B,
+                       c.nu, c.dus, c.du, c.tt, idx, first, (float)gs, (float)(gs * c.tan_w), mem.partial, partial_tan);
+  else if (un)
     hipLaunchKernelGGL(train_output1_k, dim3(Bp / 64), dim3(256), 0, s, backward ? mem.dz[0] : nullptr, head.aout, head.N, B,
-                       c.nu, hrelu ? 1 : 0, c.du, idx, first, (float)(2.0 / ((double)B * c.nu)), mem.partial);
+                       c.nu, hrelu ? 1 : 0, c.du, idx, first, (float)gs, mem.partial);
   else
     hipLaunchKernelGGL(train_output_k, dim3(Bp / 64), dim3(256), 0, s, backward ? mem.dz[0] : nullptr, head.aout, head.N, Bp, B,
-                       c.nu, c.dus, c.du, idx, first, (float)(2.0 / ((double)B * c.nu)), mem.partial);
-  hipLaunchKernelGGL(train_loss_finish_k, dim3(1), dim3(64), 0, s, mem.partial, Bp / 64, loss_scale, acc_w, mem.loss, mem.acc);
+                       c.nu, c.dus, c.du, idx, first, (float)gs, mem.partial);
+  if (tan)
+    hipLaunchKernelGGL(train_loss_finish_tan_k, dim3(1), dim3(64), 0, s, mem.partial, partial_tan, Bp / 64, loss_scale, acc_w, c.tan_w,
+                       mem.loss, mem.acc);
+  else
+    hipLaunchKernelGGL(train_loss_finish_k, dim3(1), dim3(64), 0, s, mem.partial, Bp / 64, loss_scale, acc_w, mem.loss, mem.acc);
   hipEventRecord(e.b0, s);
   if (backward) {
     int cur = 0;
@@ -188,8 +276,16 @@ int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backwar
         hipLaunchKernelGGL(gemm_tn_f32_k<64>, dim3(K / 64, N / 64, S), dim3(256), TileCfgTN<64>::LDS_FLOATS * 4, s,
                            d.planes, plane, (size_t)K, dZ, (size_t)N, d.ain, (size_t)K, M, slice_rows);
       if (has_bias(c.form, L, l))
-        hipLaunchKernelGGL(train_colsum_k, dim3(N / 64, M / 128), dim3(256), 0, s, d.bplanes, dZ, N);
-      if (l > 0) {                                           // dZ_{l-1} [M][K] = (dZ_l [M][N] Wk_l [K][N]') * mask(A_l input = ain)
+        hipLaunchKernelGGL(train_colsum_k, dim3(N / 64, train_rows(c.form, Bp) / 128), dim3(256), 0, s, d.bplanes, dZ, N);   // never the tangent rows
+      if (l > 0 && tan) {                                    // the same over 3Bp rows, a tangent row masked by its pass-1 row
+        if (K % 128 == 0)
+          hipLaunchKernelGGL(gemm_nt_mask_wrap_k<128>, dim3(K / 128, M / 128), dim3(256), TileCfg<128>::LDS_FLOATS * 4, s,
+                             mem.dz[cur ^ 1], (size_t)K, dZ, (size_t)N, d.Wk, (size_t)N, N, d.ain, 2 * Bp);
+        else
+          hipLaunchKernelGGL(gemm_nt_mask_wrap_k<64>, dim3(K / 64, M / 64), dim3(256), TileCfg<64>::LDS_FLOATS * 4, s,
+                             mem.dz[cur ^ 1], (size_t)K, dZ, (size_t)N, d.Wk, (size_t)N, N, d.ain, 2 * Bp);
+        cur ^= 1;
+      } else if (l > 0) {                                    // dZ_{l-1} [M][K] = (dZ_l [M][N] Wk_l [K][N]') * mask(A_l input = ain)
         if (K % 128 == 0)
           hipLaunchKernelGGL(gemm_nt_mask_k<128>, dim3(K / 128, M / 128), dim3(256), TileCfg<128>::LDS_FLOATS * 4, s,
                              mem.dz[cur ^ 1], (size_t)K, dZ, (size_t)N, d.Wk, (size_t)N, N, d.ain);
@@ -223,11 +319,13 @@ int enqueue_rows(nnmpc_train* h, const char* who, int32_t B, const int32_t* rows
   TrainCommon& c = h->c;
   if (int rc = check_batch(c, who, B)) return rc;
   if (int rc = check_rows(c, who, (size_t)B, rows)) return rc;
+  if (int rc = check_tangents(c, who)) return rc;
   HIPCHK(hipSetDevice(c.device));
   if (int rc = staged_upload(c, nullptr, 0, rows, (size_t)B)) return rc;
   hipEventRecord(c.e0, c.stream);
   if (int rc = enqueue_batch(h, B, (const int*)c.dcall, 0, true, 1.0 / ((double)B * c.nu), 0.0, 0)) return rc;
   c.nsets = 1;
+  h->last = nnmpc_train::LAST_BATCH; h->last_tan = tan_active(c); h->last_den = 1.0;
   return NNMPC_OK;
 }
 }  // namespace
@@ -241,13 +339,14 @@ int nnmpc_train_destroy(nnmpc_train* h) {
   return NNMPC_OK;
 }
 
-// Both create entry points; `who` is the one that was called.
+// The create entry points; `who` is the one that was called.  tan: a tangent handle (nnmpc_train_create_tan).
 static int train_create(const char* who, nnmpc_train** out, int32_t nlayers, const int32_t* dims, const double* const* W,
                         const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev, int32_t max_batch,
-                        double lr, double beta1, double beta2, double eps, int32_t form) {
+                        double lr, double beta1, double beta2, double eps, int32_t form, bool tan = false) {
   GUARD_BEGIN
   if (!out || nlayers < 1 || !dims || !W || !b || nx <= 0 || nu <= 0 || max_batch < 1) { set_error("%s: bad arguments", who); return NNMPC_EINVAL; }
   if (int rc = check_form(who, form)) return rc;
+  if (tan && form != NNMPC_NN_STRUCTURED) { set_error("%s: form %d: the tangent loss is built for the structured form only (NNMPC_NN_STRUCTURED)", who, form); return NNMPC_EINVAL; }
   if (int rc = check_network(who, "", nlayers, dims, W, b, nx, nu, with_uprev, form)) return rc;
   if (int rc = check_adam(who, lr, beta1, beta2, eps)) return rc;
   if (int rc = check_device(who)) return rc;
@@ -255,10 +354,15 @@ static int train_create(const char* who, nnmpc_train** out, int32_t nlayers, con
   nnmpc_train* h = guard.get();
   TrainCommon& c = h->c;
   if (int rc = common_init(who, c, nlayers, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form)) return rc;
+  c.tan = tan ? 1 : 0;                                      // before the shapes: workspaces, planes and slices for 3 cap_batch rows
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));   // the unstructured head
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_mask_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+  if (tan) {
+    HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_pair_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+    HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_mask_wrap_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+  }
   HIPCHK(hipFuncSetAttribute((const void*)gemm_tn_f32_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfgTN<128>::LDS_FLOATS * 4));
   member_shapes(c, h->m, dims);
   h->slices.assign(nlayers, 1);
@@ -285,6 +389,40 @@ int nnmpc_train_create_ex(nnmpc_train** out, int32_t nlayers, const int32_t* dim
                           const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev, int32_t max_batch,
                           double lr, double beta1, double beta2, double eps, int32_t form) {
   return train_create(__func__, out, nlayers, dims, W, b, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form);
+}
+
+int nnmpc_train_create_tan(nnmpc_train** out, int32_t nlayers, const int32_t* dims, const double* const* W,
+                           const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev, int32_t max_batch,
+                           double lr, double beta1, double beta2, double eps, int32_t form) {
+  return train_create(__func__, out, nlayers, dims, W, b, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form, true);
+}
+
+int nnmpc_train_set_tangents(nnmpc_train* h, int32_t n, const double* dx, const double* duprev, const double* t, int32_t ptr_kind) {
+  GUARD_BEGIN
+  if (!h) { set_error("nnmpc_train_set_tangents: bad arguments"); return NNMPC_EINVAL; }
+  return set_tangents(__func__, h->c, n, dx, duprev, t, ptr_kind);
+  GUARD_END
+}
+
+int nnmpc_train_set_tan_weight(nnmpc_train* h, double w) {
+  if (!h) { set_error("nnmpc_train_set_tan_weight: bad arguments"); return NNMPC_EINVAL; }
+  if (!h->c.tan) { set_error("nnmpc_train_set_tan_weight: a plain handle has no tangent loss (nnmpc_train_create_tan builds the handle that has)"); return NNMPC_EINVAL; }
+  if (!(w >= 0.0) || !isfinite(w)) { set_error("nnmpc_train_set_tan_weight: weight %g (finite and >= 0)", w); return NNMPC_EINVAL; }
+  h->c.tan_w = w;
+  return NNMPC_OK;
+}
+
+int nnmpc_train_last_losses(nnmpc_train* h, double* mse, double* tan_mse) {
+  GUARD_BEGIN
+  if (!h) { set_error("nnmpc_train_last_losses: bad arguments"); return NNMPC_EINVAL; }
+  if (h->last == nnmpc_train::LAST_NONE) { set_error("nnmpc_train_last_losses: no grad, step, epoch or eval yet"); return NNMPC_EINVAL; }
+  HIPCHK(hipSetDevice(h->c.device));
+  double v[3] = {0.0, 0.0, 0.0};
+  if (int rc = read_doubles(h->c, h->last == nnmpc_train::LAST_BATCH ? h->m.mem.loss : h->m.mem.acc, v, h->last_tan ? 3 : 1)) return rc;
+  if (mse) *mse = (h->last_tan ? v[1] : v[0]) / h->last_den;   // without the tangent term the loss is the mse
+  if (tan_mse) *tan_mse = h->last_tan ? v[2] / h->last_den : 0.0;
+  return NNMPC_OK;
+  GUARD_END
 }
 
 int nnmpc_train_set_data(nnmpc_train* h, int32_t n, const double* x, const double* uprev, const double* xs, const double* us,
@@ -334,10 +472,11 @@ int nnmpc_train_epoch(nnmpc_train* h, int32_t nrows, const int32_t* perm, int32_
   TrainCommon& c = h->c;
   if (int rc = check_batch(c, __func__, batch)) return rc;
   if (int rc = check_rows(c, __func__, (size_t)nrows, perm)) return rc;
+  if (int rc = check_tangents(c, __func__)) return rc;
   HIPCHK(hipSetDevice(c.device));
   hipStream_t s = c.stream;
   if (int rc = staged_upload(c, nullptr, 0, perm, (size_t)nrows)) return rc;
-  HIPCHK(hipMemsetAsync(h->m.mem.acc, 0, 8, s));
+  HIPCHK(hipMemsetAsync(h->m.mem.acc, 0, 24, s));           // L, and under the tangent loss mse and tan_mse
   hipEventRecord(c.e0, s);
   size_t set = 0;
   for (int i = 0; i < nrows; i += batch, ++set) {
@@ -346,6 +485,7 @@ int nnmpc_train_epoch(nnmpc_train* h, int32_t nrows, const int32_t* perm, int32_
     enqueue_adam(h, pad128_host(B));
   }
   c.nsets = set;
+  h->last = nnmpc_train::LAST_SUMS; h->last_tan = tan_active(c); h->last_den = (double)nrows;
   hipEventRecord(c.e1, s);
   double sum = 0.0;
   if (int rc = read_doubles(c, h->m.mem.acc, &sum, 1)) return rc;
@@ -360,9 +500,10 @@ int nnmpc_train_eval(nnmpc_train* h, int32_t first, int32_t count, double* mse) 
   TrainCommon& c = h->c;
   if (int rc = check_data(c, __func__)) return rc;
   if (first < 0 || count < 1 || (int64_t)first + count > c.n) { set_error("nnmpc_train_eval: rows [%d, %d + %d) outside [0, %d)", first, first, count, c.n); return NNMPC_EINVAL; }
+  if (int rc = check_tangents(c, __func__)) return rc;
   HIPCHK(hipSetDevice(c.device));
   hipStream_t s = c.stream;
-  HIPCHK(hipMemsetAsync(h->m.mem.acc, 0, 8, s));
+  HIPCHK(hipMemsetAsync(h->m.mem.acc, 0, 24, s));
   hipEventRecord(c.e0, s);
   size_t set = 0;
   for (int i = 0; i < count; i += c.max_batch, ++set) {
@@ -370,6 +511,7 @@ int nnmpc_train_eval(nnmpc_train* h, int32_t first, int32_t count, double* mse) 
     if (int rc = enqueue_batch(h, B, nullptr, first + i, false, 1.0, 1.0, set)) return rc;
   }
   c.nsets = set;
+  h->last = nnmpc_train::LAST_SUMS; h->last_tan = tan_active(c); h->last_den = (double)count * c.nu;
   hipEventRecord(c.e1, s);
   double sum = 0.0;
   if (int rc = read_doubles(c, h->m.mem.acc, &sum, 1)) return rc;

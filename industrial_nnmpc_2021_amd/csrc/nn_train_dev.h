@@ -13,6 +13,8 @@ namespace nnmpc {
 
 // Rows of the stacked batch of Bp padded samples: two passes for the structured form (0), one for the unstructured forms.
 __host__ __device__ inline int train_rows(int form, int Bp) { return form == 0 ? 2 * Bp : Bp; }
+// The same under the tangent loss (structured form only): a third block, the tangent rows, in [2Bp, 3Bp).
+__host__ __device__ inline int train_rows_tan(int form, int Bp, int tan) { return tan ? 3 * Bp : train_rows(form, Bp); }
 
 // Row slices of the dW reduction over M = train_rows(form, Bp) rows for a layer with `tiles` output tiles: as many as keep tiles x slices
 // within the device's CUs (num_cus: the device property, 256 on MI355X) (one workgroup each: a second round would cost a
@@ -197,6 +199,143 @@ __device__ __forceinline__ void train_fwd_tile(float* __restrict__ C, size_t ldc
         if (BIAS) v += bias[col];
         if (RELU) v = relu_nan(v);
         C[(size_t)row * ldc + col] = v;
+      }
+}
+
+// ---- the tangent loss (structured form):  L = mean (pred - u)^2 + w mean (J d - t)^2,  J d the tangent of pred along the
+// row's direction d = [dx, (duprev)], propagated forward through the same weights in a third row block [2Bp, 3Bp):
+//   a'_0 = [dx, (duprev), 0, 0],  a'_l = (a'_{l-1} W_l) * [a_l(pass 1) > 0],  J d = a'_{L-1} W_L     (no bias anywhere).
+// ReLU has no second derivative, so the masks are constants of the backward pass: the tangent rows are ordinary rows of
+// dW = dZ' A, send nothing into the primal rows or the biases, and take their dA mask from the pass-1 row they belong to.
+
+// The tangent block of the gather: row 2Bp + b = [dx, (duprev), 0, 0] of dataset row idx[b]; zero for b >= B and in the
+// pad columns.  Same row walk as train_gather_rows, whose two blocks the same kernel writes.
+__device__ __forceinline__ void train_gather_tan_rows(float* __restrict__ in, int ldk, int Bp, int B, int nx, int nu,
+                                                      int with_uprev, const float* __restrict__ tdx,
+                                                      const float* __restrict__ tdup, const int* __restrict__ idx,
+                                                      int first, int b_first, int b_step) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int dd = nx + (with_uprev ? nu : 0);               // width of the direction
+  for (int b = b_first; b < Bp; b += b_step) {
+    float* d3 = in + (size_t)(2 * Bp + b) * ldk;
+    if (b >= B) {
+      for (int k = tid; k < ldk; k += nt) d3[k] = 0.f;
+      continue;
+    }
+    const size_t row = idx ? (size_t)idx[b] : (size_t)first + b;
+    for (int k = tid; k < nx; k += nt) d3[k] = tdx[row * nx + k];
+    if (with_uprev)
+      for (int k = tid; k < nu; k += nt) d3[nx + k] = tdup[row * nu + k];
+    for (int k = dd + tid; k < ldk; k += nt) d3[k] = 0.f;
+  }
+}
+
+// train_output_block over o [3Bp][ldo] with the tangent rows: the primal squared error and +-g exactly as there, and beside
+// them e' = J d - t of the tangent rows: a second fp64 partial (same lane order, same LDS tree) and dZ'_L = gw e' on rows
+// [2Bp, 3Bp), gw = gscale w; exactly zero on padding rows and pad columns.  256 threads.
+__device__ __forceinline__ void train_output_tan_block(float* __restrict__ dz, const float* __restrict__ o, int ldo, int Bp,
+                                                       int B, int nu, const float* __restrict__ us,
+                                                       const float* __restrict__ u, const float* __restrict__ t,
+                                                       const int* __restrict__ idx, int first, float gscale, float gw,
+                                                       double* __restrict__ partial, double* __restrict__ partial_tan,
+                                                       int blk) {
+  __shared__ double red[2][256];
+  const int b0 = blk * 64, tid = threadIdx.x;
+  double acc = 0.0, acct = 0.0;
+  for (int e = tid; e < 64 * ldo; e += 256) {
+    const int b = b0 + e / ldo, c = e % ldo;
+    float g = 0.f, gt = 0.f;
+    if (b < B && c < nu) {
+      const size_t row = idx ? (size_t)idx[b] : (size_t)first + b;
+      const float pred = us[row * nu + c] + (o[(size_t)b * ldo + c] - o[(size_t)(Bp + b) * ldo + c]);
+      const float d = pred - u[row * nu + c];
+      acc += (double)d * (double)d;
+      g = gscale * d;
+      const float dt = o[(size_t)(2 * Bp + b) * ldo + c] - t[row * nu + c];
+      acct += (double)dt * (double)dt;
+      gt = gw * dt;
+    }
+    if (dz) {
+      dz[(size_t)b * ldo + c] = g;
+      dz[(size_t)(Bp + b) * ldo + c] = 0.f - g;
+      dz[(size_t)(2 * Bp + b) * ldo + c] = gt;
+    }
+  }
+  red[0][tid] = acc; red[1][tid] = acct;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
+    __syncthreads();
+  }
+  if (tid == 0) { partial[blk] = red[0][0]; partial_tan[blk] = red[1][0]; }
+}
+
+// train_loss_finish with the second sum: loss[0] = L = mse + w tan_mse (in double), loss[1] = mse = scale * sum,
+// loss[2] = tan_mse = scale * tangent sum; acc[0..2] += weight * each (the epoch's running sums).
+__device__ __forceinline__ void train_loss_finish_tan(const double* __restrict__ partial, const double* __restrict__ partial_tan,
+                                                      int np, double scale, double weight, double w,
+                                                      double* __restrict__ loss, double* __restrict__ acc) {
+  double s = 0.0, st = 0.0;
+  for (int i = 0; i < np; ++i) s += partial[i];
+  for (int i = 0; i < np; ++i) st += partial_tan[i];
+  const double mse = s * scale, tan = st * scale, l = mse + w * tan;
+  loss[0] = l; loss[1] = mse; loss[2] = tan;
+  acc[0] += weight * l; acc[1] += weight * mse; acc[2] += weight * tan;
+}
+
+// Hidden-layer forward of pass-1 row tile tm TOGETHER with its tangent tile.  First the primal tile, byte for byte
+// train_fwd_tile<NB, true, true> (same loop, same epilogue, same store order); the sign pattern of what it stored stays in
+// registers, one bit per accumulator entry (16 MT^2 bits per lane: 64 at NB = 128).  Then the same workgroup runs the same
+// tile_gemm_nt loop over the tangent rows 2Bp + tm NB ... against the same weights and stores that tile without bias, zero
+// where the primal activation is <= 0 (derivative 0 at 0, a NaN passes, as in train_nt_mask_tile).  One after the other:
+// no LDS beyond the 4 stages and no accumulators beyond the one set, so two workgroups per CU still fit.
+template <int NB>
+__device__ __forceinline__ void train_fwd_pair_tile(float* __restrict__ C, size_t ldc, const float* __restrict__ A,
+                                                    size_t lda, const float* __restrict__ B, size_t ldb, int K,
+                                                    const float* __restrict__ bias, int Bp, int tm, int tn, float* lds) {
+  using Cf = TileCfg<NB>;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int m0 = tm * NB, n0 = tn * NB;
+  f32x16 acc[Cf::MT][Cf::MT];
+  zero_acc<NB>(acc);
+  PlainOp b{B + (size_t)n0 * ldb, ldb};
+  {
+    PlainOp a{A + (size_t)m0 * lda, lda};
+    tile_gemm_nt<NB>(acc, a, b, K, lds, false);
+  }
+  uint32_t live[Cf::MT][Cf::MT];                            // bit r: entry r of acc[mi][mj] has a non-zero derivative
+#pragma unroll
+  for (int mi = 0; mi < Cf::MT; ++mi)
+#pragma unroll
+    for (int mj = 0; mj < Cf::MT; ++mj) {
+      uint32_t bits = 0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wr * Cf::WT + mi * 32 + acc_row(r, lane);
+        const int col = n0 + wc * Cf::WT + mj * 32 + acc_col(lane);
+        float v = acc[mi][mj][r];
+        v += bias[col];
+        v = relu_nan(v);
+        C[(size_t)row * ldc + col] = v;
+        bits |= (v <= 0.f ? 0u : 1u) << r;
+      }
+      live[mi][mj] = bits;
+    }
+  zero_acc<NB>(acc);
+  {
+    PlainOp a{A + (size_t)(2 * Bp + m0) * lda, lda};
+    tile_gemm_nt<NB>(acc, a, b, K, lds, false);
+  }
+#pragma unroll
+  for (int mi = 0; mi < Cf::MT; ++mi)
+#pragma unroll
+    for (int mj = 0; mj < Cf::MT; ++mj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = 2 * Bp + m0 + wr * Cf::WT + mi * 32 + acc_row(r, lane);
+        const int col = n0 + wc * Cf::WT + mj * 32 + acc_col(lane);
+        C[(size_t)row * ldc + col] = (live[mi][mj] >> r) & 1u ? acc[mi][mj][r] : 0.f;
       }
 }
 

@@ -47,6 +47,11 @@ struct TrainCommon {                                        // what a handle hol
   double lr = 0, beta1 = 0, beta2 = 0, eps = 0;
   int n = 0;                                                // dataset rows
   float *dx = nullptr, *dup = nullptr, *dxs = nullptr, *dus = nullptr, *du = nullptr;
+  // The tangent loss (nnmpc_train_create_tan; never set in a group): the handle stacks a third row block, tan_w is the
+  // weight w of the tangent term (0: the plain step), tdx / tdup / tt the dataset's directions and targets as f32.
+  int tan = 0;
+  double tan_w = 0.0;
+  float *tdx = nullptr, *tdup = nullptr, *tt = nullptr;
   char* dcall = nullptr;                                    // what the last call uploaded: its row lists (behind its step table, in a group)
   hipEvent_t stage_done[2] = {nullptr, nullptr};            // the upload out of the pinned image k (used in turn) has finished
   int stage_turn = 0;
@@ -59,6 +64,10 @@ struct TrainCommon {                                        // what a handle hol
 };
 
 inline int pad128_host(int B) { return ((B + 127) / 128) * 128; }
+// Most stacked rows of a batch of Bp padded samples on this handle: what its workspaces and planes are sized for.
+inline int max_rows(const TrainCommon& c, int Bp) { return train_rows_tan(c.form, Bp, c.tan); }
+// The tangent term is part of this handle's loss.
+inline bool tan_active(const TrainCommon& c) { return c.tan && c.tan_w > 0.0; }
 
 // ---- argument checks that need no device (made before one is looked for) ----
 
@@ -119,7 +128,7 @@ inline int common_init(const char* who, TrainCommon& c, int L, int nx, int nu, i
 // ---- one network ----
 
 // The padding rule (as nnmpc_nn_create: input to 64, wide layers to 128, head to 64) and the most dW slices a layer can
-// take (dw_slices_wanted is non-decreasing in M: its value at the most stacked rows, train_rows(form, cap_batch), sizes the planes).
+// take (dw_slices_wanted is non-decreasing in M: its value at the most stacked rows, max_rows(c, cap_batch), sizes the planes).
 inline void member_shapes(const TrainCommon& c, Member& mb, const int32_t* dims) {
   mb.dims.assign(dims, dims + c.L + 1);
   for (int l = 0; l < c.L; ++l) {
@@ -128,7 +137,7 @@ inline void member_shapes(const TrainCommon& c, Member& mb, const int32_t* dims)
     mb.kpad.push_back(kp); mb.npad.push_back(np_);
     mb.maxw = std::max(mb.maxw, std::max(kp, np_));
     const int nb = (np_ % 128 == 0 && kp % 128 == 0) ? 128 : 64;
-    mb.max_slices.push_back(dw_slices_wanted(c.force_slices, c.num_cus, train_rows(c.form, c.cap_batch), (np_ / nb) * (kp / nb)));
+    mb.max_slices.push_back(dw_slices_wanted(c.force_slices, c.num_cus, max_rows(c, c.cap_batch), (np_ / nb) * (kp / nb)));
   }
 }
 // The dW slices of layer l at M stacked rows and their row count: the rule of nn_train_dev.h at this handle's device and override.
@@ -143,7 +152,7 @@ inline int member_slices(const TrainCommon& c, const Member& mb, int l, int M, i
 inline size_t layout_member(const TrainCommon& c, Member& mb, char* base, size_t off) {
   auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 4095) & ~(size_t)4095; return p; };
   const int L = c.L;
-  const size_t Mmax = (size_t)train_rows(c.form, c.cap_batch);   // the unstructured forms stack one pass: half the workspaces
+  const size_t Mmax = (size_t)max_rows(c, c.cap_batch);   // the unstructured forms stack one pass: half the workspaces; a tangent handle three blocks
   mb.lay.assign(L, GLayer{});
   mb.param_floats = 0;
   for (int l = 0; l < L; ++l) mb.param_floats += 2 * (size_t)mb.npad[l] * mb.kpad[l] + mb.npad[l];   // multiples of 64 floats
@@ -167,7 +176,7 @@ inline size_t layout_member(const TrainCommon& c, Member& mb, char* base, size_t
   }
   mb.mem.dz[0] = (float*)take(Mmax * mb.maxw * 4);
   mb.mem.dz[1] = (float*)take(Mmax * mb.maxw * 4);
-  mb.mem.partial = (double*)take((size_t)c.cap_batch / 64 * 8);
+  mb.mem.partial = (double*)take((size_t)c.cap_batch / 64 * 8 * (c.tan ? 2 : 1));   // a tangent handle: the tangent partials behind the primal ones
   mb.mem.loss = (double*)take(8);
   return off;
 }
@@ -273,7 +282,23 @@ __global__ void train_cvt_k(float* __restrict__ d, const double* __restrict__ s,
   for (; i < n; i += (size_t)gridDim.x * blockDim.x) d[i] = (float)s[i];
 }
 
-// The f32 dataset from f64 columns on the host or (ptr_kind NNMPC_DEVICE) already in HBM.
+// One f32 column of cnt entries from f64 on the host or (ptr_kind NNMPC_DEVICE) already in HBM; the caller waits for the stream.
+inline int upload_column(TrainCommon& c, float** d, const double* s, size_t cnt, int32_t ptr_kind, std::vector<float>& tmp) {
+  if (int rc = c.res.alloc(d, cnt)) return rc;
+  if (ptr_kind == NNMPC_HOST) {
+    tmp.resize(cnt);
+    for (size_t i = 0; i < cnt; ++i) tmp[i] = (float)s[i];
+    HIPCHK(hipMemcpy(*d, tmp.data(), cnt * 4, hipMemcpyHostToDevice));
+  } else {
+    hipLaunchKernelGGL(train_cvt_k, dim3(1024), dim3(256), 0, c.stream, *d, s, cnt);
+  }
+  return NNMPC_OK;
+}
+inline void drop_tangents(TrainCommon& c) {
+  for (float** p : {&c.tdx, &c.tdup, &c.tt}) { c.res.give_back(*p); *p = nullptr; }
+}
+
+// The f32 dataset from f64 columns on the host or (ptr_kind NNMPC_DEVICE) already in HBM.  Tangents of the earlier dataset go with it.
 inline int set_data(const char* who, TrainCommon& c, int32_t n, const double* x, const double* uprev, const double* xs,
                     const double* us, const double* u, int32_t ptr_kind) {
   if (n < 1 || !x || !xs || !us || !u) { set_error("%s: bad arguments", who); return NNMPC_EINVAL; }
@@ -281,25 +306,45 @@ inline int set_data(const char* who, TrainCommon& c, int32_t n, const double* x,
   HIPCHK(hipSetDevice(c.device));
   HIPCHK(stream_sync(c.stream));
   for (float** p : {&c.dx, &c.dup, &c.dxs, &c.dus, &c.du}) { c.res.give_back(*p); *p = nullptr; }
+  drop_tangents(c);
   c.n = 0;
   struct { float** d; const double* s; int w; } col[5] = {{&c.dx, x, c.nx}, {&c.dup, c.with_uprev ? uprev : nullptr, c.nu},
                                                           {&c.dxs, xs, c.nx}, {&c.dus, us, c.nu}, {&c.du, u, c.nu}};
   std::vector<float> tmp;
   for (auto& k : col) {
     if (!k.s) continue;
-    const size_t cnt = (size_t)n * k.w;
-    if (int rc = c.res.alloc(k.d, cnt)) return rc;
-    if (ptr_kind == NNMPC_HOST) {
-      tmp.resize(cnt);
-      for (size_t i = 0; i < cnt; ++i) tmp[i] = (float)k.s[i];
-      HIPCHK(hipMemcpy(*k.d, tmp.data(), cnt * 4, hipMemcpyHostToDevice));
-    } else {
-      hipLaunchKernelGGL(train_cvt_k, dim3(1024), dim3(256), 0, c.stream, *k.d, k.s, cnt);
-    }
+    if (int rc = upload_column(c, k.d, k.s, (size_t)n * k.w, ptr_kind, tmp)) return rc;
   }
   HIPCHK(stream_sync(c.stream));
   HIPCHK(hipGetLastError());
   c.n = n;
+  return NNMPC_OK;
+}
+
+// The dataset's tangent directions and targets (a tangent handle only), one per row of the dataset set_data gave.
+inline int set_tangents(const char* who, TrainCommon& c, int32_t n, const double* dx, const double* duprev, const double* t,
+                        int32_t ptr_kind) {
+  if (!c.tan) { set_error("%s: a plain handle has no tangent loss (nnmpc_train_create_tan builds the handle that has)", who); return NNMPC_EINVAL; }
+  if (int rc = check_data(c, who)) return rc;
+  if (!dx || !t) { set_error("%s: bad arguments", who); return NNMPC_EINVAL; }
+  if (n != c.n) { set_error("%s: tangents of %d rows for a dataset of %d", who, n, c.n); return NNMPC_EINVAL; }
+  if (c.with_uprev && !duprev) { set_error("%s: uprev is an input of the network, no duprev given", who); return NNMPC_EINVAL; }
+  HIPCHK(hipSetDevice(c.device));
+  HIPCHK(stream_sync(c.stream));
+  drop_tangents(c);
+  struct { float** d; const double* s; int w; } col[3] = {{&c.tdx, dx, c.nx}, {&c.tdup, c.with_uprev ? duprev : nullptr, c.nu}, {&c.tt, t, c.nu}};
+  std::vector<float> tmp;
+  for (auto& k : col) {
+    if (!k.s) continue;
+    if (int rc = upload_column(c, k.d, k.s, (size_t)n * k.w, ptr_kind, tmp)) { drop_tangents(c); return rc; }
+  }
+  HIPCHK(stream_sync(c.stream));
+  HIPCHK(hipGetLastError());
+  return NNMPC_OK;
+}
+// grad, step, epoch and eval of a handle whose loss has the tangent term need the tangents (before any launch).
+inline int check_tangents(const TrainCommon& c, const char* who) {
+  if (tan_active(c) && !c.tt) { set_error("%s: the tangent weight is %g and the dataset has no tangents (set_tangents comes after set_data, which drops them)", who, c.tan_w); return NNMPC_EINVAL; }
   return NNMPC_OK;
 }
 

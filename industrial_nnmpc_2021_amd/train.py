@@ -17,6 +17,9 @@ one lock-step launch group (csrc/nn_train_group.hip, ``HipGroupTrainer``).
 ``train_unstd_nn_controller`` trains the reference's unstructured comparison
 network (``cstrs_train_unstd.py``) on the one-pass form of the single-network step,
 ``train_unstd_nn_controllers`` a sweep of them in one launch group of that form.
+
+``train_nn_controller(..., tan_weight=w)`` trains the structured network on the MPC's value AND its local slope (the
+tangent loss, ``tangent_loss``); ``tangent_data`` makes the slope targets from a solved batch.
 """
 import copy
 import ctypes as C
@@ -177,21 +180,28 @@ class HipTrainer:
     ``_lib.NN_UNSTD_RELU`` (the same with relu on the head).  ``grad``, ``get_weights`` and ``set_weights`` exchange the
     list of the form.
 
+    ``tangents=True`` (structured form only) builds the handle of the tangent loss (``nnmpc_train_create_tan``):
+    ``set_tangents`` after ``set_data``, ``set_tan_weight(w)``; then ``grad``, ``step``, ``epoch`` and ``eval`` work on
+    L = mse + w tan_mse (``tangent_loss``) and ``last_losses()`` returns the two parts.  With w = 0 (as created) it
+    computes the bytes of a plain handle.
+
     Adam as ``torch.optim.Adam(lr, betas, eps)``.  There is no CPU fallback: without a device the constructor raises
     ``_lib.NnmpcError``."""
 
     def __init__(self, weights, nx, nu, *, nnwithuprev=True, max_batch=2048, lr=1e-3, betas=(0.9, 0.999), eps=1e-7,
-                 form=_lib.NN_STRUCTURED):
+                 form=_lib.NN_STRUCTURED, tangents=False):
         self.form = _check_form(form)
+        self.tangents = bool(tangents)
         Ws, bs = _split_keras(weights, self.form)               # refused on the host, before the library is loaded
         lib = _lib.load()
         L = len(Ws)
         self.dims = [Ws[0].shape[0]] + [w.shape[1] for w in Ws]
         self.L, self.nx, self.nu, self.nnwithuprev, self.n = L, nx, nu, bool(nnwithuprev), 0
         self._lib, self._h = lib, C.c_void_p()
-        _lib.check(lib.nnmpc_train_create_ex(C.byref(self._h), L, (C.c_int32 * (L + 1))(*self.dims), self._plist(Ws),
-                                             self._plist(bs), nx, nu, int(self.nnwithuprev), int(max_batch),
-                                             lr, betas[0], betas[1], eps, self.form), "nnmpc_train_create_ex")
+        create, who = ((lib.nnmpc_train_create_tan, "nnmpc_train_create_tan") if self.tangents
+                       else (lib.nnmpc_train_create_ex, "nnmpc_train_create_ex"))
+        _lib.check(create(C.byref(self._h), L, (C.c_int32 * (L + 1))(*self.dims), self._plist(Ws), self._plist(bs), nx, nu,
+                          int(self.nnwithuprev), int(max_batch), lr, betas[0], betas[1], eps, self.form), who)
 
     @staticmethod
     def _plist(arrays):
@@ -220,6 +230,32 @@ class HipTrainer:
         _lib.check(self._lib.nnmpc_train_set_data(self._h, int(n), q(x), q(uprev), q(xs), q(us), q(u), _lib.DEVICE),
                    "nnmpc_train_set_data")
         self.n = int(n)
+
+    def set_tangents(self, tangents):
+        """dict(dx, duprev, du): per dataset row one direction [dx, (duprev)] in the units of the dataset's x and the
+        target du (``tangent_data`` returns them); after ``set_data``, which drops earlier ones.  Uploaded once as f32."""
+        c = lambda a, w: np.ascontiguousarray(a, np.float64).reshape(-1, w)
+        dx, du = c(tangents["dx"], self.nx), c(tangents["du"], self.nu)
+        dup = c(tangents["duprev"], self.nu) if self.nnwithuprev and tangents.get("duprev") is not None else None
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_train_set_tangents(self._h, dx.shape[0], p(dx), p(dup), p(du), _lib.HOST),
+                   "nnmpc_train_set_tangents")
+
+    def set_tangents_device(self, n, dx, duprev, du):
+        """The same from HBM-resident f64 buffers (objects with data_ptr(); ``duprev`` None without uprev)."""
+        q = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+        _lib.check(self._lib.nnmpc_train_set_tangents(self._h, int(n), q(dx), q(duprev), q(du), _lib.DEVICE),
+                   "nnmpc_train_set_tangents")
+
+    def set_tan_weight(self, w):
+        """The weight of the tangent term, finite and >= 0 (0: the plain step)."""
+        _lib.check(self._lib.nnmpc_train_set_tan_weight(self._h, float(w)), "nnmpc_train_set_tan_weight")
+
+    def last_losses(self):
+        """(mse, tan_mse) of what the last grad / step / epoch / eval returned (L = mse + w tan_mse)."""
+        a, b = C.c_double(), C.c_double()
+        _lib.check(self._lib.nnmpc_train_last_losses(self._h, C.byref(a), C.byref(b)), "nnmpc_train_last_losses")
+        return a.value, b.value
 
     @staticmethod
     def _rows(rows):
@@ -564,13 +600,17 @@ def train_unstd_nn_controllers(models, data, *, num_samples=None, epochs=2000, b
     return _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr, seed, log, forms[0])
 
 
-def _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log, form=_lib.NN_STRUCTURED):
+def _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log, form=_lib.NN_STRUCTURED,
+               tan_weight=0.0):
     """The "hip" backend of train_nn_controller / train_unstd_nn_controller: same Keras semantics, every step on the
-    device in f32."""
+    device in f32.  ``tan_weight > 0``: the tangent handle, so run and validation losses are L."""
     tr = HipTrainer(model.get_weights(), model.Nx, model.Nu, nnwithuprev=model.nnwithuprev, max_batch=batch_size,
-                    lr=lr, eps=1e-7, form=form)
+                    lr=lr, eps=1e-7, form=form, tangents=tan_weight > 0)
     try:
         tr.set_data(data)
+        if tan_weight > 0:
+            tr.set_tangents(data)
+            tr.set_tan_weight(tan_weight)
         n = tr.n
         nval = int(n * validation_split)
         ntr = n - nval
@@ -597,8 +637,68 @@ def _train_hip(model, data, epochs, batch_size, validation_split, lr, device, se
     return model, ttime, hist
 
 
+def tangent_loss(model, x, uprev, xs, us, u, dx, duprev, du, w):
+    """(L, mse, tan_mse) of a structured ``RegulatorModel`` on a batch, in stock torch:
+
+        L = mean (pred - u)^2 + w mean (J d - du)^2,
+
+    J d the tangent of pred along d = [dx, (duprev)], propagated forward through the same weights -- a'_0 = [dx, (duprev), 0, 0],
+    a'_l = (a'_{l-1} W_l) * [a_l(pass 1) > 0], J d = a'_{L-1} W_L; no bias, ReLU derivative 0 at 0 (a NaN activation passes,
+    as in the native step), pass 2 does not depend on x or uprev.  The masks carry no gradient (ReLU has no second
+    derivative), so autograd through this is the gradient the native step computes.  ``duprev`` is ignored without uprev."""
+    if model.nnwithuprev:
+        z1, z2 = torch.cat((x, uprev, xs, us), -1), torch.cat((xs, us, xs, us), -1)
+        ta = torch.cat((dx, duprev, torch.zeros_like(xs), torch.zeros_like(us)), -1)
+    else:
+        z1, z2 = torch.cat((x, xs, us), -1), torch.cat((xs, xs, us), -1)
+        ta = torch.cat((dx, torch.zeros_like(xs), torch.zeros_like(us)), -1)
+    a = z1
+    for lin in model.layers[:-1]:
+        a = torch.relu(lin(a))
+        ta = (ta @ lin.weight.T) * (~(a <= 0)).to(a.dtype)
+    head = model.layers[-1]
+    pred = us + head(a) - model._mlp(z2)
+    mse = torch.mean((pred - u) ** 2)
+    tan = torch.mean((ta @ head.weight.T - du) ** 2)
+    return mse + w * tan, mse, tan
+
+
+def tangent_data(regulator, data, xscale, *, ulb, uub, seed=0, nnwithuprev=True):
+    """Tangent targets for ``train_nn_controller(..., tan_weight=w)`` from the regulator's own solves.
+
+    ``data``: the raw generated rows dict(x, uprev, xs, us) (before scaling); ``xscale``: what
+    ``_get_data_for_training`` divides x and xs by; ``ulb`` / ``uub``: the plant's input bounds (Nu,).  Per row one
+    standard-normal direction is drawn in the units of the scaled dataset, d = [dx, duprev] (``seed``); the batch
+    X0 = [x - xs, uprev - us] is solved with bounds ulb - us, uub - us and ``first_move_only=True``, and
+    ``regulator.sensitivity_batch(info, dX0=[dx * xscale, duprev], first_move_only=True)`` gives du, the change of the
+    MPC's first move along the direction inside the row's critical region.  ``nnwithuprev=False`` (a network that
+    does not see uprev; the regulator still starts from ``data["uprev"]``): the duprev part of dX0, and the returned
+    ``duprev``, are zero.
+
+    Returns dict(dx (n, Nx), duprev (n, Nu), du (n, Nu), flag (n,)).  A row whose sensitivity flag is not 0, or whose
+    solve status is not 0, has no certified slope: its direction AND its target are set to zero, so J d = 0 = du and the
+    row contributes exactly nothing to the tangent term or its gradient.  The mean's denominator stays B nu all the same
+    (such rows weigh the term down, they do not bias it)."""
+    x, xs = np.asarray(data["x"], float), np.asarray(data["xs"], float)
+    us, up = np.asarray(data["us"], float), np.asarray(data["uprev"], float)
+    n, nx, nu = x.shape[0], x.shape[1], us.shape[1]
+    xscale = np.asarray(xscale, float).reshape(1, nx)
+    rng = np.random.default_rng(seed)
+    dx = rng.standard_normal((n, nx))
+    dup = rng.standard_normal((n, nu)) if nnwithuprev else np.zeros((n, nu))
+    lb = np.asarray(ulb, float).reshape(1, nu) - us
+    ub = np.asarray(uub, float).reshape(1, nu) - us
+    _, info = regulator.solve_batch(np.concatenate((x - xs, up - us), axis=1), lb, ub, first_move_only=True)
+    out = regulator.sensitivity_batch(info, np.concatenate((dx * xscale, dup), axis=1), first_move_only=True)
+    flag = np.asarray(out["flag"]).astype(np.int32).ravel().copy()
+    bad = (flag != 0) | (np.asarray(info["status"]).ravel() != 0)
+    du = np.array(out["du"], float).reshape(n, nu)
+    dx[bad] = 0.0; dup[bad] = 0.0; du[bad] = 0.0
+    return dict(dx=dx, duprev=dup, du=du, flag=flag)
+
+
 def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation_split=0.05, lr=1e-3,
-                        device=None, seed=1, log=None, backend="torch"):
+                        device=None, seed=1, log=None, backend="torch", tan_weight=0.0):
     """Adam + MSE on ``data`` = dict(x, uprev, xs, us, u) (rows = samples, already scaled like
     the reference's _get_data_for_training).  Keras semantics: the LAST fraction of the rows is
     the validation set, the rest is reshuffled every epoch; the weights of the best validation
@@ -606,10 +706,24 @@ def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation
 
     ``backend="torch"``: stock PyTorch ops in the model's dtype on ``device``.  ``backend="hip"``: the native f32
     step (``HipTrainer``), shuffled by a numpy generator seeded with ``seed``; ``model`` comes back carrying the
-    trained weights.  No device: ``_lib.NnmpcError`` (no CPU fallback)."""
+    trained weights.  No device: ``_lib.NnmpcError`` (no CPU fallback).
+
+    ``tan_weight = w > 0`` (a structured ``RegulatorModel`` only): the loss is ``tangent_loss``, L = mse + w tan_mse, and
+    ``data`` also holds dx, (duprev) and du, one direction and one slope target per row (``tangent_data``).  Both backends
+    serve it; the history, the validation loss and the best-epoch checkpoint are then those of L.  0 (the default) is
+    the plain loss, exactly as without the argument."""
+    tan_weight = float(tan_weight)
+    if not (tan_weight >= 0.0 and np.isfinite(tan_weight)):
+        raise ValueError(f"tan_weight {tan_weight!r}: finite and >= 0")
+    if tan_weight > 0:
+        if getattr(model, "unstructured", False):
+            raise ValueError("train_nn_controller: the tangent loss is built for the structured RegulatorModel only")
+        need = ("dx", "du") + (("duprev",) if model.nnwithuprev else ())
+        if any(data.get(k) is None for k in need):
+            raise ValueError(f"train_nn_controller: tan_weight > 0 needs {', '.join(need)} in data (tangent_data makes them)")
     if backend == "hip":
         _refuse_unstructured(model, "train_nn_controller(backend=\"hip\")")
-        return _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log)
+        return _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log, tan_weight=tan_weight)
     if backend != "torch":
         raise ValueError(f"unknown backend {backend!r}: 'torch' or 'hip'")
     torch.manual_seed(seed)
@@ -619,6 +733,16 @@ def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation
     T = {k: torch.as_tensor(np.asarray(data[k]), dtype=dt, device=device) for k in ("x", "xs", "us", "u")}
     T["uprev"] = (torch.as_tensor(np.asarray(data["uprev"]), dtype=dt, device=device)
                   if model.nnwithuprev else torch.zeros_like(T["us"]))
+    if tan_weight > 0:
+        T["dx"], T["du"] = (torch.as_tensor(np.asarray(data[k]), dtype=dt, device=device) for k in ("dx", "du"))
+        T["duprev"] = (torch.as_tensor(np.asarray(data["duprev"]), dtype=dt, device=device)
+                       if model.nnwithuprev else torch.zeros_like(T["us"]))
+
+        def loss_of(S, idx):
+            return tangent_loss(model, *(S[k][idx] for k in ("x", "uprev", "xs", "us", "u", "dx", "duprev", "du")), tan_weight)[0]
+    else:
+        def loss_of(S, idx):
+            return torch.mean((model(S["x"][idx], S["uprev"][idx], S["xs"][idx], S["us"][idx]) - S["u"][idx]) ** 2)
     n = T["x"].shape[0]
     nval = int(n * validation_split)
     ntr = n - nval
@@ -633,15 +757,14 @@ def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation
         run = 0.0
         for i in range(0, ntr, batch_size):
             idx = perm[i:i + batch_size]
-            pred = model(tr["x"][idx], tr["uprev"][idx], tr["xs"][idx], tr["us"][idx])
-            loss = torch.mean((pred - tr["u"][idx]) ** 2)
+            loss = loss_of(tr, idx)
             opt.zero_grad(set_to_none=True)
             loss.backward()
             opt.step()
             run += float(loss.detach()) * idx.numel()
         model.eval()
         with torch.no_grad():
-            vl = float(torch.mean((model(va["x"], va["uprev"], va["xs"], va["us"]) - va["u"]) ** 2)) if nval else run / ntr
+            vl = float(loss_of(va, slice(None))) if nval else run / ntr
         hist.append((run / ntr, vl))
         if vl < best:                                   # ModelCheckpoint(save_best_only=True)
             best, best_state = vl, copy.deepcopy(model.state_dict())
