@@ -146,6 +146,7 @@ typedef struct {
   int64_t adj_lds_problems;  /* problems nnmpc_qp_adjoint ran in the LDS instance (sets of at most 160 bounds, and the flagged ones); counted always */
   int64_t adj_slab_problems; /* ... and in the slab instance (161 to 768 bounds) */
   double adj_total_ms;       /* hipEvent time of whole nnmpc_qp_adjoint calls on the handle's stream, the host's sorting between the launches included (profiling on) */
+  int64_t asm_carried;       /* problems whose round was a copy of the corrected multipliers the f32 screen before it had kept for the same set (NNMPC_CARRY) */
 } nnmpc_qp_stats;
 
 const char* nnmpc_last_error(void);

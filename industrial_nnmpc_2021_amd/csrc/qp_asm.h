@@ -78,9 +78,10 @@ __host__ __device__ constexpr int asm_list_counter(int list) {
 __host__ __device__ constexpr int asm_list_of_counter(int c) { return c >= ASM_CNT_F32 ? ASM_NBIN + c - ASM_CNT_F32 : c - 4; }   // size-class lists only
 constexpr int ASM_NKG = 3;         // rows of a round are ordered by the last active stage (groups: <= median, +1, beyond),
                                    // so that a 128-row block of the GEMM stops its k-loop at ITS last active bound
-constexpr int ASM_NSCAN = ASM_NLIST + 9 + 2 * ASM_NKG;  // scan columns: large sets, the lists, (fp64, f32) x group rows, the problems the
-                                                        // full-width pass handled (number, sum of last active index + 1), sum and max of
-                                                        // the last active indices of the running problems
+constexpr int ASM_NSCAN = ASM_NLIST + 10 + 2 * ASM_NKG; // scan columns: large sets, the lists, (fp64, f32) x group rows, the problems the
+                                                        // full-width pass handled (number, sum of last active index + 1), the carried
+                                                        // problems, sum and max of the last active indices of the running problems
+constexpr int ASM_CNT_CARRY = 24;  // counters[24]: length of AsmDev::carrylist (problems whose round is a copy of the stashed multipliers)
 constexpr int ASM_CNT_ROWS32 = 15; // counters[15]: rows of LAM32 / XH32 handed out ([2]: rows of LAM / XH)
 __host__ __device__ constexpr int asm_bin_cap(int b) { return 16 * (b + 4); }
 
@@ -166,6 +167,13 @@ struct AsmDev {
   double refine_tol;               // residual of a corrected f32 solve, relative to max |b|, that counts as an fp64 solve (ASM_REFINE_TOL)
   int refine_later;                // ... from the next round on (this one may still be a plain f32 screen): a set that settles in f32 now is NOT sent to the fp64 kernel
   int early64;                     // an f32 round that moves at most this many bounds is followed by an fp64 round (0: only a settled set is)
+  // Carry: the plain f32 screen that precedes the corrected rounds (refine_later set, refine not yet) runs the
+  // fp64 correction as well and keeps its result; a problem whose set that screen leaves unchanged gets the kept multipliers copied
+  // into its fp64 row of the next round (asm_carry_copy) instead of the same solve a second time.
+  int carry;                       // 1: this round stashes corrected multipliers, 2: this round copies them for the carried problems, 0: neither
+  double* stash;                   // [nseg][ASM_MLDS] corrected multipliers of the stashing round's set, in list order
+  unsigned char* cflag;            // [nseg] 1: stash holds this round's set (asm_lambda_reg), 2: carried -- the next round is a copy (asm_update_k); else 0
+  int* carrylist;                  // [nseg] the carried problems of this round (asm_bins_b_k), counters[ASM_CNT_CARRY] of them
   int* wflag;                      // [nseg] set by asm_wide_gemm_k when a bound beyond the window is violated (cleared by asm_wide_k)
   double* work;                    // [nseg][3] statistics: flops (m^3/3 + 2 m^2) and gathered bytes of the lambda kernels, flops of the f32 rounds
   double* scratch;                 // [pool][tiles(max_active) * ASM_TS] tile slabs of the queue kernel
@@ -220,6 +228,7 @@ __global__ __launch_bounds__(256) void asm_init_k(AsmDev d, int nrows) {
     d.rounds[p] = 0; d.state[p] = invalid ? ASM_INVALID : ASM_RUN;
     d.prec[p] = (d.use_f32 && !d.guess && !(d.pred_w && d.pred_f64)) ? 0 : 1;   // a caller's guess (a predicted set) is expected to be right: fp64 at once
     d.redo[p] = 0;
+    if (d.cflag) d.cflag[p] = 0;
     d.ninf_best[p] = 0x7fffffff; d.alpha[p] = ASM_GRACE;
     d.hi[p] = max(wi, d.guess ? 0 : d.pred_w);           // (a predicted set may hold bounds anywhere in the predictor's window)
   }
@@ -311,6 +320,8 @@ __device__ __forceinline__ int asm_count_wave(const AsmDev& d, int p, int hi_p) 
   }
   return m;
 }
+// carried: the round before stashed the corrected multipliers of this very set (asm_update_k found nothing to move)
+__device__ __forceinline__ bool asm_carried(const AsmDev& d, int p) { return d.carry == 2 && d.cflag[p] == 2; }
 #if ASM_OWN_KERNELS
 __global__ __launch_bounds__(256) void asm_count_k(AsmDev d) {
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -318,7 +329,7 @@ __global__ __launch_bounds__(256) void asm_count_k(AsmDev d) {
   const int m = asm_count_wave(d, p, d.hi[p]);
   if ((threadIdx.x & 63) == 0) {
     d.mg[p] = m;
-    if (m <= d.max_active && d.work) {
+    if (m <= d.max_active && d.work && !asm_carried(d, p)) {   // (a carried problem's round is a copy: nothing is factored)
       const double md = (double)m;
       d.work[3 * p] += md * md * md / 3.0 + 2.0 * md * md;             // per-problem slots: same-address atomics
       d.work[3 * p + 1] += 8.0 * (md * (md + 1.0) / 2.0 + 2.0 * md);   // (one per workgroup) serialise the launch
@@ -336,14 +347,17 @@ __global__ __launch_bounds__(256) void asm_count_k(AsmDev d) {
 // counters: [2] / [ASM_CNT_ROWS32] running problems solved in fp64 / f32 this round (the host adds them up), [1] sets too large for LDS, [3] largest active variable index, [4 + b] length
 // of size-class list b.  counters[ASM_CNT_WIDEG..] (filled by asm_update_k, consumed by asm_wide_k earlier in
 // the round) is reset here.
-// scan columns: 0 large sets, 1 + list (lists 0 .. ASM_NLIST + 3), ASM_COL_ROW + prec * ASM_NKG + group (rows of LAM / LAM32), then the sum of
-// (last active index + 1) and the max index
+// scan columns: 0 large sets, 1 + list (lists 0 .. ASM_NLIST + 3), ASM_COL_ROW + prec * ASM_NKG + group (rows of LAM / LAM32), the problems
+// the full-width pass handled, ASM_COL_CARRY (carried problems: a row of LAM like the others, but no size-class list -- their own
+// list, for asm_carry_copy), then the sum of (last active index + 1) and the max index
 constexpr int ASM_COL_ROW = 5 + ASM_NLIST;
-constexpr int ASM_COL_WCNT = ASM_COL_ROW + 2 * ASM_NKG, ASM_COL_WK = ASM_COL_WCNT + 1;
+constexpr int ASM_COL_WCNT = ASM_COL_ROW + 2 * ASM_NKG, ASM_COL_WK = ASM_COL_WCNT + 1, ASM_COL_CARRY = ASM_COL_WK + 1;
+static_assert(ASM_COL_CARRY == ASM_NSCAN - 3, "the scan columns end with: carried, sum, max");
 constexpr int ASM_WG_SETS = 256;   // largest set of the four-wave register kernels (qp_wg.h)
-__device__ __forceinline__ int asm_scan_col(const AsmDev& d, int p, bool& run) {   // 0 large set, 1 + list otherwise
+__device__ __forceinline__ int asm_scan_col(const AsmDev& d, int p, bool& run) {   // 0 large set, 1 + list, ASM_COL_CARRY
   run = p < d.nseg && d.state[p] == ASM_RUN;
   if (!run) return -1;
+  if (asm_carried(d, p)) return ASM_COL_CARRY;
   const int m = d.mg[p];
   if (m > ASM_MLDS) return (d.prec[p] == 0 && m <= ASM_BIG32) ? 1 + ASM_NLIST : ((d.use_wg && m <= ASM_WG_SETS) ? 2 + ASM_NLIST : ((d.use_wg && d.prec[p] == 0 && m <= ASM_BIG32B) ? 3 + ASM_NLIST : ((d.use_wg && d.prec[p] == 1 && m <= ASM_BIG32B) ? 4 + ASM_NLIST : 0)));   // (prec 2: the refinement gave up on this set)
   const int b = max((m + 15) / 16, 4) - 4;
@@ -385,6 +399,11 @@ __global__ __launch_bounds__(1024) void asm_bins_a_k(AsmDev d) {
     const unsigned long long mk = __ballot(col == c);
     if (col == c) myrank = __popcll(mk & lt);
     if (lane == 0) wtot[c][wave] = __popcll(mk);
+  }
+  {
+    const unsigned long long mk = __ballot(col == ASM_COL_CARRY);
+    if (col == ASM_COL_CARRY) myrank = __popcll(mk & lt);
+    if (lane == 0) wtot[ASM_COL_CARRY][wave] = __popcll(mk);
   }
   int km = kl, ks = run ? kl + 1 : 0;                        // ks: columns of LAM this row really has
   // problems the full-width pass at the start of this round handled (asm_wide_k marked them): number, sum of (last active index + 1)
@@ -428,6 +447,7 @@ __global__ __launch_bounds__(1024) void asm_bins_b_k(AsmDev d) {
     } else if (tid == ASM_NSCAN - 2) d.counters[0] = total[tid];   // sum of (last active index + 1): algorithmic k of the GEMM
     else if (tid == ASM_COL_WCNT) d.counters[ASM_CNT_WIDE + 1] = total[tid];
     else if (tid == ASM_COL_WK) d.counters[ASM_CNT_WKSUM] = total[tid];
+    else if (tid == ASM_COL_CARRY) d.counters[ASM_CNT_CARRY] = total[tid];
     else if (tid == 0) d.counters[1] = total[0];
     else if (tid <= ASM_NLIST + 4) d.counters[asm_list_counter(tid - 1)] = total[tid];
     else if (tid == ASM_COL_ROW) { int t = 0; for (int g = 0; g < ASM_NKG; ++g) t += total[ASM_COL_ROW + g]; d.counters[2] = t; }
@@ -448,6 +468,7 @@ __global__ __launch_bounds__(1024) void asm_bins_b_k(AsmDev d) {
   atomicMax(&d.kblk[(r32 ? d.nkblk / 2 : 0) + (row >> 6)], kl);   // last active bound of this 64-row block
   const int pos = base[col] + d.lrank[p];
   if (col == 0) d.biglist[pos] = p;
+  else if (col == ASM_COL_CARRY) d.carrylist[pos] = p;
   else d.binlist[(size_t)(col - 1) * d.nseg + pos] = p;
 }
 #endif
@@ -1199,8 +1220,21 @@ __device__ __forceinline__ void asm_lambda_reg(const AsmDev& d, int list, int wg
   // f32 rounds with a row of LAM (fp64): asm_bins hands those out when d.refine is set -- a result that can be final gets its fp64 correction
   AsmRefine<MB> rf;
   const bool refine = N::F32 && d.rowk[p] == 0;
+  // the plain f32 screen before the corrected rounds (d.carry == 1): the same correction, kept aside for the next round -- the f32
+  // result goes to LAM32 as ever (the correction does not touch lam)
+  const bool keep = N::F32 && !refine && d.carry == 1;
   if (N::F32) { rf.xunc = d.xunc + o; rf.lb = d.lb + (size_t)p * d.nu; rf.ub = d.ub + (size_t)p * d.nu; rf.st = st; rf.idx = idx; }
-  const int bad = asm_reg_core<T, MB, asm_nl<T>(MB), false, N::F32>(d, m, ix, dt, Yt, ys, rv, lt, idt, lam, lane, wg, wave, rf, refine);
+  int bad = asm_reg_core<T, MB, asm_nl<T>(MB), false, N::F32>(d, m, ix, dt, Yt, ys, rv, lt, idt, lam, lane, wg, wave, rf, refine || keep);
+  if (N::F32 && keep && bad == 2) {
+    double* sp = d.stash + (size_t)p * ASM_MLDS;
+#pragma unroll
+    for (int I = 0; I < MB; ++I) {
+      const int i = 16 * I + li;
+      if (lq == 0 && i < m) sp[i] = rf.lam64[I];
+    }
+    if (lane == 0) d.cflag[p] = 1;
+    bad = 0;
+  }
   if (N::F32 && refine && bad != 1) {
     if (bad == 2 && lane == 0) d.redo[p] = 2;               // corrected in fp64: asm_update_k verifies the residual and may accept the set
     double* lrow64 = d.lam + (size_t)d.row[p] * d.np;
@@ -1452,6 +1486,22 @@ __global__ __launch_bounds__(128, 1) void asm_lambda_reg2_k(AsmDev d) {
   static_assert(ASM_NBIN == 8 && ASM_MLDS == 176, "classes 6 and 7 are the 10- and 11-block sets");
 }
 #endif
+// The round of a carried problem (AsmDev::carry): the corrected multipliers the screen before kept for this very set -> its fp64
+// row of LAM, marked for asm_update_k's residual test like a corrected solve of this round.  One wave per problem, four per
+// workgroup: the last class of asm_lambda_reg32_k's grid (as a launch of its own after that kernel the copy was 0.05 ms on the
+// main stream at 55 000 problems; here its workgroups start while the last solves drain).
+__device__ __forceinline__ void asm_carry_copy(const AsmDev& d, int wg) {
+  const int lane = threadIdx.x & 63;
+  const int it = wg * 4 + (threadIdx.x >> 6);
+  if (it >= d.counters[ASM_CNT_CARRY]) return;
+  const int p = d.carrylist[it];
+  const int m = min(d.mg[p], ASM_MLDS);
+  const int* idx = d.idxg + (size_t)p * d.max_active;
+  const double* sp = d.stash + (size_t)p * ASM_MLDS;
+  double* lrow = d.lam + (size_t)d.row[p] * d.np;
+  for (int i = lane; i < m; i += 64) lrow[idx[i]] = sp[i];
+  if (lane == 0) { d.redo[p] = 2; d.cflag[p] = 0; }
+}
 // The f32 rounds of classes 0..5: two workgroups per CU (two waves per SIMD).
 constexpr int ASM_REG32_LDS = (4 * asm_rw<float>(ASM_NREG + 3) + ASM_TS) * 4;
 #if ASM_OWN_KERNELS
@@ -1465,6 +1515,7 @@ __global__ __launch_bounds__(256, 2) void asm_lambda_reg32_k(AsmDev d) {
   }
   ASM_REG_CLASS(5) ASM_REG_CLASS(4) ASM_REG_CLASS(3) ASM_REG_CLASS(2) ASM_REG_CLASS(1) ASM_REG_CLASS(0)
 #undef ASM_REG_CLASS
+  asm_carry_copy(d, w);                                    // (the launch has workgroups beyond the classes only for these)
 }
 #endif
 
@@ -1502,11 +1553,12 @@ __global__ __launch_bounds__(256) void asm_update_k(AsmDev d) {   // one WAVE pe
   if (p >= d.nseg || d.state[p] != ASM_RUN) return;
   const int rdo = d.redo[p];
   if (rdo == 1) {                                            // the f32 kernel gave up on this set: nothing was computed,
-    if (lane == 0) d.redo[p] = 0;                            // the same set runs again in fp64
+    if (lane == 0) { d.redo[p] = 0; if (d.cflag) d.cflag[p] = 0; }   // the same set runs again in fp64
     return;
   }
   if (rdo && lane == 0) d.redo[p] = 0;                       // 2: an f32 solve with its fp64 correction (asm_reg_core): verified below
   const bool f32_phase = d.rowk[p] != 0;                     // f32 solve and GEMM: only good enough to move the set
+  const bool kept = d.carry == 1 && d.cflag[p] == 1;         // the stash holds the corrected multipliers of this round's set
   const size_t o = (size_t)p * d.np, orow = (size_t)d.row[p] * d.np;
   unsigned char* st = d.st + (size_t)p * d.n;
   const int W = min(d.W, d.n);                               // every active bound lies inside the window
@@ -1620,6 +1672,9 @@ __global__ __launch_bounds__(256) void asm_update_k(AsmDev d) {   // one WAVE pe
     if (tot > 0 && d.hi[p] < W) d.hi[p] = W;                 // bounds inside the window may have joined
     const bool refine_next = d.refine_later && m <= ASM_MLDS;   // (the classes asm_lambda_reg serves: larger sets keep the f32 -> fp64 ladder)
     if (tot == 0 && !grade64 && !(f32_phase && refine_next)) d.prec[p] = 1;   // (refine_later: the next round solves it in f32 with the fp64 correction)
+    // ... unless this round's kernel already did and kept the corrected multipliers: the next round copies them.  In every other
+    // case the flag goes back to 0 (only a round with d.carry == 1 can have raised one)
+    if (kept) d.cflag[p] = (f32_phase && tot == 0 && refine_next) ? 2 : 0;
     // ... and so is one that is about to: when at most early64 bounds moved, the next set is most often the final one, and
     // solving it in fp64 at once saves the f32 round that would only have confirmed it (CDU batch: 4.65 -> 3.7 f32 solves
     // per problem, still one fp64 solve for nine in ten)

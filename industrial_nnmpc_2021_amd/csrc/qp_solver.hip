@@ -707,7 +707,8 @@ struct nnmpc_qp {
   unsigned char* asm_wmark;
   unsigned char* asm_st;
   int *asm_state, *asm_rounds, *asm_biglist, *asm_status, *asm_binlist, *asm_idxg, *asm_mg, *asm_row, *asm_lrank, *asm_ctot;
-  unsigned char *asm_prec, *asm_redo, *asm_alpha, *asm_rowk;
+  unsigned char *asm_prec, *asm_redo, *asm_alpha, *asm_rowk, *asm_cflag;
+  int* asm_carrylist;
   float* H32;
   int *asm_ninf, *asm_hi;
   double tqmax;         // max |tq| entry
@@ -771,6 +772,9 @@ struct nnmpc_qp {
          // nnmpc_qp_adjoint works in the same ones (SC_S_T: the padded V, then Z; SC_S_LAM: Y = V Hinv'; SC_S_X: GX = Z KuncT') and
          // keeps the transposed image of Kunc64 in a slot of its own (kunct_ok: it holds the accepted pair's)
          SC_A_KT,
+         // the corrected multipliers the f32 screen keeps for the round after it (AsmDev::stash): seg_max x ASM_MLDS doubles, made by
+         // the first call that carries
+         SC_CARRY,
          SC_COUNT };
   bool kunct_ok = false;
   DevRes res{SC_COUNT};         // owns every buffer, stream and event below and above
@@ -819,6 +823,7 @@ const AsmSwitches& asm_switches() {
 // Read at every call: tests toggle them inside one process.
 bool env_no_small() { return env_set("NNMPC_NO_SMALL"); }              // A/B, tests of the rounds at small sizes
 bool env_overlap_off() { return env_int("NNMPC_OVERLAP", 1) == 0; }   // A/B runs, 0 = off
+bool env_carry_off() { return env_int("NNMPC_CARRY", 1) == 0; }       // A/B runs, 0 = off
 // Read at create (tests only): rows of the second row space, dflt when unset.
 long long env_overlap_rows(long long dflt) { const char* e = getenv("NNMPC_OVERLAP_ROWS"); return e ? std::max(0, atoi(e) / 128 * 128) : dflt; }
 
@@ -1181,6 +1186,7 @@ struct AsmCall {
   bool lazy, small, tail_only;  // which form the call takes (solve_segment_asm)
   bool defer_cnt;               // a tail-only call reads its counters with the status, at the end
   bool overlap_on;              // a far-field pass may run beside a round
+  bool carry_on;                // the f32 screen keeps its corrected multipliers for the round after it (AsmDev::carry)
   int vW[2] = {0, 0}, vrows[2] = {0, 0};   // per view: window and fp64 rows of the last round that ran in it
   bool tail_ran[2] = {false, false};
   int pend = -1;                // the view whose settled rows await the full-width pass (-1: none)
@@ -1239,6 +1245,7 @@ void asm_args(AsmCall& c, const double* lb_dev, const double* ub_dev, const unsi
   a.tail_gi = c.sw->tail_gi; a.use_wg = c.sw->use_wg;
   a.refine = 0; a.refine_later = c.sw->refine && a.use_f32; a.refine_tol = c.sw->refine_tol;
   a.early64 = c.sw->early64;
+  a.carry = 0; a.stash = nullptr; a.cflag = h->asm_cflag; a.carrylist = h->asm_carrylist;
   a.pred_w = 0; a.pred_f64 = 0;
 }
 
@@ -1294,6 +1301,11 @@ std::vector<int> fetch_ints(const int* dev, int n) {
   hipMemcpy(v.data(), dev, n * sizeof(int), hipMemcpyDeviceToHost);
   return v;
 }
+std::vector<unsigned char> fetch_bytes(const unsigned char* dev, int n) {
+  std::vector<unsigned char> v(n);
+  hipMemcpy(v.data(), dev, n, hipMemcpyDeviceToHost);
+  return v;
+}
 // the small pass: iterations and set sizes per problem
 int trace_small(AsmCall& c) {
   nnmpc_qp* h = c.h;
@@ -1335,6 +1347,15 @@ void trace_round(int rounds, bool inflight, const int* cnt) {
   fprintf(stderr, " | f32 classes");
   for (int b = 0; b < ASM_NBIN; ++b) fprintf(stderr, " %d", cnt[ASM_CNT_F32 + b]);
   fprintf(stderr, "\n");
+}
+// the carry: corrected multipliers the f32 screen kept (before its asm_update_k decides which are of use), problems whose round is a copy
+int trace_carry(AsmCall& c, int rounds, const int* cnt) {
+  HIPCHK(stream_sync(c.s));
+  const std::vector<unsigned char> fl = fetch_bytes(c.h->asm_cflag, c.nprob);
+  long kept = 0;
+  for (int i = 0; i < c.nprob; ++i) kept += fl[i] == 1;
+  fprintf(stderr, "asm round %d carry: corrected-and-stashed %ld, carried %d of %d\n", rounds, kept, cnt[ASM_CNT_CARRY], c.nprob);
+  return 0;
 }
 // the tail after a round: iterations of its nrun problems
 void trace_tail(AsmCall& c, int rounds, int nrun) {
@@ -1605,6 +1626,8 @@ int launch_multipliers(AsmCall& c, const int* cnt, bool inflight) {
   }
   // fp64 first (its waves are the long ones), then the f32 rounds of the problems whose set still moves
   if (nreg_wg) { EvScope e8(h, EV_LAMBDA64, 0.0); hipLaunchKernelGGL(asm_lambda_reg_k, dim3(nreg_wg), dim3(256), ASM_REG_LDS, s, a); }
+  // (... and, at the end of that grid, the problems whose solve the round before already did: a copy -- asm_carry_copy)
+  nreg32_wg += (cnt[ASM_CNT_CARRY] + 3) / 4;
   if (nreg32_wg) { EvScope e7(h, EV_LAMBDA32, 0.0); hipLaunchKernelGGL(asm_lambda_reg32_k, dim3(nreg32_wg), dim3(256), ASM_REG32_LDS, s, a); }
   if (side2) HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
   if (side3) HIPCHK(hipStreamWaitEvent(s, h->ev_join3, 0));
@@ -1770,6 +1793,10 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   if (c.tail_only)
     if (int rc = tail_only_pass(c)) return rc;
   c.overlap_on = h->opts.asm_overlap >= 0 && h->view[1].rows > 0 && !env_overlap_off();
+  // (as refine_later: only behind predicted first sets)
+  c.carry_on = a.refine_later && a.pred_w && !c.tail_only && !env_carry_off();
+  if (c.carry_on)
+    if (int rc = h->res.slot(nnmpc_qp::SC_CARRY, &a.stash, (size_t)h->seg_max * ASM_MLDS * sizeof(double))) return rc;
   c.vW[0] = c.vW[1] = h->np;
 
   // ---- The pass beside the round.  A far-field full-width pass does not wait on the main stream: asm_wide_t_k (+ asm_wide_tnorm_k) and
@@ -1797,6 +1824,9 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       if (int rc = launch_pass(c, pv, pl)) return rc;
     if (!a.pred_w) a.refine_later = 0;                   // (only behind predicted first sets: from other starts the f32 rounds are many and their sets still move)
     a.refine = a.refine_later && rounds >= 1;            // round 0 stays the plain f32 screen
+    // ... which keeps the corrected multipliers of the sets it leaves as they are: round 1 copies them (a flag asm_update_k raised
+    // in round 0 is read by round 1's count and bins, cleared by its asm_carry_copy, and by nobody after that)
+    a.carry = c.carry_on ? (rounds == 0 ? 1 : (rounds == 1 ? 2 : 0)) : 0;
     a.kref = c.kprev;
     // the round's view: beside a pass the one it does not occupy, view 0 otherwise
     int rv = pl.inflight ? 1 - pv : 0;
@@ -1833,6 +1863,7 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       continue;                                           // (the next count ends the loop, or finds what asm_wide_k sent back)
     }
     h->stats.asm_rounds += 1;
+    h->stats.asm_carried += cnt[ASM_CNT_CARRY];
     // column window of this round: past the last active bound of any running problem plus one stage; a
     // problem that settles inside it gets one full-width pass (asm_wide_k) at the start of the next round
     a.W = std::min(h->np, ((cnt[ASM_CNT_LAST] + 1 + h->nu + 127) / 128) * 128);
@@ -1842,6 +1873,8 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       extend_xunc(c, a.W, c.segp, false);
     }
     if (int rc = launch_multipliers(c, cnt, pl.inflight)) return rc;
+    if (sw.trace && a.carry)
+      if (int rc = trace_carry(c, rounds, cnt)) return rc;
     if (int rc = window_gemms_and_update(c, rv, n64, n32, cnt)) return rc;
     c.vW[rv] = a.W;
     c.vrows[rv] = a.W < h->n ? n64 : 0;                  // fp64 rows of this round: the problems that settled in them await the full-width check
@@ -1996,7 +2029,7 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   A_(v0.tnorm, G + 128 * (ASM_NKG + 1)); A_(v0.tslack, G + 128 * (ASM_NKG + 1));
   A_(h->asm_st, G * n); A_(h->asm_state, G); A_(h->asm_rounds, G); A_(v0.counters, 2 * ASM_NCNT);
   A_(h->asm_biglist, G); A_(h->asm_status, G); A_(h->asm_binlist, (size_t)(ASM_NLIST + 4) * G);
-  A_(h->asm_idxg, G * o.asm_max_active); A_(h->asm_mg, G); A_(h->asm_row, G); A_(h->asm_lrank, G); A_(h->asm_ctot, ((G + 1023) / 1024) * ASM_NSCAN); A_(h->asm_prec, G); A_(h->asm_redo, G); A_(h->asm_rowk, G); A_(v0.lam32, G * np); A_(v0.xh32, G * np); A_(h->asm_alpha, G); A_(h->asm_ninf, G); A_(h->asm_hi, G); A_(v0.kblk, 2 * (G / 64 + 2)); A_(h->asm_work, 3 * G);
+  A_(h->asm_idxg, G * o.asm_max_active); A_(h->asm_mg, G); A_(h->asm_row, G); A_(h->asm_lrank, G); A_(h->asm_ctot, ((G + 1023) / 1024) * ASM_NSCAN); A_(h->asm_prec, G); A_(h->asm_redo, G); A_(h->asm_rowk, G); A_(h->asm_cflag, G); A_(h->asm_carrylist, G); A_(v0.lam32, G * np); A_(v0.xh32, G * np); A_(h->asm_alpha, G); A_(h->asm_ninf, G); A_(h->asm_hi, G); A_(v0.kblk, 2 * (G / 64 + 2)); A_(h->asm_work, 3 * G);
   v0.rows = (int)G;
   A_(h->asm_scratch, (size_t)h->asm_pool * ((size_t)(o.asm_max_active / 16) * (o.asm_max_active / 16 + 1) / 2 * ASM_TS));
   {
