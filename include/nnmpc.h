@@ -115,7 +115,7 @@ typedef struct {
   int64_t asm_gemm_launches; /* launches of its dominant kernel (gemm_nt_f64_k: LAM * Hinv) */
   double asm_gemm_ms;        /* hipEvent time of those (profiling on) */
   double asm_gemm_flops;     /* algorithmic flops: 2 * columns evaluated * k_max per problem and round (+ one full-width pass) */
-  double asm_lambda_ms;      /* hipEvent time of the multiplier-system kernels (asm_lambda_reg_k, asm_lambda_tile_k) */
+  double asm_lambda_ms;      /* hipEvent time of the multiplier-system kernels (asm_lambda_reg*_k, asm_lambda_wg*_k, asm_lambda_tile_k<1>) */
   double asm_update_ms;      /* hipEvent time of the set bookkeeping (asm_count_k, asm_bins_*_k, asm_update_k, asm_wide_k) */
   double asm_lambda_flops;   /* algorithmic fp64 flops of the multiplier systems: sum of m^3/3 + 2 m^2 */
   double asm_lambda_bytes;   /* ... and their algorithmic bytes (gathered Pinv block + rhs/result) */

@@ -53,9 +53,8 @@ constexpr int ASM_CNT_LAST = 3;    // counters[3]: largest active variable index
 constexpr int ASM_CNT_F64 = 4;     // counters[4 + b]: length of the fp64 list of size class b
 constexpr int ASM_CNT_F32 = 16;    // counters[16 + b]: length of the f32 list of size class b
 constexpr int ASM_NLIST = 2 * ASM_NBIN;   // lists in AsmDev::binlist: fp64 classes, then f32 classes, then (list ASM_NLIST) the
-                                          // f32 rounds of sets of ASM_MLDS + 1 .. ASM_BIG32 bounds (asm_lambda_tile32_k)
-constexpr int ASM_BIG32 = 256;            // largest set whose f32 rounds run with the tiles in LDS (16 x 16 lower f32 tiles, one
-                                          // workgroup per problem); beyond: fp64 from the start, tiles in an L2 slab
+                                          // f32 rounds of sets of ASM_MLDS + 1 .. ASM_BIG32 bounds (asm_lambda_wg32_k)
+constexpr int ASM_BIG32 = 256;            // largest set whose f32 rounds run on four waves per problem (asm_lambda_wg32_k, qp_wg.h)
 constexpr int ASM_CNT_BIG64 = 37;         // counters[37]: length of list ASM_NLIST + 1 (fp64 rounds of sets of 177 .. 256 bounds: asm_lambda_wg64_k)
 constexpr int ASM_CNT_BIG32 = 36;         // counters[36]: length of list ASM_NLIST
 constexpr int ASM_BIG32B = 384;           // largest set whose f32 rounds run in registers at all: 257 .. 384 bounds on EIGHT waves per problem
@@ -83,7 +82,6 @@ constexpr int ASM_NSCAN = ASM_NLIST + 10 + 2 * ASM_NKG; // scan columns: large s
                                                         // problems, sum and max of the last active indices of the running problems
 constexpr int ASM_CNT_CARRY = 24;  // counters[24]: length of AsmDev::carrylist (problems whose round is a copy of the stashed multipliers)
 constexpr int ASM_CNT_ROWS32 = 15; // counters[15]: rows of LAM32 / XH32 handed out ([2]: rows of LAM / XH)
-__host__ __device__ constexpr int asm_bin_cap(int b) { return 16 * (b + 4); }
 
 struct AsmDev {
   int n, np, nu, nseg;
@@ -95,7 +93,6 @@ struct AsmDev {
   int ka;
   const double* Kunc;              // [np][ka]: x_unc = Kunc x0
   int pred_w;                      // bound states of the columns [0, pred_w) were named by asm_predict_k (qp_predict.h): asm_init_k leaves them
-  int pred_f64;                    // ... and the rounds start in fp64 (a predicted set is close to the final one: an f32 round would mostly confirm it)
   int winit;                       // columns the first sets are drawn from (without a guess): the leading eighth of the horizon, 512 at least
   int Wx;                          // x_unc exists in HBM for the columns [0, Wx) only (Wx = np: all of them); beyond, the full-width
                                    // pass forms it inside its GEMM (qp_wide.h), the rare consumers below from Kunc and x0
@@ -161,8 +158,6 @@ struct AsmDev {
   int wrows;                       // fp64 rows of the round whose settled problems the pass at hand checks
   unsigned char* wmark;            // [nseg] set by asm_wide_k for the problems it handled, counted and cleared by asm_bins (statistics)
   const double* xhw;               // [rows] = lam * H beyond the window (shapes the fused kernels' tiles do not fit)
-  int tail_gi;                     // asm_tail_k: dual active-set steps (Goldfarb-Idnani) instead of Murty's single exchanges once block exchanges stop making progress (off: measured slower, see there)
-  int use_wg;                      // sets of 145 .. 256 bounds go to the four-wave register kernels (qp_wg.h); 0: the single-wave / LDS-tile / slab kernels (A/B)
   int refine;                      // f32 rounds of sets of <= ASM_MLDS bounds get rows of LAM (fp64) and correct a result that can be final in fp64 (asm_reg_core)
   double refine_tol;               // residual of a corrected f32 solve, relative to max |b|, that counts as an fp64 solve (ASM_REFINE_TOL)
   int refine_later;                // ... from the next round on (this one may still be a plain f32 screen): a set that settles in f32 now is NOT sent to the fp64 kernel
@@ -226,7 +221,7 @@ __global__ __launch_bounds__(256) void asm_init_k(AsmDev d, int nrows) {
   // an empty set runs one round like the others: x = x_unc is checked and certified by asm_update_k / asm_wide_k
   if (lane == 0) {
     d.rounds[p] = 0; d.state[p] = invalid ? ASM_INVALID : ASM_RUN;
-    d.prec[p] = (d.use_f32 && !d.guess && !(d.pred_w && d.pred_f64)) ? 0 : 1;   // a caller's guess (a predicted set) is expected to be right: fp64 at once
+    d.prec[p] = (d.use_f32 && !d.guess) ? 0 : 1;   // a caller's guess (a predicted set) is expected to be right: fp64 at once
     d.redo[p] = 0;
     if (d.cflag) d.cflag[p] = 0;
     d.ninf_best[p] = 0x7fffffff; d.alpha[p] = ASM_GRACE;
@@ -333,7 +328,7 @@ __global__ __launch_bounds__(256) void asm_count_k(AsmDev d) {
       const double md = (double)m;
       d.work[3 * p] += md * md * md / 3.0 + 2.0 * md * md;             // per-problem slots: same-address atomics
       d.work[3 * p + 1] += 8.0 * (md * (md + 1.0) / 2.0 + 2.0 * md);   // (one per workgroup) serialise the launch
-      if (d.prec[p] == 0 && m <= (d.use_wg ? ASM_BIG32B : ASM_BIG32)) d.work[3 * p + 2] += md * md * md / 3.0 + 2.0 * md * md;   // ... of which in an f32 round
+      if (d.prec[p] == 0 && m <= ASM_BIG32B) d.work[3 * p + 2] += md * md * md / 3.0 + 2.0 * md * md;   // ... of which in an f32 round
     }
     if (m > d.max_active) d.state[p] = ASM_FALLBACK;
   }
@@ -359,7 +354,13 @@ __device__ __forceinline__ int asm_scan_col(const AsmDev& d, int p, bool& run) {
   if (!run) return -1;
   if (asm_carried(d, p)) return ASM_COL_CARRY;
   const int m = d.mg[p];
-  if (m > ASM_MLDS) return (d.prec[p] == 0 && m <= ASM_BIG32) ? 1 + ASM_NLIST : ((d.use_wg && m <= ASM_WG_SETS) ? 2 + ASM_NLIST : ((d.use_wg && d.prec[p] == 0 && m <= ASM_BIG32B) ? 3 + ASM_NLIST : ((d.use_wg && d.prec[p] == 1 && m <= ASM_BIG32B) ? 4 + ASM_NLIST : 0)));   // (prec 2: the refinement gave up on this set)
+  if (m > ASM_MLDS) {
+    if (d.prec[p] == 0 && m <= ASM_BIG32) return 1 + ASM_NLIST;
+    if (m <= ASM_WG_SETS) return 2 + ASM_NLIST;
+    if (d.prec[p] == 0 && m <= ASM_BIG32B) return 3 + ASM_NLIST;
+    if (d.prec[p] == 1 && m <= ASM_BIG32B) return 4 + ASM_NLIST;
+    return 0;                                          // (prec 2: the refinement gave up on this set)
+  }
   const int b = max((m + 15) / 16, 4) - 4;
   return 1 + (d.prec[p] == 0 ? ASM_NBIN + b : b);
 }
@@ -473,12 +474,11 @@ __global__ __launch_bounds__(1024) void asm_bins_b_k(AsmDev d) {
 }
 #endif
 
-// Workgroup-per-problem variant (the first implementation; the solver uses it for the rare sets beyond 176
-// bounds, BIG = 1): r_A = x_unc,A - b_A, S = H_AA as 16 x 16 fp64 tiles, blocked right-looking Cholesky:
-// diagonal tile + its inverse by wave 0 (asm_diag16), TRSM and trailing updates on v_mfma_f64_16x16x4_f64 by
+// Workgroup-per-problem variant (the first implementation; the solver uses it for the fp64 solves of sets beyond 256
+// bounds and every round of sets beyond 384): r_A = x_unc,A - b_A, S = H_AA as 16 x 16 fp64 tiles, blocked right-looking
+// Cholesky: diagonal tile + its inverse by wave 0 (asm_diag16), TRSM and trailing updates on v_mfma_f64_16x16x4_f64 by
 // all four waves, blocked triangular solves by wave 0.  3 barriers per block column.
-// BIG = 1: persistent workgroups walk the big-set queue with the tiles in a global scratch slab (L2).
-// BIG = 0: one workgroup per entry of size-class list `bin`, tiles in LDS (kept for scripts/micro comparisons).
+// Persistent workgroups walk the big-set queue with the tiles in a global scratch slab (L2).
 typedef double f64x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ double rdlane_d(double x, int l) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
@@ -501,7 +501,7 @@ template <class T> __device__ __forceinline__ int asm_diag16(const T* Tk, T* Yt,
 __device__ __noinline__ int asm_diag16_call(const double* Tk, double* Yt, int lane);
 
 // One workgroup, one problem: rA <- lam = (H_AA)^-1 (x_unc,A - b_A) for the set idx[0..m).  rA [>= 16 ceil(m/16)]
-// and Yt [ASM_TS] in LDS, T: the lower 16 x 16 tiles (LDS or a global slab).  Returns 1 (to all threads) when H_AA
+// and Yt [ASM_TS] in LDS, T: the lower 16 x 16 tiles (a global slab).  Returns 1 (to all threads) when H_AA
 // is not positive definite in fp64.  *s_bad: an int in LDS.
 __device__ __forceinline__ int asm_tile_solve(const AsmDev& d, int p, int m, const int* idx, double* rA, double* Yt, double* T,
                                               int* s_bad) {
@@ -621,20 +621,19 @@ __device__ __forceinline__ int asm_tile_solve(const AsmDev& d, int p, int m, con
 }
 
 #if ASM_OWN_KERNELS
-template <int BIG>
+template <int BIG>   // (the template argument and `bin` are what is left of an LDS variant: traces and tools know the kernel as asm_lambda_tile_k<1>)
 __global__ __launch_bounds__(256, 4) void asm_lambda_tile_k(AsmDev d, int bin) {
+  static_assert(BIG == 1, "the tiles live in the L2 slab");
   extern __shared__ __attribute__((aligned(16))) double sm[];
   __shared__ int s_bad;
   const int tid = threadIdx.x;
-  const int cap = BIG ? d.max_active : asm_bin_cap(bin);  // rhs capacity of this variant
+  const int cap = d.max_active;                          // rhs capacity
   double* rA = sm;                                       // [cap]
   double* Yt = rA + cap;                                 // inverse of the current diagonal tile
-  double* T = BIG ? d.scratch + (size_t)blockIdx.x * ((size_t)(cap / 16) * (cap / 16 + 1) / 2 * ASM_TS)
-                  : Yt + ASM_TS;                         // lower tiles
-  const int nitem = BIG ? d.counters[1] : d.counters[4 + bin];
-  const int* list = BIG ? d.biglist : d.binlist + (size_t)bin * d.nseg;
+  double* T = d.scratch + (size_t)blockIdx.x * ((size_t)(cap / 16) * (cap / 16 + 1) / 2 * ASM_TS);   // lower tiles
+  const int nitem = d.counters[ASM_CNT_SLAB];
   for (int it = blockIdx.x; it < nitem; it += gridDim.x) {
-    const int p = list[it];
+    const int p = d.biglist[it];
     const int* idx = d.idxg + (size_t)p * d.max_active;
     const int m = d.mg[p];
     if (asm_tile_solve(d, p, m, idx, rA, Yt, T, &s_bad)) { if (tid == 0) d.state[p] = ASM_FALLBACK; continue; }
@@ -658,8 +657,7 @@ __global__ __launch_bounds__(256, 4) void asm_lambda_tile_k(AsmDev d, int bin) {
 // four lane rows use v_permlane16/32_swap.
 // The 512 registers of a wave hold 32 tiles next to the working set; for MB = 8, 9 (10, 11) the strictly
 // lower tiles of the first NL = 2 (4) block columns -- touched by one TRSM, one pass as operands and the
-// backward substitution only -- live in LDS instead (C layout, 2 KB each).  10- and 11-block sets then need
-// ~70 KB of LDS per wave: two waves per workgroup (asm_lambda_reg2_k).
+// backward substitution only -- live in LDS instead (C layout, 2 KB each).
 //
 // The same code runs in f32 (AsmNum<float>, v_mfma_f32_16x16x4_f32): tiles take half the registers, so two
 // waves share a SIMD and hide each other's pivot chains, and the chain itself is shorter (one v_readlane
@@ -1262,198 +1260,6 @@ __device__ __forceinline__ void asm_lambda_reg(const AsmDev& d, int list, int wg
   }
 }
 
-// ---- f32 rounds of the sets beyond the register kernels (ASM_MLDS + 1 .. ASM_BIG32 bounds): the same blocked Cholesky as
-// asm_tile_solve, one workgroup (eight waves) per problem, in f32 with ALL tiles in LDS (136 tiles of 16 x 17 floats at 256
-// bounds: 148 KB) -- the eight waves share the TRSM and trailing MFMAs (v_mfma_f32_16x16x4_f32) of a block column.  As in the
-// register kernels an f32 result only moves the set; a set that settles is solved again in fp64 (asm_lambda_tile_k<1>).
-typedef float f32x4v_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4v_t tile_mma_nt32(const float* A, const float* B, int lane) {
-  f32x4v_t acc = {0.f, 0.f, 0.f, 0.f};
-  const int li = lane & 15, kq = lane >> 4;
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[li * 17 + 4 * s + kq], B[li * 17 + 4 * s + kq], acc, 0, 0, 0);
-  return acc;                                            // reg r of lane (li, lq): row 4 lq + r, column li
-}
-__device__ __forceinline__ float* asm_tile32(float* T, int I, int J) { return T + ((size_t)I * (I + 1) / 2 + J) * ASM_TS; }
-
-// rA [>= 16 ceil(m/16)], Yt [ASM_TS], T [tiles] in LDS; returns 1 (to all threads) when H_AA is not positive definite in f32
-__device__ __forceinline__ int asm_tile_solve32(const AsmDev& d, int p, int m, const int* idx, float* rA, float* Yt, float* T, int* s_bad) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef ASM_STAMPS
-  const int wg = blockIdx.x;
-#endif
-  __syncthreads();
-  ASM_STAMP(48);
-  if (tid == 0) *s_bad = 0;
-  const size_t o = (size_t)p * d.np;
-  const unsigned char* st = d.st + (size_t)p * d.n;
-  const int mb = (m + 15) / 16;
-  __syncthreads();
-  for (int i = tid; i < mb * 16; i += 512) {
-    float v = 0.f;
-    if (i < m) {
-      const int a = idx[i], k = a % d.nu;
-      v = (float)(d.xunc[o + a] - (st[a] == 1 ? d.ub[(size_t)p * d.nu + k] : d.lb[(size_t)p * d.nu + k]));
-    }
-    rA[i] = v;
-  }
-  const int ntile = mb * (mb + 1) / 2;
-  {
-    // thread (half, ti, tj) fetches element (ti, tj) of every second tile, 8 at a time: 8 gathers in flight per thread
-    // (the entries come from L2 / Infinity Cache, ~1 us each: the gather is a latency chain, not a bandwidth one)
-    const int half = tid >> 8, ti = (tid >> 4) & 15, tj = tid & 15;
-    for (int t0 = half; t0 < ntile; t0 += 2 * 8) {
-      float v[8];
-      int tt[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int t = t0 + 2 * u;
-        // tile t -> (I, J): I = largest with I (I + 1) / 2 <= t
-        int I = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
-        while ((I + 1) * (I + 2) / 2 <= t) ++I;
-        while (I * (I + 1) / 2 > t) --I;
-        const int J = t - I * (I + 1) / 2;
-        tt[u] = t;
-        const int gi = 16 * I + ti, gj = 16 * J + tj;
-        v[u] = gi == gj ? 1.f : 0.f;
-        if (t < ntile && gi < m && gj < m) v[u] = d.H32[(size_t)idx[gi] * d.np + idx[gj]];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (tt[u] < ntile) (T + (size_t)tt[u] * ASM_TS)[ti * 17 + tj] = v[u];
-    }
-  }
-  __syncthreads();
-  // Two barriers per block column: [TRSM of column K by all waves] | [wave 0: its tile (K+1, K+1) of the trailing update,
-  // Y_K' saved for the solves, then the NEXT diagonal step -- the long dependent chain -- while waves 1..7 share the rest
-  // of the trailing update].  (The first version ran diagonal step, TRSM and trailing update one after the other behind
-  // four barriers: the diagonal steps alone, seven waves waiting, were 45 % of the factorisation.)
-  ASM_STAMP(49);
-  if (wave == 0) {
-    const int bad = asm_diag16<float>(asm_tile32(T, 0, 0), Yt, lane);
-    if (bad && lane == 0) *s_bad = 1;
-  }
-  __syncthreads();
-  ASM_STAMP(50);
-  for (int K = 0; K < mb; ++K) {
-    float* TKK = asm_tile32(T, K, K);
-    for (int I = K + 1 + wave; I < mb; I += 8) {         // TRSM: T(I,K) <- T(I,K) Y'   (eight waves)
-      float* TIK = asm_tile32(T, I, K);
-      const f32x4v_t acc = tile_mma_nt32(TIK, Yt, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) TIK[(4 * (lane >> 4) + r) * 17 + (lane & 15)] = acc[r];
-    }
-    __syncthreads();
-    if (wave == 0) {
-      if (lane < 16) {                                     // Y_K' into the upper part of T(K,K) for the solves
-        const int row = lane;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) if (k >= row) TKK[row * 17 + k] = Yt[k * 17 + row];
-      }
-      if (K + 1 < mb) {
-        const f32x4v_t acc = tile_mma_nt32(asm_tile32(T, K + 1, K), asm_tile32(T, K + 1, K), lane);
-        float* Tn = asm_tile32(T, K + 1, K + 1);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Tn[(4 * (lane >> 4) + r) * 17 + (lane & 15)] -= acc[r];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the tile and the saved Y' are in LDS before the sweep reads / overwrites
-        const int bad = asm_diag16<float>(Tn, Yt, lane);
-        if (bad && lane == 0) *s_bad = 1;
-      }
-    } else {
-      int b = 0;
-      for (int I = K + 1; I < mb; ++I)
-        for (int J = K + 1; J <= I; ++J) {
-          if (I == K + 1) continue;                        // (K+1, K+1): wave 0
-          if ((b++ % 7) + 1 != wave) continue;
-          const f32x4v_t acc = tile_mma_nt32(asm_tile32(T, I, K), asm_tile32(T, J, K), lane);
-          float* TIJ = asm_tile32(T, I, J);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) TIJ[(4 * (lane >> 4) + r) * 17 + (lane & 15)] -= acc[r];
-        }
-    }
-    __syncthreads();
-  }
-  ASM_STAMP(51);
-  if (*s_bad) return 1;
-  // ---- substitutions, column oriented, all eight waves (one wave alone spent 29 % of the kernel here): as soon as y_K
-  // (lam_K) is known every wave takes it out of the right-hand sides of its share of the remaining block rows.
-  {
-    const int i = lane & 15, kq = lane >> 4;
-    for (int K = 0; K < mb; ++K) {                       // forward:  L y = r
-      if (wave == 0) {                                   // y_K = Y_K t_K,  Y_K[i][k] (k <= i) stored at TKK[k][i]
-        const float* TKK = asm_tile32(T, K, K);
-        const float t = rA[16 * K + i];
-        float yv = t * TKK[i * 17 + i];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { const float tk = __shfl(t, k); if (k < i) yv += TKK[k * 17 + i] * tk; }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane < 16) rA[16 * K + i] = yv;
-      }
-      __syncthreads();
-      for (int I = K + 1 + wave; I < mb; I += 8) {       // r_I -= L(I,K) y_K
-        const float* TIK = asm_tile32(T, I, K);
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t += TIK[i * 17 + 4 * kq + k] * rA[16 * K + 4 * kq + k];
-        t += __shfl_xor(t, 16); t += __shfl_xor(t, 32);
-        if (lane < 16) rA[16 * I + i] -= t;
-      }
-      __syncthreads();
-    }
-    for (int K = mb - 1; K >= 0; --K) {                  // backward:  L' lam = y
-      if (wave == 0) {                                   // lam_K = Y_K' t_K,  Y_K[k][i] (k > i) stored at TKK[i][k]
-        const float* TKK = asm_tile32(T, K, K);
-        const float t = rA[16 * K + i];
-        float lv = t * TKK[i * 17 + i];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { const float tk = __shfl(t, k); if (k > i) lv += TKK[i * 17 + k] * tk; }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane < 16) rA[16 * K + i] = lv;
-      }
-      __syncthreads();
-      for (int J = K - 1 - wave; J >= 0; J -= 8) {       // y_J -= L(K,J)' lam_K
-        const float* TKJ = asm_tile32(T, K, J);
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t += TKJ[(4 * kq + k) * 17 + i] * rA[16 * K + 4 * kq + k];
-        t += __shfl_xor(t, 16); t += __shfl_xor(t, 32);
-        if (lane < 16) rA[16 * J + i] -= t;
-      }
-      __syncthreads();
-    }
-  }
-  ASM_STAMP(52);
-  __syncthreads();
-  return 0;
-}
-
-constexpr int ASM_TILE32_LDS = (ASM_BIG32 + ASM_TS + (ASM_BIG32 / 16) * (ASM_BIG32 / 16 + 1) / 2 * ASM_TS) * 4;
-#if ASM_OWN_KERNELS
-__global__ __launch_bounds__(512, 1) void asm_lambda_tile32_k(AsmDev d) {
-  extern __shared__ __attribute__((aligned(16))) float smf[];
-  __shared__ int s_bad;
-  const int tid = threadIdx.x;
-  float* rA = smf;                                       // [ASM_BIG32]
-  float* Yt = rA + ASM_BIG32;
-  float* T = Yt + ASM_TS;
-  const int nitem = d.counters[ASM_CNT_BIG32];
-  const int* list = d.binlist + (size_t)ASM_NLIST * d.nseg;
-  for (int it = blockIdx.x; it < nitem; it += gridDim.x) {
-    const int p = list[it];
-    const int* idx = d.idxg + (size_t)p * d.max_active;
-    const int m = d.mg[p];
-    if (asm_tile_solve32(d, p, m, idx, rA, Yt, T, &s_bad)) {
-      // not positive definite in f32: the round is void (the LAM32 row is still zero), the next one runs in fp64
-      if (tid == 0) { d.prec[p] = 1; d.redo[p] = 1; }
-      continue;
-    }
-    float* lrow = d.lam32 + (size_t)d.row[p] * d.np;
-    for (int i = tid; i < m; i += 512) lrow[idx[i]] = rA[i];
-  }
-}
-#endif
-
 // All register-resident fp64 size classes 0..5 in ONE launch (their workgroups are independent; separate
 // launches would serialise six tails): workgroup w walks the classes from the largest down and takes
 // four problems of the class its index falls into.  Grid: sum_b ceil(count_b / 4).
@@ -1470,20 +1276,6 @@ __global__ __launch_bounds__(256, 1) void asm_lambda_reg_k(AsmDev d) {
   ASM_REG_CLASS(5) ASM_REG_CLASS(4) ASM_REG_CLASS(3) ASM_REG_CLASS(2) ASM_REG_CLASS(1) ASM_REG_CLASS(0)
 #undef ASM_REG_CLASS
   static_assert(ASM_NREG == 6, "one ASM_REG_CLASS line per register-resident size class");
-}
-#endif
-// The 10- and 11-block classes (145..176 bounds): same code, two waves (problems) per workgroup.
-constexpr int ASM_REG2_LDS = (2 * asm_rw<double>(11) + ASM_TS) * 8;
-#if ASM_OWN_KERNELS
-__global__ __launch_bounds__(128, 1) void asm_lambda_reg2_k(AsmDev d) {
-  int w = blockIdx.x;
-  {
-    const int nb = (d.counters[4 + 7] + 1) >> 1;
-    if (w < nb) { asm_lambda_reg<double, 11, 2>(d, 7, w); return; }
-    w -= nb;
-  }
-  asm_lambda_reg<double, 10, 2>(d, 6, w);
-  static_assert(ASM_NBIN == 8 && ASM_MLDS == 176, "classes 6 and 7 are the 10- and 11-block sets");
 }
 #endif
 // The round of a carried problem (AsmDev::carry): the corrected multipliers the screen before kept for this very set -> its fp64
@@ -1905,7 +1697,7 @@ __device__ unsigned long long asm_tail_prof[8];            // diagnostics build 
 #if ASM_OWN_KERNELS
 __global__ __launch_bounds__(256) void asm_tail_k(AsmDev d, int budget) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  __shared__ int s_bad, wsum[4], s_i[4], s_n[4], s_m, s_fast;
+  __shared__ int s_bad, wsum[4], s_i[4], s_m, s_fast;
   __shared__ double s_d[12];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if ((int)blockIdx.x >= d.counters[ASM_CNT_TAIL]) return;
@@ -1917,7 +1709,7 @@ __global__ __launch_bounds__(256) void asm_tail_k(AsmDev d, int budget) {
   unsigned char* dec = reinterpret_cast<unsigned char*>(Tl + ASM_TAIL_AREA);   // [n] decisions
   double* rhs = reinterpret_cast<double*>(dec + ((d.n + 15) / 16) * 16);   // [ASM_FM] x_unc,A - b_A in factor order
   double* vv = rhs + ASM_FM;                                 // [ASM_FM] work vector
-  double* ww = vv + ASM_FM;                                  // [ASM_FM] second work vector (dual steps)
+  double* ww = vv + ASM_FM;                                  // [ASM_FM] second work vector (no user at present: part of ASM_TAIL_EXTRA)
   int* al = reinterpret_cast<int*>(ww + ASM_FM);             // [ASM_FM] active indices in factor order
   double* Tg = d.scratch + (size_t)blockIdx.x * ((size_t)(d.max_active / 16) * (d.max_active / 16 + 1) / 2 * ASM_TS);
   const size_t o = (size_t)p * d.np;
@@ -1929,7 +1721,6 @@ __global__ __launch_bounds__(256) void asm_tail_k(AsmDev d, int budget) {
   if (tid == 0) d.hi[p] = d.n;                               // (from here on bounds anywhere may join: asm_certify_k scans [0, hi))
   int single = 0;                                            // the previous iteration ended with a single exchange
   int fast = 0, m = 0;                                       // dense factor valid for the current set (of size m)
-  int gi = 0;                                                // dual active-set phase (see the exchange rule below)
   // one row leaves the dense factor (wave 0): the logical arrays and the rows of L move up, Givens rotations restore the triangle
   auto drop_row = [&](int j, int mm) {
     int av[3]; double hv[3], lv[3];
@@ -1981,7 +1772,7 @@ __global__ __launch_bounds__(256) void asm_tail_k(AsmDev d, int budget) {
     if (!fast) {
       m = asm_count_one(d, p, hi, wsum);
       if (m > d.max_active) { if (tid == 0) d.state[p] = ASM_FALLBACK; return; }
-      if (single && (m > 0 || gi) && m < ASM_FM) {
+      if (single && m > 0 && m < ASM_FM) {
         // ---- build the dense factor: gather the lower triangle, right-looking Cholesky (three barriers per column)
         __syncthreads();                                       // idx (asm_count_one) complete
         for (int i = tid; i < m; i += 256) {
@@ -2031,7 +1822,6 @@ __global__ __launch_bounds__(256) void asm_tail_k(AsmDev d, int budget) {
     const int* lst = fast ? al : idx;                        // the set the multipliers rA[0..m) belong to
     // x and the tests, decisions recorded (255: stays)
     int ninf = 0, rmin = 0x7fffffff;                         // rmin: the infeasible index a single exchange takes (the smallest)
-    int nneg = 0;                                            // active bounds whose multiplier has the wrong sign
     double l1 = 0.0, lmin = 1e300;
     // Column window, as in the lock-step rounds: while the set is still moving only the columns up to one stage past the last
     // active bound are evaluated (in MPC the active bounds sit in the first stages: 512 of 4480 columns at CDU size -- the x loop
@@ -2113,18 +1903,17 @@ __global__ __launch_bounds__(256) void asm_tail_k(AsmDev d, int budget) {
       const int a = lst[i], sa = st[a];
       const double l = rA[i];
       l1 += fabs(l); lmin = fmin(lmin, fabs(l));
-      if ((sa == 1 && l <= 0.0) || (sa == 2 && l >= 0.0)) { dec[a] = 0; ++ninf; ++nneg; if (!gi) rmin = min(rmin, a); }
+      if ((sa == 1 && l <= 0.0) || (sa == 2 && l >= 0.0)) { dec[a] = 0; ++ninf; rmin = min(rmin, a); }
     }
     for (int off = 32; off > 0; off >>= 1) {
-      ninf += __shfl_xor(ninf, off); rmin = min(rmin, __shfl_xor(rmin, off)); nneg += __shfl_xor(nneg, off);
+      ninf += __shfl_xor(ninf, off); rmin = min(rmin, __shfl_xor(rmin, off));
       l1 += __shfl_xor(l1, off); lmin = fmin(lmin, __shfl_xor(lmin, off));
     }
     __syncthreads();
-    if (lane == 0) { wsum[wave] = ninf; s_i[wave] = rmin; s_n[wave] = nneg; s_d[wave] = l1; s_d[4 + wave] = lmin; }
+    if (lane == 0) { wsum[wave] = ninf; s_i[wave] = rmin; s_d[wave] = l1; s_d[4 + wave] = lmin; }
     __syncthreads();
     ninf = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    nneg = s_n[0] + s_n[1] + s_n[2] + s_n[3];
-    rmin = min(min(s_i[0], s_i[1]), min(s_i[2], s_i[3]));           // (dual phase: the smallest VIOLATED index)
+    rmin = min(min(s_i[0], s_i[1]), min(s_i[2], s_i[3]));
     if (ninf == 0 && xlim < d.n) {                           // settled inside the window: the columns beyond, once
       int ninf2 = 0, rmin2 = 0x7fffffff;
       xpass(xlim, d.n, ninf2, rmin2);
@@ -2168,101 +1957,11 @@ __global__ __launch_bounds__(256) void asm_tail_k(AsmDev d, int budget) {
     single = 0;
     // (the problems that reach the tail have shown that block exchanges do not settle them: a new minimum buys
     // ASM_TAIL_GRACE block exchanges here, not ASM_GRACE, so most iterations are cheap single exchanges)
-    if (gi) single = 1;
-    else if (ninf < best) { best = ninf; grace = ASM_TAIL_GRACE; }
+    if (ninf < best) { best = ninf; grace = ASM_TAIL_GRACE; }
     else if (grace > 0) --grace;
     else single = 1;
-    if (single && !gi && d.tail_gi && m + 1 < ASM_FM) {
-      // (NNMPC_TAIL_GI=1 only; OFF by default.)  From here on: DUAL active-set steps (Goldfarb & Idnani 1983) instead of Murty's
-      // one-index-per-iteration rule.  Measured: no better -- the stragglers of the cond-4e7 plant need the same number of
-      // iterations either way (36 at most in a 10 000-problem batch), a dual iteration costs more (the purge refactors, every
-      // step takes two more substitutions): 5.8 against 5.2 ms per CSTRs-size step; on random dense Hessians with cond >= 1e5
-      // and half the bounds active (scripts/stress_asm.py, seeds 1 and 3) it exhausts the iteration budget MORE often (174 and
-      // 308 of ~1600 problems against 130 and 166): after the purge it has to add the missing bounds one by one.  Kept for A/B.
-      // (i) Purge: drop ALL bounds with a wrong-sign multiplier, solve again, until the set is
-      // dual feasible -- x is then the optimum on that set with multipliers >= 0.  (ii) Add the violated bound with the smallest
-      // index by a dual step: multipliers of the set move along -w, w = S^-1 H[A,r] (two substitutions with the dense factor);
-      // a bound whose multiplier reaches zero first leaves (Givens downdate) and the step is repeated, else the new bound
-      // joins (append a row).  Every step raises the dual objective: no cycling, and the number of steps is about the number of
-      // bounds still missing.  Multipliers and x are recomputed from the factor after every completed step; a set that settles
-      // is confirmed by a fresh factorisation and the certificate like any other.
-      gi = 1;
-    }
-    if (gi && m + 1 >= ASM_FM) gi = 0;                       // too large for the dense factor: Murty's rule on fresh factorisations
     const int dsel = dec[rmin < d.n ? rmin : 0];             // what the single exchange does: 1 / 2 add at that bound, 0 drop
     __syncthreads();
-    if (gi) {
-      hi = d.n;
-      if (nneg > 0 || !fast) {
-        // (i) purge -- or, dual feasible already, nothing: the next iteration builds the dense factor of the set as it stands
-        for (int r = tid; r < xdone; r += 256) if (dec[r] == 0) st[r] = 0;
-        fast = 0;
-        __syncthreads();
-        continue;
-      }
-      // (ii) dual step for bound rmin (violated; the set is dual feasible, the dense factor valid), wave 0
-      if (wave == 0) {
-        int ok = 1, mm = m;
-        const int r = rmin, sp = dsel == 1 ? 1 : -1;
-        const double bp = dsel == 1 ? ubp[r % d.nu] : lbp[r % d.nu];
-        double viol = sp * (d.x[o + r] - bp), mup = 0.0;     // > bound_tol
-        const double* Hr = d.H + (size_t)r * d.np;
-        const double hd = Hr[r];
-        int done = 0;
-        for (int step = 0; step < ASM_FM + 8 && ok && !done; ++step) {
-          for (int i = lane; i < mm; i += 64) vv[i] = Hr[al[i]];
-          ASM_FENCE();
-          asm_fwd(Ld, vv, mm, lane);
-          double s2 = 0.0;
-          for (int i = lane; i < mm; i += 64) s2 += vv[i] * vv[i];
-          for (int off = 32; off > 0; off >>= 1) s2 += __shfl_xor(s2, off);
-          const double d2 = hd - s2;                         // n_p' (H - H[:,A] S^-1 H[A,:]) n_p > 0
-          if (!(d2 > 1e-13 * hd)) { ok = 0; break; }
-          for (int i = lane; i < mm; i += 64) ww[i] = vv[i];
-          ASM_FENCE();
-          asm_bwd(Ld, ww, mm, lane);                         // w = S^-1 H[A,r]
-          // largest step that keeps every multiplier of the set >= 0:  mu_j = s_j lam_j falls by t s_j s_p w_j
-          double t1 = 1e300; int k1 = -1;
-          for (int i = lane; i < mm; i += 64) {
-            const int sj = st[al[i]] == 1 ? 1 : -1;
-            const double rj = sj * sp * ww[i];
-            if (rj > 0.0) { const double q = fmax(sj * rA[i], 0.0) / rj; if (q < t1) { t1 = q; k1 = i; } }
-          }
-          for (int off = 32; off > 0; off >>= 1) {
-            const double t_o = __shfl_xor(t1, off); const int k_o = __shfl_xor(k1, off);
-            if (t_o < t1 || (t_o == t1 && k_o >= 0 && (k1 < 0 || k_o < k1))) { t1 = t_o; k1 = k_o; }
-          }
-          const double t2 = viol / d2;                       // full step: the new bound becomes active
-          const double t = t2 <= t1 ? t2 : t1;
-          for (int i = lane; i < mm; i += 64) rA[i] -= t * sp * ww[i];
-          mup += t;
-          ASM_FENCE();
-          if (t2 <= t1) {
-            if (mm + 1 >= ASM_FM) { ok = 0; break; }
-            double* row = Ld + asm_frow(mm);
-            for (int i = lane; i < mm; i += 64) row[i] = vv[i];
-            if (lane == 0) {
-              row[mm] = sqrt(d2); al[mm] = r; rhs[mm] = d.xunc[o + r] - bp; rA[mm] = sp * mup;
-              st[r] = (unsigned char)dsel;
-            }
-            ASM_FENCE();
-            ++mm; done = 1;
-          } else {
-            viol -= t * d2;
-            if (lane == 0) st[al[k1]] = 0;
-            ASM_FENCE();
-            drop_row(k1, mm);
-            --mm;
-          }
-        }
-        if (!done) ok = 0;
-        if (lane == 0) { s_m = mm; s_fast = ok; }
-      }
-      __syncthreads();
-      m = s_m; fast = s_fast;
-      __syncthreads();
-      continue;
-    }
     for (int r = tid; r < xdone; r += 256) {
       const unsigned char dc = dec[r];
       if (dc != 255 && (!single || r == rmin)) st[r] = dc;

@@ -791,14 +791,11 @@ struct AsmSwitches {
   bool no_farfield;     // NNMPC_NO_FARFIELD: dense form of the full-width pass (A/B)
   bool no_small_gemm;   // NNMPC_NO_SMALL_GEMM: A/B of the 64 x 64 kernel for GEMMs of few tiles (gemm64_choice)
   bool trace;           // NNMPC_TRACE_ROUNDS: the populations of every round, iterations and set sizes per problem of the small pass and the tails
-  int tail_gi;          // NNMPC_TAIL_GI: A/B of the tail's exchange rule
-  int use_wg;           // NNMPC_NO_WG (0 when set): A/B against the kernels the workgroup kernels replaced
   int refine;           // NNMPC_REFINE, 1: A/B against separate f32 and fp64 rounds ...
   double refine_tol;    // NNMPC_REFINE_TOL, ASM_REFINE_TOL: ... and the residual below which a corrected solve counts as an fp64 solve
   int early64;          // NNMPC_EARLY64, 4: A/B of the rule
   int pred_iters;       // NNMPC_PRED_ITERS, -1: A/B; 0 = off, > 0 that many (overrides opts.asm_predict_iters)
   int pred_wide;        // NNMPC_PRED_WIDE, -1: A/B; 0 / 1 forces the choice of the predictor's window
-  int pred_f64;         // NNMPC_PRED_F64, 0: A/B (the rounds after a prediction start in fp64)
   int pred_factor;      // NNMPC_PRED_FACTOR, 3: tenths of an iteration per bound x_unc violates (adaptive count)
   int small_grace;      // NNMPC_SMALL_GRACE, ASM_SM_GRACE: iterations of grace of asm_small_k before single exchanges (small_pass)
   int tail_max;         // NNMPC_TAIL_MAX, 256: stragglers go to the device tail at this many running problems; > 1024 doubles the slab pool
@@ -809,10 +806,9 @@ AsmSwitches read_switches() {
   AsmSwitches w;
   w.no_fused_wide = env_set("NNMPC_NO_FUSED_WIDE"); w.no_lazy_xunc = env_set("NNMPC_NO_LAZY_XUNC"); w.no_farfield = env_set("NNMPC_NO_FARFIELD");
   w.no_small_gemm = env_set("NNMPC_NO_SMALL_GEMM"); w.trace = env_set("NNMPC_TRACE_ROUNDS");
-  w.tail_gi = env_set("NNMPC_TAIL_GI") ? 1 : 0; w.use_wg = env_set("NNMPC_NO_WG") ? 0 : 1;
   w.refine = env_int("NNMPC_REFINE", 1); w.early64 = env_int("NNMPC_EARLY64", 4);
   { const char* e = getenv("NNMPC_REFINE_TOL"); w.refine_tol = e ? atof(e) : ASM_REFINE_TOL; }
-  w.pred_iters = env_int("NNMPC_PRED_ITERS", -1); w.pred_wide = env_int("NNMPC_PRED_WIDE", -1); w.pred_f64 = env_int("NNMPC_PRED_F64", 0);
+  w.pred_iters = env_int("NNMPC_PRED_ITERS", -1); w.pred_wide = env_int("NNMPC_PRED_WIDE", -1);
   w.pred_factor = env_int("NNMPC_PRED_FACTOR", 3); w.small_grace = env_int("NNMPC_SMALL_GRACE", ASM_SM_GRACE); w.tail_max = env_int("NNMPC_TAIL_MAX", 256);
   return w;
 }
@@ -1242,11 +1238,10 @@ void asm_args(AsmCall& c, const double* lb_dev, const double* ub_dev, const unsi
   a.st = h->asm_st; a.guess = guess_dev; a.state = h->asm_state; a.rounds = h->asm_rounds;
   a.biglist = h->asm_biglist; a.binlist = h->asm_binlist; a.idxg = h->asm_idxg; a.mg = h->asm_mg; a.row = h->asm_row; a.tqmax = h->tqmax; a.lrank = h->asm_lrank; a.ctot = h->asm_ctot; a.prec = h->asm_prec; a.redo = h->asm_redo; a.rowk = h->asm_rowk; a.H32 = h->H32; a.alpha = h->asm_alpha; a.ninf_best = h->asm_ninf; a.hi = h->asm_hi; a.nkblk = 2 * (h->seg_max / 64 + 2); a.kref = 0; a.use_f32 = h->opts.asm_f32_rounds >= 0; a.wrows = 0; a.wmark = h->asm_wmark; a.wflag = h->asm_wflag; a.W = h->np; a.scratch = h->asm_scratch; a.work = h->asm_work;
   a.u_out = u_dev; a.ldu = h->ldu; a.nout = h->nout; a.act_out = act_dev; a.status_out = h->asm_status; a.iters_out = it_dev; a.words = h->words;
-  a.tail_gi = c.sw->tail_gi; a.use_wg = c.sw->use_wg;
   a.refine = 0; a.refine_later = c.sw->refine && a.use_f32; a.refine_tol = c.sw->refine_tol;
   a.early64 = c.sw->early64;
   a.carry = 0; a.stash = nullptr; a.cflag = h->asm_cflag; a.carrylist = h->asm_carrylist;
-  a.pred_w = 0; a.pred_f64 = 0;
+  a.pred_w = 0;
 }
 
 // First sets: named by the dual projected-gradient predictor inside its window (qp_predict.h), by the bounds x_unc violates beyond
@@ -1288,7 +1283,6 @@ int first_sets(AsmCall& c) {
       const int rc = launch_predictor(h, a, nprob, iters_req, wide, &W, &MR, &c.pred_flops_per_it);
       if (rc) return rc;
       a.pred_w = W;
-      a.pred_f64 = c.sw->pred_f64;
     }
   }
   hipLaunchKernelGGL(asm_init_k, dim3((c.segp + 3) / 4), dim3(256), 0, c.s, a, c.segp);
@@ -1580,21 +1574,21 @@ int launch_multipliers(AsmCall& c, const int* cnt, bool inflight) {
   const int lds_big = (a.max_active + ASM_TS) * 8;
   EvScope es(h, EV_LAMBDA, 0.0);
   // one wave per problem, S in registers: size classes 0..5 (<= 144 bounds) in one launch, four problems per
-  // workgroup; classes 6, 7 (<= 176) two per workgroup and the rare larger sets (tiles in an L2 slab, one
-  // workgroup each: long latency chains on a handful of CUs) beside it on the side stream.
-  const int nreg2_wg = (cnt[ASM_CNT_F64 + 6] + 1) / 2 + (cnt[ASM_CNT_F64 + 7] + 1) / 2;
+  // workgroup; classes 6, 7 (<= 176: four per workgroup in f32, one workgroup of two waves each in fp64) and the rare larger
+  // sets (tiles in an L2 slab, one workgroup each: long latency chains on a handful of CUs) beside it on the side streams.
+  const int nwg64s = cnt[ASM_CNT_F64 + 6] + cnt[ASM_CNT_F64 + 7];
   const int nreg32b_wg = (cnt[ASM_CNT_F32 + 6] + 3) / 4 + (cnt[ASM_CNT_F32 + 7] + 3) / 4;
-  // (use_wg, the default: sets of 177 .. 256 bounds, one workgroup of four or eight waves each -- qp_wg.h)
-  const int nwg64 = a.use_wg ? cnt[ASM_CNT_BIG64] : 0;
-  const int nwg32 = a.use_wg ? cnt[ASM_CNT_BIG32] : 0;
-  const int nwg32b = a.use_wg ? cnt[ASM_CNT_BIG32B] : 0;   // f32 rounds of 257 .. 384 bounds: eight waves per problem
-  const int nwg64r = a.use_wg ? cnt[ASM_CNT_BIG64R] : 0;   // ... and their fp64 solves: the same factorisation, refined to fp64 residuals
-  int nbig = cnt[ASM_CNT_SLAB] + cnt[ASM_CNT_BIG32] + nreg2_wg + nreg32b_wg + nwg64 + nwg32b + nwg64r, nreg_wg = 0, nreg32_wg = 0;
+  // sets of 177 .. 384 bounds: one workgroup of four or eight waves each (qp_wg.h)
+  const int nwg64 = cnt[ASM_CNT_BIG64];
+  const int nwg32 = cnt[ASM_CNT_BIG32];
+  const int nwg32b = cnt[ASM_CNT_BIG32B];   // f32 rounds of 257 .. 384 bounds: eight waves per problem
+  const int nwg64r = cnt[ASM_CNT_BIG64R];   // ... and their fp64 solves: the same factorisation, refined to fp64 residuals
+  int nbig = cnt[ASM_CNT_SLAB] + nwg32 + nwg64s + nreg32b_wg + nwg64 + nwg32b + nwg64r, nreg_wg = 0, nreg32_wg = 0;
   for (int b = 0; b < ASM_NREG; ++b) { nreg_wg += (cnt[ASM_CNT_F64 + b] + 3) / 4; nreg32_wg += (cnt[ASM_CNT_F32 + b] + 3) / 4; }
   // three side streams: [slab kernel: few workgroups, long chains -- it starts first and runs beside everything else],
-  // [four-wave kernels of the 12 .. 16-block sets], [single-wave kernels of the 10- and 11-block classes]
+  // [four- and eight-wave kernels of the 12 .. 24-block sets], [kernels of the 10- and 11-block classes]
   // (beside a pass stream4 carries the pass: the slab kernel then goes first on stream2)
-  const bool side4 = cnt[ASM_CNT_SLAB] > 0, side2 = nwg64 + nwg32 + nwg32b + nwg64r > 0 || (cnt[ASM_CNT_BIG32] && !a.use_wg), side3 = nreg2_wg + nreg32b_wg > 0;
+  const bool side4 = cnt[ASM_CNT_SLAB] > 0, side2 = nwg64 + nwg32 + nwg32b + nwg64r > 0, side3 = nwg64s + nreg32b_wg > 0;
   hipStream_t st4 = inflight ? h->stream2 : h->stream4;
   if (nbig) {
     HIPCHK(hipEventRecord(h->ev_fork, s));
@@ -1610,16 +1604,14 @@ int launch_multipliers(AsmCall& c, const int* cnt, bool inflight) {
       if (nwg64r) hipLaunchKernelGGL(asm_lambda_wg64r_k, dim3(nwg64r), dim3(512), (asm_wg_lds_bytes_refine<float, ASM_WG_MB8>()), h->stream2, a);
       if (nwg32b) hipLaunchKernelGGL(asm_lambda_wg32b_k, dim3(nwg32b), dim3(512), (asm_wg_lds_bytes<float, ASM_WG_MB8>()), h->stream2, a);
       if (nwg32) hipLaunchKernelGGL(asm_lambda_wg32_k, dim3(nwg32), dim3(256), asm_wg_lds_bytes<float>(), h->stream2, a);
-      if (cnt[ASM_CNT_BIG32] && !a.use_wg) hipLaunchKernelGGL(asm_lambda_tile32_k, dim3(std::min(cnt[ASM_CNT_BIG32], 4096)), dim3(512), ASM_TILE32_LDS, h->stream2, a);
       HIPCHK(hipEventRecord(h->ev_join, h->stream2));
     }
     if (side3) {
       HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_fork, 0));
       EvScope e9(h, EV_SIDE, 0.0, h->stream3);
       // fp64, 145 .. 176 bounds: two waves per problem (7.3 / 5.2 problems per microsecond at 160 / 176 bounds against the 6.0 / 4.5
-      // of the single-wave kernel; in f32 the single-wave kernel wins, 18.1 against 14.3)
-      if (nreg2_wg && a.use_wg) hipLaunchKernelGGL(asm_lambda_wg64s_k, dim3(cnt[ASM_CNT_F64 + 6] + cnt[ASM_CNT_F64 + 7]), dim3(128), asm_wg_lds_bytes<double>(), h->stream3, a);
-      else if (nreg2_wg) hipLaunchKernelGGL(asm_lambda_reg2_k, dim3(nreg2_wg), dim3(128), ASM_REG2_LDS, h->stream3, a);
+      // of one wave per problem; in f32 the single-wave kernel wins, 18.1 against 14.3)
+      if (nwg64s) hipLaunchKernelGGL(asm_lambda_wg64s_k, dim3(nwg64s), dim3(128), asm_wg_lds_bytes<double>(), h->stream3, a);
       if (nreg32b_wg) hipLaunchKernelGGL(asm_lambda_reg32b_k, dim3(nreg32b_wg), dim3(256), ASM_REG32B_LDS, h->stream3, a);
       HIPCHK(hipEventRecord(h->ev_join3, h->stream3));
     }
@@ -1965,11 +1957,9 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   for (hipEvent_t* ev : {&h->ev_fork, &h->ev_join3, &h->ev_join4, &h->ev_join, &h->ev_wfork, &h->ev_wide})
     if (int rc = res.event(ev, hipEventDisableTiming)) return rc;
   HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG_LDS));
-  HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg2_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG2_LDS));
   HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32_LDS));
   HIPCHK(hipFuncSetAttribute((const void*)asm_tail_k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg32b_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32B_LDS));
-  HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_tile32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_TILE32_LDS));
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f64_t128_k, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));
   HIPCHK(hipFuncSetAttribute((const void*)asm_wide_gemm_k<WIDE_XUNC>, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));
   HIPCHK(hipFuncSetAttribute((const void*)asm_wide_gemm_k<WIDE_LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, G64_LDS));

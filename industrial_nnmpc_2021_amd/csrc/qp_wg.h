@@ -2,9 +2,9 @@
 // tile in registers.  (Included by qp_asm.h after the single-wave kernels, whose building blocks it uses.)
 //
 // Why: a single wave holds at most 32 + a few LDS-resident tiles (asm_lambda_reg: <= 11 blocks, and from 10 blocks on at half
-// the rate of the 9-block class), and the LDS-tile kernels beyond (asm_lambda_tile32_k, asm_lambda_tile_k) move every
-// operand of every MFMA through LDS behind three barriers per block column: 7 - 9 TFLOP/s at 192 .. 256 bounds against the
-// 51 TFLOP/s of the 9-block register kernel (scripts/micro/lambda_micro.hip).  Here the lower tiles of an MB-block set are
+// the rate of the 9-block class), and a kernel that keeps the tiles in LDS or an L2 slab (asm_lambda_tile_k) moves every
+// operand of every MFMA through that memory behind three barriers per block column: 7 - 9 TFLOP/s at 192 .. 256 bounds against
+// the 51 TFLOP/s of the 9-block register kernel ("Larger sets").  Here the lower tiles of an MB-block set are
 // spread over the four waves BY BLOCK ROW, so that
 //   * TRSM  L(I,K)' = Y_K S(I,K)'  and the trailing update  S(I,J)' += L(J,K) L(I,K)'  run MFMA register to register exactly
 //     as in asm_lambda_reg (the accumulator of a transposed tile IS its operand fragment); the only operand a wave does not
@@ -451,22 +451,18 @@ __device__ __forceinline__ void asm_lambda_wg_any(const AsmDev& d, int p) {
     case 14: asm_lambda_wg<T, 14, 4>(d, p, m); break;
     case 13: asm_lambda_wg<T, 13, 4>(d, p, m); break;
     case 12: asm_lambda_wg<T, 12, 4>(d, p, m); break;
-#ifdef ASM_WG_MICRO                                        // (scripts/micro only: the solver's lists hold sets of 177 .. 256 bounds)
-    case 11: asm_lambda_wg<T, 11, 4>(d, p, m); break;
-    default: asm_lambda_wg<T, 10, 4>(d, p, m); break;
-#else
     default: if (threadIdx.x == 0) d.state[p] = ASM_FALLBACK; break;   // not reachable through asm_scan_col; the PDIP path if it ever is
-#endif
   }
 }
 
 // f32 rounds of the sets of 177 .. 256 bounds (list ASM_NLIST), fp64 rounds (list ASM_NLIST + 1): one workgroup each.
-// (The 10- and 11-block classes stay with the single-wave kernels asm_lambda_reg32b_k / asm_lambda_reg2_k: four independent
-// pivot chains per CU and no barrier beat four waves on one chain there -- 17.9 against 14.9 problems per microsecond at 160
-// bounds in f32; from 12 blocks on the single-wave kernels have no room.  scripts/micro/lambda_micro.hip, problems per
-// microsecond at 192 / 224 / 256 bounds: f32 11.8 / 8.6 / 6.4 here against 2.9 / 2.2 / 1.65 of asm_lambda_tile32_k; fp64
-// 4.2 / 2.8 / 2.3.  Eight waves per problem -- half the tiles per wave, no spills at 16 blocks -- were SLOWER: 4.5 at 256
-// bounds in f32, one workgroup per CU and twice the barrier traffic.)
+// (The 10- and 11-block classes do not come here: in f32 they stay with the single-wave kernel asm_lambda_reg32b_k -- four
+// independent pivot chains per CU and no barrier beat four waves on one chain there, 17.9 against 14.9 problems per microsecond
+// at 160 bounds; from 12 blocks on a single wave has no room -- and in fp64 they take two waves per problem, asm_lambda_wg64s_k
+// below.  scripts/micro/lambda_micro.hip, problems per microsecond at 192 / 224 / 256 bounds: f32 11.8 / 8.6 / 6.4, fp64
+// 4.2 / 2.8 / 2.3 (the f32 kernel with all tiles in LDS this one replaced: 2.9 / 2.2 / 1.65).  Eight waves per problem -- half
+// the tiles per wave, no spills at 16 blocks -- were SLOWER: 4.5 at 256 bounds in f32, one workgroup per CU and twice the
+// barrier traffic.)
 #if ASM_WG_DEF(0)
 __global__ __launch_bounds__(256, 2) void asm_lambda_wg32_k(AsmDev d) {
   if ((int)blockIdx.x < d.counters[ASM_CNT_BIG32]) asm_lambda_wg_any<float>(d, d.binlist[(size_t)ASM_NLIST * d.nseg + blockIdx.x]);
@@ -529,30 +525,14 @@ __global__ __launch_bounds__(512, 1) void asm_lambda_wg64r_k(AsmDev d) {
 __global__ void asm_lambda_wg64r_k(AsmDev d);
 #endif
 
-// (The same for the sets of 177 .. 256 bounds -- four waves, f32 tiles, two workgroups per CU, refined -- is no faster than the fp64
+// (The same for the sets of 177 .. 256 bounds -- four waves, f32 tiles, two workgroups per CU, refined -- was no faster than the fp64
 // register kernel asm_lambda_wg64_k there: 4.4 / 3.0 / 2.5 against 4.3 / 3.3 / 2.3 problems per microsecond at 192 / 224 / 256
-// bounds (scripts/micro/lambda_micro.hip, variant 14 against 6): the three residual passes and two extra solves cost what the f32
-// tiles save.  Not instantiated in the library.)
-#ifdef ASM_WG_MICRO
-__global__ __launch_bounds__(256, 2) void asm_lambda_wg64r4_k(AsmDev d) {
-  if ((int)blockIdx.x >= d.counters[ASM_CNT_BIG64]) return;
-  const int p = d.binlist[(size_t)(ASM_NLIST + 1) * d.nseg + blockIdx.x];
-  const int m = __builtin_amdgcn_readfirstlane(d.mg[p]);
-  if (m <= 176 || m > ASM_WG_MAX) return;
-  switch ((m + 15) >> 4) {
-    case 16: asm_lambda_wg<float, 16, 4, true>(d, p, m); break;
-    case 15: asm_lambda_wg<float, 15, 4, true>(d, p, m); break;
-    case 14: asm_lambda_wg<float, 14, 4, true>(d, p, m); break;
-    case 13: asm_lambda_wg<float, 13, 4, true>(d, p, m); break;
-    default: asm_lambda_wg<float, 12, 4, true>(d, p, m); break;
-  }
-}
-#endif
+// bounds: the three residual passes and two extra solves cost what the f32 tiles save.)
 
-// The 10- and 11-block classes (145 .. 176 bounds) with TWO waves per problem: the same number of problems per CU as the
-// single-wave kernels (four in f32, two in fp64), half the tiles and half the trailing update per wave.  The solver uses the
-// fp64 instance (7.3 / 5.2 problems per microsecond at 160 / 176 bounds, asm_lambda_reg2_k: 6.0 / 4.5); the f32 instance
-// loses to asm_lambda_reg32b_k (14.3 against 18.1 at 160) and is kept for scripts/micro only.
+// The 10- and 11-block classes (145 .. 176 bounds) with TWO waves per problem: the same number of problems per CU as one wave
+// per problem would allow (four in f32, two in fp64), half the tiles and half the trailing update per wave.  Used in fp64
+// (7.3 / 5.2 problems per microsecond at 160 / 176 bounds against 6.0 / 4.5 of one wave per problem); in f32 it lost to
+// asm_lambda_reg32b_k (14.3 against 18.1 at 160).
 template <class T>
 __device__ __forceinline__ void asm_lambda_wg2(const AsmDev& d, int c7, int c6) {
   int w = blockIdx.x, list;
@@ -566,9 +546,6 @@ __device__ __forceinline__ void asm_lambda_wg2(const AsmDev& d, int c7, int c6) 
   if (m > 160) asm_lambda_wg<T, 11, 2>(d, p, m);
   else asm_lambda_wg<T, 10, 2>(d, p, m);
 }
-#ifdef ASM_WG_MICRO
-__global__ __launch_bounds__(128, 4) void asm_lambda_wg32s_k(AsmDev d) { asm_lambda_wg2<float>(d, ASM_CNT_F32 + 7, ASM_CNT_F32 + 6); }
-#endif
 #if ASM_WG_DEF(4)
 __global__ __launch_bounds__(128, 2) void asm_lambda_wg64s_k(AsmDev d) { asm_lambda_wg2<double>(d, 4 + 7, 4 + 6); }
 #else

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(512, 2) void wg32_8_k(AsmDev d) { if ((int)blockIdx
 int main(int argc, char** argv) {
   const int m = argc > 1 ? atoi(argv[1]) : 112;
   const int nseg = argc > 2 ? atoi(argv[2]) : 14336;
-  const int variant = argc > 3 ? atoi(argv[3]) : 0;      // 0 tile kernel, 1 register kernel (fp64), 2 register kernel (f32)
+  const int variant = argc > 3 ? atoi(argv[3]) : 1;      // 1 register kernel (fp64, <= 144 bounds), 2 register kernels (f32, <= 176); the others: see the launches
   const int n = 512, np = 512, nu = 32, max_active = 768;
   const int win0 = argc > 4 ? atoi(argv[4]) : 416;        // the active indices are drawn from [0, win): win = m makes them contiguous
   const int win = win0 > 0 ? win0 : 512;                   // win < 0: -win inputs saturated over the first steps (indices step * nu + input: the solver's pattern)
@@ -90,7 +90,7 @@ int main(int argc, char** argv) {
   if (variant == 5) { cnt[ASM_CNT_F32 + 6] = cnt[ASM_CNT_F32 + 7] = 0; }            // four-wave register kernels (qp_wg.h): one list each
   if (variant == 13) cnt[ASM_CNT_BIG64R] = nseg;             // ... and its refined (fp64-residual) instance
   if (variant == 12) cnt[ASM_CNT_BIG32B] = nseg;             // eight-wave f32 kernel of the solver: 257 .. 384 bounds
-  if (variant == 6 || variant == 10 || variant == 14) { cnt[4 + 6] = cnt[4 + 7] = 0; cnt[ASM_CNT_BIG64] = nseg; }
+  if (variant == 6 || variant == 10) { cnt[4 + 6] = cnt[4 + 7] = 0; cnt[ASM_CNT_BIG64] = nseg; }
   CK(hipMalloc(&dcnt, sizeof cnt)); CK(hipMemcpy(dcnt, cnt, sizeof cnt, hipMemcpyHostToDevice));
   CK(hipMalloc(&dbin, (size_t)(ASM_NLIST + 4) * nseg * 4));
   for (int b = 0; b <= ASM_NLIST + 3; ++b) CK(hipMemcpy(dbin + (size_t)b * nseg, list.data(), nseg * 4, hipMemcpyHostToDevice));
@@ -109,11 +109,7 @@ int main(int argc, char** argv) {
   float* dlam32; CK(hipMalloc(&dlam32, xunc.size() * 4)); CK(hipMemset(dlam32, 0, xunc.size() * 4)); d.lam32 = dlam32;
   unsigned char* drowk; CK(hipMalloc(&drowk, nseg)); CK(hipMemset(drowk, variant == 20 ? 0 : 1, nseg)); d.rowk = drowk;   // variant 20: the f32 register kernels with rows of LAM -- every solve gets its fp64 correction (build with -DASM_REFINE_ALWAYS: the synthetic sets have random multiplier signs)
   int* drow; CK(hipMalloc(&drow, nseg * 4)); CK(hipMemcpy(drow, list.data(), nseg * 4, hipMemcpyHostToDevice)); d.row = drow;
-  const int mbc = asm_bin_cap(bin) / 16;
-  const int lds_tile = (asm_bin_cap(bin) + ASM_TS + mbc * (mbc + 1) / 2 * ASM_TS) * 8;
-  CK(hipFuncSetAttribute((const void*)asm_lambda_tile_k<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (ASM_MLDS + ASM_TS + 66 * ASM_TS) * 8));
   CK(hipFuncSetAttribute((const void*)asm_lambda_reg_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG_LDS));
-  CK(hipFuncSetAttribute((const void*)asm_lambda_reg2_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG2_LDS));
   CK(hipFuncSetAttribute((const void*)asm_lambda_reg32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32_LDS));
   CK(hipFuncSetAttribute((const void*)asm_lambda_reg32b_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32B_LDS));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
@@ -121,22 +117,15 @@ int main(int argc, char** argv) {
   for (int rep = 0; rep < 6; ++rep) {
     CK(hipEventRecord(e0, 0));
 #ifndef ASM_NO_WG_KERNELS
-    if (variant == 7) hipLaunchKernelGGL(asm_lambda_wg32s_k, dim3(nseg), dim3(128), asm_wg_lds_bytes<float>(), 0, d);
-    else if (variant == 8) hipLaunchKernelGGL(asm_lambda_wg64s_k, dim3(nseg), dim3(128), asm_wg_lds_bytes<double>(), 0, d);
+    if (variant == 8) hipLaunchKernelGGL(asm_lambda_wg64s_k, dim3(nseg), dim3(128), asm_wg_lds_bytes<double>(), 0, d);
     else if (variant == 5) hipLaunchKernelGGL(asm_lambda_wg32_k, dim3(nseg), dim3(256), asm_wg_lds_bytes<float>(), 0, d);
     else if (variant == 6) hipLaunchKernelGGL(asm_lambda_wg64_k, dim3(nseg), dim3(256), asm_wg_lds_bytes<double>(), 0, d);
-    else if (variant == 14) hipLaunchKernelGGL(asm_lambda_wg64r4_k, dim3(nseg), dim3(256), (asm_wg_lds_bytes_refine<float, ASM_WG_MB>()), 0, d);
     else if (variant == 13) hipLaunchKernelGGL(asm_lambda_wg64r_k, dim3(nseg), dim3(512), (asm_wg_lds_bytes_refine<float, ASM_WG_MB8>()), 0, d);
     else if (variant == 12) hipLaunchKernelGGL(asm_lambda_wg32b_k, dim3(nseg), dim3(512), (asm_wg_lds_bytes<float, ASM_WG_MB8>()), 0, d);
     else if (variant == 10) hipLaunchKernelGGL(wg64_8_k, dim3(nseg), dim3(512), asm_wg_lds_bytes<double>(), 0, d);
     else if (variant == 11) hipLaunchKernelGGL(wg32_8_k, dim3(nseg), dim3(512), asm_wg_lds_bytes<float>(), 0, d);
     else
 #endif
-    if (variant == 4) {                                  // f32 LDS-tile workgroup kernel (177..256 bounds)
-      static bool once4 = false;
-      if (!once4) { CK(hipFuncSetAttribute((const void*)asm_lambda_tile32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_TILE32_LDS)); once4 = true; }
-      hipLaunchKernelGGL(asm_lambda_tile32_k, dim3(std::min(nseg, 4096)), dim3(512), ASM_TILE32_LDS, 0, d);
-    } else
 #ifdef PROBE_MB
     if (variant == 3) {
       static bool once = false;
@@ -145,13 +134,10 @@ int main(int argc, char** argv) {
       hipLaunchKernelGGL(probe_k, dim3((nseg + 3) / 4), dim3(256), lds, 0, d);
     } else
 #endif
-    if (variant == 0) hipLaunchKernelGGL((asm_lambda_tile_k<0>), dim3(nseg), dim3(256), lds_tile, 0, d, bin);
-    else if ((variant == 2 || variant == 20) && bin < ASM_NREG) hipLaunchKernelGGL(asm_lambda_reg32_k, dim3((nseg + 3) / 4 + ASM_NREG), dim3(256), ASM_REG32_LDS, 0, d);
+    if ((variant == 2 || variant == 20) && bin < ASM_NREG) hipLaunchKernelGGL(asm_lambda_reg32_k, dim3((nseg + 3) / 4 + ASM_NREG), dim3(256), ASM_REG32_LDS, 0, d);
     else if (variant == 2 || variant == 20) hipLaunchKernelGGL(asm_lambda_reg32b_k, dim3((nseg + 3) / 4 + 2), dim3(256), ASM_REG32B_LDS, 0, d);
-    else {
-      if (bin < ASM_NREG) hipLaunchKernelGGL(asm_lambda_reg_k, dim3((nseg + 3) / 4 + ASM_NREG), dim3(256), ASM_REG_LDS, 0, d);
-      else hipLaunchKernelGGL(asm_lambda_reg2_k, dim3((nseg + 1) / 2 + 2), dim3(128), ASM_REG2_LDS, 0, d);
-    }
+    else if (variant == 1 && bin < ASM_NREG) hipLaunchKernelGGL(asm_lambda_reg_k, dim3((nseg + 3) / 4 + ASM_NREG), dim3(256), ASM_REG_LDS, 0, d);
+    else { printf("variant %d has no kernel for %d bounds\n", variant, m); return 1; }
     CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1)); if (rep) best = std::min(best, ms);
   }
@@ -169,7 +155,7 @@ int main(int argc, char** argv) {
   double worst = 0.0;
   for (int pp = 0; pp < 2; ++pp) {
     const int p = pp == 0 ? 0 : nseg - 1;
-    if (variant == 2 || variant == 3 || variant == 4 || variant == 5 || variant == 7 || variant == 11 || variant == 12) {
+    if (variant == 2 || variant == 3 || variant == 5 || variant == 11 || variant == 12) {
       std::vector<float> l32(np);
       CK(hipMemcpy(l32.data(), dlam32 + (size_t)p * np, np * 4, hipMemcpyDeviceToHost));
       for (int i = 0; i < np; ++i) lam[i] = l32[i];
@@ -191,7 +177,6 @@ int main(int argc, char** argv) {
       printf("  column %d: start %llu  trsm-issued +%llu  trail-issued +%llu  (next column at +%llu)\n", K, st_[4 + 3 * K] - st_[0], st_[5 + 3 * K] - st_[4 + 3 * K],
              st_[6 + 3 * K] > st_[5 + 3 * K] ? st_[6 + 3 * K] - st_[5 + 3 * K] : 0ull, st_[4 + 3 * (K + 1)] > st_[4 + 3 * K] ? st_[4 + 3 * (K + 1)] - st_[4 + 3 * K] : 0ull);
     printf("  factor done %llu, backward substitution %llu\n", st_[40] - st_[0], st_[41] - st_[40]);
-    if (st_[52]) printf("  tile32: rhs+gather %llu, first diagonal step %llu, factorisation %llu, substitutions %llu\n", st_[49] - st_[48], st_[50] - st_[49], st_[51] - st_[50], st_[52] - st_[51]);
   }
 #endif
   printf("variant %d m %d nseg %d: %.3f ms  (%.2f problems/us)  max residual %.2e  fallback %d\n", variant, m, nseg, best, nseg / (best * 1e3), worst, nfb);

@@ -21,10 +21,6 @@ Tolerances: first family 1e-9 max(1, |x|inf) and bit-equal sets (tests/test_asm_
 1e-7 max(1, cond / 1e3) = 1e-6 (tests/test_random_shapes_gpu.py's).  Which kernels these tests launch, and what seeded defects they
 catch: profiles/large_sets_coverage.md.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -360,26 +356,17 @@ def test_small_kernels_at_their_edges(monkeypatch):
     _judge("n = 720", P, q, lb, ub, out, state, xref)
 
 
-# ---- the kernels the workgroup kernels replaced --------------------------------------------------------------------------------
+# ---- sizes inside the classes of 145 .. 256 bounds ----------------------------------------------------------------------------
 
-def test_replaced_kernels_in_a_child_process(fam, handles, tmp_path):
-    """NNMPC_NO_WG (read once per process) sends 145 .. 176 bounds to asm_lambda_reg2_k and the f32 rounds of 177 .. 256 to
-    asm_lambda_tile32_k -- still compiled, still reachable.  One fresh child process solves the sizes 145 .. 256 that way."""
+def test_sizes_inside_the_two_and_four_wave_classes(fam, handles):
+    """145 .. 176 and 177 .. 256 bounds at sizes between the boundaries (160: a full 10-block set, 200: 13 blocks with a ragged
+    last one) next to the ends of both classes, f32 rounds first and fp64 throughout."""
     P, rows = fam
     sizes = [145, 160, 176, 177, 200, 256] * 2
     q, lb, ub, state, _, xref = rows(sizes, 31)
-    path = str(tmp_path / "no_wg.npz")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, NNMPC_NO_WG="1")
-    subprocess.run([sys.executable, "-m", "tests.large_sets_worker", path, str(PSEED), "31"] + [str(s) for s in sizes],
-                   cwd=root, env=env, check=True, timeout=300)
-    with np.load(path) as f:
-        child = {k: f[k] for k in f.files}
     for f32 in (0, -1):
-        out, _ = _solve(handles(asm_f32_rounds=f32, **ROUNDS), q, lb, ub)
-        got = dict(u=child[f"u{f32}"], active=child[f"active{f32}"])
-        print(f"LARGE_SETS no-wg f32={f32}: status {child[f'status{f32}']} |du| {np.abs(got['u'] - out['u']).max():.3e}")
-        assert (child[f"status{f32}"] == 0).all() and (out["status"] == 0).all()
-        assert child[f"solved{f32}"] == len(sizes) and child[f"factorizations{f32}"] == 0
-        _judge(f"no-wg f32={f32}", P, q, lb, ub, got, state, xref)
-        assert np.array_equal(got["active"], out["active"]) and np.abs(got["u"] - out["u"]).max() <= 1e-9
+        out, st = _solve(handles(asm_f32_rounds=f32, **ROUNDS), q, lb, ub)
+        print(f"LARGE_SETS inside f32={f32}: status {out['status']} asm_solved {st['asm_solved']} factorizations {st['factorizations']}")
+        assert (out["status"] == 0).all(), (out["status"], sizes)
+        assert st["asm_solved"] == len(sizes) and st["factorizations"] == 0
+        _judge(f"inside f32={f32}", P, q, lb, ub, out, state, xref)
