@@ -551,6 +551,30 @@ int nnmpc_train_group_padding_max(nnmpc_train_group* h, double* maxabs);
 int nnmpc_train_group_last_ms(nnmpc_train_group* h, double* gemm_ms, double* total_ms);
 /* Kernel launches the last epoch / eval enqueued (counted where they are launched): what a loop over G handles multiplies by G. */
 int nnmpc_train_group_last_launches(nnmpc_train_group* h, int64_t* n);
+/* The tangent loss of nnmpc_train_create_tan for a sweep: a structured group whose members each carry their OWN weight
+ * w[g] >= 0 of the tangent term; one set of tangents is shared, as the dataset is.  Arguments as nnmpc_train_create_group_ex;
+ * form must be NNMPC_NN_STRUCTURED (anything else: NNMPC_EINVAL before a device is looked for).  Workspaces for 3 stacked row
+ * blocks of max_batch rows per member.  Every weight is 0 after create.  In a lock-step step a member with w[g] > 0 stacks
+ * 3 Bp rows, a member with w[g] == 0 the plain 2 Bp; the step keeps its 6 nlayers launches whatever the mix.  A member's bytes
+ * do not depend on the rest of the group: with w[g] > 0 its weights and losses (L, mse, tan_mse) equal those of an
+ * nnmpc_train_create_tan handle at that weight fed the same rows, with w[g] == 0 those of an nnmpc_train_create handle, which
+ * are those of a member of a plain group.  Every nnmpc_train_group_* function serves the handle. */
+int nnmpc_train_create_group_tan(nnmpc_train_group** out, int32_t G, int32_t nlayers, const int32_t* dims,
+                                 const double* const* W, const double* const* b, int32_t nx, int32_t nu,
+                                 int32_t with_uprev, int32_t max_batch, double lr, double beta1,
+                                 double beta2, double eps, int32_t form);
+/* nnmpc_train_set_tangents for the group's shared dataset, with its errors: a plain group, no dataset yet, n != the dataset's
+ * rows, a with-uprev group without duprev: NNMPC_EINVAL.  A later nnmpc_train_group_set_data drops them. */
+int nnmpc_train_set_group_tangents(nnmpc_train_group* h, int32_t n, const double* dx,
+                                   const double* duprev, const double* t, int32_t ptr_kind);
+/* The members' weights, G entries, each finite and >= 0 (NNMPC_EINVAL names the member; nothing is changed); a plain group:
+ * NNMPC_EINVAL.  With any w[g] > 0 and no tangents, nnmpc_train_group_epoch and _eval return NNMPC_EINVAL before any launch.
+ * They return L = mse + w[g] tan_mse where they return the plain group's loss. */
+int nnmpc_train_set_group_tan_weights(nnmpc_train_group* h, const double* w);
+/* nnmpc_train_last_losses per member (G entries each, either may be NULL): the two parts of what the last epoch (row-weighted
+ * means) or eval (over its rows) returned.  A member with w[g] == 0, and any member of a plain group: mse is that loss and
+ * tan_mse 0.  A member without rows in that call: both NaN.  Before the first epoch or eval: NNMPC_EINVAL. */
+int nnmpc_train_last_group_losses(nnmpc_train_group* h, double* mse, double* tan_mse);
 
 /* ---- Lock-step closed-loop chains, device resident  <-  simulate_offline (lib/linearMPC.py:827-880), one OS process
  * per chain in the reference (:814-825).  All nc chains of a task advance together; per step (loop :845-866):

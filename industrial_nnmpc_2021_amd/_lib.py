@@ -75,6 +75,8 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_train_group_set_weights", "nnmpc_train_group_snapshot", "nnmpc_train_group_restore",
            "nnmpc_train_group_padding_max", "nnmpc_train_group_last_ms", "nnmpc_train_group_last_launches",
            "nnmpc_train_create_group_ex",
+           "nnmpc_train_create_group_tan", "nnmpc_train_set_group_tangents", "nnmpc_train_set_group_tan_weights",
+           "nnmpc_train_last_group_losses",
            "nnmpc_chain_create", "nnmpc_chain_destroy", "nnmpc_chain_run", "nnmpc_chain_reset", "nnmpc_chain_last_ms",
            "nnmpc_ts_create", "nnmpc_ts_destroy", "nnmpc_ts_solve_batch",
            "nnmpc_cl_create", "nnmpc_cl_destroy", "nnmpc_cl_run", "nnmpc_cl_reset", "nnmpc_cl_last_ms",
@@ -211,6 +213,14 @@ def load():
     lib.nnmpc_train_group_last_ms.argtypes = [vp, pf64, pf64]
     lib.nnmpc_train_group_last_launches.restype = i32             # (new: launches of the last epoch / eval)
     lib.nnmpc_train_group_last_launches.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.nnmpc_train_create_group_tan.restype = i32                # nnmpc_train_create_tan: a group with one tangent weight per member
+    lib.nnmpc_train_create_group_tan.argtypes = lib.nnmpc_train_create_group_ex.argtypes
+    lib.nnmpc_train_set_group_tangents.restype = i32              # nnmpc_train_set_tangents (one shared set)
+    lib.nnmpc_train_set_group_tangents.argtypes = [vp, i32, dp, dp, dp, i32]
+    lib.nnmpc_train_set_group_tan_weights.restype = i32           # (h, w[G])
+    lib.nnmpc_train_set_group_tan_weights.argtypes = [vp, dp]
+    lib.nnmpc_train_last_group_losses.restype = i32               # nnmpc_train_last_losses, (h, mse[G], tan_mse[G])
+    lib.nnmpc_train_last_group_losses.argtypes = [vp, dp, dp]
     u64 = C.c_uint64
     lib.nnmpc_qp_solve_batch_ex.restype = i32
     lib.nnmpc_qp_solve_batch_ex.argtypes = [vp, i32, dp, dp, dp, dp, dp, dp, dp, dp, i32, i32]

@@ -47,8 +47,9 @@ struct TrainCommon {                                        // what a handle hol
   double lr = 0, beta1 = 0, beta2 = 0, eps = 0;
   int n = 0;                                                // dataset rows
   float *dx = nullptr, *dup = nullptr, *dxs = nullptr, *dus = nullptr, *du = nullptr;
-  // The tangent loss (nnmpc_train_create_tan; never set in a group): the handle stacks a third row block, tan_w is the
-  // weight w of the tangent term (0: the plain step), tdx / tdup / tt the dataset's directions and targets as f32.
+  // The tangent loss (nnmpc_train_create_tan, nnmpc_train_create_group_tan): the handle stacks a third row block, tdx / tdup /
+  // tt are the dataset's directions and targets as f32.  tan_w is a single handle's weight w of the tangent term (0: the
+  // plain step); a group keeps one weight per member itself and leaves tan_w alone.
   int tan = 0;
   double tan_w = 0.0;
   float *tdx = nullptr, *tdup = nullptr, *tt = nullptr;
@@ -177,7 +178,7 @@ inline size_t layout_member(const TrainCommon& c, Member& mb, char* base, size_t
   mb.mem.dz[0] = (float*)take(Mmax * mb.maxw * 4);
   mb.mem.dz[1] = (float*)take(Mmax * mb.maxw * 4);
   mb.mem.partial = (double*)take((size_t)c.cap_batch / 64 * 8 * (c.tan ? 2 : 1));   // a tangent handle: the tangent partials behind the primal ones
-  mb.mem.loss = (double*)take(8);
+  mb.mem.loss = (double*)take(24);                          // L, and under the tangent loss mse and tan_mse
   return off;
 }
 

@@ -362,11 +362,20 @@ class HipGroupTrainer:
     Wout.  ``_lib.NN_UNSTD`` / ``_lib.NN_UNSTD_RELU``: every member is the one-pass network with a bias (and relu) on the
     head, the lists are [W1, b1, ..., WL, bL] and ``get_weights`` / ``set_weights`` exchange that list.
 
+    ``tangents=True`` (structured form only) builds the group of the tangent loss (``nnmpc_train_create_group_tan``):
+    ``set_tangents`` after ``set_data``, ``set_tan_weights(ws)`` with one weight per member; then ``epoch`` and ``eval``
+    return each member's L = mse + w tan_mse and ``last_losses()`` the two parts.  A member with weight 0 (all are, as
+    created) computes the bytes of a member of a plain group, one with w > 0 those of a ``HipTrainer(tangents=True)`` at
+    that weight; the lock-step step has the plain group's launches whatever the mix.
+
     No device: ``_lib.NnmpcError`` (no CPU fallback)."""
 
     def __init__(self, weights, nx, nu, *, nnwithuprev=True, max_batch=2048, lr=1e-3, betas=(0.9, 0.999), eps=1e-7,
-                 form=_lib.NN_STRUCTURED):
+                 form=_lib.NN_STRUCTURED, tangents=False):
         self.form = _check_form(form)
+        self.tangents = bool(tangents)
+        if self.tangents and self.form != _lib.NN_STRUCTURED:   # refused on the host, before the library is loaded
+            raise ValueError("HipGroupTrainer: the tangent loss is built for the structured form only (_lib.NN_STRUCTURED)")
         lib = _lib.load()
         self.G = len(weights)
         Ws, bs, self.dims = [], [], []
@@ -381,11 +390,11 @@ class HipGroupTrainer:
         self.max_batch = int(max_batch)
         self._lib, self._h = lib, C.c_void_p()
         flat = lambda ll: [a for l in ll for a in l]
-        _lib.check(lib.nnmpc_train_create_group_ex(C.byref(self._h), self.G, L,
-                                                   (C.c_int32 * max(1, self.G * (L + 1)))(*flat(self.dims)),
-                                                   HipTrainer._plist(flat(Ws)), HipTrainer._plist(flat(bs)), nx, nu,
-                                                   int(self.nnwithuprev), self.max_batch, lr, betas[0], betas[1], eps,
-                                                   self.form), "nnmpc_train_create_group_ex")
+        create, who = ((lib.nnmpc_train_create_group_tan, "nnmpc_train_create_group_tan") if self.tangents
+                       else (lib.nnmpc_train_create_group_ex, "nnmpc_train_create_group_ex"))
+        _lib.check(create(C.byref(self._h), self.G, L, (C.c_int32 * max(1, self.G * (L + 1)))(*flat(self.dims)),
+                          HipTrainer._plist(flat(Ws)), HipTrainer._plist(flat(bs)), nx, nu, int(self.nnwithuprev),
+                          self.max_batch, lr, betas[0], betas[1], eps, self.form), who)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -410,6 +419,38 @@ class HipGroupTrainer:
         _lib.check(self._lib.nnmpc_train_group_set_data(self._h, int(n), q(x), q(uprev), q(xs), q(us), q(u), _lib.DEVICE),
                    "nnmpc_train_group_set_data")
         self.n = int(n)
+
+    def set_tangents(self, tangents):
+        """dict(dx, duprev, du) for every row of the shared dataset, as ``HipTrainer.set_tangents`` takes them; after
+        ``set_data``, which drops earlier ones.  Uploaded once as f32 for all members."""
+        c = lambda a, w: np.ascontiguousarray(a, np.float64).reshape(-1, w)
+        dx, du = c(tangents["dx"], self.nx), c(tangents["du"], self.nu)
+        dup = c(tangents["duprev"], self.nu) if self.nnwithuprev and tangents.get("duprev") is not None else None
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.nnmpc_train_set_group_tangents(self._h, dx.shape[0], p(dx), p(dup), p(du), _lib.HOST),
+                   "nnmpc_train_set_group_tangents")
+
+    def set_tangents_device(self, n, dx, duprev, du):
+        """The same from HBM-resident f64 buffers (objects with data_ptr(); ``duprev`` None without uprev)."""
+        q = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+        _lib.check(self._lib.nnmpc_train_set_group_tangents(self._h, int(n), q(dx), q(duprev), q(du), _lib.DEVICE),
+                   "nnmpc_train_set_group_tangents")
+
+    def set_tan_weights(self, ws):
+        """One weight of the tangent term per member, each finite and >= 0 (0: the member runs the plain step)."""
+        w = np.ascontiguousarray(ws, np.float64).ravel()
+        if w.size != self.G:
+            raise ValueError(f"set_tan_weights: {w.size} entries for a group of {self.G}")
+        _lib.check(self._lib.nnmpc_train_set_group_tan_weights(self._h, w.ctypes.data_as(C.c_void_p)),
+                   "nnmpc_train_set_group_tan_weights")
+
+    def last_losses(self):
+        """(mse list, tan_mse list) of what the last epoch / eval returned per member (L = mse + w tan_mse); NaN for a
+        member that had no rows in it."""
+        a, b = np.empty(max(1, self.G)), np.empty(max(1, self.G))
+        _lib.check(self._lib.nnmpc_train_last_group_losses(self._h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)),
+                   "nnmpc_train_last_group_losses")
+        return [float(v) for v in a[:self.G]], [float(v) for v in b[:self.G]]
 
     def _i32(self, values, what):
         a = np.ascontiguousarray(values, np.int32).ravel()
@@ -502,17 +543,49 @@ def _sweep_args(who, models, data, num_samples, backend):
 
 
 def _first_rows(data, n):
-    return {k: (None if data.get(k) is None else np.asarray(data[k])[:n]) for k in ("x", "uprev", "xs", "us", "u")}
+    """The first n rows of the dataset, the tangent columns (``tangent_data``) with them where it has any."""
+    out = {k: (None if data.get(k) is None else np.asarray(data[k])[:n]) for k in ("x", "uprev", "xs", "us", "u")}
+    out.update({k: np.asarray(data[k])[:n] for k in ("dx", "duprev", "du") if data.get(k) is not None})
+    return out
 
 
-def _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr, seed, log, form=_lib.NN_STRUCTURED):
+def _sweep_tan_weights(who, models, data, tan_weights):
+    """One finite weight >= 0 per model from a scalar, a list or None (all 0); with any > 0 the models are structured and
+    ``data`` holds the tangent columns.  Host only."""
+    if tan_weights is None:
+        return [0.0] * len(models)
+    ws = [float(v) for v in np.atleast_1d(np.asarray(tan_weights, dtype=np.float64)).ravel()]
+    if np.ndim(tan_weights) == 0:
+        ws = ws * len(models)
+    if len(ws) != len(models):
+        raise ValueError(f"tan_weights: a scalar or one entry per model, got {len(ws)} for {len(models)} models")
+    for i, w in enumerate(ws):
+        if not (w >= 0.0 and np.isfinite(w)):
+            raise ValueError(f"tan_weights[{i}] {w!r}: finite and >= 0")
+    if any(w > 0 for w in ws):
+        for m in models:
+            if getattr(m, "unstructured", False):
+                raise ValueError(f"{who}: the tangent loss is built for the structured RegulatorModel only")
+        need = ("dx", "du") + (("duprev",) if models[0].nnwithuprev else ())
+        if any(data.get(k) is None for k in need):
+            raise ValueError(f"{who}: tan_weight > 0 needs {', '.join(need)} in data (tangent_data makes them)")
+    return ws
+
+
+def _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr, seed, log, form=_lib.NN_STRUCTURED,
+                     tan_weights=None):
     """The "hip" backend of train_nn_controllers / train_unstd_nn_controllers: one ``HipGroupTrainer`` of ``form``, the
-    epoch loop of ``_train_hip`` for every member at once (own rows, own generator, own best epoch)."""
+    epoch loop of ``_train_hip`` for every member at once (own rows, own generator, own best epoch).  ``tan_weights`` with
+    an entry > 0: the tangent group at those weights, so the members' run and validation losses are their L."""
     m0, G = models[0], len(models)
+    tan = tan_weights is not None and any(w > 0 for w in tan_weights)
     tr = HipGroupTrainer([m.get_weights() for m in models], m0.Nx, m0.Nu, nnwithuprev=m0.nnwithuprev,
-                         max_batch=batch_size, lr=lr, eps=1e-7, form=form)
+                         max_batch=batch_size, lr=lr, eps=1e-7, form=form, **({"tangents": True} if tan else {}))
     try:
         tr.set_data(data)
+        if tan:
+            tr.set_tangents(data)
+            tr.set_tan_weights(tan_weights)
         nval = [int(v * validation_split) for v in ns]
         ntr = [v - w for v, w in zip(ns, nval)]
         rngs = [np.random.default_rng(seed) for _ in range(G)]
@@ -543,7 +616,7 @@ def _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr,
 
 
 def train_nn_controllers(models, data, *, num_samples=None, epochs=1500, batch_size=2048, validation_split=0.05,
-                         lr=1e-3, seed=1, log=None, backend="hip"):
+                         lr=1e-3, seed=1, log=None, backend="hip", tan_weights=None):
     """``train_nn_controller`` for a sweep: member i is ``models[i]`` trained on the first ``num_samples[i]`` rows of
     ``data`` (default: all), which is what the reference's loop over ``itertools.product(regulator_dims, num_samples)``
     hands each of its calls.  Keras semantics per member: the last ``int(n_i * validation_split)`` of its rows are its
@@ -553,13 +626,21 @@ def train_nn_controllers(models, data, *, num_samples=None, epochs=1500, batch_s
 
     ``backend="hip"``: one ``HipGroupTrainer``, all members in lock step; the models must agree in Nx, Nu, nnwithuprev
     and depth (``ValueError`` otherwise; build one group per depth), and an ``UnstdRegulatorModel`` is refused: its sweep
-    is ``train_unstd_nn_controllers``.  ``backend="torch"``: a loop over ``train_nn_controller``."""
+    is ``train_unstd_nn_controllers``.  ``backend="torch"``: a loop over ``train_nn_controller``.
+
+    ``tan_weights``: a scalar or one weight per model, each finite and >= 0: member i trains on
+    L = mse + tan_weights[i] tan_mse (``train_nn_controller(tan_weight=...)``; ``data`` then also holds dx, (duprev), du)
+    and its history holds L.  ``backend="hip"`` builds one tangent group when any weight is > 0 -- a member's weights and
+    history are, byte for byte, those of its own ``train_nn_controller(..., backend="hip", tan_weight=w_i, seed=seed)`` --
+    and the plain group otherwise; ``backend="torch"`` loops over ``train_nn_controller(tan_weight=w_i)``."""
     models, ns = _sweep_args("train_nn_controllers", models, data, num_samples, backend)
+    ws = _sweep_tan_weights("train_nn_controller", models, data, tan_weights)
     if backend == "torch":
         t0, hists = time.time(), []
         for i, m in enumerate(models):
             models[i], _, h = train_nn_controller(m, _first_rows(data, ns[i]), epochs=epochs, batch_size=batch_size,
-                                                  validation_split=validation_split, lr=lr, seed=seed, log=log)
+                                                  validation_split=validation_split, lr=lr, seed=seed, log=log,
+                                                  tan_weight=ws[i])
             hists.append(h)
         return models, time.time() - t0, hists
     for m in models:
@@ -568,7 +649,8 @@ def train_nn_controllers(models, data, *, num_samples=None, epochs=1500, batch_s
     for m in models[1:]:
         if (m.Nx, m.Nu, bool(m.nnwithuprev), len(m.layers)) != (m0.Nx, m0.Nu, bool(m0.nnwithuprev), len(m0.layers)):
             raise ValueError("train_nn_controllers: the models of a group agree in Nx, Nu, nnwithuprev and depth")
-    return _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr, seed, log)
+    return _train_group_hip(models, data, ns, epochs, batch_size, validation_split, lr, seed, log,
+                            tan_weights=ws if any(w > 0 for w in ws) else None)
 
 
 def train_unstd_nn_controllers(models, data, *, num_samples=None, epochs=2000, batch_size=1024, validation_split=0.1,

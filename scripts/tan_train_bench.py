@@ -13,6 +13,20 @@ The row count alone predicts 1.5 x the plain step (3 Bp stacked rows for 2 Bp); 
 
     python scripts/tan_train_bench.py [--rows 100000] [--batch 2048] [--epochs 5] [--repeats 5] [--shapes cdu,small] [--weight 0.5]
     python scripts/tan_train_bench.py --one-step small     # a single tangent step and nothing else: what a kernel trace counts
+
+--sweep cstrs|cdu times a whole sweep WITH the tangent loss, on the grid of scripts/train_bench.py --sweep (its SWEEPS: 48
+networks [36, w, w, w, 6] on 40 000 .. 150 000 rows, or 52 networks [536, w, w, w, 32]) at --batch and the grid's
+validation_split, every member at --weight, with that script's protocol (one warm-up epoch, --repeats runs of --epochs sweep
+epochs, the epoch loop's own clock around epoch + eval):
+
+  loop    the networks one after another, each a HipTrainer(tangents=True)
+  group   one HipGroupTrainer(tangents=True) (csrc/nn_train_group.hip): one grouped epoch + one grouped eval per sweep epoch
+  plain   the plain HipGroupTrainer on the same grid and batch: what 3-over-2 stacked row blocks are measured against
+
+One JSON line per way, printed and appended to --out (profiles/tan_train_bench.jsonl); the grouped ways also carry the
+hipEvent time of the epoch calls (last_ms) and the launches per lock-step step (last_launches).
+
+    python scripts/tan_train_bench.py --sweep cstrs [--batch 2048] [--weight 0.5] [--ways loop,group] [--epochs 5] [--repeats 5]
 """
 import argparse
 import json
@@ -82,6 +96,80 @@ def run_hip_events(dims, uprev, data, batch, epochs, repeats, w, vs):
     return dict(epoch_event_ms=spread(tot), epoch_gemm_event_ms=spread(gemm), dw_slices=slices)
 
 
+def run_sweep(name, batch, w, epochs, repeats, ways, out):
+    import itertools
+    import time
+    from industrial_nnmpc_2021_amd.train import HipGroupTrainer, HipTrainer, RegulatorModel, group_schedule
+    from train_bench import SWEEPS
+    sw = SWEEPS[name]
+    uprev, vs = sw["uprev"], sw["validation_split"]
+    members = list(itertools.product(sw["dims"], sw["rows"]))                 # the reference's loop order
+    nx, nu = geometry(members[0][0], uprev)
+    data = with_tangents(synthetic(max(sw["rows"]), nx, nu), nx, nu)
+    weights = [RegulatorModel(nx, nu, d, nnwithuprev=uprev).get_weights() for d, _ in members]
+    nval = [int(n * vs) for _, n in members]
+    ntr = [n - v for (_, n), v in zip(members, nval)]
+    sched = group_schedule(ntr, batch)
+    steps = max(len(s) for s in sched)
+    common = dict(sweep=name, members=len(members), batch=batch, validation_split=vs, tan_weight=w, epochs=epochs, repeats=repeats,
+                  member_steps_per_epoch=sum(len(s) for s in sched), lockstep_steps_per_epoch=steps)
+
+    def emit(r):
+        line = json.dumps(dict(common, **r))
+        print(line, flush=True)
+        if out:
+            with open(out, "a") as f:
+                f.write(line + "\n")
+
+    if "loop" in ways:
+        runs, ev = [0.0] * repeats, [0.0] * repeats
+        for (d, n), wk, a, v in zip(members, weights, ntr, nval):
+            tr = HipTrainer(wk, nx, nu, nnwithuprev=uprev, max_batch=batch, tangents=True)
+            part = {k: x[:n] for k, x in data.items()}
+            tr.set_data(part)
+            tr.set_tangents(part)
+            tr.set_tan_weight(w)
+            rng = np.random.default_rng(1)
+            tr.epoch(rng.permutation(a), batch)                               # warm-up
+            tr.eval(a, v)
+            for r in range(repeats):
+                t0 = time.time()
+                for _ep in range(epochs):
+                    tr.epoch(rng.permutation(a), batch)
+                    ev[r] += tr.last_ms()[1]
+                    tr.eval(a, v)
+                runs[r] += time.time() - t0
+            tr.close()
+        emit(dict(way="loop", epoch_ms=spread([1e3 * t / epochs for t in runs]), epoch_event_ms=spread([e / epochs for e in ev])))
+    for way in ("group", "plain"):
+        if way not in ways:
+            continue
+        tr = HipGroupTrainer(weights, nx, nu, nnwithuprev=uprev, max_batch=batch, **({"tangents": True} if way == "group" else {}))
+        tr.set_data(data)
+        if way == "group":
+            tr.set_tangents(data)
+            tr.set_tan_weights([w] * len(members))
+        rngs = [np.random.default_rng(1) for _ in members]
+        tr.epoch([g.permutation(a) for g, a in zip(rngs, ntr)], batch)        # warm-up
+        tr.eval(ntr, nval)
+        runs, ev, gemm = [], [], []
+        for r in range(repeats):
+            t0, e, ge = time.time(), 0.0, 0.0
+            for _ep in range(epochs):
+                tr.epoch([g.permutation(a) for g, a in zip(rngs, ntr)], batch)
+                launches = tr.last_launches()
+                g_ms, t_ms = tr.last_ms()
+                e += t_ms
+                ge += g_ms
+                tr.eval(ntr, nval)
+            runs.append(1e3 * (time.time() - t0) / epochs)
+            ev.append(e / epochs)
+            gemm.append(ge / epochs)
+        tr.close()
+        emit(dict(way=way, epoch_ms=spread(runs), epoch_event_ms=spread(ev), epoch_gemm_event_ms=spread(gemm),
+                  last_launches=launches, launches_per_lockstep_step=launches / steps))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100000)
@@ -92,7 +180,15 @@ def main():
     ap.add_argument("--weight", type=float, default=0.5)
     ap.add_argument("--validation-split", type=float, default=0.05)
     ap.add_argument("--one-step", default="", help="shape: one tangent step of a full batch and nothing else (for a kernel trace)")
+    ap.add_argument("--sweep", default="", help="cstrs or cdu: time the whole sweep with the tangent loss instead of the shapes")
+    ap.add_argument("--ways", default="loop,group", help="with --sweep: loop, group, plain")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "tan_train_bench.jsonl"),
+                    help="with --sweep: the file the JSON lines are appended to ('' for none)")
     a = ap.parse_args()
+    if a.sweep:
+        for name in a.sweep.split(","):
+            run_sweep(name, a.batch, a.weight, a.epochs, a.repeats, a.ways.split(","), a.out)
+        return
     if a.one_step:
         dims, uprev = SHAPES[a.one_step]
         nx, nu = geometry(dims, uprev)
