@@ -147,6 +147,7 @@ typedef struct {
   int64_t adj_slab_problems; /* ... and in the slab instance (161 to 768 bounds) */
   double adj_total_ms;       /* hipEvent time of whole nnmpc_qp_adjoint calls on the handle's stream, the host's sorting between the launches included (profiling on) */
   int64_t asm_carried;       /* problems whose round was a copy of the corrected multipliers the f32 screen before it had kept for the same set (NNMPC_CARRY) */
+  int64_t asm_shared_passes; /* full-width passes beside which a second iteration ran, in the third row space (NNMPC_VIEWS) */
 } nnmpc_qp_stats;
 
 const char* nnmpc_last_error(void);

@@ -38,7 +38,7 @@ class QpStats(C.Structure):
                 ("sens_slab_problems", C.c_int64), ("sens_total_ms", C.c_double),
                 ("adj_ms", C.c_double), ("adj_launches", C.c_int64), ("adj_lds_problems", C.c_int64),
                 ("adj_slab_problems", C.c_int64), ("adj_total_ms", C.c_double),
-                ("asm_carried", C.c_int64)]
+                ("asm_carried", C.c_int64), ("asm_shared_passes", C.c_int64)]
 
 
 CL_MPC, CL_NN, CL_SATDLQR, CL_US, CL_NN_UNSTD = 0, 1, 2, 3, 4

@@ -721,15 +721,18 @@ struct nnmpc_qp {
   double p_inf = 0.0;       // max row sum of |P|
   // Row spaces ("views") of the active-set rounds: the buffers indexed by the ROW a round hands a running problem (and that round's
   // counters and k-ranges) rather than by the problem.  view[0] has seg_max rows; view[1] is a second, small one for the round that
-  // runs beside a full-width pass (solve_segment_asm).  Everything indexed by problem is shared.  The counters of both views are one
-  // array of 2 ASM_NCNT ints at view[0].counters (read_counters).
+  // runs beside a full-width pass, view[2] a third of the same size for the iteration after that round, beside the same pass
+  // (solve_segment_asm).  Everything indexed by problem is shared.  The counters of all views are one array of ASM_NVIEW ASM_NCNT
+  // ints at view[0].counters (read_counters).
+  enum { ASM_NVIEW = 3 };
   struct AsmView {
     double *lam = nullptr, *xh = nullptr, *xhw = nullptr, *tnorm = nullptr, *tslack = nullptr;
     float *lam32 = nullptr, *xh32 = nullptr;
     int *rowprob = nullptr, *kblk = nullptr, *counters = nullptr;
     int rows = 0;                    // running problems a round in this view can hold (multiple of 128; 0: no such view)
   };
-  AsmView view[2];
+  AsmView view[ASM_NVIEW];
+  int nview = 1;                     // views that have rows: 1 .. ASM_NVIEW, the first nview of them
   // first-set predictor (qp_predict.h): bf16 fragments of Pinv[0:512, 0:512], step sizes; set by nnmpc_qp_set_inverse when the problem is large enough
   struct PredWin { pu32x4* Hf = nullptr; double L = 0.0; int W = 0; };   // L = 1.05 lambda_max(D^-1/2 Pinv_WW D^-1/2); 0: window not available
   PredWin pred[2];              // [0]: 512 columns, 64 problems per workgroup; [1]: 1024 columns, 32 per workgroup (sets that reach further)
@@ -747,11 +750,12 @@ struct nnmpc_qp {
   hipStream_t stream3 = nullptr, stream4 = nullptr;
   int asm_tail_budget = 50000;       // iterations of asm_tail_k per problem (set in nnmpc_qp_create)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr, ev_join4 = nullptr;
-  hipEvent_t ev_wfork = nullptr, ev_wide = nullptr;   // fork / join of a full-width pass that runs on stream4 beside a round
+  hipEvent_t ev_wfork = nullptr;                      // fork of a full-width pass that runs on stream4 beside a round ...
+  hipEvent_t ev_wide[ASM_NVIEW] = {};                 // ... and its join, one per view: two passes can be in flight (solve_segment_asm)
   // pinned host copies of the active-set pass's read-backs (the round counters, the status of a segment): into pageable memory a
   // "hipMemcpyAsync" is staged and waited for inside the runtime (a blocking wait); pinned, the copy is a packet on the stream and
   // stream_sync polls for it.
-  int* pin_cnt = nullptr;            // [2 ASM_NCNT + 4]: the round counters of both views, then the predictor's iteration sum
+  int* pin_cnt = nullptr;            // [ASM_NVIEW ASM_NCNT + 4]: the round counters of all views, then the predictor's iteration sum
   int* pin_st = nullptr;             // [seg_max]
   bool profiling;
   bool gemm_error = false;      // a GEMM was asked for in a form no kernel implements (gemm64): the call in progress fails
@@ -820,7 +824,8 @@ const AsmSwitches& asm_switches() {
 bool env_no_small() { return env_set("NNMPC_NO_SMALL"); }              // A/B, tests of the rounds at small sizes
 bool env_overlap_off() { return env_int("NNMPC_OVERLAP", 1) == 0; }   // A/B runs, 0 = off
 bool env_carry_off() { return env_int("NNMPC_CARRY", 1) == 0; }       // A/B runs, 0 = off
-// Read at create (tests only): rows of the second row space, dflt when unset.
+bool env_two_views() { return env_int("NNMPC_VIEWS", 3) == 2; }      // A/B runs, 2 = no second iteration beside a pass
+// Read at create (tests only): rows of the second and the third row space, dflt when unset.
 long long env_overlap_rows(long long dflt) { const char* e = getenv("NNMPC_OVERLAP_ROWS"); return e ? std::max(0, atoi(e) / 128 * 128) : dflt; }
 
 // The next profiling event of the call in progress, recorded on st.  nullptr when none could be created: the record that
@@ -1173,6 +1178,7 @@ int launch_predictor(nnmpc_qp* h, const AsmDev& a, int nprob, int iters_req, int
 
 // ---- The shared-inverse active-set pass over one segment (solve_segment_asm, at the end of this part, holds its loop).
 // The state of one call: what its phases below share.
+constexpr int NVIEW = nnmpc_qp::ASM_NVIEW;
 struct WideStat { bool open; int view, far_rp, skip, cols; double far_ksum; };
 struct AsmCall {
   nnmpc_qp* h; hipStream_t s; const AsmSwitches* sw;
@@ -1183,27 +1189,34 @@ struct AsmCall {
   bool defer_cnt;               // a tail-only call reads its counters with the status, at the end
   bool overlap_on;              // a far-field pass may run beside a round
   bool carry_on;                // the f32 screen keeps its corrected multipliers for the round after it (AsmDev::carry)
-  int vW[2] = {0, 0}, vrows[2] = {0, 0};   // per view: window and fp64 rows of the last round that ran in it
-  bool tail_ran[2] = {false, false};
+  bool views3;                  // ... and a second iteration beside the same pass, in the third view
+  int vW[NVIEW] = {}, vrows[NVIEW] = {};   // per view: window and fp64 rows of the last round that ran in it
+  bool tail_ran[NVIEW] = {};
   int pend = -1;                // the view whose settled rows await the full-width pass (-1: none)
   // the pass whose asm_wide_k ran last: its flops are counted from the scans of the next bins (they count what asm_wide_k marked)
-  // (wnext: the pass just launched -- beside a round its asm_wide_k comes after the bins that count the pass before it)
-  WideStat wst = {false, 0, 0, 0, 0, 0.0}, wnext = wst;
-  int fft_prev[2] = {0, 0};
+  // (PassLaunch::stat: a pass just launched -- beside a round its asm_wide_k comes after the bins that count the pass before it)
+  WideStat wst = {false, 0, 0, 0, 0, 0.0};
+  int fft_prev[NVIEW] = {};
   double pred_flops_per_it = 0.0;
   int kprev = 0;                // largest active index of the round before (AsmDev::kref)
 };
-// A full-width pass as launch_pass left it: what finish_pass needs to decide its problems.
-struct PassLaunch { AsmDev ap; int fused_c0; bool inflight; };   // inflight: on stream4, its asm_wide_k still to come
+// A full-width pass as launch_pass left it: what finish_passes needs to decide its problems.
+struct PassLaunch { AsmDev ap; int fused_c0; bool inflight; int view; WideStat stat; };   // inflight: on stream4, its asm_wide_k still to come
+// The passes in flight, in launch order (stream4 serialises them): at most two, the second launched behind the first.
+struct PassFifo {
+  PassLaunch pl[2];
+  int n = 0;
+  bool holds(int v) const { for (int i = 0; i < n; ++i) if (pl[i].view == v) return true; return false; }
+};
 
 void set_view(const nnmpc_qp* h, AsmDev& d, int v) {
   const nnmpc_qp::AsmView& V = h->view[v];
   d.lam = V.lam; d.xh = V.xh; d.xhw = V.xhw; d.T = V.xhw; d.tnorm = V.tnorm; d.tslack = V.tslack; d.lam32 = V.lam32; d.xh32 = V.xh32;
   d.rowprob = V.rowprob; d.kblk = V.kblk; d.counters = V.counters;
 }
-// Both views' round counters -> h->pin_cnt, waited for.
+// All views' round counters -> h->pin_cnt, waited for.
 int read_counters(nnmpc_qp* h) {
-  HIPCHK(hipMemcpyAsync(h->pin_cnt, h->view[0].counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(h->pin_cnt, h->view[0].counters, NVIEW * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(stream_sync(h->stream));
   return 0;
 }
@@ -1334,8 +1347,8 @@ void trace_tail_only(AsmCall& c) {
   fprintf(stderr, "asm tail only: %d problems, iterations mean %.2f max %d, active bounds mean %.1f max %d\n", nprob, (double)sum / nprob, mx, (double)sm / nprob, mm);
 }
 // the populations of a round (cnt: its counters)
-void trace_round(int rounds, bool inflight, const int* cnt) {
-  fprintf(stderr, "asm round %d%s: fp64 %d f32 %d last-active %d wide-checked %d big %d big32 %d | fp64 classes", rounds, inflight ? " (beside the pass)" : "",
+void trace_round(int rounds, int beside, const int* cnt) {
+  fprintf(stderr, "asm round %d%s: fp64 %d f32 %d last-active %d wide-checked %d big %d big32 %d | fp64 classes", rounds, beside > 1 ? " (beside two passes)" : (beside ? " (beside the pass)" : ""),
           cnt[ASM_CNT_ROWS64], cnt[ASM_CNT_ROWS32], cnt[ASM_CNT_LAST], cnt[ASM_CNT_WIDE + 1], cnt[ASM_CNT_SLAB], cnt[ASM_CNT_BIG32] + cnt[ASM_CNT_BIG32B]);
   for (int b = 0; b < ASM_NBIN; ++b) fprintf(stderr, " %d", cnt[ASM_CNT_F64 + b]);
   fprintf(stderr, " | f32 classes");
@@ -1432,39 +1445,54 @@ void account(AsmCall& c, const int* cnt) {
   }
 }
 
+// The form the pass over view pv takes: its first column c0, fused_c0 (>= 0: the fused kernel's 128-column tiles fit -- the check
+// is in the GEMM's epilogue), and the far-field factors of its window if the handle has them (nullptr: a dense form).
+const nnmpc_qp::Far* pass_form(const AsmCall& c, int pv, int* c0_out, int* fused_c0_out) {
+  const nnmpc_qp* h = c.h;
+  const int W = c.vW[pv];   // (that round's window: those columns are in that round's XH rows already)
+  const int c0 = (W < h->np && (h->np - W) % 128 == 0) ? W : 0;
+  const int fused_c0 = ((h->np - c0) % 128 == 0 && !c.sw->no_fused_wide) ? c0 : -1;
+  const nnmpc_qp::Far* ff = nullptr;
+  if (c.lazy && fused_c0 > 0 && !c.sw->no_farfield)
+    for (const auto& f : h->far) if (f.W == c0) ff = &f;
+  *c0_out = c0; *fused_c0_out = fused_c0;
+  return ff;
+}
+// Statistics only: a pass is about to mark its problems while those of the pass before it (c.wst) are still uncounted -- the two may
+// be priced differently: count the marks now (scans of the bins in the free view fv; every list and row they write is written again
+// by the bins of the next count)
+int account_now(AsmCall& c, int fv) {
+  nnmpc_qp* h = c.h;
+  AsmDev af = c.a;
+  set_view(h, af, fv);
+  hipLaunchKernelGGL(asm_bins_a_k, dim3((c.nprob + 1023) / 1024), dim3(1024), 0, c.s, af);
+  hipLaunchKernelGGL(asm_bins_b_k, dim3((c.nprob + 1023) / 1024), dim3(1024), 0, c.s, af);
+  if (int rc = read_counters(h)) return rc;
+  account(c, h->pin_cnt + fv * ASM_NCNT);
+  return 0;
+}
 // The full-width pass over the rows of the pending view pv: the problems that settled inside last round's column window get all
-// columns of x, once.  On stream4 beside the coming round (pl.inflight: finish_pass decides its problems), else in sequence here.
-int launch_pass(AsmCall& c, int pv, PassLaunch& pl) {
+// columns of x, once.  On stream4 beside the coming round (pl.inflight: finish_passes decides its problems), else in sequence here.
+// behind: a pass is in flight already -- this one queues behind it on stream4 (the loop has made sure it has the far-field form)
+int launch_pass(AsmCall& c, int pv, PassLaunch& pl, bool behind) {
   nnmpc_qp* h = c.h;
   hipStream_t s = c.s;
-  const AsmDev& a = c.a;
-  const int nprob = c.nprob;
   AsmDev& ap = pl.ap;                                  // the pass's arguments: the pending view, its round's window
   const int prev_rows = c.vrows[pv];
   set_view(h, ap, pv);
   ap.W = c.vW[pv]; ap.wrows = prev_rows;
-  // (ap.W is that round's window: those columns are in that round's XH rows already)
-  const int c0 = (ap.W < h->np && (h->np - ap.W) % 128 == 0) ? ap.W : 0;
-  pl.fused_c0 = ((h->np - c0) % 128 == 0 && !c.sw->no_fused_wide) ? c0 : -1;     // the fused kernel's 128-column tiles fit: check in the GEMM's epilogue
+  pl.view = pv;
+  int c0 = 0;
+  const nnmpc_qp::Far* ff = pass_form(c, pv, &c0, &pl.fused_c0);
   const int ntm = (prev_rows + 127) / 128, ntn = (h->np - c0) / 128;
-  const nnmpc_qp::Far* ff = nullptr;
-  if (c.lazy && pl.fused_c0 > 0 && !c.sw->no_farfield) {
-    for (const auto& f : h->far) if (f.W == c0) ff = &f;
-    if (!ff && h->far_missing.size() < 16 && std::find(h->far_missing.begin(), h->far_missing.end(), c0) == h->far_missing.end())
-      h->far_missing.push_back(c0);                // (the host wrapper may add the factors for this window: nnmpc_qp_farfield_missing)
-  }
-  const bool ovl = ff && c.overlap_on && h->view[1 - pv].rows > 0;
-  if (!ovl && c.wst.open && h->profiling && h->view[1 - pv].rows > 0) {
-    // statistics only: a pass in sequence is about to mark its problems while those of an overlapped pass are still uncounted
-    // -- the two may be priced differently: count the marks now (scans of the bins in the free view; every list and row they
-    // write is written again by the bins that follow this pass)
-    AsmDev af = a;
-    set_view(h, af, 1 - pv);
-    hipLaunchKernelGGL(asm_bins_a_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, af);
-    hipLaunchKernelGGL(asm_bins_b_k, dim3((nprob + 1023) / 1024), dim3(1024), 0, s, af);
-    if (int rc = read_counters(h)) return rc;
-    account(c, h->pin_cnt + (1 - pv) * ASM_NCNT);
-  }
+  if (c.lazy && pl.fused_c0 > 0 && !c.sw->no_farfield && !ff && h->far_missing.size() < 16 &&
+      std::find(h->far_missing.begin(), h->far_missing.end(), c0) == h->far_missing.end())
+    h->far_missing.push_back(c0);                  // (the host wrapper may add the factors for this window: nnmpc_qp_farfield_missing)
+  const int ov = pv ? 0 : 1;                           // the view a round beside this pass would run in
+  const bool ovl = ff && c.overlap_on && h->view[ov].rows > 0;
+  if (behind && !ovl) { set_error("launch_pass: a pass behind another one must have the far-field form"); return NNMPC_EINVAL; }
+  if (!ovl && c.wst.open && h->profiling && h->view[ov].rows > 0)   // (a pass in sequence after an overlapped one)
+    if (int rc = account_now(c, ov)) return rc;
   hipStream_t ps = ovl ? h->stream4 : s;
   if (ovl) {
     HIPCHK(hipEventRecord(h->ev_wfork, s));
@@ -1495,26 +1523,34 @@ int launch_pass(AsmCall& c, int pv, PassLaunch& pl) {
              h->np - c0, h->np, nullptr, 0, h->view[pv].kblk, nullptr, true);
     }
   }
-  c.wnext.view = pv; c.wnext.far_rp = far_rp; c.wnext.far_ksum = far_ksum; c.wnext.skip = ap.ff_skip; c.wnext.cols = h->np - c0; c.wnext.open = true;
+  pl.stat.view = pv; pl.stat.far_rp = far_rp; pl.stat.far_ksum = far_ksum; pl.stat.skip = ap.ff_skip; pl.stat.cols = h->np - c0; pl.stat.open = true;
   if (ovl) {
-    HIPCHK(hipEventRecord(h->ev_wide, ps));
+    HIPCHK(hipEventRecord(h->ev_wide[pv], ps));
     pl.inflight = true;
   } else {
     EvScope es(h, EV_UPDATE, 0.0);
     hipLaunchKernelGGL(asm_wide_k, dim3((prev_rows + 3) / 4), dim3(256), 0, s, ap, pl.fused_c0);
-    c.wst = c.wnext;
+    c.wst = pl.stat;
   }
   c.pend = -1; c.vrows[pv] = 0;
   return 0;
 }
-// The main stream joins the pass on stream4 and decides its problems (rule 1: after everything the round enqueued)
-int finish_pass(AsmCall& c, PassLaunch& pl) {
+// The main stream joins the passes on stream4, in launch order, and decides their problems (rule 1: after everything the iterations
+// beside them enqueued)
+int finish_passes(AsmCall& c, PassFifo& f) {
   nnmpc_qp* h = c.h;
-  HIPCHK(hipStreamWaitEvent(c.s, h->ev_wide, 0));
-  EvScope es(h, EV_UPDATE, 0.0);
-  hipLaunchKernelGGL(asm_wide_k, dim3((pl.ap.wrows + 3) / 4), dim3(256), 0, c.s, pl.ap, pl.fused_c0);
-  c.wst = c.wnext;
-  pl.inflight = false;
+  for (int i = 0; i < f.n; ++i) {
+    PassLaunch& pl = f.pl[i];
+    // (statistics only: the first pass's marks are counted before the second one adds its own; its view is free from here on)
+    if (i > 0 && c.wst.open && h->profiling)
+      if (int rc = account_now(c, f.pl[i - 1].view)) return rc;
+    HIPCHK(hipStreamWaitEvent(c.s, h->ev_wide[pl.view], 0));
+    EvScope es(h, EV_UPDATE, 0.0);
+    hipLaunchKernelGGL(asm_wide_k, dim3((pl.ap.wrows + 3) / 4), dim3(256), 0, c.s, pl.ap, pl.fused_c0);
+    c.wst = pl.stat;
+    pl.inflight = false;
+  }
+  f.n = 0;
   return 0;
 }
 
@@ -1657,7 +1693,11 @@ int window_gemms_and_update(AsmCall& c, int rv, int n64, int n32, const int* cnt
 }
 
 // Problems finished but not certified by the inverse-error bound, counted in the view a problem finished in (h->pin_cnt)
-int ndone(const nnmpc_qp* h) { return h->pin_cnt[ASM_CNT_DONE] + h->pin_cnt[ASM_NCNT + ASM_CNT_DONE]; }
+int ndone(const nnmpc_qp* h) {
+  int t = 0;
+  for (int v = 0; v < NVIEW; ++v) t += h->pin_cnt[v * ASM_NCNT + ASM_CNT_DONE];
+  return t;
+}
 // Certification with P itself (rows the inverse-error bound could not certify): q = tq x0 and px = x P; the status of the segment
 // read back (h->pin_st) and handed to the caller.  fb: the problems left for the PDIP path (status 3).
 // capped: the loop was left by the round cap -- the last counters are not final.
@@ -1678,9 +1718,9 @@ int certify_and_collect(AsmCall& c, bool capped, int32_t* st_dev, std::vector<in
   hipLaunchKernelGGL(asm_certify_k, dim3(nprob), dim3(256), 0, s, a, h->pscale);
   int* st = h->pin_st;
   HIPCHK(hipMemcpyAsync(st, h->asm_status, (size_t)nprob * sizeof(int), hipMemcpyDeviceToHost, s));
-  int* pin_its = h->pin_cnt + 2 * ASM_NCNT;
+  int* pin_its = h->pin_cnt + NVIEW * ASM_NCNT;
   if (h->profiling && c.pred_flops_per_it > 0.0) HIPCHK(hipMemcpyAsync(pin_its, h->pred_cnt + 1, 4, hipMemcpyDeviceToHost, s));
-  if (c.defer_cnt) HIPCHK(hipMemcpyAsync(h->pin_cnt, h->view[0].counters, 2 * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (c.defer_cnt) HIPCHK(hipMemcpyAsync(h->pin_cnt, h->view[0].counters, NVIEW * ASM_NCNT * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(stream_sync(s));
   if (c.defer_cnt) h->stats.asm_full_checks += ndone(h);
   if (h->profiling && c.pred_flops_per_it > 0.0) h->stats.asm_predict_flops += c.pred_flops_per_it * (double)*pin_its;
@@ -1777,8 +1817,8 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   // asm_update_k / asm_wide_k of the same round
   if (!guess_dev) HIPCHK(hipMemsetAsync(h->asm_st, 0, (size_t)nprob * h->n, s));   // bound states: asm_init_k writes the leading window only
   if (int rc = first_sets(c)) return rc;
-  memset(h->pin_cnt, 0, 2 * ASM_NCNT * sizeof(int));
-  HIPCHK(hipMemsetAsync(h->view[0].counters, 0, 2 * ASM_NCNT * sizeof(int), s));   // (both views' counters)
+  memset(h->pin_cnt, 0, NVIEW * ASM_NCNT * sizeof(int));
+  HIPCHK(hipMemsetAsync(h->view[0].counters, 0, NVIEW * ASM_NCNT * sizeof(int), s));   // (all views' counters)
   if (c.small)
     if (int rc = small_pass(c)) return rc;
   c.defer_cnt = c.tail_only && !sw.trace;
@@ -1789,16 +1829,17 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   c.carry_on = a.refine_later && a.pred_w && !c.tail_only && !env_carry_off();
   if (c.carry_on)
     if (int rc = h->res.slot(nnmpc_qp::SC_CARRY, &a.stash, (size_t)h->seg_max * ASM_MLDS * sizeof(double))) return rc;
-  c.vW[0] = c.vW[1] = h->np;
+  c.views3 = c.overlap_on && h->nview == NVIEW && !env_two_views();
+  for (int v = 0; v < NVIEW; ++v) c.vW[v] = h->np;
 
   // ---- The pass beside the round.  A far-field full-width pass does not wait on the main stream: asm_wide_t_k (+ asm_wide_tnorm_k) and
   // asm_wide_gemm_k run on stream4 over the rows of the view the last round ran in (the pending view, c.pend; its rows and window:
   // c.vrows, c.vW), while the problems that did NOT settle in that round -- known since its asm_update_k -- are counted and, if they
   // fit, run their next round (or the device tail) on the main stream in the other, free view (rv): its own rows of LAM / XH, its own
-  // counters and k-ranges.  Then the main stream waits for the pass and runs asm_wide_k (finish_pass).  Views swap roles from
+  // counters and k-ranges.  Then the main stream waits for the pass and runs asm_wide_k (finish_passes).  Views swap roles from
   // iteration to iteration.  Two rules keep this free of races:
   //  (1) asm_wide_k is the only kernel of the pass that writes `state` (ASM_WIDE -> RUN / CERT / DONE), and asm_count_k, the bins,
-  //      asm_update_k and asm_taillist_k scan `state` over all problems: finish_pass runs on the main stream after everything the
+  //      asm_update_k and asm_taillist_k scan `state` over all problems: finish_passes runs on the main stream after everything the
   //      round enqueued there and on its side streams (their joins come before the round's GEMMs: launch_multipliers).  Problems it
   //      sends back to ASM_RUN are found by the next iteration's count, which is why the loop goes on after an overlapped tail.
   //  (2) asm_wide_t_k / asm_wide_gemm_k write st / wflag / u_out / T only for rows with rowprob >= 0: problems in state ASM_WIDE, which
@@ -1806,52 +1847,75 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
   //      x_unc extension or the tail's gathered x_unc rows (extend_xunc: c.Wx, c.a.Wx) do not collide with it.  The dense, lazy and
   //      plain-GEMM forms of the pass keep the serial order (launch_pass leaves pl.inflight false).
   // The size-class lists, ranks and chunk totals (binlist, biglist, lrank, ctot) live from a round's bins to its multiplier kernels,
-  // all ordered on the main stream, and the pass reads none of them: both views share them.
+  // all ordered on the main stream, and the pass reads none of them: all views share them.
+  // ---- A second iteration beside the same pass (the third view).  After a round that ran beside a pass the loop does not join that
+  // pass at once: the round's own pass, if it has one, is launched on stream4 BEHIND the first (stream order serialises them; each has
+  // its completion event, h->ev_wide[view]), the problems still running are counted in the view neither pass holds and run their
+  // next round or the tail there, and only then are the passes finished, in launch order (finish_passes).  Nothing in that iteration
+  // needs the first pass's outcome: its problems are ASM_RUN since the round's asm_update_k, the passes' are ASM_WIDE, and whatever an
+  // asm_wide_k sends back is found by the count after it.  Both rules hold as they stand, for either pass.  At most one such
+  // iteration per first pass (`chained`), and only behind a pass of the far-field form; after an overlapped tail nothing runs any
+  // more, so the loop joins at once as before.  NNMPC_VIEWS=2 (read per call) restores the order of two views.
   const int round_cap = 2 * a.max_rounds + 2;
   int rounds = 0;
+  PassFifo fly;
+  bool chained = false;                                  // this iteration is the second one beside fly.pl[0]
   for (; !c.tail_only && rounds < round_cap; ++rounds) {
     const int pv = c.pend;
-    PassLaunch pl = {a, -1, false};
-    if (pv >= 0)
-      if (int rc = launch_pass(c, pv, pl)) return rc;
+    if (pv >= 0) {
+      PassLaunch& pl = fly.pl[fly.n];
+      pl = PassLaunch{a, -1, false, pv, WideStat{false, 0, 0, 0, 0, 0.0}};
+      if (int rc = launch_pass(c, pv, pl, fly.n > 0)) return rc;
+      if (pl.inflight) fly.n += 1;
+    }
     if (!a.pred_w) a.refine_later = 0;                   // (only behind predicted first sets: from other starts the f32 rounds are many and their sets still move)
     a.refine = a.refine_later && rounds >= 1;            // round 0 stays the plain f32 screen
     // ... which keeps the corrected multipliers of the sets it leaves as they are: round 1 copies them (a flag asm_update_k raised
     // in round 0 is read by round 1's count and bins, cleared by its asm_carry_copy, and by nobody after that)
     a.carry = c.carry_on ? (rounds == 0 ? 1 : (rounds == 1 ? 2 : 0)) : 0;
     a.kref = c.kprev;
-    // the round's view: beside a pass the one it does not occupy, view 0 otherwise
-    int rv = pl.inflight ? 1 - pv : 0;
+    // the round's view: beside passes the first one none of them occupies, view 0 otherwise
+    int rv = 0;
+    while (fly.n && fly.holds(rv)) ++rv;
+    if (rv >= h->nview) { set_error("solve_segment_asm: no free row space beside %d passes", fly.n); return NNMPC_EINVAL; }
     int n64 = 0, n32 = 0, nrun = 0;
     const int* cnt = nullptr;
     for (bool recount = false;; recount = true) {
       if (int rc = count_round(c, rv, recount)) return rc;
       cnt = h->pin_cnt + rv * ASM_NCNT;
       n64 = cnt[ASM_CNT_ROWS64]; n32 = cnt[ASM_CNT_ROWS32]; nrun = n64 + n32;   // solved in fp64 / f32 this round
-      if (!pl.inflight || nrun <= h->view[rv].rows) break;
+      if (!fly.n || nrun <= h->view[rv].rows) break;
       // more problems still running than the free view has rows (the early rounds of a call without predicted sets): the count was
-      // hidden behind the pass but is of no use -- finish the pass and count again, in view 0, as the serial order would have
-      if (int rc = finish_pass(c, pl)) return rc;
+      // hidden behind the pass but is of no use -- finish the passes and count again, in view 0, as the serial order would have
+      if (int rc = finish_passes(c, fly)) return rc;
+      chained = false;
       rv = 0;
     }
+    const int beside = fly.n;                            // passes this iteration runs beside
     c.kprev = cnt[ASM_CNT_LAST];
-    if (sw.trace) trace_round(rounds, pl.inflight, cnt);
+    if (sw.trace) trace_round(rounds, beside, cnt);
     if (nrun == 0) {
-      if (!pl.inflight) break;
-      // nothing left to run beside the pass; asm_wide_k may still send problems back: the next count decides (this was no round)
-      if (int rc = finish_pass(c, pl)) return rc;
+      if (!beside) break;
+      // nothing left to run beside the passes; asm_wide_k may still send problems back: the next count decides (this was no round)
+      if (int rc = finish_passes(c, fly)) return rc;
+      chained = false;
       --rounds;
       continue;
     }
+    if (beside) {
+      // (a pass is counted once, by the first iteration that runs beside it: the first pass of a chain was counted by its round)
+      h->stats.asm_overlapped_passes += chained ? beside - 1 : 1;
+      h->stats.asm_shared_passes += chained;
+    }
     if (nrun <= std::min(h->asm_pool, sw.tail_max) && (rounds >= (a.pred_w ? 2 : 6) || c.small)) {
-      if (int rc = run_tail(c, rv, nrun, rounds, pl.inflight)) return rc;
-      if (!pl.inflight) {
+      if (int rc = run_tail(c, rv, nrun, rounds, beside > 0)) return rc;
+      if (!beside) {
         rounds = 0;                                       // (regular exit: the counters just read are final)
         break;
       }
       a.Wx = c.Wx;                                        // (x_unc beyond Wx exists for the tail's problems only)
-      if (int rc = finish_pass(c, pl)) return rc;
-      h->stats.asm_overlapped_passes += 1;
+      if (int rc = finish_passes(c, fly)) return rc;
+      chained = false;
       continue;                                           // (the next count ends the loop, or finds what asm_wide_k sent back)
     }
     h->stats.asm_rounds += 1;
@@ -1864,18 +1928,26 @@ int solve_segment_asm(nnmpc_qp* h, int nprob, const double* x0_dev, const double
       EvScope es(h, EV_GEMM, 2.0 * (a.W - c.Wx) * (double)h->ka * nprob);
       extend_xunc(c, a.W, c.segp, false);
     }
-    if (int rc = launch_multipliers(c, cnt, pl.inflight)) return rc;
+    if (int rc = launch_multipliers(c, cnt, beside > 0)) return rc;
     if (sw.trace && a.carry)
       if (int rc = trace_carry(c, rounds, cnt)) return rc;
     if (int rc = window_gemms_and_update(c, rv, n64, n32, cnt)) return rc;
     c.vW[rv] = a.W;
     c.vrows[rv] = a.W < h->n ? n64 : 0;                  // fp64 rows of this round: the problems that settled in them await the full-width check
     c.pend = c.vrows[rv] ? rv : -1;
-    if (pl.inflight) {
-      if (int rc = finish_pass(c, pl)) return rc;
-      h->stats.asm_overlapped_passes += 1;
+    if (beside) {
+      // once per first pass: go round again without joining it, if the third view is there and this round's pass can queue behind it
+      int c0 = 0, fused_c0 = -1;
+      if (!chained && beside == 1 && c.views3 && (c.pend < 0 || pass_form(c, c.pend, &c0, &fused_c0))) {
+        chained = true;
+        continue;
+      }
+      if (int rc = finish_passes(c, fly)) return rc;
+      chained = false;
     }
   }
+  if (fly.n)                                             // (the round cap ended a chain)
+    if (int rc = finish_passes(c, fly)) return rc;
   std::vector<int> fb;
   if (int rc = certify_and_collect(c, rounds >= round_cap, st_dev, fb)) return rc;
   return pdip_fallback(c, fb, x0_dev, st_dev);
@@ -1954,7 +2026,7 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   if ((size_t)(h->np + 5 * h->NB) * 4 > 96 * 1024) { set_error("n too large for the LDS-resident solve vector"); return NNMPC_EINVAL; }
   for (hipStream_t* st : {&h->stream, &h->stream2, &h->stream3, &h->stream4})
     if (int rc = res.stream(st)) return rc;
-  for (hipEvent_t* ev : {&h->ev_fork, &h->ev_join3, &h->ev_join4, &h->ev_join, &h->ev_wfork, &h->ev_wide})
+  for (hipEvent_t* ev : {&h->ev_fork, &h->ev_join3, &h->ev_join4, &h->ev_join, &h->ev_wfork, &h->ev_wide[0], &h->ev_wide[1], &h->ev_wide[2]})
     if (int rc = res.event(ev, hipEventDisableTiming)) return rc;
   HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG_LDS));
   HIPCHK(hipFuncSetAttribute((const void*)asm_lambda_reg32_k, hipFuncAttributeMaxDynamicSharedMemorySize, ASM_REG32_LDS));
@@ -2005,7 +2077,7 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   A_(h->q64_all, G * np); A_(h->uunc_all, G * np);
   A_(h->lb_d, G * nu); A_(h->ub_d, G * nu);
   A_(h->in_stage, G * n_aug);
-  if (int rc = res.pinned_alloc(&h->pin_cnt, 2 * ASM_NCNT + 4)) return rc;
+  if (int rc = res.pinned_alloc(&h->pin_cnt, nnmpc_qp::ASM_NVIEW * ASM_NCNT + 4)) return rc;
   if (int rc = res.pinned_alloc(&h->pin_st, G)) return rc;
   A_(d.lb64, (size_t)S * nu); A_(d.ub64, (size_t)S * nu);
   A_(d.slot_prob, S); A_(d.age, S); A_(d.next_prob, 1);
@@ -2017,7 +2089,7 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
   A_(h->asm_xunc, G * np); A_(h->asm_x, G * np); A_(v0.lam, G * np); A_(v0.xh, G * np);
   A_(v0.xhw, (G + 256) * np); A_(v0.rowprob, G + 256); A_(h->asm_wflag, G); A_(h->asm_wmark, G);
   A_(v0.tnorm, G + 128 * (ASM_NKG + 1)); A_(v0.tslack, G + 128 * (ASM_NKG + 1));
-  A_(h->asm_st, G * n); A_(h->asm_state, G); A_(h->asm_rounds, G); A_(v0.counters, 2 * ASM_NCNT);
+  A_(h->asm_st, G * n); A_(h->asm_state, G); A_(h->asm_rounds, G); A_(v0.counters, nnmpc_qp::ASM_NVIEW * ASM_NCNT);
   A_(h->asm_biglist, G); A_(h->asm_status, G); A_(h->asm_binlist, (size_t)(ASM_NLIST + 4) * G);
   A_(h->asm_idxg, G * o.asm_max_active); A_(h->asm_mg, G); A_(h->asm_row, G); A_(h->asm_lrank, G); A_(h->asm_ctot, ((G + 1023) / 1024) * ASM_NSCAN); A_(h->asm_prec, G); A_(h->asm_redo, G); A_(h->asm_rowk, G); A_(h->asm_cflag, G); A_(h->asm_carrylist, G); A_(v0.lam32, G * np); A_(v0.xh32, G * np); A_(h->asm_alpha, G); A_(h->asm_ninf, G); A_(h->asm_hi, G); A_(v0.kblk, 2 * (G / 64 + 2)); A_(h->asm_work, 3 * G);
   v0.rows = (int)G;
@@ -2036,8 +2108,28 @@ int nnmpc_qp_create(nnmpc_qp** out, int32_t n, int32_t nu, int32_t n_aug, const 
       A_(v1.tnorm, Rr + 128 * (ASM_NKG + 1)); A_(v1.tslack, Rr + 128 * (ASM_NKG + 1)); A_(v1.rowprob, Rr + 256); A_(v1.kblk, 2 * (G / 64 + 2));
       v1.counters = v0.counters + ASM_NCNT;
       v1.rows = (int)R;
+      h->nview = 2;
+      // the third row space, sized like the second (another 0.47 GB at the CDU segment): the iteration after the round beside a
+      // pass runs in it, beside the same pass.  A handle that cannot have it works with two views.
+      nnmpc_qp::AsmView v2;
+      const bool ok = !res.alloc(&v2.lam, Rr * np) && !res.alloc(&v2.xh, Rr * np) && !res.alloc(&v2.xhw, (Rr + 256) * np) &&
+                      !res.alloc(&v2.lam32, Rr * np) && !res.alloc(&v2.xh32, Rr * np) &&
+                      !res.alloc(&v2.tnorm, Rr + 128 * (ASM_NKG + 1)) && !res.alloc(&v2.tslack, Rr + 128 * (ASM_NKG + 1)) &&
+                      !res.alloc(&v2.rowprob, Rr + 256) && !res.alloc(&v2.kblk, 2 * (G / 64 + 2));
+      if (ok) {
+        v2.counters = v0.counters + 2 * ASM_NCNT;
+        v2.rows = (int)R;
+        h->view[2] = v2;
+        h->nview = 3;
+      } else {
+        for (void* p : {(void*)v2.lam, (void*)v2.xh, (void*)v2.xhw, (void*)v2.lam32, (void*)v2.xh32, (void*)v2.tnorm, (void*)v2.tslack,
+                        (void*)v2.rowprob, (void*)v2.kblk})
+          (void)res.give_back(p);
+        (void)hipGetLastError();                    // (the failed hipMalloc is not an error of this handle)
+      }
     }
   }
+  static_assert(nnmpc_qp::ASM_NVIEW == 3, "the views made here, their events above");
 #undef A_
   d.n = n; d.np = np; d.nu = nu; d.slots = S; d.words = h->words;
   d.max_ipm = o.max_ipm_iters; d.max_polish = o.max_polish_rounds; d.max_refine = o.max_refine;
