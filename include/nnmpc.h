@@ -484,6 +484,31 @@ int nnmpc_train_create_tan(nnmpc_train** out, int32_t nlayers, const int32_t* di
  * nnmpc_train_set_data drops them.  Non-finite entries are not rejected and not hidden: a NaN gives a NaN tan_mse and L. */
 int nnmpc_train_set_tangents(nnmpc_train* h, int32_t n, const double* dx, const double* duprev,
                              const double* t, int32_t ptr_kind);
+/* The tangent loss with several directions per row, and over the whole network input.
+ *   dirs = D directions per dataset row, each with its own target: both means of L run over B D nu, and a batch stacks the D
+ *     tangent blocks behind ONE primal pair, (2 + D) Bp rows instead of the 3 D Bp of a dataset that repeats each row D times.
+ *   whole_input = 1: a direction is d = [dx, (duprev), dxs, dus].  pred = us + N(x, uprev, xs, us) - N(xs, us, xs, us) depends on
+ *     xs and us through both passes, so pass 2 carries tangents too, a''_0 = [dxs, (dus), dxs, dus] under the masks of pass 2, and
+ *     J d = dus + (a'_{L-1} W_L - a''_{L-1} W_L) in f32 in that order: (2 + 2D) Bp stacked rows.  The matching target is the
+ *     change of the MPC's absolute first move, dus + du0 along train.whole_input_perturbation (nnmpc_qp_sensitivity with dlb / dub).
+ * Everything else as nnmpc_train_create_tan, which is dirs = 1, whole_input = 0 (such a handle computes its bytes).  dirs
+ * outside 1 .. NNMPC_TAN_MAX_DIRS, whole_input neither 0 nor 1, or form != NNMPC_NN_STRUCTURED: NNMPC_EINVAL before a device
+ * is looked for.  set_tan_weight, grad, step, epoch, eval, last_losses and last_ms serve the handle with their meaning there;
+ * a step keeps its 6 nlayers launches. */
+#define NNMPC_TAN_MAX_DIRS 16
+int nnmpc_train_create_tan_ex(nnmpc_train** out, int32_t nlayers, const int32_t* dims,
+                              const double* const* W, const double* const* b, int32_t nx, int32_t nu,
+                              int32_t with_uprev, int32_t max_batch, double lr, double beta1,
+                              double beta2, double eps, int32_t form, int32_t dirs, int32_t whole_input);
+/* nnmpc_train_set_tangents for such a handle: dx n x dirs x nx, duprev n x dirs x nu (NULL unless with_uprev), dxs n x dirs x nx
+ * and dus n x dirs x nu (required on a whole-input handle, NULL otherwise), t n x dirs x nu.  NNMPC_EINVAL: dirs differs from
+ * the handle's, a plain handle, no dataset yet, n != the dataset's rows, a with-uprev network without duprev, dxs / dus
+ * missing on a whole-input handle or given on another.  nnmpc_train_set_tangents itself serves only a handle with dirs == 1
+ * and whole_input == 0; on any other tangent handle it returns NNMPC_EINVAL and names this function.  Non-finite entries are
+ * not rejected and not hidden. */
+int nnmpc_train_set_tangents_ex(nnmpc_train* h, int32_t n, int32_t dirs, const double* dx,
+                                const double* duprev, const double* dxs, const double* dus,
+                                const double* t, int32_t ptr_kind);
 /* The weight w of the tangent term: finite and >= 0, on a tangent handle (NNMPC_EINVAL otherwise).  With w > 0 and no
  * tangents, grad, step, epoch and eval return NNMPC_EINVAL before any launch. */
 int nnmpc_train_set_tan_weight(nnmpc_train* h, double w);

@@ -70,6 +70,7 @@ EXPORTS = ["nnmpc_last_error", "nnmpc_qp_create", "nnmpc_qp_destroy", "nnmpc_qp_
            "nnmpc_train_snapshot", "nnmpc_train_restore", "nnmpc_train_last_ms", "nnmpc_train_dw_slices",
            "nnmpc_train_padding_max",
            "nnmpc_train_create_tan", "nnmpc_train_set_tangents", "nnmpc_train_set_tan_weight", "nnmpc_train_last_losses",
+           "nnmpc_train_create_tan_ex", "nnmpc_train_set_tangents_ex",
            "nnmpc_train_group_create", "nnmpc_train_group_destroy", "nnmpc_train_group_set_data",
            "nnmpc_train_group_epoch", "nnmpc_train_group_eval", "nnmpc_train_group_get_weights",
            "nnmpc_train_group_set_weights", "nnmpc_train_group_snapshot", "nnmpc_train_group_restore",
@@ -186,6 +187,10 @@ def load():
     lib.nnmpc_train_set_tan_weight.argtypes = [vp, f64]
     lib.nnmpc_train_last_losses.restype = i32
     lib.nnmpc_train_last_losses.argtypes = [vp, pf64, pf64]
+    lib.nnmpc_train_create_tan_ex.restype = i32                   # nnmpc_train_create_tan + (dirs, whole_input)
+    lib.nnmpc_train_create_tan_ex.argtypes = lib.nnmpc_train_create_ex.argtypes + [i32, i32]
+    lib.nnmpc_train_set_tangents_ex.restype = i32                 # (h, n, dirs, dx, duprev, dxs, dus, t, ptr_kind)
+    lib.nnmpc_train_set_tangents_ex.argtypes = [vp, i32, i32, dp, dp, dp, dp, dp, i32]
     # the sweep in one handle: each entry replaces G calls of the nnmpc_train_* function named beside it
     lib.nnmpc_train_group_create.restype = i32                    # nnmpc_train_create
     lib.nnmpc_train_group_create.argtypes = [C.POINTER(vp), i32, i32, pi32, pdp, pdp, i32, i32, i32, i32, f64, f64, f64, f64]

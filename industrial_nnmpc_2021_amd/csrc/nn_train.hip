@@ -34,6 +34,12 @@
 //   backward    dW over 3Bp rows; db over the first 2Bp (tangent rows carry no bias gradient);    (gemm_tn_f32_k, train_colsum_k)
 //               dA over 3Bp rows, the mask row of a tangent row being its pass-1 row              (gemm_nt_mask_wrap_k)
 // With w == 0 the handle runs the plain step, launch for launch.
+//
+// nnmpc_train_create_tan_ex: D directions per row and, whole_input, directions over [dx, (duprev), dxs, dus].  The D tangent
+// blocks of pass 1 follow the two primal blocks and, whole input, D of pass 2 follow those: M = (2 + D) Bp or (2 + 2D) Bp.
+// Still 6 nlayers launches: the gather and the output kernel take D and the form, the hidden forward is a fan -- a primal
+// row tile and its D tangent tiles in one workgroup (gemm_nt_f32_fan_k; whole input: the pass-2 tiles are fans too) --, and
+// the mask of a row tile in block k >= 2 is the same tile of block (k - 2) / D.  D = 1 in [dx, (duprev)] launches the pair.
 #include "gemm_kernels.h"
 #include "tile_gemm_tn.h"
 #include "nn_train_host.h"
@@ -72,29 +78,31 @@ __global__ __launch_bounds__(256) void train_output1_k(float* __restrict__ dz, c
   train_output1_block(dz, o, ldo, B, nu, head_relu, u, idx, first, gscale, partial, blockIdx.x);
 }
 
-// The tangent loss: all three row blocks; the plain output plus the tangent rows; both sums.
+// The tangent loss: every row block; the plain output plus the tangent rows; both sums.
 __global__ __launch_bounds__(128) void train_gather_tan_k(float* __restrict__ in, int ldk, int Bp, int B, int nx, int nu,
-                                                          int with_uprev, const float* __restrict__ x,
+                                                          int with_uprev, int D, int whole, const float* __restrict__ x,
                                                           const float* __restrict__ uprev, const float* __restrict__ xs,
                                                           const float* __restrict__ us, const float* __restrict__ tdx,
-                                                          const float* __restrict__ tdup, const int* __restrict__ idx, int first) {
+                                                          const float* __restrict__ tdup, const float* __restrict__ tdxs,
+                                                          const float* __restrict__ tdus, const int* __restrict__ idx, int first) {
   train_gather_rows(in, ldk, Bp, B, nx, nu, with_uprev, x, uprev, xs, us, idx, first, blockIdx.x, gridDim.x);
-  train_gather_tan_rows(in, ldk, Bp, B, nx, nu, with_uprev, tdx, tdup, idx, first, blockIdx.x, gridDim.x);
+  train_gather_tan_rows(in, ldk, Bp, B, nx, nu, with_uprev, D, whole, tdx, tdup, tdxs, tdus, idx, first, blockIdx.x, gridDim.x);
 }
 
 __global__ __launch_bounds__(256) void train_output_tan_k(float* __restrict__ dz, const float* __restrict__ o, int ldo, int Bp,
-                                                          int B, int nu, const float* __restrict__ us,
+                                                          int B, int nu, int D, int whole, const float* __restrict__ us,
                                                           const float* __restrict__ u, const float* __restrict__ t,
-                                                          const int* __restrict__ idx, int first, float gscale, float gw,
-                                                          double* __restrict__ partial, double* __restrict__ partial_tan) {
-  train_output_tan_block(dz, o, ldo, Bp, B, nu, us, u, t, idx, first, gscale, gw, partial, partial_tan, blockIdx.x);
+                                                          const float* __restrict__ tdus, const int* __restrict__ idx, int first,
+                                                          float gscale, float gw, double* __restrict__ partial,
+                                                          double* __restrict__ partial_tan) {
+  train_output_tan_block(dz, o, ldo, Bp, B, nu, D, whole, us, u, t, tdus, idx, first, gscale, gw, partial, partial_tan, blockIdx.x);
 }
 
 __global__ void train_loss_finish_tan_k(const double* __restrict__ partial, const double* __restrict__ partial_tan, int np,
-                                        double scale, double weight, double w, double* __restrict__ loss,
+                                        double scale, double scale_tan, double weight, double w, double* __restrict__ loss,
                                         double* __restrict__ acc) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  train_loss_finish_tan(partial, partial_tan, np, scale, weight, w, loss, acc);
+  train_loss_finish_tan(partial, partial_tan, np, scale, scale_tan, weight, w, loss, acc);
 }
 
 // Hidden-layer forward under the tangent loss.  Grid (N/NB, 2Bp/NB): the low blockIdx.y are the pass-1 row tiles, each with
@@ -105,6 +113,18 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_pair_k(float* __restrict__ C,
                                                           const float* __restrict__ bias, int Bp) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if ((int)blockIdx.y < Bp / NB) train_fwd_pair_tile<NB>(C, ldc, A, lda, B, ldb, K, bias, Bp, blockIdx.y, blockIdx.x, lds);
+  else train_fwd_tile<NB, true, true>(C, ldc, A, lda, B, ldb, K, bias, blockIdx.y, blockIdx.x, lds);
+}
+
+// The same with D directions per row.  Same grid: a pass-1 row tile is a fan of 1 + D tiles, its tangents from row 2 Bp on; a
+// pass-2 row tile is the plain tile, or (whole input) a fan whose tangents start D blocks further down, at (2 + D) Bp.
+template <int NB>
+__global__ __launch_bounds__(256) void gemm_nt_f32_fan_k(float* __restrict__ C, size_t ldc, const float* __restrict__ A,
+                                                         size_t lda, const float* __restrict__ B, size_t ldb, int K,
+                                                         const float* __restrict__ bias, int Bp, int D, int whole) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  if ((int)blockIdx.y < Bp / NB) train_fwd_fan_tile<NB>(C, ldc, A, lda, B, ldb, K, bias, Bp, D, 2 * Bp, blockIdx.y, blockIdx.x, lds);
+  else if (whole) train_fwd_fan_tile<NB>(C, ldc, A, lda, B, ldb, K, bias, Bp, D, (1 + D) * Bp, blockIdx.y, blockIdx.x, lds);
   else train_fwd_tile<NB, true, true>(C, ldc, A, lda, B, ldb, K, bias, blockIdx.y, blockIdx.x, lds);
 }
 
@@ -131,14 +151,16 @@ __global__ __launch_bounds__(256) void gemm_nt_mask_k(float* __restrict__ C, siz
   train_nt_mask_tile<NB>(C, ldc, A, lda, B, ldb, K, act, blockIdx.x, blockIdx.y, lds);
 }
 
-// gemm_nt_mask_k over the 3Bp rows of the tangent loss: a row tile at or above `wrap` = 2Bp takes its mask from the
-// activation tile `wrap` rows up, the pass-1 rows its tangents belong to (tiles never straddle: wrap is a multiple of 128).
+// gemm_nt_mask_k over the stacked rows of the tangent loss: a row tile in block k >= 2 (blocks of Bp rows) takes its mask from
+// the same tile of block (k - 2) / D, the primal rows its tangents belong to: pass 1 for the first D tangent blocks, pass 2
+// for the D behind them (tiles never straddle blocks: Bp is a multiple of 128).
 template <int NB>
 __global__ __launch_bounds__(256) void gemm_nt_mask_wrap_k(float* __restrict__ C, size_t ldc, const float* __restrict__ A,
                                                            size_t lda, const float* __restrict__ B, size_t ldb, int K,
-                                                           const float* __restrict__ act, int wrap) {
+                                                           const float* __restrict__ act, int Bp, int D) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const float* mask = (int)blockIdx.y * NB >= wrap ? act - (size_t)wrap * ldc : act;
+  const int k = (int)blockIdx.y * NB / Bp;
+  const float* mask = k >= 2 ? act - (size_t)(k - (k - 2) / D) * Bp * ldc : act;
   train_nt_mask_tile<NB>(C, ldc, A, lda, B, ldb, K, mask, blockIdx.x, blockIdx.y, lds);
 }
 
@@ -189,6 +211,13 @@ void launch_fwd_pair(hipStream_t s, float* C, size_t ldc, const float* A, size_t
                      C, ldc, A, lda, Wt, ldb, K, bias, Bp);
 }
 
+template <int NB>
+void launch_fwd_fan(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda, const float* Wt, size_t ldb, int Bp, int N,
+                    int K, const float* bias, int D, int whole) {
+  hipLaunchKernelGGL((gemm_nt_f32_fan_k<NB>), dim3(N / NB, 2 * Bp / NB), dim3(256), TileCfg<NB>::LDS_FLOATS * 4, s,
+                     C, ldc, A, lda, Wt, ldb, K, bias, Bp, D, whole);
+}
+
 template <int NB, bool RELU, bool BIAS>
 void launch_fwd(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda, const float* Wt, size_t ldb, int M, int N,
                 int K, const float* bias) {
@@ -199,19 +228,21 @@ void launch_fwd(hipStream_t s, float* C, size_t ldc, const float* A, size_t lda,
 // Gather, forward, output kernel and (backward) the gradient planes of one batch on the handle's stream; no host wait.
 // idx: device row list (nullptr: rows first .. first + B - 1).  The loss goes to the network's loss word = loss_scale * sum
 // of squares, and acc += acc_w * that.  With the tangent term in the loss (tan_active) every launch is its tangent variant
-// over M = 3Bp rows, the loss words are L, mse, tan_mse and acc[0..2] take all three.
+// over M = (2 + D) Bp (whole input: (2 + 2D) Bp) rows, the loss words are L, mse, tan_mse and acc[0..2] take all three.
 int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backward, double loss_scale, double acc_w, size_t set) {
   TrainCommon& c = h->c;
   const GMember& mem = h->m.mem;
   hipStream_t s = c.stream;
   const bool tan = tan_active(c);
-  const int L = c.L, Bp = pad128_host(B), M = train_rows_tan(c.form, Bp, tan);
+  const int D = c.tan_dirs, whole = c.tan_whole;
+  const bool fan = D != 1 || whole;                        // D = 1 in [dx, (duprev)] keeps the pair launch
+  const int L = c.L, Bp = pad128_host(B), M = train_rows_tan(c.form, Bp, tan, D, whole);
   const bool un = c.form != NNMPC_NN_STRUCTURED, hrelu = c.form == NNMPC_NN_UNSTD_RELU;
   EvSet e;
   if (int rc = ev_set(c, set, &e)) return rc;
   if (tan)
     hipLaunchKernelGGL(train_gather_tan_k, dim3(std::min(Bp, 2048)), dim3(128), 0, s, h->m.lay[0].ain, h->m.lay[0].K, Bp, B, c.nx, c.nu,
-                       c.with_uprev, c.dx, c.dup, c.dxs, c.dus, c.tdx, c.tdup, idx, first);
+                       c.with_uprev, D, whole, c.dx, c.dup, c.dxs, c.dus, c.tdx, c.tdup, c.tdxs, c.tdus, idx, first);
   else if (un)
     hipLaunchKernelGGL(train_gather1_k, dim3(std::min(Bp, 2048)), dim3(128), 0, s, h->m.lay[0].ain, h->m.lay[0].K, Bp, B, c.nx, c.nu,
                        c.with_uprev, c.dx, c.dup, c.dxs, c.dus, idx, first);
@@ -223,7 +254,10 @@ int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backwar
     const GLayer& d = h->m.lay[l];
     const int K = d.K, N = d.N;
     const bool last = l == L - 1;
-    if (tan && !last) {
+    if (tan && !last && fan) {
+      if (N % 128 == 0) launch_fwd_fan<128>(s, d.aout, N, d.ain, K, d.Wt, K, Bp, N, K, d.b, D, whole);
+      else launch_fwd_fan<64>(s, d.aout, N, d.ain, K, d.Wt, K, Bp, N, K, d.b, D, whole);
+    } else if (tan && !last) {
       if (N % 128 == 0) launch_fwd_pair<128>(s, d.aout, N, d.ain, K, d.Wt, K, Bp, N, K, d.b);
       else launch_fwd_pair<64>(s, d.aout, N, d.ain, K, d.Wt, K, Bp, N, K, d.b);
     } else if (N % 128 == 0) {
@@ -244,7 +278,7 @@ int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backwar
   double* partial_tan = mem.partial + c.cap_batch / 64;
   if (tan)
     hipLaunchKernelGGL(train_output_tan_k, dim3(Bp / 64), dim3(256), 0, s, backward ? mem.dz[0] : nullptr, head.aout, head.N, Bp, B,
-                       c.nu, c.dus, c.du, c.tt, idx, first, (float)gs, (float)(gs * c.tan_w), mem.partial, partial_tan);
+                       c.nu, D, whole, c.dus, c.du, c.tt, c.tdus, idx, first, (float)gs, (float)(gs / D * c.tan_w), mem.partial, partial_tan);
   else if (un)
     hipLaunchKernelGGL(train_output1_k, dim3(Bp / 64), dim3(256), 0, s, backward ? mem.dz[0] : nullptr, head.aout, head.N, B,
                        c.nu, hrelu ? 1 : 0, c.du, idx, first, (float)gs, mem.partial);
@@ -252,7 +286,7 @@ int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backwar
     hipLaunchKernelGGL(train_output_k, dim3(Bp / 64), dim3(256), 0, s, backward ? mem.dz[0] : nullptr, head.aout, head.N, Bp, B,
                        c.nu, c.dus, c.du, idx, first, (float)gs, mem.partial);
   if (tan)
-    hipLaunchKernelGGL(train_loss_finish_tan_k, dim3(1), dim3(64), 0, s, mem.partial, partial_tan, Bp / 64, loss_scale, acc_w, c.tan_w,
+    hipLaunchKernelGGL(train_loss_finish_tan_k, dim3(1), dim3(64), 0, s, mem.partial, partial_tan, Bp / 64, loss_scale, loss_scale / D, acc_w, c.tan_w,
                        mem.loss, mem.acc);
   else
     hipLaunchKernelGGL(train_loss_finish_k, dim3(1), dim3(64), 0, s, mem.partial, Bp / 64, loss_scale, acc_w, mem.loss, mem.acc);
@@ -277,13 +311,13 @@ int enqueue_batch(nnmpc_train* h, int B, const int* idx, int first, bool backwar
                            d.planes, plane, (size_t)K, dZ, (size_t)N, d.ain, (size_t)K, M, slice_rows);
       if (has_bias(c.form, L, l))
         hipLaunchKernelGGL(train_colsum_k, dim3(N / 64, train_rows(c.form, Bp) / 128), dim3(256), 0, s, d.bplanes, dZ, N);   // never the tangent rows
-      if (l > 0 && tan) {                                    // the same over 3Bp rows, a tangent row masked by its pass-1 row
+      if (l > 0 && tan) {                                    // the same over M rows, a tangent row masked by the primal row it belongs to
         if (K % 128 == 0)
           hipLaunchKernelGGL(gemm_nt_mask_wrap_k<128>, dim3(K / 128, M / 128), dim3(256), TileCfg<128>::LDS_FLOATS * 4, s,
-                             mem.dz[cur ^ 1], (size_t)K, dZ, (size_t)N, d.Wk, (size_t)N, N, d.ain, 2 * Bp);
+                             mem.dz[cur ^ 1], (size_t)K, dZ, (size_t)N, d.Wk, (size_t)N, N, d.ain, Bp, D);
         else
           hipLaunchKernelGGL(gemm_nt_mask_wrap_k<64>, dim3(K / 64, M / 64), dim3(256), TileCfg<64>::LDS_FLOATS * 4, s,
-                             mem.dz[cur ^ 1], (size_t)K, dZ, (size_t)N, d.Wk, (size_t)N, N, d.ain, 2 * Bp);
+                             mem.dz[cur ^ 1], (size_t)K, dZ, (size_t)N, d.Wk, (size_t)N, N, d.ain, Bp, D);
         cur ^= 1;
       } else if (l > 0) {                                    // dZ_{l-1} [M][K] = (dZ_l [M][N] Wk_l [K][N]') * mask(A_l input = ain)
         if (K % 128 == 0)
@@ -342,10 +376,13 @@ int nnmpc_train_destroy(nnmpc_train* h) {
 // The create entry points; `who` is the one that was called.  tan: a tangent handle (nnmpc_train_create_tan).
 static int train_create(const char* who, nnmpc_train** out, int32_t nlayers, const int32_t* dims, const double* const* W,
                         const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev, int32_t max_batch,
-                        double lr, double beta1, double beta2, double eps, int32_t form, bool tan = false) {
+                        double lr, double beta1, double beta2, double eps, int32_t form, bool tan = false, int32_t dirs = 1,
+                        int32_t whole_input = 0) {
   GUARD_BEGIN
   if (!out || nlayers < 1 || !dims || !W || !b || nx <= 0 || nu <= 0 || max_batch < 1) { set_error("%s: bad arguments", who); return NNMPC_EINVAL; }
   if (int rc = check_form(who, form)) return rc;
+  if (dirs < 1 || dirs > NNMPC_TAN_MAX_DIRS) { set_error("%s: %d directions per row (1 .. NNMPC_TAN_MAX_DIRS = %d)", who, dirs, NNMPC_TAN_MAX_DIRS); return NNMPC_EINVAL; }
+  if (whole_input != 0 && whole_input != 1) { set_error("%s: whole_input %d (0 or 1)", who, whole_input); return NNMPC_EINVAL; }
   if (tan && form != NNMPC_NN_STRUCTURED) { set_error("%s: form %d: the tangent loss is built for the structured form only (NNMPC_NN_STRUCTURED)", who, form); return NNMPC_EINVAL; }
   if (int rc = check_network(who, "", nlayers, dims, W, b, nx, nu, with_uprev, form)) return rc;
   if (int rc = check_adam(who, lr, beta1, beta2, eps)) return rc;
@@ -354,13 +391,14 @@ static int train_create(const char* who, nnmpc_train** out, int32_t nlayers, con
   nnmpc_train* h = guard.get();
   TrainCommon& c = h->c;
   if (int rc = common_init(who, c, nlayers, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form)) return rc;
-  c.tan = tan ? 1 : 0;                                      // before the shapes: workspaces, planes and slices for 3 cap_batch rows
+  c.tan = tan ? 1 : 0; c.tan_dirs = dirs; c.tan_whole = whole_input;   // before the shapes: workspaces, planes and slices for (2 + D) or (2 + 2D) cap_batch rows
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_k<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));   // the unstructured head
   HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_mask_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   if (tan) {
     HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_pair_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
+    HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_f32_fan_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
     HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_mask_wrap_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfg<128>::LDS_FLOATS * 4));
   }
   HIPCHK(hipFuncSetAttribute((const void*)gemm_tn_f32_k<128>, hipFuncAttributeMaxDynamicSharedMemorySize, TileCfgTN<128>::LDS_FLOATS * 4));
@@ -397,10 +435,25 @@ int nnmpc_train_create_tan(nnmpc_train** out, int32_t nlayers, const int32_t* di
   return train_create(__func__, out, nlayers, dims, W, b, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form, true);
 }
 
+int nnmpc_train_create_tan_ex(nnmpc_train** out, int32_t nlayers, const int32_t* dims, const double* const* W,
+                              const double* const* b, int32_t nx, int32_t nu, int32_t with_uprev, int32_t max_batch,
+                              double lr, double beta1, double beta2, double eps, int32_t form, int32_t dirs, int32_t whole_input) {
+  return train_create(__func__, out, nlayers, dims, W, b, nx, nu, with_uprev, max_batch, lr, beta1, beta2, eps, form, true, dirs, whole_input);
+}
+
 int nnmpc_train_set_tangents(nnmpc_train* h, int32_t n, const double* dx, const double* duprev, const double* t, int32_t ptr_kind) {
   GUARD_BEGIN
   if (!h) { set_error("nnmpc_train_set_tangents: bad arguments"); return NNMPC_EINVAL; }
-  return set_tangents(__func__, h->c, n, dx, duprev, t, ptr_kind);
+  if (h->c.tan && (h->c.tan_dirs != 1 || h->c.tan_whole)) { set_error("nnmpc_train_set_tangents: the handle has %d directions per row%s: nnmpc_train_set_tangents_ex takes them", h->c.tan_dirs, h->c.tan_whole ? " over the whole input" : ""); return NNMPC_EINVAL; }
+  return set_tangents(__func__, h->c, n, 1, dx, duprev, nullptr, nullptr, t, ptr_kind);
+  GUARD_END
+}
+
+int nnmpc_train_set_tangents_ex(nnmpc_train* h, int32_t n, int32_t dirs, const double* dx, const double* duprev, const double* dxs,
+                                const double* dus, const double* t, int32_t ptr_kind) {
+  GUARD_BEGIN
+  if (!h) { set_error("nnmpc_train_set_tangents_ex: bad arguments"); return NNMPC_EINVAL; }
+  return set_tangents(__func__, h->c, n, dirs, dx, duprev, dxs, dus, t, ptr_kind);
   GUARD_END
 }
 

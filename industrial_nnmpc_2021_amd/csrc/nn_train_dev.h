@@ -13,8 +13,12 @@ namespace nnmpc {
 
 // Rows of the stacked batch of Bp padded samples: two passes for the structured form (0), one for the unstructured forms.
 __host__ __device__ inline int train_rows(int form, int Bp) { return form == 0 ? 2 * Bp : Bp; }
-// The same under the tangent loss (structured form only): a third block, the tangent rows, in [2Bp, 3Bp).
-__host__ __device__ inline int train_rows_tan(int form, int Bp, int tan) { return tan ? 3 * Bp : train_rows(form, Bp); }
+// The same under the tangent loss (structured form only).  Block 0 is pass 1, block 1 pass 2; blocks 2 .. 2 + D - 1 are the D
+// tangent blocks of pass 1 (one per direction of a row) and, with the whole-input form, blocks 2 + D .. 2 + 2D - 1 those of
+// pass 2.  D = 1, whole = 0 is the one-direction form in [dx, (duprev)]: 3 Bp rows.
+__host__ __device__ inline int train_rows_tan(int form, int Bp, int tan, int D = 1, int whole = 0) {
+  return tan ? (2 + (whole ? 2 : 1) * D) * Bp : train_rows(form, Bp);
+}
 
 // Row slices of the dW reduction over M = train_rows(form, Bp) rows for a layer with `tiles` output tiles: as many as keep tiles x slices
 // within the device's CUs (num_cus: the device property, 256 on MI355X) (one workgroup each: a second round would cost a
@@ -202,63 +206,104 @@ __device__ __forceinline__ void train_fwd_tile(float* __restrict__ C, size_t ldc
       }
 }
 
-// ---- the tangent loss (structured form):  L = mean (pred - u)^2 + w mean (J d - t)^2,  J d the tangent of pred along the
-// row's direction d = [dx, (duprev)], propagated forward through the same weights in a third row block [2Bp, 3Bp):
-//   a'_0 = [dx, (duprev), 0, 0],  a'_l = (a'_{l-1} W_l) * [a_l(pass 1) > 0],  J d = a'_{L-1} W_L     (no bias anywhere).
-// ReLU has no second derivative, so the masks are constants of the backward pass: the tangent rows are ordinary rows of
-// dW = dZ' A, send nothing into the primal rows or the biases, and take their dA mask from the pass-1 row they belong to.
+// ---- the tangent loss (structured form):  L = mean (pred - u)^2 + w mean (J d - t)^2,  J d the tangent of pred along a
+// direction d of the row, propagated forward through the same weights in a row block of its own.  A row has D directions.
+//   partial input  d = [dx, (duprev)]:            a'_0 = [dx, (duprev), 0, 0],  a'_l = (a'_{l-1} W_l) * [a_l(pass 1) > 0],
+//                                                 J d = a'_{L-1} W_L                                      (no bias anywhere)
+//   whole input    d = [dx, (duprev), dxs, dus]:  a'_0 = [dx, (duprev), dxs, dus] with the masks of pass 1,
+//                                                 a''_0 = [dxs, (dus), dxs, dus]  with the masks of pass 2,
+//                                                 J d = dus + (a'_{L-1} W_L - a''_{L-1} W_L), in f32 in that order, as pred is.
+// Both means run over B D nu.  ReLU has no second derivative, so the masks are constants of the backward pass: the tangent
+// rows are ordinary rows of dW = dZ' A, send nothing into the primal rows or the biases, and take their dA mask from the
+// primal row they belong to (pass 1 for blocks 2 .. 2 + D - 1, pass 2 for the D after them).
 
-// The tangent block of the gather: row 2Bp + b = [dx, (duprev), 0, 0] of dataset row idx[b]; zero for b >= B and in the
-// pad columns.  Same row walk as train_gather_rows, whose two blocks the same kernel writes.
+// The tangent blocks of the gather: row (2 + d) Bp + b = [dx, (duprev), 0, 0] of direction d of dataset row idx[b] (tdx is
+// [n][D][nx], tdup [n][D][nu]); with the whole-input form [dx, (duprev), dxs, dus] and row (2 + D + d) Bp + b = [dxs, (dus),
+// dxs, dus].  Zero for b >= B and in the pad columns.  Same row walk as train_gather_rows, whose two blocks the same kernel writes.
 __device__ __forceinline__ void train_gather_tan_rows(float* __restrict__ in, int ldk, int Bp, int B, int nx, int nu,
-                                                      int with_uprev, const float* __restrict__ tdx,
-                                                      const float* __restrict__ tdup, const int* __restrict__ idx,
+                                                      int with_uprev, int D, int whole, const float* __restrict__ tdx,
+                                                      const float* __restrict__ tdup, const float* __restrict__ tdxs,
+                                                      const float* __restrict__ tdus, const int* __restrict__ idx,
                                                       int first, int b_first, int b_step) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int dd = nx + (with_uprev ? nu : 0);               // width of the direction
+  const int dd = nx + (with_uprev ? nu : 0);               // width of [dx, (duprev)] = first column of the xs block
+  const int din = dd + nx + nu;
   for (int b = b_first; b < Bp; b += b_step) {
-    float* d3 = in + (size_t)(2 * Bp + b) * ldk;
-    if (b >= B) {
-      for (int k = tid; k < ldk; k += nt) d3[k] = 0.f;
-      continue;
+    const size_t row = b >= B ? 0 : idx ? (size_t)idx[b] : (size_t)first + b;
+    for (int d = 0; d < D; ++d) {
+      float* d3 = in + ((size_t)(2 + d) * Bp + b) * ldk;
+      float* d4 = in + ((size_t)(2 + D + d) * Bp + b) * ldk;   // whole input only
+      if (b >= B) {
+        for (int k = tid; k < ldk; k += nt) d3[k] = 0.f;
+        if (whole) for (int k = tid; k < ldk; k += nt) d4[k] = 0.f;
+        continue;
+      }
+      const size_t rd = row * D + d;
+      for (int k = tid; k < nx; k += nt) d3[k] = tdx[rd * nx + k];
+      if (with_uprev)
+        for (int k = tid; k < nu; k += nt) d3[nx + k] = tdup[rd * nu + k];
+      if (!whole) {
+        for (int k = dd + tid; k < ldk; k += nt) d3[k] = 0.f;
+        continue;
+      }
+      for (int k = tid; k < nx; k += nt) {
+        const float sv = tdxs[rd * nx + k];
+        d3[dd + k] = sv; d4[k] = sv; d4[dd + k] = sv;
+      }
+      for (int k = tid; k < nu; k += nt) {
+        const float uv = tdus[rd * nu + k];
+        d3[dd + nx + k] = uv; d4[dd + nx + k] = uv;
+        if (with_uprev) d4[nx + k] = uv;
+      }
+      for (int k = din + tid; k < ldk; k += nt) { d3[k] = 0.f; d4[k] = 0.f; }
     }
-    const size_t row = idx ? (size_t)idx[b] : (size_t)first + b;
-    for (int k = tid; k < nx; k += nt) d3[k] = tdx[row * nx + k];
-    if (with_uprev)
-      for (int k = tid; k < nu; k += nt) d3[nx + k] = tdup[row * nu + k];
-    for (int k = dd + tid; k < ldk; k += nt) d3[k] = 0.f;
   }
 }
 
-// train_output_block over o [3Bp][ldo] with the tangent rows: the primal squared error and +-g exactly as there, and beside
-// them e' = J d - t of the tangent rows: a second fp64 partial (same lane order, same LDS tree) and dZ'_L = gw e' on rows
-// [2Bp, 3Bp), gw = gscale w; exactly zero on padding rows and pad columns.  256 threads.
+// train_output_block over o with the tangent blocks: the primal squared error and +-g exactly as there, and beside them
+// e' = J d - t of the row's D directions, added in the order d = 0 .. D - 1 behind the primal term of the same element: a
+// second fp64 partial (same lane order, same LDS tree).  J d is the head's tangent row (2 + d) Bp + b, or with the whole-input
+// form dus + (that row - row (2 + D + d) Bp + b).  dZ'_L = gw e' on the pass-1 tangent rows and -gw e' on the pass-2 ones,
+// gw = 2 w / (B D nu); exactly zero on padding rows and pad columns.  t and tdus are [n][D][nu].  256 threads.
 __device__ __forceinline__ void train_output_tan_block(float* __restrict__ dz, const float* __restrict__ o, int ldo, int Bp,
-                                                       int B, int nu, const float* __restrict__ us,
+                                                       int B, int nu, int D, int whole, const float* __restrict__ us,
                                                        const float* __restrict__ u, const float* __restrict__ t,
-                                                       const int* __restrict__ idx, int first, float gscale, float gw,
-                                                       double* __restrict__ partial, double* __restrict__ partial_tan,
-                                                       int blk) {
+                                                       const float* __restrict__ tdus, const int* __restrict__ idx,
+                                                       int first, float gscale, float gw, double* __restrict__ partial,
+                                                       double* __restrict__ partial_tan, int blk) {
   __shared__ double red[2][256];
   const int b0 = blk * 64, tid = threadIdx.x;
   double acc = 0.0, acct = 0.0;
   for (int e = tid; e < 64 * ldo; e += 256) {
     const int b = b0 + e / ldo, c = e % ldo;
-    float g = 0.f, gt = 0.f;
-    if (b < B && c < nu) {
-      const size_t row = idx ? (size_t)idx[b] : (size_t)first + b;
+    const bool live = b < B && c < nu;
+    const size_t row = !live ? 0 : idx ? (size_t)idx[b] : (size_t)first + b;
+    float g = 0.f;
+    if (live) {
       const float pred = us[row * nu + c] + (o[(size_t)b * ldo + c] - o[(size_t)(Bp + b) * ldo + c]);
       const float d = pred - u[row * nu + c];
       acc += (double)d * (double)d;
       g = gscale * d;
-      const float dt = o[(size_t)(2 * Bp + b) * ldo + c] - t[row * nu + c];
-      acct += (double)dt * (double)dt;
-      gt = gw * dt;
     }
     if (dz) {
       dz[(size_t)b * ldo + c] = g;
       dz[(size_t)(Bp + b) * ldo + c] = 0.f - g;
-      dz[(size_t)(2 * Bp + b) * ldo + c] = gt;
+    }
+    for (int d = 0; d < D; ++d) {
+      const size_t r1 = ((size_t)(2 + d) * Bp + b) * ldo + c, r2 = ((size_t)(2 + D + d) * Bp + b) * ldo + c;
+      float gt = 0.f;
+      if (live) {
+        const size_t at = (row * D + d) * nu + c;
+        float jd = o[r1];
+        if (whole) jd = tdus[at] + (jd - o[r2]);
+        const float dt = jd - t[at];
+        acct += (double)dt * (double)dt;
+        gt = gw * dt;
+      }
+      if (dz) {
+        dz[r1] = gt;
+        if (whole) dz[r2] = 0.f - gt;
+      }
     }
   }
   red[0][tid] = acc; red[1][tid] = acct;
@@ -271,24 +316,84 @@ __device__ __forceinline__ void train_output_tan_block(float* __restrict__ dz, c
 }
 
 // train_loss_finish with the second sum: loss[0] = L = mse + w tan_mse (in double), loss[1] = mse = scale * sum,
-// loss[2] = tan_mse = scale * tangent sum; acc[0..2] += weight * each (the epoch's running sums).
+// loss[2] = tan_mse = scale_tan * tangent sum (scale_tan = scale / D); acc[0..2] += weight * each (the epoch's running sums).
 __device__ __forceinline__ void train_loss_finish_tan(const double* __restrict__ partial, const double* __restrict__ partial_tan,
-                                                      int np, double scale, double weight, double w,
+                                                      int np, double scale, double scale_tan, double weight, double w,
                                                       double* __restrict__ loss, double* __restrict__ acc) {
   double s = 0.0, st = 0.0;
   for (int i = 0; i < np; ++i) s += partial[i];
   for (int i = 0; i < np; ++i) st += partial_tan[i];
-  const double mse = s * scale, tan = st * scale, l = mse + w * tan;
+  const double mse = s * scale, tan = st * scale_tan, l = mse + w * tan;
   loss[0] = l; loss[1] = mse; loss[2] = tan;
   acc[0] += weight * l; acc[1] += weight * mse; acc[2] += weight * tan;
 }
 
-// Hidden-layer forward of pass-1 row tile tm TOGETHER with its tangent tile.  First the primal tile, byte for byte
+// Hidden-layer forward of primal row tile tm TOGETHER with its D tangent tiles (a fan).  First the primal tile, byte for byte
 // train_fwd_tile<NB, true, true> (same loop, same epilogue, same store order); the sign pattern of what it stored stays in
 // registers, one bit per accumulator entry (16 MT^2 bits per lane: 64 at NB = 128).  Then the same workgroup runs the same
-// tile_gemm_nt loop over the tangent rows 2Bp + tm NB ... against the same weights and stores that tile without bias, zero
-// where the primal activation is <= 0 (derivative 0 at 0, a NaN passes, as in train_nt_mask_tile).  One after the other:
-// no LDS beyond the 4 stages and no accumulators beyond the one set, so two workgroups per CU still fit.
+// tile_gemm_nt loop once per direction d over the tangent rows t0 + d Bp + tm NB ... against the same weights and stores that
+// tile without bias, zero where the primal activation is <= 0 (derivative 0 at 0, a NaN passes, as in train_nt_mask_tile).
+// t0 = 2 Bp for a pass-1 tile; for a pass-2 tile (tm NB >= Bp, whole-input form) t0 = (1 + D) Bp, so its tangents sit D blocks
+// further down.  One GEMM after the other: no LDS beyond the 4 stages and no accumulators beyond the one set, so two
+// workgroups per CU still fit.
+template <int NB>
+__device__ __forceinline__ void train_fwd_fan_tile(float* __restrict__ C, size_t ldc, const float* __restrict__ A,
+                                                   size_t lda, const float* __restrict__ B, size_t ldb, int K,
+                                                   const float* __restrict__ bias, int Bp, int D, int t0, int tm, int tn,
+                                                   float* lds) {
+  using Cf = TileCfg<NB>;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int m0 = tm * NB, n0 = tn * NB;
+  f32x16 acc[Cf::MT][Cf::MT];
+  zero_acc<NB>(acc);
+  PlainOp b{B + (size_t)n0 * ldb, ldb};
+  {
+    PlainOp a{A + (size_t)m0 * lda, lda};
+    tile_gemm_nt<NB>(acc, a, b, K, lds, false);
+  }
+  uint32_t live[Cf::MT][Cf::MT];                            // bit r: entry r of acc[mi][mj] has a non-zero derivative
+#pragma unroll
+  for (int mi = 0; mi < Cf::MT; ++mi)
+#pragma unroll
+    for (int mj = 0; mj < Cf::MT; ++mj) {
+      uint32_t bits = 0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wr * Cf::WT + mi * 32 + acc_row(r, lane);
+        const int col = n0 + wc * Cf::WT + mj * 32 + acc_col(lane);
+        float v = acc[mi][mj][r];
+        v += bias[col];
+        v = relu_nan(v);
+        C[(size_t)row * ldc + col] = v;
+        bits |= (v <= 0.f ? 0u : 1u) << r;
+      }
+      live[mi][mj] = bits;
+    }
+  for (int d = 0; d < D; ++d) {
+    const int tr0 = t0 + d * Bp + m0;                       // first row of tangent tile d
+    zero_acc<NB>(acc);
+    {
+      PlainOp a{A + (size_t)tr0 * lda, lda};
+      tile_gemm_nt<NB>(acc, a, b, K, lds, false);
+    }
+#pragma unroll
+    for (int mi = 0; mi < Cf::MT; ++mi)
+#pragma unroll
+      for (int mj = 0; mj < Cf::MT; ++mj)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = tr0 + wr * Cf::WT + mi * 32 + acc_row(r, lane);
+          const int col = n0 + wc * Cf::WT + mj * 32 + acc_col(lane);
+          C[(size_t)row * ldc + col] = (live[mi][mj] >> r) & 1u ? acc[mi][mj][r] : 0.f;
+        }
+  }
+}
+
+// The one-direction pair in [dx, (duprev)]: the fan of pass-1 row tile tm at D = 1, t0 = 2 Bp, written out with its constants.
+// Folding the constants into train_fwd_fan_tile leaves the compiler another schedule and register assignment; this text keeps
+// the pair kernels' instruction stream what it was before the fan existed, so a one-direction handle and the grouped trainer
+// run unchanged code.
 template <int NB>
 __device__ __forceinline__ void train_fwd_pair_tile(float* __restrict__ C, size_t ldc, const float* __restrict__ A,
                                                     size_t lda, const float* __restrict__ B, size_t ldb, int K,

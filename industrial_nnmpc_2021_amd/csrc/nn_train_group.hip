@@ -64,8 +64,8 @@ __global__ __launch_bounds__(128) void grp_gather_k(const GLayer* __restrict__ l
   if (sh.form == NNMPC_NN_STRUCTURED) {
     train_gather_rows(ld.ain, ld.K, pad128(B), B, sh.nx, sh.nu, sh.with_uprev, d.x, d.uprev, d.xs, d.us,
                       rows ? rows + st[g].at : nullptr, st[g].at, blockIdx.x, gridDim.x);
-    if (st[g].tan)                                          // train_gather_tan_k: the third block behind the two
-      train_gather_tan_rows(ld.ain, ld.K, pad128(B), B, sh.nx, sh.nu, sh.with_uprev, d.tdx, d.tdup,
+    if (st[g].tan)                                          // train_gather_tan_k: the third block behind the two (one direction, partial input)
+      train_gather_tan_rows(ld.ain, ld.K, pad128(B), B, sh.nx, sh.nu, sh.with_uprev, 1, 0, d.tdx, d.tdup, nullptr, nullptr,
                             rows ? rows + st[g].at : nullptr, st[g].at, blockIdx.x, gridDim.x);
   } else
     train_gather_rows1(ld.ain, ld.K, pad128(B), B, sh.nx, sh.nu, sh.with_uprev, d.x, d.uprev, d.xs, d.us,
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void grp_output_k(const GLayer* __restrict__ l
   if ((int)blockIdx.x * 64 >= Bp) return;
   const GLayer& ld = lay[(size_t)g * sh.L + sh.L - 1];
   if (st[g].tan)                                            // train_output_tan_k; the tangent partials behind the primal ones
-    train_output_tan_block(backward ? mem[g].dz[0] : nullptr, ld.aout, ld.N, Bp, B, sh.nu, d.us, d.u, d.tt,
+    train_output_tan_block(backward ? mem[g].dz[0] : nullptr, ld.aout, ld.N, Bp, B, sh.nu, 1, 0, d.us, d.u, d.tt, nullptr,
                            rows ? rows + st[g].at : nullptr, st[g].at, st[g].gscale, st[g].gw, mem[g].partial,
                            mem[g].partial + sh.cap / 64, blockIdx.x);
   else if (sh.form == NNMPC_NN_STRUCTURED)
@@ -140,7 +140,7 @@ __global__ void grp_loss_finish_k(const GMember* __restrict__ mem, const GStep* 
   const int g = blockIdx.x, B = st[g].B;
   if (threadIdx.x != 0 || B == 0) return;
   if (st[g].tan)
-    train_loss_finish_tan(mem[g].partial, mem[g].partial + cap / 64, pad128(B) / 64, st[g].loss_scale, st[g].acc_w, st[g].w,
+    train_loss_finish_tan(mem[g].partial, mem[g].partial + cap / 64, pad128(B) / 64, st[g].loss_scale, st[g].loss_scale, st[g].acc_w, st[g].w,
                           mem[g].loss, mem[g].acc);
   else
     train_loss_finish(mem[g].partial, pad128(B) / 64, st[g].loss_scale, st[g].acc_w, mem[g].loss, mem[g].acc);
@@ -475,7 +475,7 @@ int nnmpc_train_create_group_tan(nnmpc_train_group** out, int32_t G, int32_t nla
 int nnmpc_train_set_group_tangents(nnmpc_train_group* h, int32_t n, const double* dx, const double* duprev, const double* t, int32_t ptr_kind) {
   GUARD_BEGIN
   if (!h) { set_error("nnmpc_train_set_group_tangents: bad arguments"); return NNMPC_EINVAL; }
-  return set_tangents(__func__, h->c, n, dx, duprev, t, ptr_kind);
+  return set_tangents(__func__, h->c, n, 1, dx, duprev, nullptr, nullptr, t, ptr_kind);
   GUARD_END
 }
 

@@ -50,9 +50,11 @@ struct TrainCommon {                                        // what a handle hol
   // The tangent loss (nnmpc_train_create_tan, nnmpc_train_create_group_tan): the handle stacks a third row block, tdx / tdup /
   // tt are the dataset's directions and targets as f32.  tan_w is a single handle's weight w of the tangent term (0: the
   // plain step); a group keeps one weight per member itself and leaves tan_w alone.
-  int tan = 0;
+  // nnmpc_train_create_tan_ex: tan_dirs directions per row ([n][D][.] columns, D tangent blocks) and, tan_whole, directions
+  // over the whole network input: tdxs / tdus are their xs and us parts and pass 2 gets D tangent blocks of its own.
+  int tan = 0, tan_dirs = 1, tan_whole = 0;
   double tan_w = 0.0;
-  float *tdx = nullptr, *tdup = nullptr, *tt = nullptr;
+  float *tdx = nullptr, *tdup = nullptr, *tdxs = nullptr, *tdus = nullptr, *tt = nullptr;
   char* dcall = nullptr;                                    // what the last call uploaded: its row lists (behind its step table, in a group)
   hipEvent_t stage_done[2] = {nullptr, nullptr};            // the upload out of the pinned image k (used in turn) has finished
   int stage_turn = 0;
@@ -66,7 +68,7 @@ struct TrainCommon {                                        // what a handle hol
 
 inline int pad128_host(int B) { return ((B + 127) / 128) * 128; }
 // Most stacked rows of a batch of Bp padded samples on this handle: what its workspaces and planes are sized for.
-inline int max_rows(const TrainCommon& c, int Bp) { return train_rows_tan(c.form, Bp, c.tan); }
+inline int max_rows(const TrainCommon& c, int Bp) { return train_rows_tan(c.form, Bp, c.tan, c.tan_dirs, c.tan_whole); }
 // The tangent term is part of this handle's loss.
 inline bool tan_active(const TrainCommon& c) { return c.tan && c.tan_w > 0.0; }
 
@@ -296,7 +298,7 @@ inline int upload_column(TrainCommon& c, float** d, const double* s, size_t cnt,
   return NNMPC_OK;
 }
 inline void drop_tangents(TrainCommon& c) {
-  for (float** p : {&c.tdx, &c.tdup, &c.tt}) { c.res.give_back(*p); *p = nullptr; }
+  for (float** p : {&c.tdx, &c.tdup, &c.tdxs, &c.tdus, &c.tt}) { c.res.give_back(*p); *p = nullptr; }
 }
 
 // The f32 dataset from f64 columns on the host or (ptr_kind NNMPC_DEVICE) already in HBM.  Tangents of the earlier dataset go with it.
@@ -322,22 +324,27 @@ inline int set_data(const char* who, TrainCommon& c, int32_t n, const double* x,
   return NNMPC_OK;
 }
 
-// The dataset's tangent directions and targets (a tangent handle only), one per row of the dataset set_data gave.
-inline int set_tangents(const char* who, TrainCommon& c, int32_t n, const double* dx, const double* duprev, const double* t,
-                        int32_t ptr_kind) {
+// The dataset's tangent directions and targets (a tangent handle only): `dirs` per row of the dataset set_data gave, every
+// column [n][dirs][width]; dxs / dus on a whole-input handle and only there.
+inline int set_tangents(const char* who, TrainCommon& c, int32_t n, int32_t dirs, const double* dx, const double* duprev,
+                        const double* dxs, const double* dus, const double* t, int32_t ptr_kind) {
   if (!c.tan) { set_error("%s: a plain handle has no tangent loss (nnmpc_train_create_tan builds the handle that has)", who); return NNMPC_EINVAL; }
+  if (dirs != c.tan_dirs) { set_error("%s: %d directions per row, the handle was built for %d", who, dirs, c.tan_dirs); return NNMPC_EINVAL; }
   if (int rc = check_data(c, who)) return rc;
   if (!dx || !t) { set_error("%s: bad arguments", who); return NNMPC_EINVAL; }
   if (n != c.n) { set_error("%s: tangents of %d rows for a dataset of %d", who, n, c.n); return NNMPC_EINVAL; }
   if (c.with_uprev && !duprev) { set_error("%s: uprev is an input of the network, no duprev given", who); return NNMPC_EINVAL; }
+  if (c.tan_whole && (!dxs || !dus)) { set_error("%s: a whole-input handle takes dxs and dus", who); return NNMPC_EINVAL; }
+  if (!c.tan_whole && (dxs || dus)) { set_error("%s: dxs / dus given, the handle's directions are [dx, (duprev)] only (whole_input = 1 at create builds the handle that takes them)", who); return NNMPC_EINVAL; }
   HIPCHK(hipSetDevice(c.device));
   HIPCHK(stream_sync(c.stream));
   drop_tangents(c);
-  struct { float** d; const double* s; int w; } col[3] = {{&c.tdx, dx, c.nx}, {&c.tdup, c.with_uprev ? duprev : nullptr, c.nu}, {&c.tt, t, c.nu}};
+  struct { float** d; const double* s; int w; } col[5] = {{&c.tdx, dx, c.nx}, {&c.tdup, c.with_uprev ? duprev : nullptr, c.nu},
+                                                          {&c.tdxs, dxs, c.nx}, {&c.tdus, dus, c.nu}, {&c.tt, t, c.nu}};
   std::vector<float> tmp;
   for (auto& k : col) {
     if (!k.s) continue;
-    if (int rc = upload_column(c, k.d, k.s, (size_t)n * k.w, ptr_kind, tmp)) { drop_tangents(c); return rc; }
+    if (int rc = upload_column(c, k.d, k.s, (size_t)n * dirs * k.w, ptr_kind, tmp)) { drop_tangents(c); return rc; }
   }
   HIPCHK(stream_sync(c.stream));
   HIPCHK(hipGetLastError());

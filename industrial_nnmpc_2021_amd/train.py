@@ -19,7 +19,9 @@ network (``cstrs_train_unstd.py``) on the one-pass form of the single-network st
 ``train_unstd_nn_controllers`` a sweep of them in one launch group of that form.
 
 ``train_nn_controller(..., tan_weight=w)`` trains the structured network on the MPC's value AND its local slope (the
-tangent loss, ``tangent_loss``); ``tangent_data`` makes the slope targets from a solved batch.
+tangent loss, ``tangent_loss``); ``tangent_data`` makes the slope targets from a solved batch -- one direction per row in
+[dx, (duprev)], or D directions per row and directions over the whole input [dx, (duprev), dxs, dus]
+(``tangent_data(directions=, whole_input=)``, ``whole_input_perturbation``, ``HipTrainer(tan_dirs=, tan_whole_input=)``).
 """
 import copy
 import ctypes as C
@@ -185,23 +187,34 @@ class HipTrainer:
     L = mse + w tan_mse (``tangent_loss``) and ``last_losses()`` returns the two parts.  With w = 0 (as created) it
     computes the bytes of a plain handle.
 
+    ``tan_dirs=D`` (1 .. 16) and ``tan_whole_input=True`` build the handle of ``nnmpc_train_create_tan_ex``: D directions
+    per dataset row, each with its own target, behind ONE primal pair of stacked rows, and directions over the whole network
+    input [dx, (duprev), dxs, dus] (pass 2 then carries tangents too).  ``set_tangents`` takes every column as (n, D, width),
+    ``dxs`` and ``dus`` with them on a whole-input handle.  The defaults go through ``nnmpc_train_create_tan`` /
+    ``nnmpc_train_set_tangents`` as before.
+
     Adam as ``torch.optim.Adam(lr, betas, eps)``.  There is no CPU fallback: without a device the constructor raises
     ``_lib.NnmpcError``."""
 
     def __init__(self, weights, nx, nu, *, nnwithuprev=True, max_batch=2048, lr=1e-3, betas=(0.9, 0.999), eps=1e-7,
-                 form=_lib.NN_STRUCTURED, tangents=False):
+                 form=_lib.NN_STRUCTURED, tangents=False, tan_dirs=1, tan_whole_input=False):
         self.form = _check_form(form)
         self.tangents = bool(tangents)
+        self.tan_dirs, self.tan_whole = int(tan_dirs), int(tan_whole_input)
+        self._tan_ex = self.tan_dirs != 1 or self.tan_whole != 0
+        if self._tan_ex and not self.tangents:
+            raise ValueError("HipTrainer: tan_dirs / tan_whole_input describe a tangent handle (tangents=True)")
         Ws, bs = _split_keras(weights, self.form)               # refused on the host, before the library is loaded
         lib = _lib.load()
         L = len(Ws)
         self.dims = [Ws[0].shape[0]] + [w.shape[1] for w in Ws]
         self.L, self.nx, self.nu, self.nnwithuprev, self.n = L, nx, nu, bool(nnwithuprev), 0
         self._lib, self._h = lib, C.c_void_p()
-        create, who = ((lib.nnmpc_train_create_tan, "nnmpc_train_create_tan") if self.tangents
-                       else (lib.nnmpc_train_create_ex, "nnmpc_train_create_ex"))
+        create, who, more = ((lib.nnmpc_train_create_tan_ex, "nnmpc_train_create_tan_ex", (self.tan_dirs, self.tan_whole)) if self._tan_ex
+                             else (lib.nnmpc_train_create_tan, "nnmpc_train_create_tan", ()) if self.tangents
+                             else (lib.nnmpc_train_create_ex, "nnmpc_train_create_ex", ()))
         _lib.check(create(C.byref(self._h), L, (C.c_int32 * (L + 1))(*self.dims), self._plist(Ws), self._plist(bs), nx, nu,
-                          int(self.nnwithuprev), int(max_batch), lr, betas[0], betas[1], eps, self.form), who)
+                          int(self.nnwithuprev), int(max_batch), lr, betas[0], betas[1], eps, self.form, *more), who)
 
     @staticmethod
     def _plist(arrays):
@@ -233,19 +246,41 @@ class HipTrainer:
 
     def set_tangents(self, tangents):
         """dict(dx, duprev, du): per dataset row one direction [dx, (duprev)] in the units of the dataset's x and the
-        target du (``tangent_data`` returns them); after ``set_data``, which drops earlier ones.  Uploaded once as f32."""
-        c = lambda a, w: np.ascontiguousarray(a, np.float64).reshape(-1, w)
+        target du (``tangent_data`` returns them); after ``set_data``, which drops earlier ones.  Uploaded once as f32.
+
+        A handle with ``tan_dirs=D``: every column is (n, D, width) -- (n, width) also serves D = 1 --, and a whole-input
+        handle takes ``dxs`` and ``dus`` beside them (on any other handle they are refused)."""
+        D = self.tan_dirs
+
+        def c(a, w):
+            a = np.ascontiguousarray(a, np.float64)
+            if a.ndim == 3 and a.shape[1:] != (D, w) or a.ndim != 3 and D != 1:
+                raise ValueError(f"set_tangents: a column of shape {a.shape}, the handle takes (n, {D}, {w})")
+            return a.reshape(-1, D * w)
         dx, du = c(tangents["dx"], self.nx), c(tangents["du"], self.nu)
         dup = c(tangents["duprev"], self.nu) if self.nnwithuprev and tangents.get("duprev") is not None else None
         p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        _lib.check(self._lib.nnmpc_train_set_tangents(self._h, dx.shape[0], p(dx), p(dup), p(du), _lib.HOST),
-                   "nnmpc_train_set_tangents")
+        if not self._tan_ex:
+            if tangents.get("dxs") is not None or tangents.get("dus") is not None:
+                raise ValueError("set_tangents: dxs / dus are the columns of a whole-input handle (tan_whole_input=True)")
+            _lib.check(self._lib.nnmpc_train_set_tangents(self._h, dx.shape[0], p(dx), p(dup), p(du), _lib.HOST),
+                       "nnmpc_train_set_tangents")
+            return
+        dxs = c(tangents["dxs"], self.nx) if tangents.get("dxs") is not None else None
+        dus = c(tangents["dus"], self.nu) if tangents.get("dus") is not None else None
+        _lib.check(self._lib.nnmpc_train_set_tangents_ex(self._h, dx.shape[0], D, p(dx), p(dup), p(dxs), p(dus), p(du), _lib.HOST),
+                   "nnmpc_train_set_tangents_ex")
 
-    def set_tangents_device(self, n, dx, duprev, du):
-        """The same from HBM-resident f64 buffers (objects with data_ptr(); ``duprev`` None without uprev)."""
+    def set_tangents_device(self, n, dx, duprev, du, dxs=None, dus=None):
+        """The same from HBM-resident f64 buffers (objects with data_ptr(); ``duprev`` None without uprev), laid out
+        (n, D, width) on a handle with ``tan_dirs=D``; ``dxs`` / ``dus`` on a whole-input handle."""
         q = lambda a: None if a is None else C.c_void_p(a.data_ptr())
-        _lib.check(self._lib.nnmpc_train_set_tangents(self._h, int(n), q(dx), q(duprev), q(du), _lib.DEVICE),
-                   "nnmpc_train_set_tangents")
+        if not self._tan_ex and dxs is None and dus is None:
+            _lib.check(self._lib.nnmpc_train_set_tangents(self._h, int(n), q(dx), q(duprev), q(du), _lib.DEVICE),
+                       "nnmpc_train_set_tangents")
+            return
+        _lib.check(self._lib.nnmpc_train_set_tangents_ex(self._h, int(n), self.tan_dirs, q(dx), q(duprev), q(dxs), q(dus), q(du),
+                                                         _lib.DEVICE), "nnmpc_train_set_tangents_ex")
 
     def set_tan_weight(self, w):
         """The weight of the tangent term, finite and >= 0 (0: the plain step)."""
@@ -423,6 +458,7 @@ class HipGroupTrainer:
     def set_tangents(self, tangents):
         """dict(dx, duprev, du) for every row of the shared dataset, as ``HipTrainer.set_tangents`` takes them; after
         ``set_data``, which drops earlier ones.  Uploaded once as f32 for all members."""
+        _refuse_fan_in_a_sweep(tangents)
         c = lambda a, w: np.ascontiguousarray(a, np.float64).reshape(-1, w)
         dx, du = c(tangents["dx"], self.nx), c(tangents["du"], self.nu)
         dup = c(tangents["duprev"], self.nu) if self.nnwithuprev and tangents.get("duprev") is not None else None
@@ -542,10 +578,27 @@ def _sweep_args(who, models, data, num_samples, backend):
     return models, ns
 
 
+def _tan_form(data):
+    """(D, whole_input) of a dataset's tangent columns: D from a direction axis of dx ((n, D, nx); (n, nx) is D = 1), the
+    whole-input form from the presence of dxs / dus (both, or neither)."""
+    has = [data.get(k) is not None for k in ("dxs", "dus")]
+    if has[0] != has[1]:
+        raise ValueError("train_nn_controller: dxs and dus come together (tangent_data(whole_input=True) makes both)")
+    dx = np.asarray(data["dx"])
+    return (int(dx.shape[1]) if dx.ndim == 3 else 1), has[0]
+
+
+def _refuse_fan_in_a_sweep(data):
+    """The grouped step stacks one direction in [dx, (duprev)] per row; the richer forms are the single trainer's."""
+    if data.get("dx") is not None and (np.asarray(data["dx"]).ndim == 3 or data.get("dxs") is not None or data.get("dus") is not None):
+        raise ValueError("the sweep trainers take one direction [dx, (duprev)] per row; several directions per row (a direction "
+                         "axis) and whole-input directions (dxs, dus) are built for train_nn_controller / HipTrainer only")
+
+
 def _first_rows(data, n):
     """The first n rows of the dataset, the tangent columns (``tangent_data``) with them where it has any."""
     out = {k: (None if data.get(k) is None else np.asarray(data[k])[:n]) for k in ("x", "uprev", "xs", "us", "u")}
-    out.update({k: np.asarray(data[k])[:n] for k in ("dx", "duprev", "du") if data.get(k) is not None})
+    out.update({k: np.asarray(data[k])[:n] for k in ("dx", "duprev", "du", "dxs", "dus") if data.get(k) is not None})
     return out
 
 
@@ -563,6 +616,7 @@ def _sweep_tan_weights(who, models, data, tan_weights):
         if not (w >= 0.0 and np.isfinite(w)):
             raise ValueError(f"tan_weights[{i}] {w!r}: finite and >= 0")
     if any(w > 0 for w in ws):
+        _refuse_fan_in_a_sweep(data)
         for m in models:
             if getattr(m, "unstructured", False):
                 raise ValueError(f"{who}: the tangent loss is built for the structured RegulatorModel only")
@@ -686,8 +740,10 @@ def _train_hip(model, data, epochs, batch_size, validation_split, lr, device, se
                tan_weight=0.0):
     """The "hip" backend of train_nn_controller / train_unstd_nn_controller: same Keras semantics, every step on the
     device in f32.  ``tan_weight > 0``: the tangent handle, so run and validation losses are L."""
+    D, whole = _tan_form(data) if tan_weight > 0 else (1, False)
+    more = dict(tan_dirs=D, tan_whole_input=whole) if (D, whole) != (1, False) else {}   # the defaults: the one-direction entry points
     tr = HipTrainer(model.get_weights(), model.Nx, model.Nu, nnwithuprev=model.nnwithuprev, max_batch=batch_size,
-                    lr=lr, eps=1e-7, form=form, tangents=tan_weight > 0)
+                    lr=lr, eps=1e-7, form=form, tangents=tan_weight > 0, **more)
     try:
         tr.set_data(data)
         if tan_weight > 0:
@@ -719,7 +775,7 @@ def _train_hip(model, data, epochs, batch_size, validation_split, lr, device, se
     return model, ttime, hist
 
 
-def tangent_loss(model, x, uprev, xs, us, u, dx, duprev, du, w):
+def tangent_loss(model, x, uprev, xs, us, u, dx, duprev, du, w, dxs=None, dus=None):
     """(L, mse, tan_mse) of a structured ``RegulatorModel`` on a batch, in stock torch:
 
         L = mean (pred - u)^2 + w mean (J d - du)^2,
@@ -727,25 +783,54 @@ def tangent_loss(model, x, uprev, xs, us, u, dx, duprev, du, w):
     J d the tangent of pred along d = [dx, (duprev)], propagated forward through the same weights -- a'_0 = [dx, (duprev), 0, 0],
     a'_l = (a'_{l-1} W_l) * [a_l(pass 1) > 0], J d = a'_{L-1} W_L; no bias, ReLU derivative 0 at 0 (a NaN activation passes,
     as in the native step), pass 2 does not depend on x or uprev.  The masks carry no gradient (ReLU has no second
-    derivative), so autograd through this is the gradient the native step computes.  ``duprev`` is ignored without uprev."""
+    derivative), so autograd through this is the gradient the native step computes.  ``duprev`` is ignored without uprev.
+
+    ``dx``, ``duprev``, ``du`` may carry a direction axis, (B, D, width): D directions per row, each with its target, and the
+    second mean runs over B D nu.  With ``dxs`` and ``dus`` (both, same shape rule) the direction is over the whole input,
+    d = [dx, (duprev), dxs, dus]: a'_0 = [dx, (duprev), dxs, dus] under the masks of pass 1, a''_0 = [dxs, (dus), dxs, dus]
+    under the masks of pass 2, and J d = dus + (a'_{L-1} W_L - a''_{L-1} W_L)."""
+    if (dxs is None) != (dus is None):
+        raise ValueError("tangent_loss: dxs and dus come together")
+    whole = dxs is not None
+    ax = lambda a: a if a.dim() == 3 else a.unsqueeze(1)       # (B, D, width)
+    dx, du = ax(dx), ax(du)
+    zx, zu = torch.zeros_like(dx), torch.zeros_like(du)
+    sx, su = (ax(dxs), ax(dus)) if whole else (zx, zu)
     if model.nnwithuprev:
         z1, z2 = torch.cat((x, uprev, xs, us), -1), torch.cat((xs, us, xs, us), -1)
-        ta = torch.cat((dx, duprev, torch.zeros_like(xs), torch.zeros_like(us)), -1)
+        ta, tb = torch.cat((dx, ax(duprev), sx, su), -1), torch.cat((sx, su, sx, su), -1)
     else:
         z1, z2 = torch.cat((x, xs, us), -1), torch.cat((xs, xs, us), -1)
-        ta = torch.cat((dx, torch.zeros_like(xs), torch.zeros_like(us)), -1)
-    a = z1
+        ta, tb = torch.cat((dx, sx, su), -1), torch.cat((sx, sx, su), -1)
+    a, a2 = z1, z2
     for lin in model.layers[:-1]:
-        a = torch.relu(lin(a))
-        ta = (ta @ lin.weight.T) * (~(a <= 0)).to(a.dtype)
+        a, a2 = torch.relu(lin(a)), torch.relu(lin(a2))
+        ta = (ta @ lin.weight.T) * (~(a <= 0)).to(a.dtype).unsqueeze(1)
+        if whole:
+            tb = (tb @ lin.weight.T) * (~(a2 <= 0)).to(a.dtype).unsqueeze(1)
     head = model.layers[-1]
-    pred = us + head(a) - model._mlp(z2)
+    pred = us + head(a) - head(a2)
     mse = torch.mean((pred - u) ** 2)
-    tan = torch.mean((ta @ head.weight.T - du) ** 2)
+    jd = su + (ta @ head.weight.T - tb @ head.weight.T) if whole else ta @ head.weight.T
+    tan = torch.mean((jd - du) ** 2)
     return mse + w * tan, mse, tan
 
 
-def tangent_data(regulator, data, xscale, *, ulb, uub, seed=0, nnwithuprev=True):
+def whole_input_perturbation(dx, duprev, dxs, dus, xscale):
+    """(dX0, dulb, duub): what a whole-input direction [dx, duprev, dxs, dus] of the scaled dataset does to the regulator's
+    problem.  The MPC law is u = us + kappa(x - xs, uprev - us; ulb - us, uub - us), so along the direction
+
+        dX0 = [dx * xscale - dxs * xscale, duprev - dus],    dulb = duub = -dus,
+
+    and the absolute first move changes by dus + du0, du0 the regulator's ``sensitivity_batch(info, dX0, dulb, duub,
+    first_move_only=True)``.  Arrays of any leading shape; the last axis is nx or nu."""
+    dx, dup, dxs, dus = (np.asarray(a, float) for a in (dx, duprev, dxs, dus))
+    xscale = np.asarray(xscale, float).reshape(-1)
+    dX0 = np.concatenate((dx * xscale - dxs * xscale, dup - dus), axis=-1)
+    return dX0, -dus, -dus
+
+
+def tangent_data(regulator, data, xscale, *, ulb, uub, seed=0, nnwithuprev=True, directions=1, whole_input=False):
     """Tangent targets for ``train_nn_controller(..., tan_weight=w)`` from the regulator's own solves.
 
     ``data``: the raw generated rows dict(x, uprev, xs, us) (before scaling); ``xscale``: what
@@ -760,23 +845,46 @@ def tangent_data(regulator, data, xscale, *, ulb, uub, seed=0, nnwithuprev=True)
     Returns dict(dx (n, Nx), duprev (n, Nu), du (n, Nu), flag (n,)).  A row whose sensitivity flag is not 0, or whose
     solve status is not 0, has no certified slope: its direction AND its target are set to zero, so J d = 0 = du and the
     row contributes exactly nothing to the tangent term or its gradient.  The mean's denominator stays B nu all the same
-    (such rows weigh the term down, they do not bias it)."""
+    (such rows weigh the term down, they do not bias it).
+
+    ``directions=D`` and ``whole_input``: D directions per row from the same one solve and ONE ``sensitivity_batch`` call;
+    dx, duprev, du are then (n, D, .) -- whenever either argument is given, so ``directions=1, whole_input=True`` has the axis
+    too.  With ``whole_input`` the direction is over the whole network input: dxs (n, D, Nx) and dus (n, D, Nu) are drawn
+    and returned as well, the regulator's problem moves along ``whole_input_perturbation`` and the target is the change of
+    the absolute first move, du = dus + du0.  A row without a certified slope is zero in every direction, dxs and dus
+    included (so J d = 0 = du still holds).  The defaults draw and return exactly what they did before the arguments existed."""
     x, xs = np.asarray(data["x"], float), np.asarray(data["xs"], float)
     us, up = np.asarray(data["us"], float), np.asarray(data["uprev"], float)
     n, nx, nu = x.shape[0], x.shape[1], us.shape[1]
     xscale = np.asarray(xscale, float).reshape(1, nx)
     rng = np.random.default_rng(seed)
-    dx = rng.standard_normal((n, nx))
-    dup = rng.standard_normal((n, nu)) if nnwithuprev else np.zeros((n, nu))
+    D = int(directions)
+    if D < 1:
+        raise ValueError(f"tangent_data: directions {directions!r} (>= 1)")
+    fan = D != 1 or bool(whole_input)
+    shape = (lambda w: (n, D, w)) if fan else (lambda w: (n, w))
+    dx = rng.standard_normal(shape(nx))
+    dup = rng.standard_normal(shape(nu)) if nnwithuprev else np.zeros(shape(nu))
     lb = np.asarray(ulb, float).reshape(1, nu) - us
     ub = np.asarray(uub, float).reshape(1, nu) - us
     _, info = regulator.solve_batch(np.concatenate((x - xs, up - us), axis=1), lb, ub, first_move_only=True)
-    out = regulator.sensitivity_batch(info, np.concatenate((dx * xscale, dup), axis=1), first_move_only=True)
+    if whole_input:
+        dxs, dus = rng.standard_normal(shape(nx)), rng.standard_normal(shape(nu))
+        dX0, dlb, dub = whole_input_perturbation(dx, dup, dxs, dus, xscale)
+        out = regulator.sensitivity_batch(info, dX0, dulb=dlb, duub=dub, first_move_only=True)
+    else:
+        out = regulator.sensitivity_batch(info, np.concatenate((dx * xscale, dup), axis=-1), first_move_only=True)
     flag = np.asarray(out["flag"]).astype(np.int32).ravel().copy()
     bad = (flag != 0) | (np.asarray(info["status"]).ravel() != 0)
-    du = np.array(out["du"], float).reshape(n, nu)
+    du = np.array(out["du"], float).reshape(shape(nu))
+    if whole_input:
+        du = dus + du
+        dxs[bad] = 0.0; dus[bad] = 0.0
     dx[bad] = 0.0; dup[bad] = 0.0; du[bad] = 0.0
-    return dict(dx=dx, duprev=dup, du=du, flag=flag)
+    res = dict(dx=dx, duprev=dup, du=du, flag=flag)
+    if whole_input:
+        res.update(dxs=dxs, dus=dus)
+    return res
 
 
 def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation_split=0.05, lr=1e-3,
@@ -793,7 +901,9 @@ def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation
     ``tan_weight = w > 0`` (a structured ``RegulatorModel`` only): the loss is ``tangent_loss``, L = mse + w tan_mse, and
     ``data`` also holds dx, (duprev) and du, one direction and one slope target per row (``tangent_data``).  Both backends
     serve it; the history, the validation loss and the best-epoch checkpoint are then those of L.  0 (the default) is
-    the plain loss, exactly as without the argument."""
+    the plain loss, exactly as without the argument.  The form is read from ``data``: dx of shape (n, D, Nx) means D
+    directions per row (duprev and du likewise), and dxs / dus beside them mean directions over the whole network input
+    (``tangent_data(directions=D, whole_input=True)``)."""
     tan_weight = float(tan_weight)
     if not (tan_weight >= 0.0 and np.isfinite(tan_weight)):
         raise ValueError(f"tan_weight {tan_weight!r}: finite and >= 0")
@@ -803,6 +913,7 @@ def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation
         need = ("dx", "du") + (("duprev",) if model.nnwithuprev else ())
         if any(data.get(k) is None for k in need):
             raise ValueError(f"train_nn_controller: tan_weight > 0 needs {', '.join(need)} in data (tangent_data makes them)")
+        whole = _tan_form(data)[1]
     if backend == "hip":
         _refuse_unstructured(model, "train_nn_controller(backend=\"hip\")")
         return _train_hip(model, data, epochs, batch_size, validation_split, lr, device, seed, log, tan_weight=tan_weight)
@@ -818,10 +929,15 @@ def train_nn_controller(model, data, *, epochs=1500, batch_size=2048, validation
     if tan_weight > 0:
         T["dx"], T["du"] = (torch.as_tensor(np.asarray(data[k]), dtype=dt, device=device) for k in ("dx", "du"))
         T["duprev"] = (torch.as_tensor(np.asarray(data["duprev"]), dtype=dt, device=device)
-                       if model.nnwithuprev else torch.zeros_like(T["us"]))
+                       if model.nnwithuprev else torch.zeros_like(T["du"]))
+        keys = ("x", "uprev", "xs", "us", "u", "dx", "duprev", "du")
+        if whole:
+            T["dxs"], T["dus"] = (torch.as_tensor(np.asarray(data[k]), dtype=dt, device=device) for k in ("dxs", "dus"))
+            keys += ("dxs", "dus")
 
         def loss_of(S, idx):
-            return tangent_loss(model, *(S[k][idx] for k in ("x", "uprev", "xs", "us", "u", "dx", "duprev", "du")), tan_weight)[0]
+            a = [S[k][idx] for k in keys]
+            return tangent_loss(model, *a[:8], tan_weight, *a[8:])[0]
     else:
         def loss_of(S, idx):
             return torch.mean((model(S["x"][idx], S["uprev"][idx], S["xs"][idx], S["us"][idx]) - S["u"][idx]) ** 2)

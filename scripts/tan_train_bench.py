@@ -27,6 +27,20 @@ One JSON line per way, printed and appended to --out (profiles/tan_train_bench.j
 hipEvent time of the epoch calls (last_ms) and the launches per lock-step step (last_launches).
 
     python scripts/tan_train_bench.py --sweep cstrs [--batch 2048] [--weight 0.5] [--ways loop,group] [--epochs 5] [--repeats 5]
+
+--fan times the step with several directions per row and whole-input directions (nnmpc_train_create_tan_ex) beside what it
+replaces, per shape of --shapes at --batch, hipEvent ms per optimiser step (nnmpc_train_last_ms over epoch calls of --fan-rows
+rows, one warm-up epoch, the median (min, max) of --repeats runs of --epochs epochs).  Legs (--legs):
+
+  plain   the tangent handle at w = 0: the plain step          d1    one direction in [dx, (duprev)]: the pair launch
+  rep4    the d1 handle on a dataset that repeats each row four times: ms per FOUR steps, the work d4 does in one
+  d4      four directions per row in one step, partial input   w1, w2, w4   whole-input directions, D = 1, 2, 4
+
+The stacked rows give d4 / rep4 = (2 + 4) / (3 x 4) = 0.5.  --root runs the legs on the package of another checkout (an
+older build knows plain, d1 and rep4 only), so two builds can be alternated in one session.  One JSON line per (shape, leg),
+printed and appended to --out.
+
+    python scripts/tan_train_bench.py --fan [--legs plain,d1,rep4,d4,w1,w2,w4] [--fan-rows 40960] [--root PATH] [--tag NAME]
 """
 import argparse
 import json
@@ -36,7 +50,10 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if "--root" in sys.argv:                                                      # the package of another checkout, before ours
+    sys.path.insert(0, os.path.abspath(sys.argv[sys.argv.index("--root") + 1]))
+else:
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from train_bench import SHAPES, geometry, spread, synthetic   # noqa: E402
 
@@ -170,6 +187,55 @@ def run_sweep(name, batch, w, epochs, repeats, ways, out):
                   last_launches=launches, launches_per_lockstep_step=launches / steps))
 
 
+FAN_LEGS = {"plain": (1, False, 1, 0.0), "d1": (1, False, 1, None), "rep4": (1, False, 4, None), "d4": (4, False, 1, None),
+            "w1": (1, True, 1, None), "w2": (2, True, 1, None), "w4": (4, True, 1, None)}   # D, whole input, row repeats, weight
+
+
+def run_fan(shapes, legs, batch, rows, w, epochs, repeats, tag, out):
+    from industrial_nnmpc_2021_amd.train import HipTrainer, RegulatorModel
+    for sname in shapes:
+        dims, uprev = SHAPES[sname]
+        nx, nu = geometry(dims, uprev)
+        base = synthetic(rows, nx, nu)
+        weights = RegulatorModel(nx, nu, dims, nnwithuprev=uprev).get_weights()
+        for leg in legs:
+            D, whole, reps, wl = FAN_LEGS[leg]
+            rng = np.random.default_rng(1)
+            data = {k: np.repeat(v, reps, axis=0) for k, v in base.items()}
+            n = rows * reps
+            shape = (lambda k: (n, D, k)) if (D > 1 or whole) else (lambda k: (n, k))
+            data.update(dx=rng.standard_normal(shape(nx)), duprev=rng.standard_normal(shape(nu)), du=0.5 * rng.standard_normal(shape(nu)))
+            more = {}
+            if D > 1 or whole:
+                more = dict(tan_dirs=D, tan_whole_input=whole)
+            if whole:
+                data.update(dxs=rng.standard_normal(shape(nx)), dus=rng.standard_normal(shape(nu)))
+            tr = HipTrainer(weights, nx, nu, nnwithuprev=uprev, max_batch=batch, tangents=True, **more)
+            tr.set_data(data)
+            tr.set_tangents(data)
+            tr.set_tan_weight(w if wl is None else wl)
+            steps = -(-n // batch)
+            tr.epoch(rng.permutation(n), batch)                                                   # warm-up
+            tot, gemm = [], []
+            for _ in range(repeats):
+                t = g = 0.0
+                for _ep in range(epochs):
+                    tr.epoch(rng.permutation(n), batch)
+                    ge, te = tr.last_ms()
+                    t += te
+                    g += ge
+                tot.append(reps * t / epochs / steps)
+                gemm.append(reps * g / epochs / steps)
+            tr.close()
+            line = json.dumps(dict(fan_leg=leg, build=tag, shape=sname, dims=dims, batch=batch, rows=rows, dirs=D, whole_input=whole,
+                                   row_repeats=reps, tan_weight=w if wl is None else wl, steps_counted_as_one=reps,
+                                   step_event_ms=spread(tot), step_gemm_event_ms=spread(gemm), epochs=epochs, repeats=repeats))
+            print(line, flush=True)
+            if out:
+                with open(out, "a") as f:
+                    f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100000)
@@ -184,7 +250,15 @@ def main():
     ap.add_argument("--ways", default="loop,group", help="with --sweep: loop, group, plain")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "tan_train_bench.jsonl"),
                     help="with --sweep: the file the JSON lines are appended to ('' for none)")
+    ap.add_argument("--fan", action="store_true", help="time the step with several directions per row / whole-input directions")
+    ap.add_argument("--legs", default="plain,d1,rep4,d4,w1,w2,w4", help="with --fan")
+    ap.add_argument("--fan-rows", type=int, default=40960, help="with --fan: dataset rows (rep4 repeats each four times)")
+    ap.add_argument("--root", default="", help="with --fan: the checkout whose package is measured (default: this one)")
+    ap.add_argument("--tag", default="this", help="with --fan: the name of the build in the JSON lines")
     a = ap.parse_args()
+    if a.fan:
+        run_fan(a.shapes.split(","), a.legs.split(","), a.batch, a.fan_rows, a.weight, a.epochs, a.repeats, a.tag, a.out)
+        return
     if a.sweep:
         for name in a.sweep.split(","):
             run_sweep(name, a.batch, a.weight, a.epochs, a.repeats, a.ways.split(","), a.out)
