@@ -44,7 +44,7 @@ constexpr int ASM_TS = 16 * 17;    // doubles per LDS tile (16 rows, stride 17: 
 enum { ASM_RUN = 0, ASM_DONE = 1, ASM_FALLBACK = 2, ASM_CERT = 3, ASM_WIDE = 4, ASM_INVALID = 5 };   // CERT: finished and certified by the
                                    // inverse-error bound; INVALID: NaN / Inf in x0 or lb > ub (status NNMPC_ST_NUMERIC, u = NaN)
 constexpr int ASM_NBIN = 8;        // size classes by the number of 16-blocks: class b holds sets of 16 (b + 4) or fewer
-constexpr int ASM_NREG = 6;        // classes 0..5 (<= 144 bounds): four problems per workgroup (asm_lambda_reg_k); 6, 7: two
+constexpr int ASM_NREG = 6;        // classes 0..5 (<= 144 bounds): one wave per problem, S in registers (asm_lambda_reg_k); 6, 7: two waves in fp64
 constexpr int ASM_NCNT = 40;       // ints in AsmDev::counters
 constexpr int ASM_CNT_KSUM = 0;    // counters[0]: sum of (last active index + 1) over the running problems: algorithmic k of the window GEMM
 constexpr int ASM_CNT_SLAB = 1;    // counters[1]: length of the list of sets too large for LDS (tiles in an L2 slab: asm_lambda_tile_k)
@@ -1190,8 +1190,8 @@ __device__ __forceinline__ void asm_lambda_reg(const AsmDev& d, int list, int wg
   T* ys = Yt + ASM_TS;                                     // y (forward result), [MB][16]
   T* rv = ys + MB * 16;                                    // right-hand side, [MB][16]
   T* lt = rv + MB * 16 + lane;                             // LDS-resident tiles: slot * 256 + r * 64 (+ lane)
-  T* idt = reinterpret_cast<T*>(sm_raw) + (size_t)WPB * asm_rw<T>(MB);   // identity tile (every wave writes all of it: same
-  for (int i = lane; i < ASM_TS; i += 64) idt[i] = (i / 17 == i % 17) ? T(1) : T(0);   // values, so no barrier is needed)
+  T* idt = reinterpret_cast<T*>(sm_raw) + (size_t)WPB * asm_rw<T>(MB);   // identity tile (every wave of the workgroup writes all
+  for (int i = lane; i < ASM_TS; i += 64) idt[i] = (i / 17 == i % 17) ? T(1) : T(0);   // of it: same values, so no barrier is needed)
   const int nitem = d.counters[asm_list_counter(list)];
   const int it = wg * WPB + wave;
   if (it >= nitem) return;
@@ -1260,18 +1260,39 @@ __device__ __forceinline__ void asm_lambda_reg(const AsmDev& d, int list, int wg
   }
 }
 
+// Problems (= waves) per workgroup of the three register kernels: 1 or 4.  Every wave of asm_lambda_reg solves its problem on its
+// own -- no barrier, no shared LDS but the identity tile -- so the workgroup is only the unit in which the CU hands out wave slots
+// and LDS: with four problems per workgroup the slots of three finished waves wait for the slowest (a wave that leaves before the
+// correction, a smaller set of the same class); with one the next problem starts in a freed slot at once.  The waves per SIMD (1 /
+// 2 / 1: registers) and the LDS per wave are the same either way.  (scripts/micro builds both values.)
+#ifndef ASM_REG64_WPB
+#define ASM_REG64_WPB 1            // asm_lambda_reg_k
+#endif
+#ifndef ASM_REG32_WPB
+#define ASM_REG32_WPB 1            // asm_lambda_reg32_k
+#endif
+#ifndef ASM_REG32B_WPB
+#define ASM_REG32B_WPB 1           // asm_lambda_reg32b_k
+#endif
+static_assert((ASM_REG64_WPB == 1 || ASM_REG64_WPB == 4) && (ASM_REG32_WPB == 1 || ASM_REG32_WPB == 4) &&
+              (ASM_REG32B_WPB == 1 || ASM_REG32B_WPB == 4), "one or four problems per workgroup");
+// workgroups of a list of `count` problems, WPB each (host grids and the kernels' class walk: the same expression)
+template <int WPB> __host__ __device__ constexpr int asm_reg_wgs(int count) { return (int)((unsigned)(count + WPB - 1) / (unsigned)WPB); }
+// bytes of dynamic LDS: WPB wave areas of the largest class + the identity tile
+template <class T, int WPB> __host__ __device__ constexpr int asm_reg_lds(int mb) { return (WPB * asm_rw<T>(mb) + ASM_TS) * (int)sizeof(T); }
+
 // All register-resident fp64 size classes 0..5 in ONE launch (their workgroups are independent; separate
 // launches would serialise six tails): workgroup w walks the classes from the largest down and takes
-// four problems of the class its index falls into.  Grid: sum_b ceil(count_b / 4).
-constexpr int ASM_REG_LDS = (4 * asm_rw<double>(ASM_NREG + 3) + ASM_TS) * 8;  // bytes of dynamic LDS (largest class) + the identity tile
+// ASM_REG64_WPB problems of the class its index falls into.  Grid: sum_b ceil(count_b / ASM_REG64_WPB).
+constexpr int ASM_REG_LDS = asm_reg_lds<double, ASM_REG64_WPB>(ASM_NREG + 3);
 #if ASM_OWN_KERNELS
-__global__ __launch_bounds__(256, 1) void asm_lambda_reg_k(AsmDev d) {
+__global__ __launch_bounds__(64 * ASM_REG64_WPB, 1) void asm_lambda_reg_k(AsmDev d) {
   int w = blockIdx.x;
-#define ASM_REG_CLASS(B)                                                   \
-  {                                                                        \
-    const int nb = (d.counters[4 + B] + 3) >> 2;                           \
-    if (w < nb) { asm_lambda_reg<double, B + 4, 4>(d, B, w); return; }     \
-    w -= nb;                                                               \
+#define ASM_REG_CLASS(B)                                                               \
+  {                                                                                    \
+    const int nb = asm_reg_wgs<ASM_REG64_WPB>(d.counters[ASM_CNT_F64 + B]);            \
+    if (w < nb) { asm_lambda_reg<double, B + 4, ASM_REG64_WPB>(d, B, w); return; }     \
+    w -= nb;                                                                           \
   }
   ASM_REG_CLASS(5) ASM_REG_CLASS(4) ASM_REG_CLASS(3) ASM_REG_CLASS(2) ASM_REG_CLASS(1) ASM_REG_CLASS(0)
 #undef ASM_REG_CLASS
@@ -1279,49 +1300,56 @@ __global__ __launch_bounds__(256, 1) void asm_lambda_reg_k(AsmDev d) {
 }
 #endif
 // The round of a carried problem (AsmDev::carry): the corrected multipliers the screen before kept for this very set -> its fp64
-// row of LAM, marked for asm_update_k's residual test like a corrected solve of this round.  One wave per problem, four per
-// workgroup: the last class of asm_lambda_reg32_k's grid (as a launch of its own after that kernel the copy was 0.05 ms on the
-// main stream at 55 000 problems; here its workgroups start while the last solves drain).
+// row of LAM, marked for asm_update_k's residual test like a corrected solve of this round.  ASM_CARRY_GROUP problems per
+// workgroup whatever its size -- one per wave of four, or four in a row by a single wave, so that the copy is the same number of
+// workgroups either way (a workgroup per problem would be ~55 000 of a few dozen stores each): the last class of
+// asm_lambda_reg32_k's grid (as a launch of its own after that kernel the copy was 0.05 ms on the main stream at 55 000 problems;
+// here its workgroups start while the last solves drain).
+constexpr int ASM_CARRY_GROUP = 4;
+template <int WPB>
 __device__ __forceinline__ void asm_carry_copy(const AsmDev& d, int wg) {
+  static_assert(ASM_CARRY_GROUP % WPB == 0, "every wave copies the same number of problems");
   const int lane = threadIdx.x & 63;
-  const int it = wg * 4 + (threadIdx.x >> 6);
-  if (it >= d.counters[ASM_CNT_CARRY]) return;
-  const int p = d.carrylist[it];
-  const int m = min(d.mg[p], ASM_MLDS);
-  const int* idx = d.idxg + (size_t)p * d.max_active;
-  const double* sp = d.stash + (size_t)p * ASM_MLDS;
-  double* lrow = d.lam + (size_t)d.row[p] * d.np;
-  for (int i = lane; i < m; i += 64) lrow[idx[i]] = sp[i];
-  if (lane == 0) { d.redo[p] = 2; d.cflag[p] = 0; }
+  const int ncarry = d.counters[ASM_CNT_CARRY];
+  const int it0 = wg * ASM_CARRY_GROUP + (int)(threadIdx.x >> 6) * (ASM_CARRY_GROUP / WPB);
+  for (int it = it0; it < min(it0 + ASM_CARRY_GROUP / WPB, ncarry); ++it) {
+    const int p = d.carrylist[it];
+    const int m = min(d.mg[p], ASM_MLDS);
+    const int* idx = d.idxg + (size_t)p * d.max_active;
+    const double* sp = d.stash + (size_t)p * ASM_MLDS;
+    double* lrow = d.lam + (size_t)d.row[p] * d.np;
+    for (int i = lane; i < m; i += 64) lrow[idx[i]] = sp[i];
+    if (lane == 0) { d.redo[p] = 2; d.cflag[p] = 0; }
+  }
 }
-// The f32 rounds of classes 0..5: two workgroups per CU (two waves per SIMD).
-constexpr int ASM_REG32_LDS = (4 * asm_rw<float>(ASM_NREG + 3) + ASM_TS) * 4;
+// The f32 rounds of classes 0..5: two waves per SIMD, eight per CU (two workgroups of four or eight of one).
+constexpr int ASM_REG32_LDS = asm_reg_lds<float, ASM_REG32_WPB>(ASM_NREG + 3);
 #if ASM_OWN_KERNELS
-__global__ __launch_bounds__(256, 2) void asm_lambda_reg32_k(AsmDev d) {
+__global__ __launch_bounds__(64 * ASM_REG32_WPB, 2) void asm_lambda_reg32_k(AsmDev d) {
   int w = blockIdx.x;
-#define ASM_REG_CLASS(B)                                                            \
-  {                                                                                 \
-    const int nb = (d.counters[ASM_CNT_F32 + B] + 3) >> 2;                          \
-    if (w < nb) { asm_lambda_reg<float, B + 4, 4>(d, ASM_NBIN + B, w); return; }    \
-    w -= nb;                                                                        \
+#define ASM_REG_CLASS(B)                                                                        \
+  {                                                                                             \
+    const int nb = asm_reg_wgs<ASM_REG32_WPB>(d.counters[ASM_CNT_F32 + B]);                     \
+    if (w < nb) { asm_lambda_reg<float, B + 4, ASM_REG32_WPB>(d, ASM_NBIN + B, w); return; }    \
+    w -= nb;                                                                                    \
   }
   ASM_REG_CLASS(5) ASM_REG_CLASS(4) ASM_REG_CLASS(3) ASM_REG_CLASS(2) ASM_REG_CLASS(1) ASM_REG_CLASS(0)
 #undef ASM_REG_CLASS
-  asm_carry_copy(d, w);                                    // (the launch has workgroups beyond the classes only for these)
+  asm_carry_copy<ASM_REG32_WPB>(d, w);                     // (the launch has workgroups beyond the classes only for these)
 }
 #endif
 
-// ... and of classes 6, 7: four waves per workgroup, one workgroup per CU (LDS).
-constexpr int ASM_REG32B_LDS = (4 * asm_rw<float>(11) + ASM_TS) * 4;
+// ... and of classes 6, 7: one wave per SIMD, four per CU (LDS).
+constexpr int ASM_REG32B_LDS = asm_reg_lds<float, ASM_REG32B_WPB>(11);
 #if ASM_OWN_KERNELS
-__global__ __launch_bounds__(256, 1) void asm_lambda_reg32b_k(AsmDev d) {
+__global__ __launch_bounds__(64 * ASM_REG32B_WPB, 1) void asm_lambda_reg32b_k(AsmDev d) {
   int w = blockIdx.x;
   {
-    const int nb = (d.counters[ASM_CNT_F32 + 7] + 3) >> 2;
-    if (w < nb) { asm_lambda_reg<float, 11, 4>(d, ASM_NBIN + 7, w); return; }
+    const int nb = asm_reg_wgs<ASM_REG32B_WPB>(d.counters[ASM_CNT_F32 + 7]);
+    if (w < nb) { asm_lambda_reg<float, 11, ASM_REG32B_WPB>(d, ASM_NBIN + 7, w); return; }
     w -= nb;
   }
-  asm_lambda_reg<float, 10, 4>(d, ASM_NBIN + 6, w);
+  asm_lambda_reg<float, 10, ASM_REG32B_WPB>(d, ASM_NBIN + 6, w);
 }
 #endif
 

@@ -1609,18 +1609,18 @@ int launch_multipliers(AsmCall& c, const int* cnt, bool inflight) {
   const AsmDev& a = c.a;
   const int lds_big = (a.max_active + ASM_TS) * 8;
   EvScope es(h, EV_LAMBDA, 0.0);
-  // one wave per problem, S in registers: size classes 0..5 (<= 144 bounds) in one launch, four problems per
-  // workgroup; classes 6, 7 (<= 176: four per workgroup in f32, one workgroup of two waves each in fp64) and the rare larger
+  // one wave per problem, S in registers: size classes 0..5 (<= 144 bounds) in one launch, ASM_REG64_WPB / ASM_REG32_WPB problems
+  // per workgroup; classes 6, 7 (<= 176: ASM_REG32B_WPB per workgroup in f32, one workgroup of two waves each in fp64) and the rare larger
   // sets (tiles in an L2 slab, one workgroup each: long latency chains on a handful of CUs) beside it on the side streams.
   const int nwg64s = cnt[ASM_CNT_F64 + 6] + cnt[ASM_CNT_F64 + 7];
-  const int nreg32b_wg = (cnt[ASM_CNT_F32 + 6] + 3) / 4 + (cnt[ASM_CNT_F32 + 7] + 3) / 4;
+  const int nreg32b_wg = asm_reg_wgs<ASM_REG32B_WPB>(cnt[ASM_CNT_F32 + 6]) + asm_reg_wgs<ASM_REG32B_WPB>(cnt[ASM_CNT_F32 + 7]);
   // sets of 177 .. 384 bounds: one workgroup of four or eight waves each (qp_wg.h)
   const int nwg64 = cnt[ASM_CNT_BIG64];
   const int nwg32 = cnt[ASM_CNT_BIG32];
   const int nwg32b = cnt[ASM_CNT_BIG32B];   // f32 rounds of 257 .. 384 bounds: eight waves per problem
   const int nwg64r = cnt[ASM_CNT_BIG64R];   // ... and their fp64 solves: the same factorisation, refined to fp64 residuals
   int nbig = cnt[ASM_CNT_SLAB] + nwg32 + nwg64s + nreg32b_wg + nwg64 + nwg32b + nwg64r, nreg_wg = 0, nreg32_wg = 0;
-  for (int b = 0; b < ASM_NREG; ++b) { nreg_wg += (cnt[ASM_CNT_F64 + b] + 3) / 4; nreg32_wg += (cnt[ASM_CNT_F32 + b] + 3) / 4; }
+  for (int b = 0; b < ASM_NREG; ++b) { nreg_wg += asm_reg_wgs<ASM_REG64_WPB>(cnt[ASM_CNT_F64 + b]); nreg32_wg += asm_reg_wgs<ASM_REG32_WPB>(cnt[ASM_CNT_F32 + b]); }
   // three side streams: [slab kernel: few workgroups, long chains -- it starts first and runs beside everything else],
   // [four- and eight-wave kernels of the 12 .. 24-block sets], [kernels of the 10- and 11-block classes]
   // (beside a pass stream4 carries the pass: the slab kernel then goes first on stream2)
@@ -1648,15 +1648,15 @@ int launch_multipliers(AsmCall& c, const int* cnt, bool inflight) {
       // fp64, 145 .. 176 bounds: two waves per problem (7.3 / 5.2 problems per microsecond at 160 / 176 bounds against the 6.0 / 4.5
       // of one wave per problem; in f32 the single-wave kernel wins, 18.1 against 14.3)
       if (nwg64s) hipLaunchKernelGGL(asm_lambda_wg64s_k, dim3(nwg64s), dim3(128), asm_wg_lds_bytes<double>(), h->stream3, a);
-      if (nreg32b_wg) hipLaunchKernelGGL(asm_lambda_reg32b_k, dim3(nreg32b_wg), dim3(256), ASM_REG32B_LDS, h->stream3, a);
+      if (nreg32b_wg) hipLaunchKernelGGL(asm_lambda_reg32b_k, dim3(nreg32b_wg), dim3(64 * ASM_REG32B_WPB), ASM_REG32B_LDS, h->stream3, a);
       HIPCHK(hipEventRecord(h->ev_join3, h->stream3));
     }
   }
   // fp64 first (its waves are the long ones), then the f32 rounds of the problems whose set still moves
-  if (nreg_wg) { EvScope e8(h, EV_LAMBDA64, 0.0); hipLaunchKernelGGL(asm_lambda_reg_k, dim3(nreg_wg), dim3(256), ASM_REG_LDS, s, a); }
+  if (nreg_wg) { EvScope e8(h, EV_LAMBDA64, 0.0); hipLaunchKernelGGL(asm_lambda_reg_k, dim3(nreg_wg), dim3(64 * ASM_REG64_WPB), ASM_REG_LDS, s, a); }
   // (... and, at the end of that grid, the problems whose solve the round before already did: a copy -- asm_carry_copy)
-  nreg32_wg += (cnt[ASM_CNT_CARRY] + 3) / 4;
-  if (nreg32_wg) { EvScope e7(h, EV_LAMBDA32, 0.0); hipLaunchKernelGGL(asm_lambda_reg32_k, dim3(nreg32_wg), dim3(256), ASM_REG32_LDS, s, a); }
+  nreg32_wg += asm_reg_wgs<ASM_CARRY_GROUP>(cnt[ASM_CNT_CARRY]);
+  if (nreg32_wg) { EvScope e7(h, EV_LAMBDA32, 0.0); hipLaunchKernelGGL(asm_lambda_reg32_k, dim3(nreg32_wg), dim3(64 * ASM_REG32_WPB), ASM_REG32_LDS, s, a); }
   if (side2) HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
   if (side3) HIPCHK(hipStreamWaitEvent(s, h->ev_join3, 0));
   if (side4) HIPCHK(hipStreamWaitEvent(s, h->ev_join4, 0));
